@@ -11,16 +11,22 @@ completed before the clock stops.  Weak scaling: every rank owns ``--batch``
 pairs per step.
 
   python bench.py [--gpus N --steps K --warmup W --batch B --height H --width W]
+  python bench.py --full ...                          (every secondary measurement too)
   torchrun --nproc-per-node N bench.py --gpus N ...   (driver, N > 1)
+
+A plain run sets up, warms up, times the K steps (``ms_per_step`` = the time of
+one of them), writes the last step's output under ``--dump-outputs DIR`` and
+prints the line.  ``--full`` adds what takes runs of its own: ``unprofiled``,
+the secondary precision, ``cpu_baseline`` and ``parity`` (null otherwise).
 
 Rank 0 prints one JSON line.  ``roofline`` is for the dominant kernel (the
 MFMA conv3x3 family): algorithmic conv FLOPs / the family's busy time (union of
 its launch spans — the batch runs as ``--streams`` parts whose launches
 overlap), measured live with HIP events recorded around every launch of the
-timed steps; ``unprofiled`` re-times the same K steps without those events
+timed steps; ``unprofiled`` (``--full``) re-times the same K steps without those events
 (their records cost ~1 % of the rate at 720p x4 and ~15 % at 640x368 x1, so
-``value`` is the conservative, profiled figure); ``cpu_baseline`` times the CPU oracle (oracle/, a restatement of
-the reference op sequence) on a bounded sample on this host.
+``value`` is the conservative, profiled figure); ``cpu_baseline`` (``--full``) times the CPU oracle (oracle/, a
+restatement of the reference op sequence) on a bounded sample on this host.
 """
 from __future__ import annotations
 
@@ -118,11 +124,19 @@ def parse():
                     help="fp32: exact fp32 (v_mfma_f32_32x32x2_f32, fp32 storage) -- the BASELINE metric; "
                          "fp32_split16: fp32-EMULATED (values as fp16 hi+lo, 3 fp16 products per fp32 "
                          "product, fp32 accumulate); fp16: fp16 storage/products")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the unprofiled re-timing of the "
+                         "K steps, the secondary precision (--no-alt skips it), the CPU baseline and the "
+                         "parity against it (--cpu-baseline off skips them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them returned as DIR/<name>.npy "
+                         "(float32; above 64 MB a fixed seeded sample of the elements)")
     ap.add_argument("--no-prof", action="store_true", help="skip the per-launch event profiler")
     ap.add_argument("--no-alt", action="store_true",
-                    help="N=1: skip the secondary line (fp32 run: the fp32-emulated split16 path; "
+                    help="--full, N=1: skip the secondary line (fp32 run: the fp32-emulated split16 path; "
                          "other precisions: the exact-fp32 path)")
-    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
+    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto",
+                    help="--full: auto = time the CPU oracle and report parity against it")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (production); gloo only to rehearse N ranks on fewer GPUs")
     ap.add_argument("--cpu-pairs", type=int, default=2, help="pairs timed on the CPU baseline")
@@ -257,6 +271,26 @@ def cpu_baseline(sd, h, w, pairs, t, gpu_out0, alt_out0=None):
     return res, parity
 
 
+DUMP_MAX_BYTES = 64 << 20  # all files of one --dump-outputs directory together
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy in float32, DUMP_MAX_BYTES in all.  An array
+    above its share is written as the elements at a fixed, seeded set of flat indices
+    (sorted; the same indices for the same shape in every run and build)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays)) // 4
+    for name, t in arrays.items():
+        t = t.detach().float().reshape(-1)
+        if t.numel() > share:
+            idx = np.sort(np.random.default_rng(1234).integers(0, t.numel(), share - 64))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        else:
+            t = t.reshape(arrays[name].shape)
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def union_ms(spans):
     """Length of the union of [t0, t1] intervals (ms)."""
     tot, end = 0.0, None
@@ -322,7 +356,7 @@ def train_main(args):
         loss = torch.sum(torch.sqrt((out - tgt).pow(2) + 1e-6)) / B  # charbonnierLoss, losses.py:39-42
         loss.backward()
         opt.step()
-        return loss
+        return loss, out
 
     from rrin_amd import autograd as ag
     for _ in range(args.warmup):
@@ -331,9 +365,11 @@ def train_main(args):
     ag.PROF = []  # per-launch conv events (forward, dgrad, wgrad) on each launch's stream
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, out = step()
     torch.cuda.synchronize(dev)
     el = time.perf_counter() - t0
+    if args.dump_outputs:  # the last timed step's interpolated frames and loss
+        dump_outputs(args.dump_outputs, {"out": out, "loss": loss.reshape(1)})
     events, ag.PROF = ag.PROF, None
     # conv busy time = the union of the conv launch spans, on one clock: every event's time
     # from the first start event
@@ -505,11 +541,15 @@ def main():
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after its last step: the frames of this
+        # rank's pairs, or the all-gathered frames of every rank
+        dump_outputs(args.dump_outputs, {"out": last_gather[0][1] if gather is not None else last[0]})
 
     # the same K steps again without the per-launch events (their records cost
     # ~1 % of the rate at 720p x4, ~15 % at 640x368 x1): reported beside `value`
     unprofiled = None
-    if prof is not None:
+    if prof is not None and (args.full or ngraph is not None):  # --graph: the roofline's eager pass
         if distributed:
             dist.barrier()
         torch.cuda.synchronize(dev)
@@ -675,6 +715,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(1e3 * elapsed / args.steps, 3),
         "higher_is_better": True,
         "scaling": "weak",
@@ -697,7 +738,7 @@ def main():
     }
     alt_out = None
     alt_key = None
-    if world == 1 and not args.no_alt:
+    if world == 1 and args.full and not args.no_alt:
         # secondary line on the same inputs: an fp32 run reports the fp32-emulated
         # split16 path beside it; any other precision reports the exact-fp32 path
         alt = "fp32_split16" if args.precision in ("fp32", "fp32_planar") else "fp32"
@@ -725,7 +766,7 @@ def main():
                         "streams": args.streams}
         del eng2
         net.precision = args.precision
-    if rank == 0 and args.cpu_baseline == "auto":
+    if rank == 0 and args.full and args.cpu_baseline == "auto":
         # every line carries parity (rank 0's pair 0 = global pair 0 vs the CPU
         # oracle) and the CPU baseline; at N > 1 the timed CPU sample is that one
         # parity pair, so the other ranks wait only seconds at the final barrier

@@ -131,6 +131,25 @@ def test_bench_union_ms():
     assert bench.union_ms([(0.0, 1.0), (1.0, 2.0)]) == 2.0            # touching
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy files, whole below the size limit, else a fixed sample."""
+    import bench
+    a = torch.arange(24, dtype=torch.float64).reshape(2, 3, 4)
+    bench.dump_outputs(str(tmp_path / "d"), {"out": a, "loss": a.sum().reshape(1)})
+    got = np.load(tmp_path / "d" / "out.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 3, 4) and np.array_equal(got, a.numpy())
+    assert np.load(tmp_path / "d" / "loss.npy").tolist() == [276.0]
+    # above the limit: the same sorted sample of the elements in every call, within the limit
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    big = torch.arange(5000, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "s1"), {"out": big})
+    bench.dump_outputs(str(tmp_path / "s2"), {"out": big + 0.0})
+    s1, s2 = np.load(tmp_path / "s1" / "out.npy"), np.load(tmp_path / "s2" / "out.npy")
+    assert s1.dtype == np.float32 and s1.ndim == 1 and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) >= 0) and 0 <= s1.min() and s1.max() < 5000
+    assert os.path.getsize(tmp_path / "s1" / "out.npy") <= 4096
+
+
 def test_size_class_tables():
     """Every tuned tile table entry names a config that exists and fits its cin
     (the library's own check), and the size classes split at the documented

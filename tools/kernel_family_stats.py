@@ -11,8 +11,8 @@ dispatch spans (the quantity bench.py's roofline divides by when the batch is sp
 over several streams).  STEPS is the number of bench steps the trace holds, or
 "auto": the dispatches of the once-per-forward-part kernel (pack_g16_*: one per
 stream part) / P (= bench --streams, default 2).  A profiled `bench.py --steps K
---warmup W` runs W + K steps plus bench's unprofiled re-run of the K steps: "auto"
-counts them all.  With --ms-per-step (the bench line's own ms_per_step), a family
+--warmup W` runs W + K steps, with `--full` plus bench's unprofiled re-run of the K
+steps: "auto" counts them all.  With --ms-per-step (the bench line's own ms_per_step), a family
 whose union per step exceeds it is an error (exit 2): a union longer than the step
 means the step count is wrong.
 
