@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define RRIN_ABI_VERSION 19
+#define RRIN_ABI_VERSION 20
 
 #define RRIN_OK 0
 #define RRIN_E_SHAPE (-1)     /* H or W not a multiple of 16, or N < 1          */
@@ -385,6 +385,15 @@ int rrin_upsample2x_h8(const rrin_h8* src, const rrin_h8* dst, int32_t n, int32_
 /* x = cat(x0, x1) (model.py:33) into the 16-channel H8 Net buffer: channels
  * 0-5 from the two NCHW frames, channels 6-15 zeroed (whole-record stores). */
 int rrin_pack_g16_h8(const float* i0, const float* i1, int32_t n, const rrin_h8* g16, int32_t prec, void* stream);
+/* ABI 20: the same from two stacks of 8-bit frames, uint8 [n][h0][w0][3] (RGB interleaved, every
+ * frame dense, img_stride bytes between frames of a stack: f0 and f1 may be two views of one
+ * [n+1] stack), any h0, w0 >= 1; g16 is round_up(h0,16) x round_up(w0,16) (RRIN_E_SHAPE
+ * otherwise).  The frame is edge-replicated on top (h - h0 rows) and on the right (w - w0
+ * columns): padded pixel (y, x) reads source pixel (max(y - (h - h0), 0), min(x, w0 - 1)); a
+ * byte u becomes float(u) / 255.0f, correctly rounded (a 256-entry table).  The records are
+ * bitwise those rrin_pack_g16_h8 writes from the padded fp32 NCHW frames. */
+int rrin_pack_g16_u8_h8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0,
+                        int32_t w0, const rrin_h8* g16, int32_t prec, void* stream);
 /* NCHW fp32 <-> H8 view (c channels starting at channel ch_off of the view). */
 int rrin_nchw_to_h8(const float* src, int32_t n, int32_t c, int32_t ch_off, const rrin_h8* dst,
                     int32_t prec, void* stream);
@@ -402,6 +411,12 @@ typedef struct rrin_head_h8_desc {
   rrin_h8 flow_raw;      /* FLOW (optional, hi NULL = skip): raw 4-ch Flow output */
   float* raw_out;        /* optional: head conv output before the glue, NCHW fp32 */
   int32_t* status;       /* optional: fp16 range flag; FINAL writes NaN pixels when it is set */
+  /* ABI 20, FINAL, optional (NULL: off): the output also (out set) or only (out NULL) as 8-bit
+     interleaved frames [n][h0][w0][3] -- the crop rows [top, top + h0), columns [0, w0) of the
+     h x w output, each value v as (uint8)(v * 255.0f) (one fp32 multiply, truncation); a pixel
+     poisoned by the range flag is written as 0.  top + h0 <= h, w0 <= w. */
+  uint8_t* out_u8;
+  int32_t h0, w0, top, pad2_;
 } rrin_head_h8_desc;
 int rrin_head_h8_fwd(const rrin_head_h8_desc* d, void* stream);
 
@@ -522,6 +537,26 @@ int64_t rrin_unet_scratch_bytes(const rrin_unet_desc* d);
 int rrin_unet_fwd(const rrin_unet_desc* d, void* stream);
 int64_t rrin_net_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t prec);
 int rrin_net_fwd(const rrin_net_desc* d, void* stream);
+
+/* ABI 20: the forward on 8-bit frames of any size, already on the device: f0 / f1 uint8
+ * [n][h0][w0][3] in, out_u8 uint8 [n][h0][w0][3] out; bit for bit the host chain "edge-pad to
+ * /16 (top, right) and divide by 255 -> rrin_net_fwd -> multiply by 255, truncate, crop"
+ * (rrin_pack_g16_u8_h8 in, the FINAL head's rrin_head_h8_desc.out_u8 store out: no fp32 NCHW
+ * frame exists on this path).  net.n / h / w are the padded size, h == round_up(h0,16) and
+ * w == round_up(w0,16) (RRIN_E_SHAPE otherwise, and for h0, w0 < 1); net.i0 / i1 / out are
+ * ignored and may be NULL; every other field of net means what it means for rrin_net_fwd.  The
+ * record precisions only: RRIN_PREC_F32 (planar) returns RRIN_E_ARG, as do null frames.  With
+ * the range guard set (net.status) the poisoned pixels are written as 0.  Arguments are
+ * validated before any HIP call. */
+typedef struct rrin_net_u8_desc {
+  rrin_net_desc net;
+  const uint8_t* f0;    /* [n][h0][w0][3], every frame dense */
+  const uint8_t* f1;
+  int64_t img_stride;   /* bytes between frames of f0 and of f1 (>= h0*w0*3) */
+  uint8_t* out_u8;      /* [n][h0][w0][3] contiguous */
+  int32_t h0, w0;
+} rrin_net_u8_desc;
+int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream);
 
 /* ---- Training path (autograd): NCHW fp32 kernels ------------------------- */
 /* With autograd on (the reference trains through Net.forward, train.py:98, and

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librrin_hip.so")
 # A/B sessions only (tools/sessions/): another build of the same library, e.g. ab/librrin_hip_X.so
 if os.environ.get("RRIN_LIB_AB"):
@@ -95,7 +95,8 @@ class HeadH8Desc(C.Structure):
     _fields_ = [("n", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("mode", C.c_int32),
                 ("prec", C.c_int32), ("pad_", C.c_int32), ("src", H8), ("g16", H8), ("w", C.c_void_p),
                 ("bias", C.c_void_p), ("coef", C.c_void_p), ("out", C.c_void_p), ("flow_raw", H8),
-                ("raw_out", C.c_void_p), ("status", C.c_void_p)]
+                ("raw_out", C.c_void_p), ("status", C.c_void_p), ("out_u8", C.c_void_p), ("h0", C.c_int32),
+                ("w0", C.c_int32), ("top", C.c_int32), ("pad2_", C.c_int32)]
 
 
 class HeadWeights(C.Structure):
@@ -109,6 +110,11 @@ class NetDesc(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
                 ("skip_flow", C.c_int32), ("prec", C.c_int32), ("prof", C.c_void_p), ("taps", C.c_void_p),
                 ("status", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
+
+
+class NetU8Desc(C.Structure):
+    _fields_ = [("net", NetDesc), ("f0", C.c_void_p), ("f1", C.c_void_p), ("img_stride", C.c_int64),
+                ("out_u8", C.c_void_p), ("h0", C.c_int32), ("w0", C.c_int32)]
 
 
 class TConvDesc(C.Structure):
@@ -193,6 +199,8 @@ SIGNATURES = {
     "rrin_subpixel_edge_fix_h8": (C.c_int, [C.POINTER(EdgeFixDesc), C.c_void_p]),
     "rrin_upsample2x_h8": (C.c_int, [C.POINTER(H8), C.POINTER(H8), C.c_int32, C.c_int32, C.c_void_p]),
     "rrin_pack_g16_h8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(H8), C.c_int32, C.c_void_p]),
+    "rrin_pack_g16_u8_h8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(H8), C.c_int32, C.c_void_p]),
     "rrin_nchw_to_h8": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(H8), C.c_int32,
                                   C.c_void_p]),
     "rrin_h8_to_nchw": (C.c_int, [C.POINTER(H8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
@@ -202,6 +210,7 @@ SIGNATURES = {
     "rrin_flow_tblend_h8": (C.c_int, [C.POINTER(H8), C.POINTER(H8), C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_void_p]),
     "rrin_net_fwd": (C.c_int, [C.POINTER(NetDesc), C.c_void_p]),
+    "rrin_net_u8_fwd": (C.c_int, [C.POINTER(NetU8Desc), C.c_void_p]),
     "rrin_unet_conv_count": (C.c_int64, [C.c_int32]),
     "rrin_unet_fwd": (C.c_int, [C.POINTER(UNetDesc), C.c_void_p]),
     "rrin_prof_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),

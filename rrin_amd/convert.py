@@ -72,6 +72,41 @@ def to_uint8_image(t: torch.Tensor, meta) -> np.ndarray:
     return a.permute(1, 2, 0).contiguous().numpy()
 
 
+def load_frame_u8(path):
+    """PIL RGB -> the raw uint8 [H,W,3] frame (no padding, no float) and load_frame's metadata:
+    what the byte pipeline of interpolate_folder hands to ``interpolate_u8``."""
+    from PIL import Image
+    with Image.open(path) as im:
+        arr = np.asarray(im.convert("RGB"), dtype=np.uint8)
+    h, w = arr.shape[:2]
+    top, _ = pad_amounts(w, h)
+    return torch.from_numpy(arr.copy()), {"width": w, "height": h, "top": top,
+                                          "filetype": os.path.splitext(path)[1], "path": path}
+
+
+def frames_u8_to_float(frames: torch.Tensor) -> torch.Tensor:
+    """The input mapping of the byte path in plain torch: uint8 [...,H0,W0,3] -> float32
+    [...,3,H,W] with H, W the next multiples of 16, edge-replicated on top and on the right
+    (padded pixel (y, x) reads source pixel (max(y - top, 0), min(x, W0 - 1))) and divided by
+    255 -- bit for bit load_frame's tensor.  ``Net.forward_u8`` does this inside its input pack."""
+    h0, w0 = frames.shape[-3], frames.shape[-2]
+    top, right = pad_amounts(w0, h0)
+    rows = (torch.arange(h0 + top, device=frames.device) - top).clamp_(min=0)
+    cols = torch.arange(w0 + right, device=frames.device).clamp_(max=w0 - 1)
+    x = frames.index_select(-3, rows).index_select(-2, cols)
+    return x.movedim(-1, -3).float().div_(255.0)
+
+
+def frames_float_to_u8(t: torch.Tensor, height: int, width: int) -> torch.Tensor:
+    """The output mapping of the byte path in plain torch: float [...,3,H,W] -> uint8
+    [...,height,width,3], mul(255) truncated toward zero and cropped to rows
+    [H - height, H), columns [0, width) -- bit for bit to_uint8_image.  ``Net.forward_u8`` does
+    this inside its last head's store."""
+    top = t.shape[-2] - height
+    a = t.mul(255).to(torch.uint8)[..., top:top + height, :width]
+    return a.movedim(-3, -1).contiguous()
+
+
 def save_image(arr, path):
     from PIL import Image
     Image.fromarray(arr).save(path)
@@ -99,15 +134,15 @@ class _Reader:
     exception in the thread (unreadable / corrupt image) is re-raised in the
     consumer instead of leaving it blocked."""
 
-    def __init__(self, src, frames, lo, hi, depth):
+    def __init__(self, src, frames, lo, hi, depth, load=load_frame):
         self.q: Queue = Queue(maxsize=depth)
-        self.t = threading.Thread(target=self._run, args=(src, frames, lo, hi), daemon=True)
+        self.t = threading.Thread(target=self._run, args=(src, frames, lo, hi, load), daemon=True)
         self.t.start()
 
-    def _run(self, src, frames, lo, hi):
+    def _run(self, src, frames, lo, hi, load):
         try:
             for k in range(lo, hi + 1):
-                self.q.put(("frame", k, *load_frame(os.path.join(src, frames[k]))))
+                self.q.put(("frame", k, *load(os.path.join(src, frames[k]))))
             self.q.put(("end",))
         except BaseException as e:  # noqa: BLE001 - handed to the consumer
             self.q.put(("error", e))
@@ -120,7 +155,7 @@ class _Reader:
 
 
 def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None, writers=4, log=print,
-                       rank=0, world=1, group=None, gather=True):
+                       rank=0, world=1, group=None, gather=True, u8="auto"):
     """Interpolate every consecutive pair of frames in ``src`` into ``dest``.
 
     ``model`` is an ``rrin_amd.Net`` (anything with ``interpolate(i0, i1, ts)``
@@ -134,7 +169,21 @@ def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None,
     ``gather=True``, one all-gather (RCCL over xGMI on GPUs, gloo on CPU)
     reassembles that step's frames of all ranks in rank order on every rank, and
     rank 0 writes the whole sequence.  ``gather=False`` lets every rank write its
-    own frames (the file names are global, so the outputs are the same)."""
+    own frames (the file names are global, so the outputs are the same).
+
+    ``u8`` selects the byte pipeline: the reader hands over raw uint8 [H,W,3] frames (no padding,
+    no float conversion), a step's nloc + 1 frames go to the device as one pinned uint8 stack
+    (every frame once per step, a quarter of the fp32 bytes), ``model.interpolate_u8`` runs on
+    two views of that stack and returns uint8 [N,H,W,3] frames, which are copied back and
+    written as they are -- the padding, /255, *255 truncation and crop happen inside the model
+    (``Net.forward_u8``: inside its kernels).  The files are the same bytes either way.
+    ``"auto"``: when ``device`` is given and the model has ``interpolate_u8`` (and is not a Net
+    of the planar fp32 precision); ``True`` forces it, ``False`` forbids it."""
+    if u8 == "auto":
+        u8 = (device is not None and hasattr(model, "interpolate_u8")
+              and getattr(model, "precision", None) != "fp32_planar")
+    if u8 and not hasattr(model, "interpolate_u8"):
+        raise ValueError("u8=True needs a model with interpolate_u8(f0, f1, ts)")
     frames = list_frames(src)
     if len(frames) < 2:
         raise ValueError(f"need at least two frames in {src}")
@@ -167,7 +216,7 @@ def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None,
             os.path.join(dest, f"{img_count0:09d}{os.path.splitext(frames[first_pair])[1]}"))
     t0 = time.time()
     steps = max((b - a + batch - 1) // batch for a, b in shards)
-    reader = _Reader(src, frames, lo, hi, 2 * batch + 2) if hi > lo else None
+    reader = _Reader(src, frames, lo, hi, 2 * batch + 2, load_frame_u8 if u8 else load_frame) if hi > lo else None
     prev = reader.get() if reader else None
     pending = []
     for s_ in range(steps):
@@ -182,6 +231,16 @@ def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None,
         outs = None
         if nloc:
             prev = group_items[-1]
+        if nloc and u8:
+            # one uint8 stack of the step's nloc + 1 frames; pair j is (stack[j], stack[j + 1])
+            stack = torch.empty((len(group_items),) + tuple(group_items[0][1].shape), dtype=torch.uint8,
+                                pin_memory=device is not None)
+            torch.stack([g[1] for g in group_items], out=stack)
+            if device is not None:
+                stack = stack.to(device, non_blocking=True)
+            with torch.no_grad():
+                outs = model.interpolate_u8(stack[:-1], stack[1:], ts)
+        elif nloc:
             i0 = torch.stack([g[1] for g in group_items[:-1]])
             i1 = torch.stack([g[1] for g in group_items[1:]])
             if device is not None:
@@ -270,8 +329,11 @@ def _retire(item, sf, dest, put, model=None):
         model.check_range(wait=False)  # fp16-stored precisions: raise instead of writing NaN frames
     for p, (m0, m1, base) in enumerate(zip(metas0, metas1, bases)):
         for i in range(sf):
-            put(lambda t, m, path: save_image(to_uint8_image(t, m), path), host[i][p], m0,
-                os.path.join(dest, f"{base + i + 1:09d}{m0['filetype']}"))
+            path = os.path.join(dest, f"{base + i + 1:09d}{m0['filetype']}")
+            if host[i].dtype == torch.uint8:  # the byte pipeline: already cropped [H,W,3] frames
+                put(lambda t, path: save_image(t.numpy(), path), host[i][p], path)
+                continue
+            put(lambda t, m, path: save_image(to_uint8_image(t, m), path), host[i][p], m0, path)
         put(shutil.copy, m1["path"], os.path.join(dest, f"{base + sf + 1:09d}{m1['filetype']}"))
 
 

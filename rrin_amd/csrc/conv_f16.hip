@@ -931,7 +931,21 @@ struct HeadH8Args {
   uint4* fr32;      // F32R: raw Flow output, 1 record (nullable)
   float* raw;       // optional: head conv output before the glue, NCHW [n][COUT][h][w]
   int* status;      // optional fp16 range flag: glue stores set it, FINAL poisons on it
+  uint8_t* out8;    // FINAL, optional: uint8 [n][h0][w0][3] crop (rows top .. top + h0 - 1, columns < w0)
+  int h0, w0, top;
 };
+
+// FINAL with a uint8 output: the clamped pixel q of padded position (y, x) as three interleaved
+// bytes of the crop, (uint8)(q * 255.0f) -- one fp32 multiply, truncation toward zero, as
+// t.mul(255).to(torch.uint8); a poisoned pixel (fp16 range guard) is written as 0.  Pixels of the
+// padding (rows above top, columns from w0) are not written.
+__device__ inline void final_store_u8(const HeadH8Args& a, int img, int y, int x, const float* q, bool poison) {
+  const int yo = y - a.top;
+  if (yo < 0 || yo >= a.h0 || x >= a.w0) return;
+  uint8_t* o = a.out8 + (((int64_t)img * a.h0 + yo) * a.w0 + x) * 3;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) o[ch] = poison ? (uint8_t)0 : (uint8_t)(q[ch] * 255.0f);
+}
 
 template <int COUT, int MODE, int PLANES>
 __global__ void __launch_bounds__(256) head_h8_kernel(HeadH8Args a) {
@@ -1138,13 +1152,19 @@ __global__ void __launch_bounds__(256) head_h8_kernel(HeadH8Args a) {
     load8(rec0, g0);
     load8(rec1, g1);
     const float base[3] = {g0[6], g0[7], g1[0]};
-    float* o = a.out + ((int64_t)img * 3) * a.h * a.w_ + (int64_t)y * a.w_ + x;
     const bool poison = a.status && *a.status != 0;  // an fp16 overflow upstream (range guard)
+    float q[3];
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       const float v = acc[ch] + base[ch];
-      o[(int64_t)ch * a.h * a.w_] = poison ? __builtin_nanf("") : (v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v));
+      q[ch] = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
     }
+    if (a.out) {
+      float* o = a.out + ((int64_t)img * 3) * a.h * a.w_ + (int64_t)y * a.w_ + x;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) o[(int64_t)ch * a.h * a.w_] = poison ? __builtin_nanf("") : q[ch];
+    }
+    if (a.out8) final_store_u8(a, img, y, x, q, poison);
   }
   }
 }
@@ -1236,6 +1256,79 @@ __global__ void pack_g16_r32_kernel(const float* __restrict__ i0, const float* _
   g[rec + gp] = f4rec(b1, b2, 0.f, 0.f);
   g[rec + 2 * gp] = make_uint4(0u, 0u, 0u, 0u);
   g[rec + 3 * gp] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// ---- 8-bit frames straight into g16 (rrin_pack_g16_u8_h8) --------------------------
+// float(u) / 255.0f, correctly rounded, for every byte value: evaluated by the host compiler
+// (a multiply by 1 / 255.0f differs from the division for 126 of the 256 values)
+struct U8ScaleTab {
+  float v[256];
+  constexpr U8ScaleTab() : v{} {
+    for (int i = 0; i < 256; ++i) v[i] = (float)i / 255.0f;
+  }
+};
+__constant__ const U8ScaleTab kU8Scale{};
+
+// x = cat(x0, x1) from two uint8 [n][h0][w0][3] frame stacks, edge-replicated on top (`top` rows)
+// and on the right to the h x w of g16: padded pixel (y, x) reads source pixel
+// (max(y - top, 0), min(x, w0 - 1)).  One workgroup per row and run of 256 pixels: the run's
+// 768 source bytes of each frame are loaded one byte per lane (a wave's load is 64 consecutive
+// bytes, whatever the alignment of the row) into LDS, then every lane converts its pixel through
+// the LDS copy of the scale table and writes the whole records pack_g16_h8_kernel /
+// pack_g16_r32_kernel write.  MODE 0: fp32 records, 1: fp16, 2: split16 (hi and lo planes).
+template <int MODE>
+__global__ void __launch_bounds__(256) pack_g16_u8_kernel(const uint8_t* __restrict__ f0,
+                                                          const uint8_t* __restrict__ f1, int64_t f_img, int w0,
+                                                          int top, uint4* ghi, uint4* glo, int64_t img_stride,
+                                                          int64_t gp, int wp, int w) {
+  __shared__ float s_tab[256];
+  __shared__ uint8_t s_px[2][768];
+  const int tid = threadIdx.x;
+  const int xs = blockIdx.x * 256, y = blockIdx.y, img = blockIdx.z;
+  s_tab[tid] = kU8Scale.v[tid];
+  const int sy = y > top ? y - top : 0;
+  const int64_t row = (int64_t)img * f_img + ((int64_t)sy * w0 + xs) * 3;
+  const int nb = min(256, w0 - xs) * 3;  // xs < w0: the right pad is < 16 columns, xs a multiple of 256
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int b = tid + 256 * k;
+    if (b < nb) {
+      s_px[0][b] = f0[row + b];
+      s_px[1][b] = f1[row + b];
+    }
+  }
+  __syncthreads();
+  const int x = xs + tid;
+  if (x >= w) return;
+  const int c = (min(x, w0 - 1) - xs) * 3;
+  float a[3], b[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    a[k] = s_tab[s_px[0][c + k]];
+    b[k] = s_tab[s_px[1][c + k]];
+  }
+  const int64_t rec = (int64_t)img * img_stride + (int64_t)(y + 1) * wp + x + kH8PadLeft;
+  if constexpr (MODE == 0) {
+    ghi[rec] = f4rec(a[0], a[1], a[2], b[0]);
+    ghi[rec + gp] = f4rec(b[1], b[2], 0.f, 0.f);
+    ghi[rec + 2 * gp] = make_uint4(0u, 0u, 0u, 0u);
+    ghi[rec + 3 * gp] = make_uint4(0u, 0u, 0u, 0u);
+  } else {
+    half8 hi = {}, lo = {};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      hi[k] = (_Float16)a[k];
+      hi[3 + k] = (_Float16)b[k];
+      lo[k] = lo_of(a[k], hi[k]);
+      lo[3 + k] = lo_of(b[k], hi[3 + k]);
+    }
+    ghi[rec] = __builtin_bit_cast(uint4, hi);
+    ghi[rec + gp] = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (MODE == 2) {
+      glo[rec] = __builtin_bit_cast(uint4, lo);
+      glo[rec + gp] = make_uint4(0u, 0u, 0u, 0u);
+    }
+  }
 }
 
 // Ft0 / Ft1 (model.py:38-39) from a kept raw Flow record -> g16 channels 6-9
@@ -1451,12 +1544,18 @@ __global__ void __launch_bounds__(256) head_r32_kernel(HeadH8Args a) {
 #pragma clang fp contract(off)
       const floatx4 r1 = ld(1), r2v = ld(2);
       const float base[3] = {r1[2], r1[3], r2v[0]};
-      float* o = a.out + ((int64_t)img * 3) * a.h * a.w_ + (int64_t)y * a.w_ + x;
+      float q[3];
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) {
         const float v = acc[ch] + base[ch];
-        o[(int64_t)ch * a.h * a.w_] = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
+        q[ch] = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
       }
+      if (a.out) {
+        float* o = a.out + ((int64_t)img * 3) * a.h * a.w_ + (int64_t)y * a.w_ + x;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) o[(int64_t)ch * a.h * a.w_] = q[ch];
+      }
+      if (a.out8) final_store_u8(a, img, y, x, q, false);
     }
   }
 }
@@ -2451,7 +2550,10 @@ static int head_prepare(const rrin_head_h8_desc* d, HeadH8Args& a, int& grid) {
   } else if (cpr * d->g16.groups < d->cout) {
     return RRIN_E_ARG;
   }
-  if (d->mode == RRIN_HEAD_FINAL && !d->out) return RRIN_E_ARG;
+  if (d->mode == RRIN_HEAD_FINAL && !d->out && !d->out_u8) return RRIN_E_ARG;
+  if (d->mode == RRIN_HEAD_FINAL && d->out_u8 &&
+      (d->h0 < 1 || d->w0 < 1 || d->top < 0 || d->top + d->h0 > h || d->w0 > w))
+    return RRIN_E_SHAPE;
   const int planes = planes_of(d->prec);
   memset(&a, 0, sizeof(a));
   const int64_t sg = (int64_t)d->src.g_off * d->src.g.plane;
@@ -2476,6 +2578,12 @@ static int head_prepare(const rrin_head_h8_desc* d, HeadH8Args& a, int& grid) {
   a.out = d->out;
   a.raw = d->raw_out;
   a.status = d->status;
+  if (d->mode == RRIN_HEAD_FINAL && d->out_u8) {
+    a.out8 = d->out_u8;
+    a.h0 = d->h0;
+    a.w0 = d->w0;
+    a.top = d->top;
+  }
   if (d->mode == RRIN_HEAD_FLOW && d->flow_raw.hi) {
     if (!h8_ok(d->flow_raw, d->prec) || d->flow_raw.g.h != h || d->flow_raw.g.w != w) return RRIN_E_SHAPE;
     const int64_t fo = (int64_t)d->flow_raw.g_off * d->flow_raw.g.plane * 8;
@@ -2570,5 +2678,29 @@ extern "C" int rrin_pack_g16_h8(const float* i0, const float* i1, int32_t n, con
   else
     hipLaunchKernelGGL(pack_g16_h8_kernel<1>, dim3(grid), dim3(256), 0, st, i0, i1, static_cast<uint4*>(g16->hi),
                        (uint4*)nullptr, g16->img_stride, g16->g.plane, g16->g.wp, g16->g.h, g16->g.w, total);
+  return hip_code(hipGetLastError());
+}
+
+extern "C" int rrin_pack_g16_u8_h8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0,
+                                   int32_t w0, const rrin_h8* g16, int32_t prec, void* stream) {
+  if (!f0 || !f1 || !g16 || n < 1 || !rec_prec(prec)) return RRIN_E_ARG;
+  if (!h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16) return RRIN_E_SHAPE;
+  const int h = g16->g.h, w = g16->g.w;
+  if (h0 < 1 || w0 < 1 || h != (h0 + 15) / 16 * 16 || w != (w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  if (img_stride < (int64_t)h0 * w0 * 3 && n > 1) return RRIN_E_ARG;
+  if (n > 65535 || h > 65535) return RRIN_E_SHAPE;  // grid y / z
+  const dim3 grid((w + 255) / 256, h, n);
+  const int top = h - h0;
+  hipStream_t st = (hipStream_t)stream;
+  if (prec == RRIN_PREC_F32R)
+    hipLaunchKernelGGL(pack_g16_u8_kernel<0>, grid, dim3(256), 0, st, f0, f1, img_stride, w0, top,
+                       static_cast<uint4*>(g16->hi), (uint4*)nullptr, g16->img_stride, g16->g.plane, g16->g.wp, w);
+  else if (planes_of(prec) == 2)
+    hipLaunchKernelGGL(pack_g16_u8_kernel<2>, grid, dim3(256), 0, st, f0, f1, img_stride, w0, top,
+                       static_cast<uint4*>(g16->hi), static_cast<uint4*>(g16->lo), g16->img_stride, g16->g.plane,
+                       g16->g.wp, w);
+  else
+    hipLaunchKernelGGL(pack_g16_u8_kernel<1>, grid, dim3(256), 0, st, f0, f1, img_stride, w0, top,
+                       static_cast<uint4*>(g16->hi), (uint4*)nullptr, g16->img_stride, g16->g.plane, g16->g.wp, w);
   return hip_code(hipGetLastError());
 }

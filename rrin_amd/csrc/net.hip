@@ -285,6 +285,9 @@ struct HeadIO {
   const float* coef;
   float* out;
   float* raw;
+  // FINAL on the record layout: the 8-bit crop (rrin_head_h8_desc.out_u8); NULL: off
+  uint8_t* out_u8 = nullptr;
+  int h0 = 0, w0 = 0, top = 0;
 };
 
 // Debug taps (rrin_net_desc.taps): where U-Net u's raw output goes, or NULL.
@@ -593,6 +596,12 @@ int run_unet_h8(const Plan& p, const UNetSpec& u, const rrin_conv_weights* cw, c
   hd.out = io.out;
   hd.raw_out = io.raw;
   hd.status = p.status;
+  if (u.head_mode == RRIN_HEAD_FINAL && io.out_u8) {
+    hd.out_u8 = io.out_u8;
+    hd.h0 = io.h0;
+    hd.w0 = io.w0;
+    hd.top = io.top;
+  }
   if (u.head_mode == RRIN_HEAD_FLOW) hd.flow_raw = hview(p.FLOWRAW, 0, 4);
   if (p.dry) return 0;
   ProfScope ps(p.prof, st, RRIN_KIND_HEAD, 2.0 * 9 * 32 * u.out_ch * (double)x.g.h * x.g.w * p.n);
@@ -664,11 +673,10 @@ extern "C" int64_t rrin_net_scratch_bytes(const rrin_net_desc* d) {
   return scratch_bytes_of(d->n, d->h, d->w, d->prec, d->convs, kUNets, 4);
 }
 
-extern "C" int rrin_net_fwd(const rrin_net_desc* d, void* stream) {
-  if (!d || !d->i0 || !d->i1 || !d->out || !d->coef || !d->convs || !d->heads || !d->workspace)
-    return RRIN_E_ARG;
-  if (d->n < 1 || d->h < 16 || d->w < 16 || (d->h % 16) || (d->w % 16)) return RRIN_E_SHAPE;
-  if (d->prec < RRIN_PREC_F32 || d->prec > RRIN_PREC_F32R) return RRIN_E_ARG;
+// The schedule of both forwards: rrin_net_fwd (u8 NULL: fp32 NCHW frames d->i0 / i1 in, d->out
+// out) and rrin_net_u8_fwd (8-bit frames in and out; d->i0 / i1 / out unused; record layouts
+// only).  The callers have validated d (and u8).
+static int net_fwd_impl(const rrin_net_desc* d, const rrin_net_u8_desc* u8, void* stream) {
   Plan p;
   make_plan(d->n, d->h, d->w, d->prec, reinterpret_cast<char*>(d->workspace), p);
   if (d->workspace_bytes < p.bytes) return RRIN_E_WORKSPACE;
@@ -688,7 +696,8 @@ extern "C" int rrin_net_fwd(const rrin_net_desc* d, void* stream) {
       ProfScope ps(p.prof, st, RRIN_KIND_LAYOUT, 0.0);
       // x0, x1 into channels 0-5; channels 6-15 zeroed, so the first convs (cin 6/9/10)
       // can stage whole records (their tail channels are finite and meet zero weights)
-      rc = rrin_pack_g16_h8(d->i0, d->i1, d->n, &gall, d->prec, st);
+      rc = u8 ? rrin_pack_g16_u8_h8(u8->f0, u8->f1, u8->img_stride, d->n, u8->h0, u8->w0, &gall, d->prec, st)
+              : rrin_pack_g16_h8(d->i0, d->i1, d->n, &gall, d->prec, st);
       if (!rc && d->skip_flow) {
         const rrin_h8 fr = hview(p.FLOWRAW, 0, 4);
         rc = rrin_flow_tblend_h8(&fr, &gall, d->coef, d->n, d->prec, st);
@@ -696,8 +705,16 @@ extern "C" int rrin_net_fwd(const rrin_net_desc* d, void* stream) {
     }
     int k = 0;
     for (int u = 0; u < 4 && !rc; ++u) {
-      if (!(u == 0 && d->skip_flow))
-        rc = run_unet_h8(p, kUNets[u], d->convs + k, d->heads[u], HeadIO{d->coef, d->out, tap_of(d, kUNets[u])}, st);
+      if (!(u == 0 && d->skip_flow)) {
+        HeadIO io{d->coef, u8 ? nullptr : d->out, tap_of(d, kUNets[u])};
+        if (u8) {
+          io.out_u8 = u8->out_u8;
+          io.h0 = u8->h0;
+          io.w0 = u8->w0;
+          io.top = d->h - u8->h0;
+        }
+        rc = run_unet_h8(p, kUNets[u], d->convs + k, d->heads[u], io, st);
+      }
       k += convs_of(kUNets[u].depth);
     }
     return rc;
@@ -724,6 +741,26 @@ extern "C" int rrin_net_fwd(const rrin_net_desc* d, void* stream) {
     k += convs_of(kUNets[u].depth);
   }
   return rc;
+}
+
+extern "C" int rrin_net_fwd(const rrin_net_desc* d, void* stream) {
+  if (!d || !d->i0 || !d->i1 || !d->out || !d->coef || !d->convs || !d->heads || !d->workspace)
+    return RRIN_E_ARG;
+  if (d->n < 1 || d->h < 16 || d->w < 16 || (d->h % 16) || (d->w % 16)) return RRIN_E_SHAPE;
+  if (d->prec < RRIN_PREC_F32 || d->prec > RRIN_PREC_F32R) return RRIN_E_ARG;
+  return net_fwd_impl(d, nullptr, stream);
+}
+
+extern "C" int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream) {
+  if (!d || !d->f0 || !d->f1 || !d->out_u8) return RRIN_E_ARG;
+  const rrin_net_desc* nd = &d->net;
+  if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
+  // the record precisions only: the planar fp32 path has no 8-bit pack / store
+  if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
+  if (nd->n < 1 || d->h0 < 1 || d->w0 < 1) return RRIN_E_SHAPE;
+  if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  if (nd->n > 1 && d->img_stride < (int64_t)d->h0 * d->w0 * 3) return RRIN_E_ARG;
+  return net_fwd_impl(nd, d, stream);
 }
 
 // One U-Net alone (reference UNet.forward, unet.py:40-51): NCHW in -> NCHW out,

@@ -824,6 +824,92 @@ class RRINEngine:
                 off += n * c * h * w
         return out
 
+    def forward_u8(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, reuse_flow: bool = False,
+                   streams: int | None = None, split=None) -> torch.Tensor:
+        """One Net.forward on 8-bit frames of any size: ``f0`` / ``f1`` uint8 ``[N,H0,W0,3]`` (RGB
+        interleaved) on the engine's device -> uint8 ``[N,H0,W0,3]``.  Bit for bit
+        ``convert.load_frame`` -> :meth:`forward` -> ``convert.to_uint8_image``: the edge padding
+        to a multiple of 16 (top, right) and the /255 happen in the input pack
+        (rrin_pack_g16_u8_h8), the *255 truncation and the crop in the FINAL head's store
+        (rrin_net_u8_fwd); no fp32 frame exists on the device.  Every frame must be dense; a
+        uniform stride over dim 0 is taken as it is, so ``frames[:-1]`` and ``frames[1:]`` of one
+        stack need no copy.  Workspaces, scratch, the stream split, ``reuse_flow`` and the range
+        guard behave as in :meth:`forward` (with the guard set, the poisoned frames are 0 and
+        ``check_range`` raises); a kept raw Flow is only reused by the path that computed it."""
+        if self.prec == _lib.PREC_F32:
+            raise RuntimeError("forward_u8 needs a record-layout precision: 'fp32', 'fp32_split16' or 'fp16' "
+                               "(not 'fp32_planar')")
+        if f0.device != self.device or f1.device != self.device:
+            raise RuntimeError(f"inputs on {f0.device}/{f1.device}, model on {self.device}")
+        if f0.dtype != torch.uint8 or f1.dtype != torch.uint8:
+            raise TypeError("forward_u8 takes uint8 frames (forward takes float32)")
+        if f0.dim() != 4 or f0.shape != f1.shape or f0.shape[3] != 3:
+            raise ValueError(f"expected two [N,H0,W0,3] uint8 tensors, got {tuple(f0.shape)} / {tuple(f1.shape)}")
+        n, h0, w0, _ = f0.shape
+        if n < 1 or h0 < 1 or w0 < 1:
+            raise ValueError(f"empty frames: {tuple(f0.shape)}")
+        h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
+        frame = h0 * w0 * 3
+
+        def stride_of(f):  # bytes between frames, or None if f needs a copy
+            if f.stride(3) != 1 or (w0 > 1 and f.stride(2) != 3) or (h0 > 1 and f.stride(1) != 3 * w0):
+                return None
+            return frame if n == 1 else (f.stride(0) if f.stride(0) >= frame else None)
+
+        s0, s1 = stride_of(f0), stride_of(f1)
+        if s0 is None or s0 != s1:
+            f0, f1 = f0.contiguous(), f1.contiguous()
+            s0 = frame
+        if streams is None:
+            streams = default_streams(self.precision, n)
+        self._poll_range()
+        out = torch.empty((n, h0, w0, 3), dtype=torch.uint8, device=self.device)
+        coef = t_coefficients(t, n).to(self.device, non_blocking=True)
+        bounds = self._bounds(n, streams, split)
+        with torch.cuda.device(self.device):
+            main = torch.cuda.current_stream(self.device)
+            wss = [self.workspace(hi - lo, h, w, j) for j, (lo, hi) in enumerate(bounds)]
+            for j, (lo, hi) in enumerate(bounds):
+                self._net_scratch(hi - lo, h, w, j)
+            sides = self._side_streams(len(bounds) - 1)
+            for s in sides:
+                s.wait_stream(main)
+            for j, (lo, hi) in enumerate(bounds):
+                st = main if j == 0 else sides[j - 1]
+                self._forward_part_u8(f0[lo:hi], f1[lo:hi], s0, out[lo:hi], coef[lo:hi], h, w, j, wss[j], st,
+                                      reuse_flow)
+            for s in sides:
+                main.wait_stream(s)
+        return out
+
+    def _forward_part_u8(self, f0, f1, img_stride, out, coef, h, w, slot, ws, stream, reuse_flow):
+        n, h0, w0, _ = f0.shape
+        key = (n, h, w, slot)
+        skip = bool(reuse_flow) and self._flow_valid.get(key, False) == "u8"
+        sc = self._net_scratch(n, h, w, slot)
+        st = self._status_of(slot) if self.prec in (_lib.PREC_F16X3, _lib.PREC_F16) else None
+        d = _lib.NetU8Desc()
+        nd = d.net
+        nd.n, nd.h, nd.w = n, h, w
+        nd.coef = coef.data_ptr()
+        nd.convs = self.conv_table_for(n, h, w)
+        nd.heads = self.head_table
+        nd.workspace, nd.workspace_bytes = ws.data_ptr(), ws.numel()
+        nd.skip_flow = 1 if skip else 0
+        nd.prec = self.prec
+        if sc is not None:
+            nd.scratch, nd.scratch_bytes = sc.data_ptr(), sc.numel()
+        nd.status = st.data_ptr() if st is not None else None
+        d.f0, d.f1, d.img_stride = f0.data_ptr(), f1.data_ptr(), img_stride
+        d.out_u8 = out.data_ptr()
+        d.h0, d.w0 = h0, w0
+        _lib.check(self.lib.rrin_net_u8_fwd(C.byref(d), C.c_void_p(stream.cuda_stream)), "rrin_net_u8_fwd")
+        # the raw Flow kept in this workspace is that of 8-bit frames: forward(reuse_flow=True)
+        # must not take it for its own previous pair, nor forward_u8 the float path's
+        self._flow_valid[key] = "u8"
+        if st is not None:
+            self._queue_status(slot, stream)
+
     def unet_forward(self, x: torch.Tensor) -> torch.Tensor:
         """The single packed U-Net (engine built with one unit) on x [N,C,H,W]:
         rrin_unet_fwd, the reference UNet.forward (unet.py:40-51)."""
@@ -928,7 +1014,8 @@ class RRINEngine:
     def _forward_part(self, i0, i1, out, coef, slot, ws, stream, prof, reuse_flow, tapbuf=None):
         n, _, h, w = i0.shape
         key = (n, h, w, slot)
-        skip = bool(reuse_flow) and self._flow_valid.get(key, False)
+        # True: the kept raw Flow is that of this path's previous pair ("u8": of forward_u8's)
+        skip = bool(reuse_flow) and self._flow_valid.get(key, False) is True
         sc = self._net_scratch(n, h, w, slot)  # allocated (and zero-filled) before the fork
         st = self._status_of(slot) if self.prec in (_lib.PREC_F16X3, _lib.PREC_F16) else None
         d = self._net_desc(i0, i1, out, coef, ws, sc, st, skip, prof, tapbuf)
@@ -973,7 +1060,8 @@ class NetGraph:
     """One captured forward (RRINEngine.graph): static inputs ``i0`` / ``i1`` [n,3,h,w], output
     ``out``, device t coefficients.  :meth:`replay` writes the coefficients of t (only when t
     changes: a pinned host row, copied stream-ordered before the graph) and replays the graph on
-    the current stream; ``out`` then holds the frames until the next replay."""
+    the current stream; ``out`` then holds the frames until the next replay.  Float-only: the
+    8-bit frame path (``RRINEngine.forward_u8``) is eager, it is not captured."""
 
     def __init__(self, eng: RRINEngine, n: int, h: int, w: int, bounds):
         dev = eng.device

@@ -110,6 +110,23 @@ class Net(nn.Module):
         return [eng.forward(input0, input1, t, reuse_flow=(k > 0), streams=self.streams)
                 for k, t in enumerate(ts)]
 
+    def forward_u8(self, f0, f1, t=0.5):
+        """``forward`` on 8-bit frames of any size: uint8 ``[N,H0,W0,3]`` in and out, on the
+        device; bit for bit ``convert.load_frame`` -> ``forward`` -> ``convert.to_uint8_image``
+        (``RRINEngine.forward_u8``).  Inference-only; not for ``precision='fp32_planar'``."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("rrin_amd.Net.forward_u8 is inference-only: use torch.no_grad()")
+        return self.engine().forward_u8(f0, f1, t, streams=self.streams)
+
+    def interpolate_u8(self, f0, f1, ts):
+        """``[forward_u8(f0, f1, t) for t in ts]`` with the Flow U-Net computed once, as
+        :meth:`interpolate`."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("rrin_amd.Net.interpolate_u8 is inference-only: use torch.no_grad()")
+        eng = self.engine()
+        return [eng.forward_u8(f0, f1, t, reuse_flow=(k > 0), streams=self.streams)
+                for k, t in enumerate(ts)]
+
     def forward(self, input0, input1, t=0.5):
         if torch.is_grad_enabled() and (input0.requires_grad or input1.requires_grad or
                                         any(p.requires_grad for p in self.parameters())):
