@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define RRIN_ABI_VERSION 20
+#define RRIN_ABI_VERSION 21
 
 #define RRIN_OK 0
 #define RRIN_E_SHAPE (-1)     /* H or W not a multiple of 16, or N < 1          */
@@ -557,6 +557,30 @@ typedef struct rrin_net_u8_desc {
   int32_t h0, w0;
 } rrin_net_u8_desc;
 int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream);
+
+/* ---- Scene-cut / duplicate-frame gate of the 8-bit frame path (ABI 21) ------------------
+ * Three small kernels for the stream of a rrin_net_u8_fwd call, so that a caller can replace the
+ * interpolated frame of a pair that is a shot change or a repeated frame by one of its input
+ * frames without a host round trip.  Frames as for rrin_pack_g16_u8_h8: uint8 [n][h0][w0][3],
+ * every frame dense, img_stride bytes between frames of a stack (>= h0*w0*3, RRIN_E_ARG
+ * otherwise); f0 and f1 may be two views of one [n+1] stack, so a frame may start at any byte
+ * address.  Null pointers: RRIN_E_ARG; n, h0 or w0 < 1 (or n > 65535): RRIN_E_SHAPE.  Arguments
+ * are validated before any HIP call.
+ *
+ * rrin_pair_sad_u8: sad[p] = sum over the h0*w0*3 bytes of pair p of |f0[p] - f1[p]|, exact (an
+ * integer sum in 64 bits: the same value whatever the reduction order).  sad (8-byte aligned) is
+ * overwritten: its prior contents do not matter.
+ * rrin_gate_from_sad_u8: gate[p] = 1 if sad[p] == 0 (a duplicate), else cut_code if
+ * sad[p] > limit (a cut), else 0; cut_code is 1 or 2 (RRIN_E_ARG otherwise).
+ * rrin_gate_frames_u8: out uint8 [n][h0][w0][3] contiguous; gate[p] == 1 overwrites frame p of
+ * out with f0's frame p, gate[p] == 2 with f1's; any other code leaves every byte of the frame
+ * as it is (the pair's workgroups exit after reading the code). */
+int rrin_pair_sad_u8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0,
+                     int32_t w0, uint64_t* sad, void* stream);
+int rrin_gate_from_sad_u8(const uint64_t* sad, int32_t n, uint64_t limit, int32_t cut_code, int32_t* gate,
+                          void* stream);
+int rrin_gate_frames_u8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0,
+                        int32_t w0, const int32_t* gate, uint8_t* out, void* stream);
 
 /* ---- Training path (autograd): NCHW fp32 kernels ------------------------- */
 /* With autograd on (the reference trains through Net.forward, train.py:98, and

@@ -32,6 +32,10 @@ def build_parser():
     cv.add_argument("--batch", type=int, default=4, help="frame pairs per GPU call")
     cv.add_argument("--precision", default="fp32", choices=["fp32", "fp32_split16", "fp16"],
                     help="fp32: exact fp32 (default); fp32_split16: fp32-emulated with fp16 hi+lo x3; fp16")
+    cv.add_argument("--scene_threshold", type=float, default=None,
+                    help="scene gate, off by default: mean absolute byte difference (0-255) above which a pair "
+                         "is a shot change and yields the nearer input frame instead of a blend; repeated "
+                         "frames are passed through.  No value has been validated on real footage")
     return p
 
 

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librrin_hip.so")
 # A/B sessions only (tools/sessions/): another build of the same library, e.g. ab/librrin_hip_X.so
 if os.environ.get("RRIN_LIB_AB"):
@@ -211,6 +211,11 @@ SIGNATURES = {
                                       C.c_void_p]),
     "rrin_net_fwd": (C.c_int, [C.POINTER(NetDesc), C.c_void_p]),
     "rrin_net_u8_fwd": (C.c_int, [C.POINTER(NetU8Desc), C.c_void_p]),
+    "rrin_pair_sad_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                   C.c_void_p]),
+    "rrin_gate_from_sad_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rrin_gate_frames_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "rrin_unet_conv_count": (C.c_int64, [C.c_int32]),
     "rrin_unet_fwd": (C.c_int, [C.POINTER(UNetDesc), C.c_void_p]),
     "rrin_prof_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),
@@ -262,7 +267,11 @@ def lib():
                             "rrin_amd has no non-HIP fallback")
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            f = getattr(h, name)
+            f = getattr(h, name, None)
+            if f is None and os.environ.get("RRIN_LIB_AB"):
+                continue  # an A/B build from before the symbol was added
+            if f is None:
+                raise RRINError(f"{LIB_PATH} lacks {name}: rebuild it (`make -j16`)")
             f.restype = res
             f.argtypes = args
         # an A/B build of an earlier ABI whose changes since are appends only (RRIN_LIB_AB_ABI=16)

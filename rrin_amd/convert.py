@@ -26,6 +26,7 @@ Different (documented in DESIGN.md):
 """
 from __future__ import annotations
 
+import math
 import os
 import shutil
 import subprocess
@@ -107,6 +108,42 @@ def frames_float_to_u8(t: torch.Tensor, height: int, width: int) -> torch.Tensor
     return a.movedim(-3, -1).contiguous()
 
 
+def scene_limit(threshold, h0: int, w0: int) -> int:
+    """The largest sum of absolute byte differences of an H0 x W0 RGB pair that is not a cut:
+    ``floor(threshold * H0*W0*3)`` for a mean absolute byte difference ``threshold`` in [0, 255]."""
+    th = float(threshold)
+    if not 0.0 <= th <= 255.0:
+        raise ValueError(f"scene_threshold is a mean absolute byte difference in [0, 255], got {threshold!r}")
+    return math.floor(th * (h0 * w0 * 3))
+
+
+def scene_cut_code(t) -> int:
+    """Gate code of a cut pair at time t: 1 (the first frame) for t < 0.5, else 2 (the second)."""
+    if isinstance(t, torch.Tensor):
+        if t.numel() != 1:
+            raise ValueError("the scene gate takes one t for the whole batch")
+        t = t.item()
+    return 1 if float(t) < 0.5 else 2
+
+
+def scene_gate_codes(f0: torch.Tensor, f1: torch.Tensor, threshold, t) -> torch.Tensor:
+    """The scene gate's rule in plain torch, on any device: int32 ``[N]`` codes of the pairs of two
+    uint8 ``[N,H0,W0,3]`` stacks -- 1 for a duplicate (no byte differs), ``scene_cut_code(t)`` for a
+    cut (sum of absolute differences > ``scene_limit``), else 0.  ``Net.forward_u8(scene_threshold=)``
+    decides the same on the device."""
+    n, h0, w0 = f0.shape[0], f0.shape[1], f0.shape[2]
+    sad = (f0.to(torch.int64) - f1.to(torch.int64)).abs().reshape(n, -1).sum(1)
+    codes = torch.where(sad > scene_limit(threshold, h0, w0), scene_cut_code(t), 0)
+    return torch.where(sad == 0, 1, codes).to(torch.int32)
+
+
+def apply_gate_u8(out: torch.Tensor, f0: torch.Tensor, f1: torch.Tensor, codes: torch.Tensor) -> torch.Tensor:
+    """``out`` (uint8 ``[N,H0,W0,3]``) with the frames of code 1 replaced by ``f0``'s and those of
+    code 2 by ``f1``'s; every other code keeps the frame.  A new tensor."""
+    c = codes.to(out.device).view(-1, 1, 1, 1)
+    return torch.where(c == 1, f0, torch.where(c == 2, f1, out))
+
+
 def save_image(arr, path):
     from PIL import Image
     Image.fromarray(arr).save(path)
@@ -155,7 +192,7 @@ class _Reader:
 
 
 def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None, writers=4, log=print,
-                       rank=0, world=1, group=None, gather=True, u8="auto"):
+                       rank=0, world=1, group=None, gather=True, u8="auto", scene_threshold=None):
     """Interpolate every consecutive pair of frames in ``src`` into ``dest``.
 
     ``model`` is an ``rrin_amd.Net`` (anything with ``interpolate(i0, i1, ts)``
@@ -178,12 +215,24 @@ def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None,
     written as they are -- the padding, /255, *255 truncation and crop happen inside the model
     (``Net.forward_u8``: inside its kernels).  The files are the same bytes either way.
     ``"auto"``: when ``device`` is given and the model has ``interpolate_u8`` (and is not a Net
-    of the planar fp32 precision); ``True`` forces it, ``False`` forbids it."""
+    of the planar fp32 precision); ``True`` forces it, ``False`` forbids it.
+
+    ``scene_threshold`` (byte pipeline only; default off) switches the scene gate on: it is passed
+    to ``model.interpolate_u8(f0, f1, ts, scene_threshold=...)``, which returns a repeated frame's
+    pair as its first frame and a shot change's as the nearer input frame instead of a blend
+    (``Net.forward_u8``; the rule is ``scene_gate_codes``).  The model's ``last_gate`` codes of
+    every step -- those of ``ts[-1]``, where t >= 0.5 makes a cut code 2 and leaves 1 to the
+    duplicates -- come back with the step's output copy, and the final log line counts both.  No
+    threshold has been validated on real footage, hence no default."""
     if u8 == "auto":
         u8 = (device is not None and hasattr(model, "interpolate_u8")
               and getattr(model, "precision", None) != "fp32_planar")
     if u8 and not hasattr(model, "interpolate_u8"):
         raise ValueError("u8=True needs a model with interpolate_u8(f0, f1, ts)")
+    if scene_threshold is not None and not u8:
+        raise ValueError("scene_threshold needs the byte pipeline (u8): the gate works on 8-bit frames")
+    gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
+    gate_codes = []  # per step: (event or None, host int32 codes of its pairs)
     frames = list_frames(src)
     if len(frames) < 2:
         raise ValueError(f"need at least two frames in {src}")
@@ -239,7 +288,9 @@ def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None,
             if device is not None:
                 stack = stack.to(device, non_blocking=True)
             with torch.no_grad():
-                outs = model.interpolate_u8(stack[:-1], stack[1:], ts)
+                outs = model.interpolate_u8(stack[:-1], stack[1:], ts, **gate_kw)
+            if gate_kw:
+                gate_codes.append(_codes_to_host(getattr(model, "last_gate", None), nloc, device))
         elif nloc:
             i0 = torch.stack([g[1] for g in group_items[:-1]])
             i1 = torch.stack([g[1] for g in group_items[1:]])
@@ -278,8 +329,30 @@ def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None,
         f.result()
     if pool is not None:
         pool.shutdown(wait=True)
-    log(f"rank {rank}/{world}: interpolated pairs {lo}..{hi - 1} x {sf} frames in {time.time() - t0:.2f} s")
+    msg = f"rank {rank}/{world}: interpolated pairs {lo}..{hi - 1} x {sf} frames in {time.time() - t0:.2f} s"
+    if gate_kw:
+        cuts = dups = 0
+        for ev, codes in gate_codes:
+            if ev is not None:
+                ev.synchronize()
+            cuts += int((codes == 2).sum())
+            dups += int((codes == 1).sum())
+        msg += f"; scene gate (threshold {scene_threshold:g}): {cuts} cut pairs, {dups} duplicate pairs"
+    log(msg)
     return written[0]
+
+
+def _codes_to_host(codes, nloc, device):
+    """A step's gate codes on the host: (event of the copy or None, int32 [nloc])."""
+    if codes is None or tuple(codes.shape) != (nloc,):
+        raise ValueError("scene_threshold needs a model whose last_gate holds the step's codes")
+    if device is None:
+        return None, codes.to(torch.int32).clone()
+    host = torch.empty(nloc, dtype=torch.int32, pin_memory=True)
+    host.copy_(codes, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    return ev, host
 
 
 def _gather_step(outs, metas0, metas1, nloc, shards, s_, batch, sf, group, device, model_check=None):
@@ -431,7 +504,7 @@ def convert(args):
     net = load_net(args.model_name, dev, getattr(args, "precision", "fp32"))
     t = time.time()
     interpolate_folder(net, src, dest, args.sf, batch=getattr(args, "batch", 4), resume=args.resume, device=dev,
-                       rank=rank, world=world)
+                       rank=rank, world=world, scene_threshold=getattr(args, "scene_threshold", None))
     if world > 1:
         dist.barrier()
     print("end=", time.time() - t)

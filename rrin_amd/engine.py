@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .convert import scene_cut_code, scene_limit
 from .unet import _level_of
 
 UNET_ORDER = ("Flow", "refine_flow", "Mask", "final")
@@ -486,6 +487,7 @@ class RRINEngine:
         self._status = {}
         self._pending_status = []
         self._graphs = {}
+        self.last_gate = None
 
     def _init_h8(self, net):
         """Pack for the split-fp16 (F16X3) or fp16 (F16) path: [cob][16-ch chunk][tap][half][bm][8]
@@ -537,6 +539,9 @@ class RRINEngine:
         self._graphs = {}
         self._status = {}           # slot -> device int32 range flag (fp16-stored precisions)
         self._pending_status = []   # (event, pinned host copy) of flags not checked yet
+        self._gate_bufs = {}        # pairs -> (int64 sums, int32 codes) of the scene gate
+        self._sad_key = None        # (pairs, h0, w0, parts) whose sums the buffers hold
+        self.last_gate = None       # int32 device codes of the last gated forward_u8
 
     def _geom_splits(self, h, w):
         """Per body conv: the geometry rule's split-K slices at image size h x w (exact fp32
@@ -824,31 +829,19 @@ class RRINEngine:
                 off += n * c * h * w
         return out
 
-    def forward_u8(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, reuse_flow: bool = False,
-                   streams: int | None = None, split=None) -> torch.Tensor:
-        """One Net.forward on 8-bit frames of any size: ``f0`` / ``f1`` uint8 ``[N,H0,W0,3]`` (RGB
-        interleaved) on the engine's device -> uint8 ``[N,H0,W0,3]``.  Bit for bit
-        ``convert.load_frame`` -> :meth:`forward` -> ``convert.to_uint8_image``: the edge padding
-        to a multiple of 16 (top, right) and the /255 happen in the input pack
-        (rrin_pack_g16_u8_h8), the *255 truncation and the crop in the FINAL head's store
-        (rrin_net_u8_fwd); no fp32 frame exists on the device.  Every frame must be dense; a
-        uniform stride over dim 0 is taken as it is, so ``frames[:-1]`` and ``frames[1:]`` of one
-        stack need no copy.  Workspaces, scratch, the stream split, ``reuse_flow`` and the range
-        guard behave as in :meth:`forward` (with the guard set, the poisoned frames are 0 and
-        ``check_range`` raises); a kept raw Flow is only reused by the path that computed it."""
-        if self.prec == _lib.PREC_F32:
-            raise RuntimeError("forward_u8 needs a record-layout precision: 'fp32', 'fp32_split16' or 'fp16' "
-                               "(not 'fp32_planar')")
+    def _u8_frames(self, f0, f1, what):
+        """Checks two uint8 [N,H0,W0,3] frame stacks of ``what`` and returns them with the bytes
+        between their frames: every frame dense, a uniform stride over dim 0 taken as it is
+        (``frames[:-1]`` / ``frames[1:]`` of one stack need no copy), anything else copied."""
         if f0.device != self.device or f1.device != self.device:
             raise RuntimeError(f"inputs on {f0.device}/{f1.device}, model on {self.device}")
         if f0.dtype != torch.uint8 or f1.dtype != torch.uint8:
-            raise TypeError("forward_u8 takes uint8 frames (forward takes float32)")
+            raise TypeError(f"{what} takes uint8 frames (forward takes float32)")
         if f0.dim() != 4 or f0.shape != f1.shape or f0.shape[3] != 3:
             raise ValueError(f"expected two [N,H0,W0,3] uint8 tensors, got {tuple(f0.shape)} / {tuple(f1.shape)}")
         n, h0, w0, _ = f0.shape
         if n < 1 or h0 < 1 or w0 < 1:
             raise ValueError(f"empty frames: {tuple(f0.shape)}")
-        h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
         frame = h0 * w0 * 3
 
         def stride_of(f):  # bytes between frames, or None if f needs a copy
@@ -860,12 +853,72 @@ class RRINEngine:
         if s0 is None or s0 != s1:
             f0, f1 = f0.contiguous(), f1.contiguous()
             s0 = frame
+        return f0, f1, s0
+
+    def forward_u8(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, reuse_flow: bool = False,
+                   streams: int | None = None, split=None, scene_threshold=None, gate=None) -> torch.Tensor:
+        """One Net.forward on 8-bit frames of any size: ``f0`` / ``f1`` uint8 ``[N,H0,W0,3]`` (RGB
+        interleaved) on the engine's device -> uint8 ``[N,H0,W0,3]``.  Bit for bit
+        ``convert.load_frame`` -> :meth:`forward` -> ``convert.to_uint8_image``: the edge padding
+        to a multiple of 16 (top, right) and the /255 happen in the input pack
+        (rrin_pack_g16_u8_h8), the *255 truncation and the crop in the FINAL head's store
+        (rrin_net_u8_fwd); no fp32 frame exists on the device.  Every frame must be dense; a
+        uniform stride over dim 0 is taken as it is, so ``frames[:-1]`` and ``frames[1:]`` of one
+        stack need no copy.  Workspaces, scratch, the stream split, ``reuse_flow`` and the range
+        guard behave as in :meth:`forward` (with the guard set, the poisoned frames are 0 and
+        ``check_range`` raises); a kept raw Flow is only reused by the path that computed it.
+
+        The scene gate (off unless one of the two is given; they exclude each other):
+
+        ``scene_threshold``: a mean absolute byte difference in [0, 255].  A pair whose frames are
+        equal (a repeated frame) returns ``f0``'s frame; a pair whose sum of absolute differences
+        exceeds ``floor(scene_threshold * H0*W0*3)`` (a shot change) returns the nearer input
+        frame, ``f0``'s for t < 0.5 and ``f1``'s from t = 0.5 on (``scene_cut_code``; one t for the
+        batch).  Three small kernels per forward part, on the part's stream after its forward:
+        rrin_pair_sad_u8, rrin_gate_from_sad_u8, rrin_gate_frames_u8; the sums and codes live in
+        cached device buffers and nothing comes back to the host.  With ``reuse_flow=True`` the
+        sums of the previous gated call of the same batch are reused as the Flow is.
+        ``gate``: an int32 device tensor ``[N]`` of explicit codes (1: ``f0``'s frame, 2: ``f1``'s,
+        anything else: the interpolated frame); only the copy kernel runs.
+        The codes of the last gated call stay in :attr:`last_gate` until the next one.
+
+        The network still runs for a gated pair and its frame is overwritten afterwards:
+        skipping it would need the codes on the host, a device-to-host sync per step.  The range
+        guard does not look at the gate: a gated frame is the copied input even when its pair
+        overflowed, and ``check_range`` still raises."""
+        if self.prec == _lib.PREC_F32:
+            raise RuntimeError("forward_u8 needs a record-layout precision: 'fp32', 'fp32_split16' or 'fp16' "
+                               "(not 'fp32_planar')")
+        f0, f1, s0 = self._u8_frames(f0, f1, "forward_u8")
+        n, h0, w0, _ = f0.shape
+        h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
+        if scene_threshold is not None and gate is not None:
+            raise ValueError("scene_threshold and gate exclude each other")
+        limit = cut_code = None
+        if scene_threshold is not None:
+            limit, cut_code = scene_limit(scene_threshold, h0, w0), scene_cut_code(t)
+        if gate is not None:
+            if (not isinstance(gate, torch.Tensor) or gate.dtype != torch.int32 or gate.device != self.device
+                    or tuple(gate.shape) != (n,)):
+                raise ValueError(f"gate must be an int32 tensor [{n}] on {self.device}")
+            gate = gate.contiguous()
         if streams is None:
             streams = default_streams(self.precision, n)
         self._poll_range()
         out = torch.empty((n, h0, w0, 3), dtype=torch.uint8, device=self.device)
         coef = t_coefficients(t, n).to(self.device, non_blocking=True)
         bounds = self._bounds(n, streams, split)
+        sad = None
+        if limit is not None:
+            # the sums belong to the batch and its split: kept for the next t of the same pairs
+            skey = (n, h0, w0, tuple(bounds))
+            have_sad = bool(reuse_flow) and self._sad_key == skey
+            sad, gate = self._gate_buffers(n)
+            self._sad_key = skey
+        else:
+            self._sad_key = None  # the next call's pairs need not be these
+        if gate is not None:
+            self.last_gate = gate
         with torch.cuda.device(self.device):
             main = torch.cuda.current_stream(self.device)
             wss = [self.workspace(hi - lo, h, w, j) for j, (lo, hi) in enumerate(bounds)]
@@ -878,9 +931,46 @@ class RRINEngine:
                 st = main if j == 0 else sides[j - 1]
                 self._forward_part_u8(f0[lo:hi], f1[lo:hi], s0, out[lo:hi], coef[lo:hi], h, w, j, wss[j], st,
                                       reuse_flow)
+                if gate is None:
+                    continue
+                sp = C.c_void_p(st.cuda_stream)
+                p0, p1, m = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), hi - lo
+                if sad is not None:
+                    if not have_sad:
+                        _lib.check(self.lib.rrin_pair_sad_u8(p0, p1, s0, m, h0, w0, sad[lo:hi].data_ptr(), sp),
+                                   "rrin_pair_sad_u8")
+                    _lib.check(self.lib.rrin_gate_from_sad_u8(sad[lo:hi].data_ptr(), m, limit, cut_code,
+                                                              gate[lo:hi].data_ptr(), sp), "rrin_gate_from_sad_u8")
+                _lib.check(self.lib.rrin_gate_frames_u8(p0, p1, s0, m, h0, w0, gate[lo:hi].data_ptr(),
+                                                        out[lo:hi].data_ptr(), sp), "rrin_gate_frames_u8")
             for s in sides:
                 main.wait_stream(s)
         return out
+
+    def _gate_buffers(self, n: int):
+        """The cached device buffers of the scene gate for a batch of n pairs: int64 sums of
+        absolute differences and int32 codes (a few bytes per pair, kept like the workspaces)."""
+        b = self._gate_bufs.get(n)
+        if b is None:
+            if len(self._gate_bufs) >= 8:
+                self._gate_bufs.clear()
+            b = (torch.empty(n, dtype=torch.int64, device=self.device),
+                 torch.empty(n, dtype=torch.int32, device=self.device))
+            self._gate_bufs[n] = b
+        return b
+
+    def pair_stats_u8(self, f0: torch.Tensor, f1: torch.Tensor) -> torch.Tensor:
+        """The sum of absolute byte differences of every pair of two uint8 ``[N,H0,W0,3]`` stacks
+        (as :meth:`forward_u8` takes them): a fresh int64 device tensor ``[N]``, exact, enqueued
+        on the current stream (rrin_pair_sad_u8) -- for a caller with its own rule for ``gate``."""
+        f0, f1, s0 = self._u8_frames(f0, f1, "pair_stats_u8")
+        n, h0, w0, _ = f0.shape
+        sad = torch.empty(n, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream(self.device)
+            _lib.check(self.lib.rrin_pair_sad_u8(f0.data_ptr(), f1.data_ptr(), s0, n, h0, w0, sad.data_ptr(),
+                                                 C.c_void_p(st.cuda_stream)), "rrin_pair_sad_u8")
+        return sad
 
     def _forward_part_u8(self, f0, f1, img_stride, out, coef, h, w, slot, ws, stream, reuse_flow):
         n, h0, w0, _ = f0.shape

@@ -110,22 +110,45 @@ class Net(nn.Module):
         return [eng.forward(input0, input1, t, reuse_flow=(k > 0), streams=self.streams)
                 for k, t in enumerate(ts)]
 
-    def forward_u8(self, f0, f1, t=0.5):
+    def forward_u8(self, f0, f1, t=0.5, scene_threshold=None, gate=None):
         """``forward`` on 8-bit frames of any size: uint8 ``[N,H0,W0,3]`` in and out, on the
         device; bit for bit ``convert.load_frame`` -> ``forward`` -> ``convert.to_uint8_image``
-        (``RRINEngine.forward_u8``).  Inference-only; not for ``precision='fp32_planar'``."""
+        (``RRINEngine.forward_u8``).  Inference-only; not for ``precision='fp32_planar'``.
+
+        The scene gate is off unless ``scene_threshold`` (a mean absolute byte difference in
+        [0, 255]) or ``gate`` (an int32 device tensor ``[N]`` of codes) is given, never both: a
+        repeated frame returns ``f0``, a shot change the nearer input frame (``f1`` from t = 0.5
+        on), decided and applied on the device (``RRINEngine.forward_u8``).  The network still
+        runs for a gated pair: skipping it would need a host sync.  No threshold has been
+        validated on real footage; :attr:`last_gate` reports what a call decided."""
         if torch.is_grad_enabled():
             raise RuntimeError("rrin_amd.Net.forward_u8 is inference-only: use torch.no_grad()")
-        return self.engine().forward_u8(f0, f1, t, streams=self.streams)
+        return self.engine().forward_u8(f0, f1, t, streams=self.streams, scene_threshold=scene_threshold,
+                                        gate=gate)
 
-    def interpolate_u8(self, f0, f1, ts):
+    def interpolate_u8(self, f0, f1, ts, scene_threshold=None, gate=None):
         """``[forward_u8(f0, f1, t) for t in ts]`` with the Flow U-Net computed once, as
-        :meth:`interpolate`."""
+        :meth:`interpolate`; with ``scene_threshold`` the pairs' sums of absolute differences are
+        computed once too (the cut code depends on t, so :attr:`last_gate` is that of ``ts[-1]``)."""
         if torch.is_grad_enabled():
             raise RuntimeError("rrin_amd.Net.interpolate_u8 is inference-only: use torch.no_grad()")
         eng = self.engine()
-        return [eng.forward_u8(f0, f1, t, reuse_flow=(k > 0), streams=self.streams)
+        return [eng.forward_u8(f0, f1, t, reuse_flow=(k > 0), streams=self.streams,
+                               scene_threshold=scene_threshold, gate=gate)
                 for k, t in enumerate(ts)]
+
+    def pair_stats_u8(self, f0, f1):
+        """int64 device tensor ``[N]``: the sum of absolute byte differences of every pair of two
+        uint8 ``[N,H0,W0,3]`` stacks, exact (rrin_pair_sad_u8) -- what ``scene_threshold`` compares
+        with ``floor(threshold * H0*W0*3)``, for callers who pass their own ``gate``."""
+        return self.engine().pair_stats_u8(f0, f1)
+
+    @property
+    def last_gate(self):
+        """The int32 device codes ``[N]`` of the last gated ``forward_u8`` (0: interpolated, 1:
+        ``f0``'s frame, 2: ``f1``'s), or None; with ``scene_threshold`` a cached buffer that the
+        next gated call overwrites (stream-ordered): clone it to keep it."""
+        return self._engine.last_gate if self._engine is not None else None
 
     def forward(self, input0, input1, t=0.5):
         if torch.is_grad_enabled() and (input0.requires_grad or input1.requires_grad or

@@ -12,6 +12,11 @@ The two chains are timed alternately (``--rounds`` windows of ``--steps`` steps 
 ``--warmup`` steps of both); every window is one pair of events around its steps.  Prints one
 JSON line.  Not a test; needs a GPU.
 
+``--scene-threshold X`` adds a third chain to every round: the byte chain with the scene gate on
+(``interpolate_u8(..., scene_threshold=X)``).  The synthetic frames are unrelated random bytes
+(mean absolute difference about 85), so any X below that gates -- and copies -- every frame, the
+gate's dearest case; X = 255 gates none and times the sums alone.
+
     python tools/u8_io_bench.py --height 720 --width 1280 --pairs 4 --sf 1 --precision fp32
 """
 from __future__ import annotations
@@ -67,6 +72,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--host-reps", type=int, default=10)
+    ap.add_argument("--scene-threshold", type=float, default=None,
+                    help="also time the byte chain with the scene gate at this threshold")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("u8_io_bench needs a ROCm device")
@@ -87,6 +94,11 @@ def main():
     def step_u8():
         s = stack8.to(dev, non_blocking=True)
         for o, h in zip(net.interpolate_u8(s[:-1], s[1:], ts), out8):
+            h.copy_(o, non_blocking=True)
+
+    def step_u8_gated():
+        s = stack8.to(dev, non_blocking=True)
+        for o, h in zip(net.interpolate_u8(s[:-1], s[1:], ts, scene_threshold=a.scene_threshold), out8):
             h.copy_(o, non_blocking=True)
 
     def step_f32():
@@ -112,9 +124,16 @@ def main():
         net.check_range()
         same = all(np.array_equal(o8.numpy(), cv.frames_float_to_u8(o32, h0, w0).numpy())
                    for o8, o32 in zip(out8, out32))
-        ms8, ms32 = [], []
+        ms8, ms32, ms8g = [], [], []
+        gated = None
+        if a.scene_threshold is not None:
+            step_u8_gated()
+            torch.cuda.synchronize(dev)
+            gated = [int((net.last_gate != 0).sum())]
         for _ in range(a.rounds):
             ms8.append(window(step_u8))
+            if a.scene_threshold is not None:
+                ms8g.append(window(step_u8_gated))
             ms32.append(window(step_f32))
     load_s, store_s = host_cost(h0, w0, a.host_reps)
     frame8, frame32 = h0 * w0 * 3, int(i0h[0].numel()) * 4
@@ -126,6 +145,8 @@ def main():
         "h2d_bytes_per_step": {"byte": (n + 1) * frame8, "float": 2 * n * frame32},
         "d2h_bytes_per_step": {"byte": n * a.sf * frame8, "float": n * a.sf * frame32},
         "outputs_identical": bool(same),
+        **({"scene_threshold": a.scene_threshold, "byte_chain_gated_ms": [round(x, 3) for x in ms8g],
+            "gated_pairs_per_step": gated[0]} if gated else {}),
         "host_ms_per_frame_one_core": {"load_frame_pad_float_div": round(load_s * 1e3, 3),
                                        "to_uint8_image": round(store_s * 1e3, 3)},
     }
