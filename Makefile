@@ -57,8 +57,8 @@ $(OBJ_DIR)/%.o: $(SRC_DIR)/%.hip $(HDRS)
 $(LIB): $(OBJS) $(ISA_OK)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $@ $(OBJS)
 
-LAB_SRCS := $(SRC_DIR)/conv_f16.hip $(SRC_DIR)/conv_block0.hip $(SRC_DIR)/conv_wino.hip $(SRC_DIR)/conv_winoc.hip $(SRC_DIR)/conv_winoc42.hip $(SRC_DIR)/conv_winoh.hip
-$(LAB): $(LAB_SRCS) $(SRC_DIR)/common.hpp include/rrin_hip.h
+LAB_SRCS := $(SRC_DIR)/conv_h8.hip $(SRC_DIR)/conv_block0.hip $(SRC_DIR)/conv_wino.hip $(SRC_DIR)/conv_winoc.hip $(SRC_DIR)/conv_winoc42.hip $(SRC_DIR)/conv_winoh.hip
+$(LAB): $(LAB_SRCS) $(HDRS)
 	$(HIPCC) $(CXXFLAGS) -DRRIN_LAB -shared -o $@ $(LAB_SRCS)
 
 $(LAB32): $(SRC_DIR)/conv_mfma.hip $(SRC_DIR)/common.hpp include/rrin_hip.h

@@ -197,11 +197,11 @@ __device__ inline float warp_apply_f(const WarpTaps& t, F get) {
 }
 #pragma clang fp contract(on)
 
-// ---- record-layout conv kernels (conv_f16.hip, conv_wino.hip) -------------
+// ---- record-layout conv kernels (conv_h8.hip, conv_wino.hip) --------------
 // LeakyReLU for 0 <= slope <= 1 (h8_prepare checks): one mul + one max
 __device__ inline float leaky(float t, float slope) { return fmaxf(t, t * slope); }
 
-// sub-pixel ring fix-up (conv_f16.hip edge_fix_*): tiles of kFixPx line pixels x kFixCo output
+// sub-pixel ring fix-up (conv_h8.hip edge_fix_*): tiles of kFixPx line pixels x kFixCo output
 // channels, input channels staged kFixCi at a time
 constexpr int kFixPx = 32, kFixCo = 32, kFixCi = 32;
 
@@ -306,7 +306,7 @@ __device__ inline void dma16(const uint4* src, uint4* lds_wave_base) {
 // the record-layout table (F32R only), its LDS bytes per block and launcher.
 constexpr size_t kWinoLds = (size_t)(2 * 704 + 2 * 16 * 2 * 32) * 16;
 int launch_wino(const ConvH8Args& a, int epi, hipStream_t st);
-// zero channels [c0, c1) of a record-layout view (conv_f16.hip)
+// zero channels [c0, c1) of a record-layout view (glue_h8.hip)
 int clear_channels_h8(const rrin_h8* v, int32_t n, int32_t c0, int32_t c1, int32_t prec, hipStream_t st);
 // cfg 18's tile on 8 waves of 4 accumulators (<= 128 VGPRs: 4 waves per SIMD),
 // two stages of [raw 680 | U 1024] records (three in A/B builds: two blocks per
@@ -325,7 +325,7 @@ int launch_winoc(const ConvH8Args& a, int epi, int ct, hipStream_t st);
 constexpr size_t kWinoC42Lds = (size_t)4160 * 16;
 int launch_winoc42(const ConvH8Args& a, int epi, hipStream_t st);
 // whether rrin_conv3x3_h8_fwd runs a ring_full fix-up inside the conv's launch for tile config
-// cfg, cin input channels and precision prec (else it launches it after the conv) -- conv_f16.hip
+// cfg, cin input channels and precision prec (else it launches it after the conv) -- conv_h8.hip
 bool ring_in_launch_ok(int cfg, int cin, int prec);
 // the kind-6 tile at fp16 (conv_winoh.hip): H8 records, v_mfma_f32_32x32x16_f16, packed-f16
 // input transform; same LDS as kWinoCLds1

@@ -54,7 +54,7 @@ __device__ inline void b0_dma16(__amdgpu_buffer_rsrc_t rs, uint4* lds_wave_base,
 __device__ inline b0h8 b0_load16(__amdgpu_buffer_rsrc_t rs, uint32_t voff, int soff) {
   return __builtin_bit_cast(b0h8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
 }
-// 4 fp32 values -> 4 RNE fp16 values (one 8-B record half), as split4 of conv_f16.hip
+// 4 fp32 values -> 4 RNE fp16 values (one 8-B record half), as split4 of h8.hpp
 __device__ inline uint2 b0_pack4(const float* v) {
   const b0h2 h0 = __builtin_convertvector((b0f2){v[0], v[1]}, b0h2);
   const b0h2 h1 = __builtin_convertvector((b0f2){v[2], v[3]}, b0h2);

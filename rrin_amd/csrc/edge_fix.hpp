@@ -1,9 +1,9 @@
 // Device side of the sub-pixel up conv's ring fix-up, shared by the standalone fix-up kernel
-// (conv_f16.hip edge_fix_h8_kernel) and the conv tiles that run it in extra workgroups of their
+// (conv_h8.hip edge_fix_h8_kernel) and the conv tiles that run it in extra workgroups of their
 // own launch (rrin_conv_h8_desc.ring_full: conv3x3_h8_kernel, conv3x3_winoc_kernel), plus the
-// record-layout helpers both need (fp16 hi / lo' split, packed-FP32 experiment switches).
+// packed-FP32 experiment switches both need.
 #pragma once
-#include "common.hpp"
+#include "h8.hpp"
 
 namespace rrin {
 
@@ -38,21 +38,6 @@ __device__ inline void pk_fma4(f32x2& a01, f32x2& a23, float4 w, float u) {
 #endif
 }
 #endif
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-
-
-// lo halves are stored pre-scaled by 2^11 so they stay normal fp16 for any
-// |v| >= ~1e-4 (unscaled, v - hi ~ 2^-12 v would be subnormal below |v| = 0.125
-// and lose its bits): v = hi + lo * 2^-11.
-constexpr float kLoScale = 2048.0f;
-constexpr float kF16Max = 65504.0f;  // largest finite fp16
-constexpr float kLoUnscale = 1.0f / 2048.0f;
-__device__ inline _Float16 lo_of(float v, _Float16 hi) { return (_Float16)((v - (float)hi) * kLoScale); }
-__device__ inline float join(_Float16 hi, _Float16 lo) { return fmaf((float)lo, kLoUnscale, (float)hi); }
 
 // ---- sub-pixel up conv: ring fix-up -------------------------------------------
 // The EPI_SUBPIXEL conv equals conv3x3 over the upsampled image U with edge-
@@ -416,6 +401,5 @@ __device__ inline void edge_fix_body(const EdgeFixArgs& a, const int bx, const i
     }
   }
 }
-
 
 }  // namespace rrin

@@ -15,6 +15,7 @@
 // xt1 10-12 | xt2 13-15].  Every fused update is pointwise (reads and writes of
 // g16 at the thread's own pixel only), so in-place writes are race-free.
 #include "common.hpp"
+#include "net_glue.hpp"
 
 namespace rrin {
 
@@ -111,9 +112,11 @@ __global__ void __launch_bounds__(256) head_kernel(HeadArgs a) {
       float* fr = a.flow_raw + img * a.fr_img + (int64_t)(y + 1) * a.fr_wp + x + kPadLeft;
       for (int k = 0; k < 4; ++k) fr[k * a.fr_plane] = acc[k];
     }
+    float f0[2], f1[2];
+    flow_blend(cf, acc, f0, f1);
     for (int k = 0; k < 2; ++k) {
-      G(6 + k) = cf[0] * acc[k] + cf[1] * acc[2 + k];
-      G(8 + k) = cf[2] * acc[k] - cf[3] * acc[2 + k];
+      G(6 + k) = f0[k];
+      G(8 + k) = f1[k];
     }
   } else if constexpr (MODE == RRIN_HEAD_REFINE) {
 #pragma clang fp contract(off)
@@ -133,20 +136,19 @@ __global__ void __launch_bounds__(256) head_kernel(HeadArgs a) {
     }
   } else if constexpr (MODE == RRIN_HEAD_MASK) {
 #pragma clang fp contract(off)
-    const float m0 = 1.0f / (1.0f + expf(-acc[0]));
-    const float m1 = 1.0f / (1.0f + expf(-acc[1]));
-    const float w1 = cf[4] * m0, w2 = cf[5] * m1;
-    const float den = w1 + w2 + 1e-8f;
+    const float xt1[3] = {G(10), G(11), G(12)}, xt2[3] = {G(13), G(14), G(15)};
+    float o[3];
+    mask_blend(cf, acc[0], acc[1], xt1, xt2, o);
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) G(6 + ch) = (w1 * G(10 + ch) + w2 * G(13 + ch)) / den;
+    for (int ch = 0; ch < 3; ++ch) G(6 + ch) = o[ch];
   } else {  // FINAL
 #pragma clang fp contract(off)
+    const float base[3] = {G(6), G(7), G(8)};
+    float q[3];
+    final_clamp(acc, base, q);
     float* o = a.out + ((int64_t)img * 3) * a.h * a.w_ + (int64_t)y * a.w_ + x;
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const float v = acc[ch] + G(6 + ch);
-      o[(int64_t)ch * a.h * a.w_] = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);  // NaN passes
-    }
+    for (int ch = 0; ch < 3; ++ch) o[(int64_t)ch * a.h * a.w_] = q[ch];
   }
 }
 
@@ -213,11 +215,12 @@ __global__ void flow_tblend_kernel(const float* __restrict__ fr, int64_t fr_img,
   const float* f = fr + img * fr_img + (int64_t)(y + 1) * fr_wp + x + kPadLeft;
   float* gp = g + img * g_img + (int64_t)(y + 1) * g_wp + x + kPadLeft;
   const float* cf = coef + img * 8;
+  const float raw[4] = {f[0], f[fr_plane], f[2 * fr_plane], f[3 * fr_plane]};
+  float ft0[2], ft1[2];
+  flow_blend(cf, raw, ft0, ft1);
   for (int k = 0; k < 2; ++k) {
-#pragma clang fp contract(off)
-    const float f01 = f[k * fr_plane], f10 = f[(2 + k) * fr_plane];
-    gp[(6 + k) * g_plane] = cf[0] * f01 + cf[1] * f10;
-    gp[(8 + k) * g_plane] = cf[2] * f01 - cf[3] * f10;
+    gp[(6 + k) * g_plane] = ft0[k];
+    gp[(8 + k) * g_plane] = ft1[k];
   }
 }
 
