@@ -5,7 +5,7 @@ import numpy as np
 import torch
 
 from rrin_amd import _lib
-from rrin_amd.pp import PPTensor
+from rrin_amd.pp import H8Tensor, PPTensor
 
 
 def stream(dev):
@@ -54,7 +54,7 @@ def conv(src: PPTensor, w, b, cfg, *, src_off=0, dst=None, dst_off=0, upsample=F
     return dst, pool
 
 
-def head(src: PPTensor, g16: PPTensor, w, b, mode, coef=None, out=None):
+def head(src: PPTensor, g16: PPTensor, w, b, mode, coef=None, out=None, flow_raw: PPTensor = None, raw_out=None):
     dev = src.t.device
     d = _lib.HeadDesc()
     d.n, d.cin, d.cout, d.mode = src.n, 32, w.shape[0], mode
@@ -67,5 +67,36 @@ def head(src: PPTensor, g16: PPTensor, w, b, mode, coef=None, out=None):
         d.coef = coef.data_ptr()
     if out is not None:
         d.out = out.data_ptr()
+    if flow_raw is not None:
+        d.flow_raw = flow_raw.view(0, 4)
+    if raw_out is not None:
+        d.raw_out = raw_out.data_ptr()
     _lib.check(_lib.lib().rrin_head_fwd(C.byref(d), stream(dev)), "rrin_head_fwd")
     torch.cuda.synchronize(dev)
+
+
+def head_h8(src: H8Tensor, dst: H8Tensor, w, b, mode, coef=None, out=None, prec=_lib.PREC_F16X3, *,
+            flow_raw: H8Tensor = None, raw_out=None, status=None, out_u8=None, crop=None, rc=False):
+    """Run rrin_head_h8_fwd on the record layout.  crop = (h0, w0, top) of out_u8; rc=True
+    returns the entry's code instead of raising on it."""
+    dev = src.hi.device
+    w_d = w.detach().float().contiguous().to(dev)
+    b_d = b.detach().float().contiguous().to(dev)
+    d = _lib.HeadH8Desc()
+    d.n, d.cin, d.cout, d.mode, d.prec = src.n, 32, w.shape[0], mode, prec
+    d.src, d.g16 = src.view(0, 32), dst.view(0, dst.c)
+    d.w, d.bias = w_d.data_ptr(), b_d.data_ptr()
+    d.coef = coef.data_ptr() if coef is not None else None
+    d.out = out.data_ptr() if out is not None else None
+    if flow_raw is not None:
+        d.flow_raw = flow_raw.view(0, 4)
+    d.raw_out = raw_out.data_ptr() if raw_out is not None else None
+    d.status = status.data_ptr() if status is not None else None
+    d.out_u8 = out_u8.data_ptr() if out_u8 is not None else None
+    if crop is not None:
+        d.h0, d.w0, d.top = crop
+    code = _lib.lib().rrin_head_h8_fwd(C.byref(d), stream(dev))
+    torch.cuda.synchronize(dev)
+    if rc:
+        return code
+    _lib.check(code, "rrin_head_h8_fwd")

@@ -564,20 +564,6 @@ def test_h8_subpixel_many_tiles_per_block(gpu, prec):
                                    err_msg=f"cfg {cfg}")
 
 
-def head_h8(src: H8Tensor, dst: H8Tensor, w, b, mode, coef=None, out=None, prec=X3):
-    dev = src.hi.device
-    w_d = w.detach().float().contiguous().to(dev)
-    b_d = b.detach().float().contiguous().to(dev)
-    d = _lib.HeadH8Desc()
-    d.n, d.cin, d.cout, d.mode, d.prec = src.n, 32, w.shape[0], mode, prec
-    d.src, d.g16 = src.view(0, 32), dst.view(0, dst.c)
-    d.w, d.bias = w_d.data_ptr(), b_d.data_ptr()
-    d.coef = coef.data_ptr() if coef is not None else None
-    d.out = out.data_ptr() if out is not None else None
-    _lib.check(_lib.lib().rrin_head_h8_fwd(C.byref(d), H.stream(dev)), "rrin_head_h8_fwd")
-    torch.cuda.synchronize(dev)
-
-
 @pytest.mark.parametrize("prec", PRECS)
 @pytest.mark.parametrize("cout", [2, 3, 4])
 @pytest.mark.parametrize("n,h,w,scale", [(2, 40, 72, 1.0), (1, 20, 50, 1e-3), (3, 16, 32, 300.0)])
@@ -588,7 +574,7 @@ def test_h8_head_plain(gpu, prec, cout, n, h, w, scale):
     wt, b = keyed_conv(32, cout, "headh8")
     wt = wt * scale
     dst = H8Tensor(n, 16, h, w, gpu, prec)
-    head_h8(H8Tensor.from_nchw(x, prec), dst, wt, b, _lib.HEAD_PLAIN, prec=prec)
+    H.head_h8(H8Tensor.from_nchw(x, prec), dst, wt, b, _lib.HEAD_PLAIN, prec=prec)
     ref = ref_conv(x, wt, b)
     tol = {X3: dict(rtol=1e-4, atol=1e-4 * max(scale, 1.0)), R32: dict(rtol=1e-5, atol=1e-5 * max(scale, 1.0)),
            F16: dict(rtol=2e-2, atol=2e-2 * max(scale, 1.0))}[prec]
