@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define RRIN_ABI_VERSION 21
+#define RRIN_ABI_VERSION 22
 
 #define RRIN_OK 0
 #define RRIN_E_SHAPE (-1)     /* H or W not a multiple of 16, or N < 1          */
@@ -394,6 +394,51 @@ int rrin_pack_g16_h8(const float* i0, const float* i1, int32_t n, const rrin_h8*
  * bitwise those rrin_pack_g16_h8 writes from the padded fp32 NCHW frames. */
 int rrin_pack_g16_u8_h8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0,
                         int32_t w0, const rrin_h8* g16, int32_t prec, void* stream);
+
+/* ---- 8-bit YUV 4:2:0 frames (ABI 22) -------------------------------------------------------
+ * One stack of 4:2:0 frames: a luma plane of h0 x w0 bytes and two chroma planes of h0/2 x w0/2
+ * samples, one sample per 2x2 block of pixels.  NV12 (one interleaved UV plane): v == u + 1,
+ * c_step 2; I420 (planar): c_step 1.  h0 and w0 are even. */
+typedef struct rrin_yuv420 {
+  const uint8_t *y, *u, *v;    /* frame 0; NV12: v == u + 1 */
+  int64_t img_stride;          /* bytes between frames, the same for all three pointers */
+  int32_t y_pitch, c_pitch;    /* bytes between rows (>= w0, >= (w0/2)*c_step) */
+  int32_t c_step, pad_;        /* bytes between chroma samples of a row: 2 NV12, 1 I420 */
+} rrin_yuv420;
+
+/* The colour conversion around the 8-bit frame path, pure int32 arithmetic on Q14 coefficients
+ * (>> is the arithmetic shift: floor); clip255 clamps to [0, 255].
+ *   in,  per pixel, with the U, V of its 2x2 block (replicated, no interpolation),
+ *        c = Y - y0, d = U - 128, e = V - 128:
+ *     R = clip255((ay*c        + rv*e + 8192) >> 14)
+ *     G = clip255((ay*c + gu*d + gv*e + 8192) >> 14)
+ *     B = clip255((ay*c + bu*d        + 8192) >> 14)
+ *   out, per pixel:  Y = clip255(y0 + ((yr*R + yg*G + yb*B + 8192) >> 14))
+ *        per block, Rs / Gs / Bs the sums of its four pixels' bytes:
+ *     U = clip255(128 + ((ur*Rs + ug*Gs + ub*Bs + 32768) >> 16))
+ *     V = clip255(128 + ((vr*Rs + vg*Gs + vb*Bs + 32768) >> 16))
+ * Any 15 values with |coefficient| < 2^16 and 0 <= y0 <= 255 may be passed (RRIN_E_ARG
+ * otherwise: the sums then fit int32). */
+typedef struct rrin_yuv_coef {
+  int32_t y0, ay, rv, gu, gv, bu;                  /* YUV -> RGB */
+  int32_t yr, yg, yb, ur, ug, ub, vr, vg, vb;      /* RGB -> YUV */
+} rrin_yuv_coef;
+enum rrin_yuv_standard { RRIN_YUV_BT709 = 0, RRIN_YUV_BT601 = 1 };
+/* The coefficients of a standard: round(x * 2^14) of the matrix its Kr / Kb give, for limited
+ * (Y 16..235, chroma 16..240) or full range; yg, ug and vg are remainders (yr + yg + yb =
+ * round(2^14 * luma scale), ur + ug + ub = vr + vg + vb = 0), so grey maps to U = V = 128
+ * exactly.  Host only. */
+int rrin_yuv_coef_std(int32_t standard, int32_t full_range, rrin_yuv_coef* c);
+
+/* rrin_pack_g16_u8_h8 from two stacks of 4:2:0 frames: the records are bitwise those it writes
+ * from the frames converted to RGB bytes as above.  Padding is its rule applied to source
+ * coordinates: padded pixel (y, x) reads source pixel (sy, sx) = (max(y - (h - h0), 0),
+ * min(x, w0 - 1)), its luma and the chroma of block (sy/2, sx/2).  A frame may start at any
+ * byte.  Null planes or coef, c_step not 1 or 2, a coefficient out of range: RRIN_E_ARG; odd or
+ * < 2 h0 / w0, a pitch smaller than its row, frames of a stack that overlap (n > 1), a g16 that
+ * is not round_up(h0,16) x round_up(w0,16): RRIN_E_SHAPE.  Validated before any HIP call. */
+int rrin_pack_g16_yuv_h8(const rrin_yuv420* f0, const rrin_yuv420* f1, const rrin_yuv_coef* coef, int32_t n,
+                         int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec, void* stream);
 /* NCHW fp32 <-> H8 view (c channels starting at channel ch_off of the view). */
 int rrin_nchw_to_h8(const float* src, int32_t n, int32_t c, int32_t ch_off, const rrin_h8* dst,
                     int32_t prec, void* stream);
@@ -417,6 +462,15 @@ typedef struct rrin_head_h8_desc {
      poisoned by the range flag is written as 0.  top + h0 <= h, w0 <= w. */
   uint8_t* out_u8;
   int32_t h0, w0, top, pad2_;
+  /* ABI 22, FINAL, optional (out_yuv.y NULL: off), not together with out_u8 (RRIN_E_ARG); out may
+     still be set: the crop's RGB bytes (those out_u8 would hold) converted to 4:2:0 with
+     yuv_coef (see rrin_yuv_coef) into the planes of out_yuv, which are written through in spite
+     of the const of the struct's pointers.  h0, w0 and top must be even (RRIN_E_SHAPE).  Y is
+     written for the crop's pixels and U / V once per 2x2 block; pitch bytes beyond w0 and
+     anything outside the crop are never written. */
+  rrin_yuv420 out_yuv;
+  rrin_yuv_coef yuv_coef;
+  int32_t pad3_;
 } rrin_head_h8_desc;
 int rrin_head_h8_fwd(const rrin_head_h8_desc* d, void* stream);
 
@@ -557,6 +611,24 @@ typedef struct rrin_net_u8_desc {
   int32_t h0, w0;
 } rrin_net_u8_desc;
 int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream);
+
+/* ABI 22: the same forward on 8-bit YUV 4:2:0 frames (NV12 or I420), in and out on the device:
+ * by definition rgb_to_yuv420(rrin_net_u8_fwd(yuv420_to_rgb(f0), yuv420_to_rgb(f1))) with the
+ * integer conversions of rrin_yuv_coef, bit for bit -- rrin_pack_g16_yuv_h8 in, the FINAL head's
+ * rrin_head_h8_desc.out_yuv store out; no RGB frame exists on the device.  net as for
+ * rrin_net_u8_fwd (same schedule, skip_flow, range guard -- a poisoned pixel is RGB (0,0,0)
+ * before the conversion -- and record precisions only).  h0 and w0 even.  Null planes, a c_step
+ * not 1 or 2: RRIN_E_ARG; odd sizes, pitches smaller than a row, overlapping frames:
+ * RRIN_E_SHAPE.  Arguments are validated before any HIP call. */
+typedef struct rrin_net_yuv_desc {
+  rrin_net_desc net;
+  rrin_yuv420 f0, f1;   /* n frames each; may be two views of one [n+1] stack */
+  rrin_yuv420 out;      /* n frames, written through the const pointers */
+  rrin_yuv_coef coef;
+  int32_t h0, w0;
+  int32_t pad_;
+} rrin_net_yuv_desc;
+int rrin_net_yuv_fwd(const rrin_net_yuv_desc* d, void* stream);
 
 /* ---- Scene-cut / duplicate-frame gate of the 8-bit frame path (ABI 21) ------------------
  * Three small kernels for the stream of a rrin_net_u8_fwd call, so that a caller can replace the

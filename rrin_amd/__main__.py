@@ -36,6 +36,12 @@ def build_parser():
                     help="scene gate, off by default: mean absolute byte difference (0-255) above which a pair "
                          "is a shot change and yields the nearer input frame instead of a blend; repeated "
                          "frames are passed through.  No value has been validated on real footage")
+    cv.add_argument("--y4m_in", type=str, default=None, metavar="PATH|-",
+                    help="read an 8-bit 4:2:0 Y4M stream (\"-\": stdin, e.g. from ffmpeg -f yuv4mpegpipe) instead "
+                         "of a video or folder; needs --y4m_out.  No PNG folder, no RGB frame: the frames go "
+                         "through the network as YUV.  --fps is ignored (the rate comes from the stream)")
+    cv.add_argument("--y4m_out", type=str, default=None, metavar="PATH|-",
+                    help="write the interpolated Y4M stream here (\"-\": stdout)")
     return p
 
 

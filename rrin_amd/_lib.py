@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librrin_hip.so")
 # A/B sessions only (tools/sessions/): another build of the same library, e.g. ab/librrin_hip_X.so
 if os.environ.get("RRIN_LIB_AB"):
@@ -91,12 +91,28 @@ class EdgeFixDesc(C.Structure):
                 ("full", C.c_int32)]
 
 
+class Yuv420(C.Structure):
+    """rrin_yuv420: one stack of 8-bit 4:2:0 frames (NV12: v == u + 1, c_step 2; I420: c_step 1)."""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("img_stride", C.c_int64),
+                ("y_pitch", C.c_int32), ("c_pitch", C.c_int32), ("c_step", C.c_int32), ("pad_", C.c_int32)]
+
+
+class YuvCoef(C.Structure):
+    """rrin_yuv_coef: the 15 Q14 integers of the colour conversion (rrin_amd.yuv.Coef order)."""
+    _fields_ = [(k, C.c_int32) for k in ("y0", "ay", "rv", "gu", "gv", "bu", "yr", "yg", "yb", "ur", "ug", "ub",
+                                         "vr", "vg", "vb")]
+
+
+YUV_BT709, YUV_BT601 = 0, 1
+
+
 class HeadH8Desc(C.Structure):
     _fields_ = [("n", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("mode", C.c_int32),
                 ("prec", C.c_int32), ("pad_", C.c_int32), ("src", H8), ("g16", H8), ("w", C.c_void_p),
                 ("bias", C.c_void_p), ("coef", C.c_void_p), ("out", C.c_void_p), ("flow_raw", H8),
                 ("raw_out", C.c_void_p), ("status", C.c_void_p), ("out_u8", C.c_void_p), ("h0", C.c_int32),
-                ("w0", C.c_int32), ("top", C.c_int32), ("pad2_", C.c_int32)]
+                ("w0", C.c_int32), ("top", C.c_int32), ("pad2_", C.c_int32), ("out_yuv", Yuv420),
+                ("yuv_coef", YuvCoef), ("pad3_", C.c_int32)]
 
 
 class HeadWeights(C.Structure):
@@ -115,6 +131,11 @@ class NetDesc(C.Structure):
 class NetU8Desc(C.Structure):
     _fields_ = [("net", NetDesc), ("f0", C.c_void_p), ("f1", C.c_void_p), ("img_stride", C.c_int64),
                 ("out_u8", C.c_void_p), ("h0", C.c_int32), ("w0", C.c_int32)]
+
+
+class NetYuvDesc(C.Structure):
+    _fields_ = [("net", NetDesc), ("f0", Yuv420), ("f1", Yuv420), ("out", Yuv420), ("coef", YuvCoef),
+                ("h0", C.c_int32), ("w0", C.c_int32), ("pad_", C.c_int32)]
 
 
 class TConvDesc(C.Structure):
@@ -201,6 +222,9 @@ SIGNATURES = {
     "rrin_pack_g16_h8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(H8), C.c_int32, C.c_void_p]),
     "rrin_pack_g16_u8_h8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                       C.POINTER(H8), C.c_int32, C.c_void_p]),
+    "rrin_yuv_coef_std": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(YuvCoef)]),
+    "rrin_pack_g16_yuv_h8": (C.c_int, [C.POINTER(Yuv420), C.POINTER(Yuv420), C.POINTER(YuvCoef), C.c_int32,
+                                       C.c_int32, C.c_int32, C.POINTER(H8), C.c_int32, C.c_void_p]),
     "rrin_nchw_to_h8": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(H8), C.c_int32,
                                   C.c_void_p]),
     "rrin_h8_to_nchw": (C.c_int, [C.POINTER(H8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
@@ -211,6 +235,7 @@ SIGNATURES = {
                                       C.c_void_p]),
     "rrin_net_fwd": (C.c_int, [C.POINTER(NetDesc), C.c_void_p]),
     "rrin_net_u8_fwd": (C.c_int, [C.POINTER(NetU8Desc), C.c_void_p]),
+    "rrin_net_yuv_fwd": (C.c_int, [C.POINTER(NetYuvDesc), C.c_void_p]),
     "rrin_pair_sad_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                    C.c_void_p]),
     "rrin_gate_from_sad_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),

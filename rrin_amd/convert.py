@@ -410,6 +410,111 @@ def _retire(item, sf, dest, put, model=None):
         put(shutil.copy, m1["path"], os.path.join(dest, f"{base + sf + 1:09d}{m1['filetype']}"))
 
 
+def interpolate_y4m(model, src, dst, sf, batch=4, scene_threshold=None, coef=None, log=print):
+    """Interpolate a Y4M stream (8-bit 4:2:0) into another: no image folder, no RGB frame anywhere.
+
+    ``src`` / ``dst`` are binary file objects (files or pipes: they are read and written
+    sequentially, never sought) or paths.  Every step takes the next ``batch`` pairs: their
+    ``batch + 1`` frames go to the model's device as one pinned uint8 stack, and
+    ``model.interpolate_yuv(stack[:-1], stack[1:], ts, layout="i420")`` runs on two views of it
+    with the t schedule of :func:`interpolate_folder`.  The output holds frame k, its ``sf``
+    intermediates, ..., the last frame, at ``sf + 1`` times the input's frame rate; the input
+    frames pass through as their own bytes.  ``coef`` (``rrin_amd.yuv.coefficients``; None: BT.709
+    limited range) and ``scene_threshold`` go to ``interpolate_yuv`` -- the threshold is a mean over
+    luma and chroma bytes there, not the RGB path's number, and no value has been validated on
+    footage.  Single process: ``WORLD_SIZE`` > 1 raises.  Returns the frames written."""
+    from . import y4m
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("interpolate_y4m runs in a single process (a stream has one reader and one writer)")
+    if sf < 1 or batch < 1:
+        raise ValueError(f"sf and batch must be >= 1, got {sf} / {batch}")
+    opened = []
+    if isinstance(src, (str, os.PathLike)):
+        src = open(src, "rb")
+        opened.append(src)
+    if isinstance(dst, (str, os.PathLike)):
+        dst = open(dst, "wb")
+        opened.append(dst)
+    try:
+        rd = y4m.Reader(src)
+        w0, h0 = rd.width, rd.height
+        wr = y4m.Writer(dst, w0, h0, rd.fps_num * (sf + 1), rd.fps_den, rd.colorspace)
+        device = next(model.parameters()).device
+        ts = [i / (sf + 1) for i in range(1, sf + 1)]
+        gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
+        frames = iter(rd)
+        prev = next(frames, None)
+        if prev is None:
+            raise ValueError("need at least two frames in the Y4M stream")
+        wr.write(prev)
+        written, pairs, cuts, dups = 1, 0, 0, 0
+        t0 = time.time()
+        pending = []
+
+        def retire(item):
+            nonlocal written, cuts, dups
+            ev, host, inputs, codes = item
+            ev.synchronize()
+            if hasattr(model, "check_range"):
+                model.check_range(wait=False)  # fp16-stored precisions: raise instead of writing poisoned frames
+            for p, nxt in enumerate(inputs):
+                for i in range(sf):
+                    wr.write(host[i][p].numpy())
+                wr.write(nxt)
+                written += sf + 1
+            if codes is not None:
+                cuts += int((codes == 2).sum())
+                dups += int((codes == 1).sum())
+
+        while True:
+            group = [prev]
+            for fr in frames:
+                group.append(fr)
+                if len(group) == batch + 1:
+                    break
+            nloc = len(group) - 1
+            if nloc == 0:
+                break
+            prev = group[-1]
+            stack = torch.empty((nloc + 1, 3 * h0 // 2, w0), dtype=torch.uint8, pin_memory=True)
+            for j, fr in enumerate(group):
+                stack[j].view(-1).copy_(torch.from_numpy(fr))
+            stack = stack.to(device, non_blocking=True)
+            with torch.no_grad():
+                outs = model.interpolate_yuv(stack[:-1], stack[1:], ts, layout="i420", coef=coef, **gate_kw)
+            host = []
+            for o in outs:
+                hbuf = torch.empty(o.shape, dtype=o.dtype, pin_memory=True)
+                hbuf.copy_(o, non_blocking=True)
+                host.append(hbuf)
+            codes = None
+            if gate_kw:
+                codes = torch.empty(nloc, dtype=torch.int32, pin_memory=True)
+                codes.copy_(model.last_gate, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            pending.append((ev, host, group[1:], codes))
+            pairs += nloc
+            while len(pending) > 1:  # retire the previous step while this one computes
+                retire(pending.pop(0))
+        while pending:
+            retire(pending.pop(0))
+        if pairs == 0:
+            raise ValueError("need at least two frames in the Y4M stream")
+        if hasattr(model, "check_range"):
+            model.check_range()
+        wr.flush()
+        msg = (f"y4m: {pairs} pairs x {sf} frames of {w0}x{h0} in {time.time() - t0:.2f} s, {written} frames "
+               f"out at {rd.fps_num * (sf + 1)}:{rd.fps_den} fps")
+        if gate_kw:
+            msg += f"; scene gate (threshold {scene_threshold:g}): {cuts} cut pairs, {dups} duplicate pairs"
+        log(msg)
+        return written
+    finally:
+        for f in opened:
+            f.close()
+
+
 def find_checkpoint(model_name, models_dir="models"):
     """Last checkpoint whose name starts with model_name (convert.py:100-108);
     sorted order, so Model0150.pth wins over Model0001.pth."""
@@ -441,6 +546,30 @@ def _ffmpeg(cmd):
     return subprocess.call(cmd)
 
 
+def _convert_y4m(args):
+    """``convert --y4m_in PATH|- --y4m_out PATH|-``: a Y4M stream in, one out (``interpolate_y4m``);
+    "-" is stdin / stdout, so a decoder can pipe in and an encoder pipe out.  Everything this
+    process prints goes to stderr: stdout may be the stream."""
+    import contextlib
+    if not args.y4m_in or not args.y4m_out:
+        raise Exception("Missing arguments! --y4m_in and --y4m_out go together")
+    if args.input_video is not None or args.image_folder is not None:
+        raise Exception("--y4m_in / --y4m_out replace --input_video / --image_folder")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("the Y4M pipe runs in a single process (WORLD_SIZE > 1)")
+    if args.no_cuda or not torch.cuda.is_available():
+        raise RuntimeError("rrin_amd runs on ROCm GPUs only")
+    src = sys.stdin.buffer if args.y4m_in == "-" else args.y4m_in
+    dst = sys.stdout.buffer if args.y4m_out == "-" else args.y4m_out
+    with contextlib.redirect_stdout(sys.stderr):
+        print("--fps is ignored with --y4m_in: the output rate is the stream's times (sf + 1)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        net = load_net(args.model_name, dev, getattr(args, "precision", "fp32"))
+        interpolate_y4m(net, src, dst, args.sf, batch=getattr(args, "batch", 4),
+                        scene_threshold=getattr(args, "scene_threshold", None))
+        print("Finished conversion")
+
+
 def convert(args):
     """CLI entry (same flags as the reference __main__.py:47-63).  Under
     ``torchrun --nproc-per-node N`` (WORLD_SIZE > 1) every process drives its
@@ -448,6 +577,8 @@ def convert(args):
     over RCCL (``interpolate_folder``); rank 0 does the ffmpeg steps and the
     folder checks and broadcasts their outcome, so a failure there ends every
     rank (same message / exit code as the reference, convert.py:67-82)."""
+    if getattr(args, "y4m_in", None) or getattr(args, "y4m_out", None):
+        return _convert_y4m(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if world > 1 and int(os.environ.get("GPU_MAX_HW_QUEUES", "4")) < 8:

@@ -2,13 +2,15 @@
 // NCHW <-> records (rrin_nchw_to_h8 / rrin_h8_to_nchw), the frame pair into the Net buffer g16
 // from fp32 or uint8 frames (rrin_pack_g16_h8 / rrin_pack_g16_u8_h8), nn.Upsample(bilinear, x2)
 // (unet.py:77) as its own pass (rrin_upsample2x_h8), the head convs (Cout <= 4) fused with the
-// model.py glue they feed (rrin_head_h8_fwd; the arithmetic itself in net_glue.hpp), and the
+// model.py glue they feed (rrin_head_h8_fwd; the arithmetic itself in net_glue.hpp; the FINAL
+// head also stores 8-bit frames, interleaved RGB or 4:2:0 planes through yuv.hpp), and the
 // t-blend of a kept raw flow (rrin_flow_tblend_h8).  H8 kernels for F16X3 / F16, *_r32 kernels
 // for the fp32 records.
 #include <string.h>
 
 #include "h8.hpp"
 #include "net_glue.hpp"
+#include "yuv.hpp"
 
 namespace rrin {
 
@@ -151,21 +153,57 @@ struct HeadH8Args {
   int* status;      // optional fp16 range flag: glue stores set it, FINAL poisons on it
   uint8_t* out8;    // FINAL, optional: uint8 [n][h0][w0][3] crop (rows top .. top + h0 - 1, columns < w0)
   int h0, w0, top;
+  // FINAL, optional (the YUV kernels only): the same crop as 4:2:0 planes (rrin_head_h8_desc.out_yuv)
+  uint8_t* oy;
+  uint8_t* ou;
+  uint8_t* ov;
+  int64_t o_img;
+  int oy_pitch, oc_pitch, oc_step;
+  rrin_yuv_coef yc;
 };
 
+// The byte of a clamped FINAL value: (uint8)(q * 255.0f) -- one fp32 multiply, truncation toward
+// zero, as t.mul(255).to(torch.uint8); 0 for a poisoned pixel (fp16 range guard).
+__device__ inline uint8_t final_byte(float q, bool poison) { return poison ? (uint8_t)0 : (uint8_t)(q * 255.0f); }
+
 // FINAL with a uint8 output: the clamped pixel q of padded position (y, x) as three interleaved
-// bytes of the crop, (uint8)(q * 255.0f) -- one fp32 multiply, truncation toward zero, as
-// t.mul(255).to(torch.uint8); a poisoned pixel (fp16 range guard) is written as 0.  Pixels of the
-// padding (rows above top, columns from w0) are not written.
+// bytes (final_byte) of the crop.  Pixels of the padding (rows above top, columns from w0) are not
+// written.
 __device__ inline void final_store_u8(const HeadH8Args& a, int img, int y, int x, const float* q, bool poison) {
   const int yo = y - a.top;
   if (yo < 0 || yo >= a.h0 || x >= a.w0) return;
   uint8_t* o = a.out8 + (((int64_t)img * a.h0 + yo) * a.w0 + x) * 3;
 #pragma unroll
-  for (int ch = 0; ch < 3; ++ch) o[ch] = poison ? (uint8_t)0 : (uint8_t)(q[ch] * 255.0f);
+  for (int ch = 0; ch < 3; ++ch) o[ch] = final_byte(q[ch], poison);
 }
 
-template <int COUT, int MODE, int PLANES>
+// FINAL with a 4:2:0 output: a thread's two vertically adjacent pixels (rows y, y + 1, y even;
+// rgb: their RGB bytes) and those of its xl ^ 1 neighbour lane are one 2x2 block of the crop,
+// since top, h0 and w0 are even.  Every lane of the wave calls this (lanes outside the frame or
+// the crop with any rgb): the lane exchange comes first, the stores only for pixels of the crop.
+// Two luma bytes per lane; of a block's pair the even lane writes U and the odd one V.
+__device__ inline void final_store_yuv(const HeadH8Args& a, int img, int y, int x, const int (*rgb)[3]) {
+  int sum[3];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    sum[ch] = rgb[0][ch] + rgb[1][ch];
+    sum[ch] += __shfl_xor(sum[ch], 1);
+  }
+  const int yo = y - a.top;
+  if (yo < 0 || yo >= a.h0 || x >= a.w0) return;
+  const int64_t base = (int64_t)img * a.o_img;
+  uint8_t* py = a.oy + base + (int64_t)yo * a.oy_pitch + x;
+  py[0] = (uint8_t)rgb_to_luma(a.yc, rgb[0]);
+  py[a.oy_pitch] = (uint8_t)rgb_to_luma(a.yc, rgb[1]);
+  const int64_t c = base + (int64_t)(yo >> 1) * a.oc_pitch + (x >> 1) * a.oc_step;
+  if (x & 1)
+    a.ov[c] = (uint8_t)rgb_sum_to_chroma(a.yc.vr, a.yc.vg, a.yc.vb, sum);
+  else
+    a.ou[c] = (uint8_t)rgb_sum_to_chroma(a.yc.ur, a.yc.ug, a.yc.ub, sum);
+}
+
+// YUV (FINAL only): the 8-bit output as 4:2:0 planes (final_store_yuv) instead of interleaved RGB
+template <int COUT, int MODE, int PLANES, bool YUV = false>
 __global__ void __launch_bounds__(256) head_h8_kernel(HeadH8Args a) {
   // tile 16 rows x 32 cols; thread = 2 vertically adjacent pixels (packed fp32 FMA)
   constexpr int CIN = 32, HROWS = 18, HLC = 40;
@@ -239,6 +277,7 @@ __global__ void __launch_bounds__(256) head_h8_kernel(HeadH8Args a) {
     __syncthreads();
   }
 
+  int rgb[2][3] = {};  // YUV: the two pixels' RGB bytes
   for (int p = 0; p < 2; ++p) {
   float acc[COUT];
 #pragma unroll
@@ -357,9 +396,15 @@ __global__ void __launch_bounds__(256) head_h8_kernel(HeadH8Args a) {
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) o[(int64_t)ch * a.h * a.w_] = poison ? __builtin_nanf("") : q[ch];
     }
-    if (a.out8) final_store_u8(a, img, y, x, q, poison);
+    if constexpr (YUV) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) rgb[p][ch] = final_byte(q[ch], poison);
+    } else if (a.out8) {
+      final_store_u8(a, img, y, x, q, poison);
+    }
   }
   }
+  if constexpr (YUV) final_store_yuv(a, img, y0 + r2, x0 + xl, rgb);
 }
 
 template <int PLANES>
@@ -440,14 +485,6 @@ __global__ void pack_g16_r32_kernel(const float* __restrict__ i0, const float* _
 }
 
 // ---- 8-bit frames straight into g16 (rrin_pack_g16_u8_h8) --------------------------
-// float(u) / 255.0f, correctly rounded, for every byte value: evaluated by the host compiler
-// (a multiply by 1 / 255.0f differs from the division for 126 of the 256 values)
-struct U8ScaleTab {
-  float v[256];
-  constexpr U8ScaleTab() : v{} {
-    for (int i = 0; i < 256; ++i) v[i] = (float)i / 255.0f;
-  }
-};
 __constant__ const U8ScaleTab kU8Scale{};
 
 // x = cat(x0, x1) from two uint8 [n][h0][w0][3] frame stacks, edge-replicated on top (`top` rows)
@@ -571,7 +608,7 @@ __global__ void up2x_r32_kernel(const uint4* __restrict__ s, int64_t s_img, int6
 // 32-channel input as 8 records of 4 channels and g16 as 4 records; every g16
 // update is a whole 16-B record (records the glue only partly changes are read
 // first), no partial-record writes.
-template <int COUT, int MODE>
+template <int COUT, int MODE, bool YUV = false>
 __global__ void __launch_bounds__(256) head_r32_kernel(HeadH8Args a) {
   constexpr int CIN = 32, HROWS = 18, HLC = 40;
   __shared__ __attribute__((aligned(16))) float s_in[8 * HROWS * HLC];
@@ -639,6 +676,7 @@ __global__ void __launch_bounds__(256) head_r32_kernel(HeadH8Args a) {
     __syncthreads();
   }
 
+  int rgb[2][3] = {};  // YUV: the two pixels' RGB bytes
   for (int p = 0; p < 2; ++p) {
     float acc[COUT];
 #pragma unroll
@@ -707,9 +745,15 @@ __global__ void __launch_bounds__(256) head_r32_kernel(HeadH8Args a) {
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) o[(int64_t)ch * a.h * a.w_] = q[ch];
       }
-      if (a.out8) final_store_u8(a, img, y, x, q, false);
+      if constexpr (YUV) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) rgb[p][ch] = final_byte(q[ch], false);
+      } else if (a.out8) {
+        final_store_u8(a, img, y, x, q, false);
+      }
     }
   }
+  if constexpr (YUV) final_store_yuv(a, img, y0 + r2, x0 + xl, rgb);
 }
 
 // zero channels [c0, c1) of every interior pixel of a record-layout view (H8 hi
@@ -828,14 +872,14 @@ extern "C" int rrin_h8_to_nchw(const rrin_h8* src, int32_t n, int32_t c, int32_t
   return hip_code(hipGetLastError());
 }
 
-template <int COUT, int MODE>
+template <int COUT, int MODE, bool YUV = false>
 static int head_h8_launch(const HeadH8Args& a, int planes, int grid, hipStream_t st) {
   if (planes == 0)  // F32R
-    hipLaunchKernelGGL((head_r32_kernel<COUT, MODE>), dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((head_r32_kernel<COUT, MODE, YUV>), dim3(grid), dim3(256), 0, st, a);
   else if (planes == 2)
-    hipLaunchKernelGGL((head_h8_kernel<COUT, MODE, 2>), dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((head_h8_kernel<COUT, MODE, 2, YUV>), dim3(grid), dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL((head_h8_kernel<COUT, MODE, 1>), dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((head_h8_kernel<COUT, MODE, 1, YUV>), dim3(grid), dim3(256), 0, st, a);
   return hip_code(hipGetLastError());
 }
 
@@ -852,10 +896,17 @@ static int head_prepare(const rrin_head_h8_desc* d, HeadH8Args& a, int& grid) {
   } else if (cpr * d->g16.groups < d->cout) {
     return RRIN_E_ARG;
   }
-  if (d->mode == RRIN_HEAD_FINAL && !d->out && !d->out_u8) return RRIN_E_ARG;
-  if (d->mode == RRIN_HEAD_FINAL && d->out_u8 &&
+  const bool yuv = d->mode == RRIN_HEAD_FINAL && d->out_yuv.y;
+  if (d->mode == RRIN_HEAD_FINAL && !d->out && !d->out_u8 && !yuv) return RRIN_E_ARG;
+  if (yuv && d->out_u8) return RRIN_E_ARG;
+  if (d->mode == RRIN_HEAD_FINAL && (d->out_u8 || yuv) &&
       (d->h0 < 1 || d->w0 < 1 || d->top < 0 || d->top + d->h0 > h || d->w0 > w))
     return RRIN_E_SHAPE;
+  if (yuv) {
+    if (int rc = yuv_coef_check(&d->yuv_coef)) return rc;
+    if (int rc = yuv420_check(d->out_yuv, d->n, d->h0, d->w0)) return rc;
+    if (d->top & 1) return RRIN_E_SHAPE;
+  }
   const int planes = planes_of(d->prec);
   memset(&a, 0, sizeof(a));
   const int64_t sg = (int64_t)d->src.g_off * d->src.g.plane;
@@ -882,6 +933,19 @@ static int head_prepare(const rrin_head_h8_desc* d, HeadH8Args& a, int& grid) {
   a.status = d->status;
   if (d->mode == RRIN_HEAD_FINAL && d->out_u8) {
     a.out8 = d->out_u8;
+    a.h0 = d->h0;
+    a.w0 = d->w0;
+    a.top = d->top;
+  }
+  if (yuv) {
+    a.oy = const_cast<uint8_t*>(d->out_yuv.y);
+    a.ou = const_cast<uint8_t*>(d->out_yuv.u);
+    a.ov = const_cast<uint8_t*>(d->out_yuv.v);
+    a.o_img = d->out_yuv.img_stride;
+    a.oy_pitch = d->out_yuv.y_pitch;
+    a.oc_pitch = d->out_yuv.c_pitch;
+    a.oc_step = d->out_yuv.c_step;
+    a.yc = d->yuv_coef;
     a.h0 = d->h0;
     a.w0 = d->w0;
     a.top = d->top;
@@ -927,7 +991,9 @@ extern "C" int rrin_head_h8_fwd(const rrin_head_h8_desc* d, void* stream) {
     case RRIN_HEAD_MASK:
       return d->cout == 2 ? head_h8_launch<2, RRIN_HEAD_MASK>(a, planes, grid, st) : RRIN_E_ARG;
     case RRIN_HEAD_FINAL:
-      return d->cout == 3 ? head_h8_launch<3, RRIN_HEAD_FINAL>(a, planes, grid, st) : RRIN_E_ARG;
+      if (d->cout != 3) return RRIN_E_ARG;
+      return a.oy ? head_h8_launch<3, RRIN_HEAD_FINAL, true>(a, planes, grid, st)
+                  : head_h8_launch<3, RRIN_HEAD_FINAL>(a, planes, grid, st);
   }
   return RRIN_E_ARG;
 }

@@ -79,6 +79,16 @@ __device__ inline uint4 f4rec(float a, float b, float c, float d) {
   return make_uint4(__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(d));
 }
 
+// float(u) / 255.0f, correctly rounded, for every byte value: evaluated by the host compiler
+// (a multiply by 1 / 255.0f differs from the division for 126 of the 256 values).  The 8-bit
+// input packs (glue_h8.hip, yuv.hip) each keep a __constant__ instance.
+struct U8ScaleTab {
+  float v[256];
+  constexpr U8ScaleTab() : v{} {
+    for (int i = 0; i < 256; ++i) v[i] = (float)i / 255.0f;
+  }
+};
+
 // ---- host side: precisions and view checks -----------------------------------------
 inline int planes_of(int prec) { return prec == RRIN_PREC_F16X3 ? 2 : 1; }
 // record-layout precisions: F16X3 / F16 (8 halves per record), F32R (4 floats)

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "yuv.hpp"
 
 using namespace rrin;
 
@@ -288,6 +289,9 @@ struct HeadIO {
   // FINAL on the record layout: the 8-bit crop (rrin_head_h8_desc.out_u8); NULL: off
   uint8_t* out_u8 = nullptr;
   int h0 = 0, w0 = 0, top = 0;
+  // or the crop as 4:2:0 planes (rrin_head_h8_desc.out_yuv / yuv_coef); NULL: off
+  const rrin_yuv420* out_yuv = nullptr;
+  const rrin_yuv_coef* yuv_coef = nullptr;
 };
 
 // Debug taps (rrin_net_desc.taps): where U-Net u's raw output goes, or NULL.
@@ -596,8 +600,12 @@ int run_unet_h8(const Plan& p, const UNetSpec& u, const rrin_conv_weights* cw, c
   hd.out = io.out;
   hd.raw_out = io.raw;
   hd.status = p.status;
-  if (u.head_mode == RRIN_HEAD_FINAL && io.out_u8) {
+  if (u.head_mode == RRIN_HEAD_FINAL && (io.out_u8 || io.out_yuv)) {
     hd.out_u8 = io.out_u8;
+    if (io.out_yuv) {
+      hd.out_yuv = *io.out_yuv;
+      hd.yuv_coef = *io.yuv_coef;
+    }
     hd.h0 = io.h0;
     hd.w0 = io.w0;
     hd.top = io.top;
@@ -673,10 +681,12 @@ extern "C" int64_t rrin_net_scratch_bytes(const rrin_net_desc* d) {
   return scratch_bytes_of(d->n, d->h, d->w, d->prec, d->convs, kUNets, 4);
 }
 
-// The schedule of both forwards: rrin_net_fwd (u8 NULL: fp32 NCHW frames d->i0 / i1 in, d->out
-// out) and rrin_net_u8_fwd (8-bit frames in and out; d->i0 / i1 / out unused; record layouts
-// only).  The callers have validated d (and u8).
-static int net_fwd_impl(const rrin_net_desc* d, const rrin_net_u8_desc* u8, void* stream) {
+// The schedule of the three forwards: rrin_net_fwd (u8 and yuv NULL: fp32 NCHW frames d->i0 / i1
+// in, d->out out), rrin_net_u8_fwd (8-bit RGB frames in and out) and rrin_net_yuv_fwd (8-bit
+// 4:2:0 frames in and out); the 8-bit ones leave d->i0 / i1 / out unused and run on the record
+// layouts only.  The callers have validated d (and u8 / yuv).
+static int net_fwd_impl(const rrin_net_desc* d, const rrin_net_u8_desc* u8, const rrin_net_yuv_desc* yuv,
+                        void* stream) {
   Plan p;
   make_plan(d->n, d->h, d->w, d->prec, reinterpret_cast<char*>(d->workspace), p);
   if (d->workspace_bytes < p.bytes) return RRIN_E_WORKSPACE;
@@ -696,8 +706,9 @@ static int net_fwd_impl(const rrin_net_desc* d, const rrin_net_u8_desc* u8, void
       ProfScope ps(p.prof, st, RRIN_KIND_LAYOUT, 0.0);
       // x0, x1 into channels 0-5; channels 6-15 zeroed, so the first convs (cin 6/9/10)
       // can stage whole records (their tail channels are finite and meet zero weights)
-      rc = u8 ? rrin_pack_g16_u8_h8(u8->f0, u8->f1, u8->img_stride, d->n, u8->h0, u8->w0, &gall, d->prec, st)
-              : rrin_pack_g16_h8(d->i0, d->i1, d->n, &gall, d->prec, st);
+      rc = u8    ? rrin_pack_g16_u8_h8(u8->f0, u8->f1, u8->img_stride, d->n, u8->h0, u8->w0, &gall, d->prec, st)
+           : yuv ? rrin_pack_g16_yuv_h8(&yuv->f0, &yuv->f1, &yuv->coef, d->n, yuv->h0, yuv->w0, &gall, d->prec, st)
+                 : rrin_pack_g16_h8(d->i0, d->i1, d->n, &gall, d->prec, st);
       if (!rc && d->skip_flow) {
         const rrin_h8 fr = hview(p.FLOWRAW, 0, 4);
         rc = rrin_flow_tblend_h8(&fr, &gall, d->coef, d->n, d->prec, st);
@@ -706,12 +717,18 @@ static int net_fwd_impl(const rrin_net_desc* d, const rrin_net_u8_desc* u8, void
     int k = 0;
     for (int u = 0; u < 4 && !rc; ++u) {
       if (!(u == 0 && d->skip_flow)) {
-        HeadIO io{d->coef, u8 ? nullptr : d->out, tap_of(d, kUNets[u])};
+        HeadIO io{d->coef, u8 || yuv ? nullptr : d->out, tap_of(d, kUNets[u])};
         if (u8) {
           io.out_u8 = u8->out_u8;
           io.h0 = u8->h0;
           io.w0 = u8->w0;
           io.top = d->h - u8->h0;
+        } else if (yuv) {
+          io.out_yuv = &yuv->out;
+          io.yuv_coef = &yuv->coef;
+          io.h0 = yuv->h0;
+          io.w0 = yuv->w0;
+          io.top = d->h - yuv->h0;
         }
         rc = run_unet_h8(p, kUNets[u], d->convs + k, d->heads[u], io, st);
       }
@@ -748,7 +765,7 @@ extern "C" int rrin_net_fwd(const rrin_net_desc* d, void* stream) {
     return RRIN_E_ARG;
   if (d->n < 1 || d->h < 16 || d->w < 16 || (d->h % 16) || (d->w % 16)) return RRIN_E_SHAPE;
   if (d->prec < RRIN_PREC_F32 || d->prec > RRIN_PREC_F32R) return RRIN_E_ARG;
-  return net_fwd_impl(d, nullptr, stream);
+  return net_fwd_impl(d, nullptr, nullptr, stream);
 }
 
 extern "C" int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream) {
@@ -760,7 +777,20 @@ extern "C" int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream) {
   if (nd->n < 1 || d->h0 < 1 || d->w0 < 1) return RRIN_E_SHAPE;
   if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
   if (nd->n > 1 && d->img_stride < (int64_t)d->h0 * d->w0 * 3) return RRIN_E_ARG;
-  return net_fwd_impl(nd, d, stream);
+  return net_fwd_impl(nd, d, nullptr, stream);
+}
+
+extern "C" int rrin_net_yuv_fwd(const rrin_net_yuv_desc* d, void* stream) {
+  if (!d) return RRIN_E_ARG;
+  const rrin_net_desc* nd = &d->net;
+  if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
+  // the record precisions only, as rrin_net_u8_fwd
+  if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
+  if (int rc = yuv_coef_check(&d->coef)) return rc;
+  for (const rrin_yuv420* s : {&d->f0, &d->f1, &d->out})
+    if (int rc = yuv420_check(*s, nd->n, d->h0, d->w0)) return rc;
+  if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  return net_fwd_impl(nd, nullptr, d, stream);
 }
 
 // One U-Net alone (reference UNet.forward, unet.py:40-51): NCHW in -> NCHW out,

@@ -1,0 +1,49 @@
+// The integer colour conversion of the YUV 4:2:0 frame path (rrin_yuv_coef in rrin_hip.h), shared
+// by the input pack (yuv.hip) and the FINAL head's store (glue_h8.hip), and the host-side checks
+// of a rrin_yuv420 stack.  int32 only: no float colour math, so no FMA contraction can change a
+// bit.
+#pragma once
+#include "common.hpp"
+
+namespace rrin {
+
+__device__ inline int clip255(int v) { return min(max(v, 0), 255); }
+
+// one pixel's RGB bytes from its luma and its block's chroma
+__device__ inline void yuv_to_rgb(const rrin_yuv_coef& k, int y, int u, int v, int* rgb) {
+  const int c = k.ay * (y - k.y0) + 8192, d = u - 128, e = v - 128;
+  rgb[0] = clip255((c + k.rv * e) >> 14);
+  rgb[1] = clip255((c + k.gu * d + k.gv * e) >> 14);
+  rgb[2] = clip255((c + k.bu * d) >> 14);
+}
+
+__device__ inline int rgb_to_luma(const rrin_yuv_coef& k, const int* rgb) {
+  return clip255(k.y0 + ((k.yr * rgb[0] + k.yg * rgb[1] + k.yb * rgb[2] + 8192) >> 14));
+}
+
+// a chroma sample from the sums of its block's four pixels' bytes
+__device__ inline int rgb_sum_to_chroma(int kr, int kg, int kb, const int* sum) {
+  return clip255(128 + ((kr * sum[0] + kg * sum[1] + kb * sum[2] + 32768) >> 16));
+}
+
+// ---- host side -------------------------------------------------------------------------
+inline int yuv_coef_check(const rrin_yuv_coef* k) {
+  if (!k || k->y0 < 0 || k->y0 > 255) return RRIN_E_ARG;
+  const int32_t* v = &k->ay;
+  for (int i = 0; i < 14; ++i)
+    if (v[i] <= -65536 || v[i] >= 65536) return RRIN_E_ARG;
+  return 0;
+}
+
+// n frames of h0 x w0 in s: planes, layout, sizes and pitches (nothing is dereferenced)
+__attribute__((visibility("hidden"))) inline int yuv420_check(const rrin_yuv420& s, int n, int h0, int w0) {
+  if (!s.y || !s.u || !s.v || (s.c_step != 1 && s.c_step != 2)) return RRIN_E_ARG;
+  if (n < 1 || h0 < 2 || w0 < 2 || (h0 & 1) || (w0 & 1)) return RRIN_E_SHAPE;
+  if (s.y_pitch < w0 || s.c_pitch < (w0 / 2) * s.c_step) return RRIN_E_SHAPE;
+  const int64_t y_span = (int64_t)(h0 - 1) * s.y_pitch + w0;
+  const int64_t c_span = (int64_t)(h0 / 2 - 1) * s.c_pitch + (int64_t)(w0 / 2 - 1) * s.c_step + 1;
+  if (n > 1 && (s.img_stride < y_span || s.img_stride < c_span)) return RRIN_E_SHAPE;
+  return 0;
+}
+
+}  // namespace rrin

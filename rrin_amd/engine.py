@@ -1000,6 +1000,179 @@ class RRINEngine:
         if st is not None:
             self._queue_status(slot, stream)
 
+    # ---- 8-bit YUV 4:2:0 frames (NV12 / I420) ------------------------------------------
+    def _yuv_frames(self, f0, f1, what):
+        """Checks two uint8 [N, 3*H0//2, W0] 4:2:0 stacks of ``what`` and returns them with
+        (H0, W0) and the bytes between their frames: every frame dense, a uniform stride over dim
+        0 taken as it is (``frames[:-1]`` / ``frames[1:]`` of one stack need no copy), anything
+        else copied."""
+        from . import yuv
+        if not isinstance(f0, torch.Tensor) or not isinstance(f1, torch.Tensor):
+            raise TypeError(f"{what} takes two uint8 tensors")
+        if f0.device != self.device or f1.device != self.device:
+            raise RuntimeError(f"inputs on {f0.device}/{f1.device}, model on {self.device}")
+        if f0.dtype != torch.uint8 or f1.dtype != torch.uint8:
+            raise TypeError(f"{what} takes uint8 frames (forward takes float32)")
+        if f0.shape != f1.shape:
+            raise ValueError(f"expected two equal [N, 3*H0//2, W0] stacks, got {tuple(f0.shape)} / {tuple(f1.shape)}")
+        h0, w0 = yuv.frame_size(f0)
+        n, rows = f0.shape[0], f0.shape[1]
+        if n < 1:
+            raise ValueError(f"empty frames: {tuple(f0.shape)}")
+        frame = rows * w0
+
+        def stride_of(f):  # bytes between frames, or None if f needs a copy
+            if f.stride(2) != 1 or f.stride(1) != w0:
+                return None
+            return frame if n == 1 else (f.stride(0) if f.stride(0) >= frame else None)
+
+        s0, s1 = stride_of(f0), stride_of(f1)
+        if s0 is None or s0 != s1:
+            f0, f1 = f0.contiguous(), f1.contiguous()
+            s0 = frame
+        return f0, f1, h0, w0, s0
+
+    @staticmethod
+    def _yuv_stack(ptr: int, img_stride: int, h0: int, w0: int, layout: str) -> "_lib.Yuv420":
+        """The rrin_yuv420 of a dense-frame stack at device address ``ptr``."""
+        s = _lib.Yuv420()
+        s.y, s.u = ptr, ptr + h0 * w0
+        s.img_stride, s.y_pitch = img_stride, w0
+        if layout == "nv12":
+            s.v, s.c_pitch, s.c_step = s.u + 1, w0, 2
+        else:
+            s.v, s.c_pitch, s.c_step = s.u + (h0 // 2) * (w0 // 2), w0 // 2, 1
+        return s
+
+    def forward_yuv(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, layout: str = "nv12", coef=None,
+                    reuse_flow: bool = False, streams: int | None = None, split=None, scene_threshold=None,
+                    gate=None) -> torch.Tensor:
+        """One Net.forward on 8-bit YUV 4:2:0 frames: ``f0`` / ``f1`` uint8 ``[N, 3*H0//2, W0]``
+        (H0, W0 even; ``layout`` "nv12" or "i420", see :mod:`rrin_amd.yuv`) on the engine's device
+        -> uint8 ``[N, 3*H0//2, W0]`` of the same layout.  By definition, and bit for bit,
+        ``yuv.rgb_to_yuv420(forward_u8(yuv.yuv420_to_rgb(f0), yuv.yuv420_to_rgb(f1), t))`` with the
+        integer conversions of ``coef`` (``None``: BT.709 limited range; ``yuv.coefficients`` or
+        any 15 ints): the conversion in happens inside the input pack (rrin_pack_g16_yuv_h8), the
+        one out inside the FINAL head's store (rrin_net_yuv_fwd); no RGB frame exists on the
+        device, and a step moves 1.5 bytes per pixel each way instead of 3.
+
+        Workspaces, scratch, the stream split, ``reuse_flow`` and the range guard behave as in
+        :meth:`forward_u8` (with the guard set the poisoned pixels are RGB (0,0,0) before the
+        conversion, and ``check_range`` raises).  A kept raw Flow is only reused by a call with
+        the same layout and coefficients, never by the float or the RGB byte path.
+
+        The scene gate (``scene_threshold`` or ``gate``, never both) is :meth:`forward_u8`'s, run
+        by the same three kernels on the frames' bytes as they are -- a dense 4:2:0 frame is a
+        blob of ``H0*W0*3/2`` bytes -- so a gated pair returns its input frame's YUV bytes
+        unchanged, with no round trip through RGB.  ``scene_threshold`` is therefore a mean
+        absolute difference over luma *and* chroma bytes: a pair is a cut when its sum exceeds
+        ``floor(scene_threshold * H0*W0*3/2)``.  That is not the same number as the RGB path's
+        threshold for the same footage, and like it no value has been validated on footage."""
+        from . import yuv
+        if self.prec == _lib.PREC_F32:
+            raise RuntimeError("forward_yuv needs a record-layout precision: 'fp32', 'fp32_split16' or 'fp16' "
+                               "(not 'fp32_planar')")
+        if layout not in yuv.LAYOUTS:
+            raise ValueError(f"layout must be one of {yuv.LAYOUTS}, got {layout!r}")
+        k = yuv.as_coef(coef)
+        f0, f1, h0, w0, s0 = self._yuv_frames(f0, f1, "forward_yuv")
+        n = f0.shape[0]
+        h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
+        if scene_threshold is not None and gate is not None:
+            raise ValueError("scene_threshold and gate exclude each other")
+        limit = cut_code = None
+        if scene_threshold is not None:
+            limit, cut_code = scene_limit(scene_threshold, h0 // 2, w0), scene_cut_code(t)
+        if gate is not None:
+            if (not isinstance(gate, torch.Tensor) or gate.dtype != torch.int32 or gate.device != self.device
+                    or tuple(gate.shape) != (n,)):
+                raise ValueError(f"gate must be an int32 tensor [{n}] on {self.device}")
+            gate = gate.contiguous()
+        if streams is None:
+            streams = default_streams(self.precision, n)
+        self._poll_range()
+        out = torch.empty((n, 3 * h0 // 2, w0), dtype=torch.uint8, device=self.device)
+        tcoef = t_coefficients(t, n).to(self.device, non_blocking=True)
+        bounds = self._bounds(n, streams, split)
+        tag = "yuv:" + layout + ":" + ",".join(str(v) for v in k)
+        kc = _lib.YuvCoef(*k)
+        sad = None
+        if limit is not None:
+            skey = ("yuv", n, h0, w0, tuple(bounds))
+            have_sad = bool(reuse_flow) and self._sad_key == skey
+            sad, gate = self._gate_buffers(n)
+            self._sad_key = skey
+        else:
+            self._sad_key = None
+        if gate is not None:
+            self.last_gate = gate
+        frame = out.stride(0)
+        with torch.cuda.device(self.device):
+            main = torch.cuda.current_stream(self.device)
+            wss = [self.workspace(hi - lo, h, w, j) for j, (lo, hi) in enumerate(bounds)]
+            for j, (lo, hi) in enumerate(bounds):
+                self._net_scratch(hi - lo, h, w, j)
+            sides = self._side_streams(len(bounds) - 1)
+            for s in sides:
+                s.wait_stream(main)
+            for j, (lo, hi) in enumerate(bounds):
+                st = main if j == 0 else sides[j - 1]
+                m = hi - lo
+                p0, p1, po = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), out[lo:hi].data_ptr()
+                key = (m, h, w, j)
+                d = _lib.NetYuvDesc()
+                nd = d.net
+                nd.n, nd.h, nd.w = m, h, w
+                nd.coef = tcoef[lo:hi].data_ptr()
+                nd.convs = self.conv_table_for(m, h, w)
+                nd.heads = self.head_table
+                nd.workspace, nd.workspace_bytes = wss[j].data_ptr(), wss[j].numel()
+                nd.skip_flow = 1 if bool(reuse_flow) and self._flow_valid.get(key, False) == tag else 0
+                nd.prec = self.prec
+                sc = self._net_scratch(m, h, w, j)
+                if sc is not None:
+                    nd.scratch, nd.scratch_bytes = sc.data_ptr(), sc.numel()
+                status = self._status_of(j) if self.prec in (_lib.PREC_F16X3, _lib.PREC_F16) else None
+                nd.status = status.data_ptr() if status is not None else None
+                d.f0, d.f1 = self._yuv_stack(p0, s0, h0, w0, layout), self._yuv_stack(p1, s0, h0, w0, layout)
+                d.out = self._yuv_stack(po, frame, h0, w0, layout)
+                d.coef, d.h0, d.w0 = kc, h0, w0
+                sp = C.c_void_p(st.cuda_stream)
+                _lib.check(self.lib.rrin_net_yuv_fwd(C.byref(d), sp), "rrin_net_yuv_fwd")
+                # the raw Flow kept in this workspace is that of these frames under this layout
+                # and matrix: no other path, layout or matrix may take it for its previous pair
+                self._flow_valid[key] = tag
+                if status is not None:
+                    self._queue_status(j, st)
+                if gate is None:
+                    continue
+                # the gate of forward_u8 on the frames' bytes: (H0/2) * W0 * 3 of them per frame
+                if sad is not None:
+                    if not have_sad:
+                        _lib.check(self.lib.rrin_pair_sad_u8(p0, p1, s0, m, h0 // 2, w0, sad[lo:hi].data_ptr(), sp),
+                                   "rrin_pair_sad_u8")
+                    _lib.check(self.lib.rrin_gate_from_sad_u8(sad[lo:hi].data_ptr(), m, limit, cut_code,
+                                                              gate[lo:hi].data_ptr(), sp), "rrin_gate_from_sad_u8")
+                _lib.check(self.lib.rrin_gate_frames_u8(p0, p1, s0, m, h0 // 2, w0, gate[lo:hi].data_ptr(), po, sp),
+                           "rrin_gate_frames_u8")
+            for s in sides:
+                main.wait_stream(s)
+        return out
+
+    def pair_stats_yuv(self, f0: torch.Tensor, f1: torch.Tensor) -> torch.Tensor:
+        """The sum of absolute byte differences (luma and chroma) of every pair of two 4:2:0
+        stacks as :meth:`forward_yuv` takes them: a fresh int64 device tensor ``[N]``, exact
+        (rrin_pair_sad_u8 on the frames' bytes) -- what its ``scene_threshold`` compares with
+        ``floor(threshold * H0*W0*3/2)``."""
+        f0, f1, h0, w0, s0 = self._yuv_frames(f0, f1, "pair_stats_yuv")
+        n = f0.shape[0]
+        sad = torch.empty(n, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream(self.device)
+            _lib.check(self.lib.rrin_pair_sad_u8(f0.data_ptr(), f1.data_ptr(), s0, n, h0 // 2, w0, sad.data_ptr(),
+                                                 C.c_void_p(st.cuda_stream)), "rrin_pair_sad_u8")
+        return sad
+
     def unet_forward(self, x: torch.Tensor) -> torch.Tensor:
         """The single packed U-Net (engine built with one unit) on x [N,C,H,W]:
         rrin_unet_fwd, the reference UNet.forward (unet.py:40-51)."""

@@ -143,6 +143,41 @@ class Net(nn.Module):
         with ``floor(threshold * H0*W0*3)``, for callers who pass their own ``gate``."""
         return self.engine().pair_stats_u8(f0, f1)
 
+    def forward_yuv(self, f0, f1, t=0.5, layout="nv12", coef=None, scene_threshold=None, gate=None):
+        """``forward`` on 8-bit YUV 4:2:0 frames, as decoders and video pipes deliver them: uint8
+        ``[N, 3*H0//2, W0]`` in and out on the device (H0, W0 even; ``layout`` "nv12" or "i420").
+        By definition, and bit for bit, ``yuv.rgb_to_yuv420(forward_u8(yuv.yuv420_to_rgb(f0),
+        yuv.yuv420_to_rgb(f1), t))`` with the integer conversions of :mod:`rrin_amd.yuv` (``coef``:
+        ``yuv.coefficients(...)`` or any 15 ints; None is BT.709 limited range), computed inside
+        the input pack and the last head's store: no RGB frame exists on the device
+        (``RRINEngine.forward_yuv``).  Inference-only; not for ``precision='fp32_planar'``.
+
+        The scene gate is ``forward_u8``'s, on the frames' bytes: a gated pair returns its input
+        frame's YUV bytes unchanged.  ``scene_threshold`` is a mean absolute difference over luma
+        and chroma bytes, so not the same number as the RGB path's; no value has been validated
+        on real footage."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("rrin_amd.Net.forward_yuv is inference-only: use torch.no_grad()")
+        return self.engine().forward_yuv(f0, f1, t, layout=layout, coef=coef, streams=self.streams,
+                                         scene_threshold=scene_threshold, gate=gate)
+
+    def interpolate_yuv(self, f0, f1, ts, layout="nv12", coef=None, scene_threshold=None, gate=None):
+        """``[forward_yuv(f0, f1, t) for t in ts]`` with the Flow U-Net (and, with
+        ``scene_threshold``, the pairs' sums of absolute differences) computed once, as
+        :meth:`interpolate_u8`."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("rrin_amd.Net.interpolate_yuv is inference-only: use torch.no_grad()")
+        eng = self.engine()
+        return [eng.forward_yuv(f0, f1, t, layout=layout, coef=coef, reuse_flow=(k > 0), streams=self.streams,
+                                scene_threshold=scene_threshold, gate=gate)
+                for k, t in enumerate(ts)]
+
+    def pair_stats_yuv(self, f0, f1):
+        """int64 device tensor ``[N]``: the sum of absolute byte differences, luma and chroma, of
+        every pair of two 4:2:0 stacks -- what ``forward_yuv``'s ``scene_threshold`` compares with
+        ``floor(threshold * H0*W0*3/2)``."""
+        return self.engine().pair_stats_yuv(f0, f1)
+
     @property
     def last_gate(self):
         """The int32 device codes ``[N]`` of the last gated ``forward_u8`` (0: interpolated, 1:

@@ -1,0 +1,126 @@
+"""YUV4MPEG2 (Y4M) streams of 8-bit 4:2:0 frames: what ``ffmpeg -f yuv4mpegpipe`` writes and reads.
+
+A stream is one header line ``YUV4MPEG2 W<w> H<h> F<num>:<den> [I..] [A..] [C..] [X..]`` and, per
+frame, a line ``FRAME[ params]`` followed by the planes Y, U, V (``w*h*3/2`` bytes for 4:2:0:
+the "i420" layout of :mod:`rrin_amd.yuv`).  Reader and Writer only ever read and write
+sequentially -- no seek, no tell -- so a pipe works as well as a file.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+MAGIC = b"YUV4MPEG2"
+# colour-space tags that are all the 8-bit I420 byte layout (they differ in chroma siting only)
+C420 = ("420", "420jpeg", "420mpeg2", "420paldv")
+_MAX_LINE = 4096
+
+
+def _read_exact(f, n: int) -> np.ndarray:
+    """n bytes of f as a writable uint8 array, or fewer at the end of the stream (a pipe may
+    return short reads, so read until the count is there)."""
+    buf = np.empty(n, dtype=np.uint8)
+    view, got = memoryview(buf), 0
+    while got < n:
+        k = f.readinto(view[got:])
+        if not k:
+            break
+        got += k
+    return buf[:got]
+
+
+def _read_line(f) -> bytes:
+    """One line without its newline, read a byte at a time (no read-ahead: nothing to give back);
+    b"" at the end of the stream."""
+    out = bytearray()
+    while True:
+        b = f.read(1)
+        if not b:
+            if out:
+                raise ValueError("Y4M: the stream ends inside a header line")
+            return b""
+        if b == b"\n":
+            return bytes(out)
+        out += b
+        if len(out) > _MAX_LINE:
+            raise ValueError("Y4M: header line too long (not a Y4M stream?)")
+
+
+class Reader:
+    """Iterates over the frames of a Y4M stream open for binary reading: uint8 arrays of
+    ``height*width*3/2`` bytes (Y, then U, then V).  ``width``, ``height``, ``fps_num``,
+    ``fps_den`` and ``colorspace`` come from the header.  Anything but progressive 8-bit 4:2:0
+    (``C420``, ``C420jpeg``, ``C420mpeg2``, ``C420paldv`` or no ``C`` tag) raises ValueError
+    naming the tag; a frame cut short raises ValueError."""
+
+    def __init__(self, fileobj):
+        self.f = fileobj
+        line = _read_line(fileobj)
+        tags = line.split(b" ")
+        if tags[0] != MAGIC:
+            raise ValueError("not a Y4M stream: the header does not start with YUV4MPEG2")
+        self.width = self.height = None
+        self.fps_num, self.fps_den = 0, 1
+        self.colorspace = "420"
+        for raw in tags[1:]:
+            if not raw:
+                continue
+            tag = raw.decode("ascii", "replace")
+            key, val = tag[0], tag[1:]
+            if key == "W":
+                self.width = int(val)
+            elif key == "H":
+                self.height = int(val)
+            elif key == "F":
+                num, _, den = val.partition(":")
+                self.fps_num, self.fps_den = int(num), int(den or 1)
+            elif key == "I":
+                if val not in ("p", "?"):
+                    raise ValueError(f"Y4M: interlaced streams are not supported (tag {tag!r})")
+            elif key == "C":
+                if val not in C420:
+                    raise ValueError(f"Y4M: only 8-bit 4:2:0 is supported (tag {tag!r})")
+                self.colorspace = val
+            # A (pixel aspect) and X (comments) do not change the bytes
+        if not self.width or not self.height or self.width < 1 or self.height < 1:
+            raise ValueError("Y4M: the header lacks W or H")
+        if self.width % 2 or self.height % 2:
+            raise ValueError(f"Y4M: 4:2:0 frames need even W and H, got {self.width}x{self.height}")
+        self.frame_bytes = self.width * self.height * 3 // 2
+
+    def __iter__(self):
+        return self
+
+    def __next__(self) -> np.ndarray:
+        line = _read_line(self.f)
+        if not line:
+            raise StopIteration
+        if line != b"FRAME" and not line.startswith(b"FRAME "):
+            raise ValueError(f"Y4M: expected a FRAME line, got {line[:32]!r}")
+        data = _read_exact(self.f, self.frame_bytes)
+        if data.size != self.frame_bytes:
+            raise ValueError(f"Y4M: truncated frame ({data.size} of {self.frame_bytes} bytes)")
+        return data
+
+
+class Writer:
+    """Writes a progressive 8-bit 4:2:0 Y4M stream to a file object open for binary writing: the
+    header on construction, then :meth:`write` per frame (``height*width*3/2`` bytes: Y, U, V)."""
+
+    def __init__(self, fileobj, w: int, h: int, fps_num: int, fps_den: int = 1, colorspace: str = "420"):
+        if w < 2 or h < 2 or w % 2 or h % 2:
+            raise ValueError(f"Y4M: 4:2:0 frames need even W and H, got {w}x{h}")
+        if colorspace not in C420:
+            raise ValueError(f"Y4M: only 8-bit 4:2:0 is supported (C{colorspace})")
+        self.f, self.width, self.height = fileobj, int(w), int(h)
+        self.frame_bytes = w * h * 3 // 2
+        fileobj.write(b"%s W%d H%d F%d:%d Ip C%s\n" % (MAGIC, w, h, fps_num, fps_den, colorspace.encode()))
+
+    def write(self, frame) -> None:
+        data = np.ascontiguousarray(frame, dtype=np.uint8).reshape(-1)
+        if data.size != self.frame_bytes:
+            raise ValueError(f"Y4M: a frame is {self.frame_bytes} bytes, got {data.size}")
+        self.f.write(b"FRAME\n")
+        self.f.write(memoryview(data))
+
+    def flush(self) -> None:
+        self.f.flush()

@@ -1,0 +1,148 @@
+"""8-bit YUV 4:2:0 frames (NV12 / I420) and the integer colour conversion of ``Net.forward_yuv``.
+
+The YUV path is *defined* as::
+
+    forward_yuv(f0, f1, t) == rgb_to_yuv420(forward_u8(yuv420_to_rgb(f0), yuv420_to_rgb(f1), t))
+
+with the two conversions of this module: pure int32 arithmetic on Q14 coefficients (``>>`` is the
+arithmetic shift, i.e. floor), no float anywhere, so the same bits on any device.  The HIP kernels
+(``csrc/yuv.hip``, the FINAL head of ``csrc/glue_h8.hip``) compute exactly this without ever
+holding an RGB frame; the functions here are the written definition and the tests' oracle.
+
+A frame stack is uint8 ``[N, 3*H0//2, W0]`` with H0 and W0 even, every frame ``H0*W0*3/2`` dense
+bytes: H0 rows of luma, then
+
+* ``"nv12"``: H0/2 rows of interleaved U, V samples (what hardware decoders emit);
+* ``"i420"``: the U plane, then the V plane, each H0/2 x W0/2 (what Y4M pipes carry), the same
+  byte count laid out in the remaining H0/2 rows.
+
+Chroma is one sample per 2x2 block of pixels, replicated on the way in and the block's mean on
+the way out (no interpolated siting).
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+
+import torch
+
+LAYOUTS = ("nv12", "i420")
+
+Coef = namedtuple("Coef", "y0 ay rv gu gv bu yr yg yb ur ug ub vr vg vb")
+Coef.__doc__ = """The 15 Q14 integers of rrin_yuv_coef (include/rrin_hip.h), in its order: y0, ay, rv,
+gu, gv, bu take YUV to RGB; yr .. vb take RGB to YUV."""
+
+_KR_KB = {"bt709": (0.2126, 0.0722), "bt601": (0.299, 0.114)}
+
+
+def coefficients(standard: str = "bt709", full_range: bool = False) -> Coef:
+    """The coefficients of a standard, ``round(x * 2**14)`` of the matrix its Kr / Kb give, for
+    limited range (Y 16..235, chroma 16..240: the default) or full range.  ``yg``, ``ug`` and
+    ``vg`` are remainders, so that grey maps to U = V = 128 exactly.  ``rrin_yuv_coef_std`` holds
+    the same numbers."""
+    if standard not in _KR_KB:
+        raise ValueError(f"standard must be one of {sorted(_KR_KB)}, got {standard!r}")
+    kr, kb = _KR_KB[standard]
+    kg = 1.0 - kr - kb
+    ys, cs = (1.0, 1.0) if full_range else (219.0 / 255.0, 224.0 / 255.0)
+
+    def q(x):
+        return int(round(x * 16384.0))
+
+    yr, yb = q(kr * ys), q(kb * ys)
+    ur, ub = q(-kr / (2 * (1 - kb)) * cs), q(0.5 * cs)
+    vr, vb = q(0.5 * cs), q(-kb / (2 * (1 - kr)) * cs)
+    return Coef(y0=0 if full_range else 16, ay=q(1.0 / ys),
+                rv=q(2 * (1 - kr) / cs), gu=q(-2 * (1 - kb) * kb / kg / cs), gv=q(-2 * (1 - kr) * kr / kg / cs),
+                bu=q(2 * (1 - kb) / cs),
+                yr=yr, yg=q(ys) - yr - yb, yb=yb, ur=ur, ug=-(ur + ub), ub=ub, vr=vr, vg=-(vr + vb), vb=vb)
+
+
+def as_coef(coef) -> Coef:
+    """``None`` (bt709 limited), a :class:`Coef` or any 15 ints -> a validated :class:`Coef`."""
+    if coef is None:
+        return coefficients()
+    c = Coef(*(int(v) for v in coef))
+    if not 0 <= c.y0 <= 255 or any(abs(v) >= 65536 for v in c[1:]):
+        raise ValueError("yuv coefficients: 0 <= y0 <= 255 and |coefficient| < 2**16")
+    return c
+
+
+def frame_size(frames: torch.Tensor):
+    """(H0, W0) of a uint8 ``[N, 3*H0//2, W0]`` stack; ValueError unless both are even."""
+    if frames.dim() != 3:
+        raise ValueError(f"expected a [N, 3*H0//2, W0] 4:2:0 stack, got {tuple(frames.shape)}")
+    rows, w0 = frames.shape[1], frames.shape[2]
+    if rows < 3 or rows % 3 or w0 < 2 or w0 % 2:
+        raise ValueError(f"4:2:0 needs even H0 and W0: a [N, 3*H0//2, W0] stack, got {tuple(frames.shape)}")
+    return rows // 3 * 2, w0
+
+
+def split_planes(frames: torch.Tensor, layout: str = "nv12"):
+    """Y ``[N,H0,W0]``, U and V ``[N,H0/2,W0/2]`` of a stack (copies, same dtype)."""
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout must be one of {LAYOUTS}, got {layout!r}")
+    h0, w0 = frame_size(frames)
+    n = frames.shape[0]
+    y = frames[:, :h0]
+    c = frames[:, h0:].reshape(n, -1)
+    if layout == "nv12":
+        uv = c.reshape(n, h0 // 2, w0 // 2, 2)
+        return y, uv[..., 0], uv[..., 1]
+    uv = c.reshape(n, 2, h0 // 2, w0 // 2)
+    return y, uv[:, 0], uv[:, 1]
+
+
+def join_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, layout: str = "nv12") -> torch.Tensor:
+    """The inverse of :func:`split_planes`: a dense ``[N, 3*H0//2, W0]`` stack."""
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout must be one of {LAYOUTS}, got {layout!r}")
+    n, h0, w0 = y.shape
+    c = torch.stack((u, v), dim=3 if layout == "nv12" else 1)
+    return torch.cat((y, c.reshape(n, h0 // 2, w0)), dim=1)
+
+
+def yuv420_to_rgb(frames: torch.Tensor, layout: str = "nv12", coef=None) -> torch.Tensor:
+    """uint8 ``[N, 3*H0//2, W0]`` -> uint8 RGB ``[N,H0,W0,3]``.  Per pixel, with the U, V of its
+    2x2 block, c = Y - y0, d = U - 128, e = V - 128::
+
+        R = clip255((ay*c        + rv*e + 8192) >> 14)
+        G = clip255((ay*c + gu*d + gv*e + 8192) >> 14)
+        B = clip255((ay*c + bu*d        + 8192) >> 14)
+    """
+    if frames.dtype != torch.uint8:
+        raise TypeError("4:2:0 frames are uint8")
+    k = as_coef(coef)
+    y, u, v = split_planes(frames, layout)
+    c = (y.to(torch.int32) - k.y0) * k.ay + 8192
+    d = (u.to(torch.int32) - 128).repeat_interleave(2, 1).repeat_interleave(2, 2)
+    e = (v.to(torch.int32) - 128).repeat_interleave(2, 1).repeat_interleave(2, 2)
+    rgb = torch.stack((c + k.rv * e, c + k.gu * d + k.gv * e, c + k.bu * d), dim=3)
+    return (rgb >> 14).clamp_(0, 255).to(torch.uint8)
+
+
+def rgb_to_yuv420(rgb: torch.Tensor, layout: str = "nv12", coef=None) -> torch.Tensor:
+    """uint8 RGB ``[N,H0,W0,3]`` (H0, W0 even) -> uint8 ``[N, 3*H0//2, W0]``.  Per pixel::
+
+        Y = clip255(y0 + ((yr*R + yg*G + yb*B + 8192) >> 14))
+
+    and per 2x2 block, with Rs, Gs, Bs the sums of its four pixels' bytes::
+
+        U = clip255(128 + ((ur*Rs + ug*Gs + ub*Bs + 32768) >> 16))
+        V = clip255(128 + ((vr*Rs + vg*Gs + vb*Bs + 32768) >> 16))
+    """
+    if rgb.dtype != torch.uint8:
+        raise TypeError("RGB frames are uint8")
+    if rgb.dim() != 4 or rgb.shape[3] != 3:
+        raise ValueError(f"expected [N,H0,W0,3] RGB frames, got {tuple(rgb.shape)}")
+    n, h0, w0, _ = rgb.shape
+    if h0 < 2 or w0 < 2 or h0 % 2 or w0 % 2:
+        raise ValueError(f"4:2:0 needs even H0 and W0, got {h0}x{w0}")
+    k = as_coef(coef)
+    p = rgb.to(torch.int32)
+    r, g, b = p[..., 0], p[..., 1], p[..., 2]
+    y = (k.y0 + ((k.yr * r + k.yg * g + k.yb * b + 8192) >> 14)).clamp_(0, 255)
+    s = p.reshape(n, h0 // 2, 2, w0 // 2, 2, 3).sum(dim=(2, 4), dtype=torch.int32)
+    rs, gs, bs = s[..., 0], s[..., 1], s[..., 2]
+    u = (128 + ((k.ur * rs + k.ug * gs + k.ub * bs + 32768) >> 16)).clamp_(0, 255)
+    v = (128 + ((k.vr * rs + k.vg * gs + k.vb * bs + 32768) >> 16)).clamp_(0, 255)
+    return join_planes(y.to(torch.uint8), u.to(torch.uint8), v.to(torch.uint8), layout)
