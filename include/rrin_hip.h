@@ -670,7 +670,13 @@ int rrin_gate_frames_u8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride
  *                    h, w = the low-resolution size.
  *   rrin_twarp_bwd : backward of warp (model.py:8-21; forward = rrin_warp_fwd):
  *                    gimg (scatter, summed exactly in 64-bit fixed point:
- *                    deterministic) and gflow; work >= rrin_twarp_bwd_work_bytes. */
+ *                    deterministic) and gflow; work >= rrin_twarp_bwd_work_bytes.
+ * Codes, all returned before any HIP call: a null required pointer, a dimension < 1
+ * (pool: h or w odd or < 2), leaky with a slope outside (0, 1] or without y, a mode other
+ * than FWD / DGRAD, rrin_tpack_wino's bm not 32 or 64 or mode not 0 or 1: RRIN_E_ARG (the
+ * two size queries return it as their negative value); rrin_tconv3x3 with h * w > 2^31 - 1:
+ * RRIN_E_SHAPE; rrin_twarp_bwd with work_bytes too small: RRIN_E_WORKSPACE.  bias and gb
+ * may be NULL. */
 enum rrin_tconv_mode { RRIN_TCONV_FWD = 0, RRIN_TCONV_DGRAD = 1 };
 typedef struct rrin_tconv_desc {
   int32_t n, cin, cout, h, w;

@@ -173,7 +173,7 @@ __global__ void twgrad_reduce_kernel(const float* __restrict__ part, int slices,
   }
 }
 
-// ---- avg_pool2d(2): y[i][j] = 0.25 ((x00 + x01) + (x10 + x11)) (CPU kernel's order)
+// ---- avg_pool2d(2): y[i][j] = 0.25 (((x00 + x01) + x10) + x11) (CPU kernel's order)
 __global__ void tpool2_fwd_kernel(const float* __restrict__ x, float* y, int h, int w, int64_t total) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;

@@ -100,3 +100,69 @@ def head_h8(src: H8Tensor, dst: H8Tensor, w, b, mode, coef=None, out=None, prec=
     if rc:
         return code
     _lib.check(code, "rrin_head_h8_fwd")
+
+
+# ---- training entry points (csrc/train.hip): contiguous NCHW fp32 device tensors ----
+def nans(shape, dev):
+    """An output buffer no kernel has written: an element left out stays NaN and fails."""
+    return torch.full(tuple(shape), float("nan"), dtype=torch.float32, device=dev)
+
+
+def _p(t):
+    if t is None:
+        return None
+    assert t.is_cuda and t.dtype in (torch.float32, torch.uint8) and t.is_contiguous()
+    return t.data_ptr()
+
+
+def tconv(x, wt, bias=None, *, dgrad=False, leaky=False, slope=0.1, y=None):
+    """rrin_tconv3x3: FWD conv3x3(x, wt) + bias [, leaky]; dgrad: x is g [n][cout][h][w], y the
+    forward output of the leaky mask."""
+    cout, cin = wt.shape[:2]
+    n, _, h, w = x.shape
+    assert x.shape[1] == (cout if dgrad else cin)
+    out = nans((n, cin if dgrad else cout, h, w), x.device)
+    d = _lib.TConvDesc(n=n, cin=cin, cout=cout, h=h, w=w, mode=_lib.TCONV_DGRAD if dgrad else _lib.TCONV_FWD,
+                       leaky=int(leaky), slope=slope, x=_p(x), y=_p(y), wt=_p(wt), bias=_p(bias), out=_p(out))
+    _lib.check(_lib.lib().rrin_tconv3x3(C.byref(d), stream(x.device)), "rrin_tconv3x3")
+    torch.cuda.synchronize(x.device)
+    return out
+
+
+def twgrad(x, g, *, y=None, leaky=False, slope=0.1, bias_grad=True):
+    """rrin_tconv3x3_wgrad -> (gw, gb or None); the work buffer starts as NaN too."""
+    n, cin, h, w = x.shape
+    cout = g.shape[1]
+    nw = int(_lib.lib().rrin_tconv3x3_wgrad_work_floats(n, cin, cout, h, w))
+    assert nw > 0
+    work = nans((nw,), x.device)
+    gw = nans((cout, cin, 3, 3), x.device)
+    gb = nans((cout,), x.device) if bias_grad else None
+    d = _lib.TWgradDesc(n=n, cin=cin, cout=cout, h=h, w=w, leaky=int(leaky), slope=slope, x=_p(x), g=_p(g),
+                        y=_p(y), gw=_p(gw), gb=_p(gb), work=_p(work))
+    _lib.check(_lib.lib().rrin_tconv3x3_wgrad(C.byref(d), stream(x.device)), "rrin_tconv3x3_wgrad")
+    torch.cuda.synchronize(x.device)
+    return gw, gb
+
+
+def tresample(name, src, out_shape):
+    """rrin_tpool2_fwd / _bwd, rrin_tup2_fwd / _bwd on [nc][h][w]; h, w are the sizes of the
+    entry's argument list (pool: the full size, up: the low-resolution size)."""
+    big = src.shape if (src.shape[1] * src.shape[2] > out_shape[1] * out_shape[2]) else out_shape
+    nc, h, w = big if "pool" in name else (big[0], big[1] // 2, big[2] // 2)
+    out = nans(out_shape, src.device)
+    _lib.check(getattr(_lib.lib(), name)(_p(src), _p(out), nc, h, w, stream(src.device)), name)
+    torch.cuda.synchronize(src.device)
+    return out
+
+
+def twarp_bwd(img, flow, gout):
+    """rrin_twarp_bwd -> (gimg, gflow)."""
+    n, c, h, w = img.shape
+    nb = int(_lib.lib().rrin_twarp_bwd_work_bytes(n, c, h, w))
+    work = torch.full((nb,), 0xFF, dtype=torch.uint8, device=img.device)
+    gimg, gflow = nans(img.shape, img.device), nans(flow.shape, img.device)
+    _lib.check(_lib.lib().rrin_twarp_bwd(_p(img), _p(flow), _p(gout), _p(gimg), _p(gflow), _p(work), nb, n, c, h, w,
+                                         stream(img.device)), "rrin_twarp_bwd")
+    torch.cuda.synchronize(img.device)
+    return gimg, gflow
