@@ -15,7 +15,8 @@ Responsibilities (host side only — every FLOP runs in librrin_hip.so):
 from __future__ import annotations
 
 import ctypes as C
-from collections import OrderedDict
+import math
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -402,6 +403,175 @@ def t_coefficients(t, n: int) -> torch.Tensor:
     return c
 
 
+# ---- host-only construction: the walk over the U-Nets, the per-conv schedule, the packing ----
+# No torch device and no engine: tests/test_engine_host.py checks these without a GPU.
+
+def net_units(net):
+    """The Net's four U-Nets in execution order as (name, UNet, first-conv input permutation)."""
+    return [(name, getattr(net, name), FIRST_CONV_PERM[name]) for name in UNET_ORDER]
+
+
+def unit_convs(units):
+    """One walk over ``units``: (body convs, heads) as host fp32 arrays.  A body conv is
+    (w, b, cin, cout, tag, level, perm): level the U-Net level of its output grid, perm the int32
+    input-channel permutation of a unit's first conv, else None.  A head (a unit's ``last`` conv,
+    1x1) is (w, b)."""
+    body, heads = [], []
+    for _, unet, first_perm in units:
+        for idx, (tag, conv) in enumerate(unet.conv_list()):
+            w = conv.weight.detach().to("cpu", torch.float32).contiguous().numpy()
+            b = conv.bias.detach().to("cpu", torch.float32).contiguous().numpy()
+            if tag == "last":
+                heads.append((w, b))
+                continue
+            perm = np.asarray(first_perm, np.int32) if idx == 0 and first_perm is not None else None
+            body.append((w, b, w.shape[1], w.shape[0], tag, _level_of(unet, tag), perm))
+    return body, heads
+
+
+def pack_planar_host(convs):
+    """fp32 planar: the body convs in the MFMA slab layout (rrin_pack_conv3x3) as one fp32 blob of
+    weights and biases, every slab 16-B aligned, and per conv (weight offset, bias offset, cfg) in
+    floats.  Its one blob and its own packer share nothing with the record layouts' pack_h8_host."""
+    L = _lib.lib()
+    blobs, meta, off = [], [], 0
+    for w, b, cin, cout, _, _, perm in convs:
+        cfg = choose_cfg(cin, cout, 0)
+        bm = L.rrin_conv_cfg_bm(cfg)
+        wp = np.empty(L.rrin_pack_conv3x3_floats(cout, cin, bm), np.float32)
+        bp = np.empty(L.rrin_pack_bias_floats(cout, bm), np.float32)
+        _lib.check(L.rrin_pack_conv3x3(w.ctypes.data, b.ctypes.data, cout, cin, bm,
+                                       perm.ctypes.data if perm is not None else None,
+                                       wp.ctypes.data, bp.ctypes.data), "rrin_pack_conv3x3")
+        meta.append((off, off + wp.size, cfg))
+        off += wp.size + bp.size
+        blobs += [wp, bp, np.zeros((-off) % 4, np.float32)]
+        off += (-off) % 4
+    return np.concatenate(blobs), meta
+
+
+def h8_records(convs, subpixel_max_level: int):
+    """The body convs as the record-layout precisions run them: (w, b, cin, cout rows, grid level,
+    perm, edge) per conv.  An up conv whose output level is <= subpixel_max_level becomes a
+    sub-pixel conv on the low-res grid (the upsample folded into phase-combined weights,
+    rrin_subpixel_weights: 4 x cout rows, level + 1); its edge = (raw weights [cin,3,3,cout], raw
+    bias) for the ring fix-up, None for every other conv."""
+    L = _lib.lib()
+    out = []
+    for w, b, cin, cout, tag, level, perm in convs:
+        edge = None
+        if tag.endswith(".up") and level <= subpixel_max_level:
+            level += 1
+            ws = np.empty((4 * cout, cin, 3, 3), np.float32)
+            bs = np.empty(4 * cout, np.float32)
+            _lib.check(L.rrin_subpixel_weights(w.ctypes.data, b.ctypes.data, cout, cin, ws.ctypes.data,
+                                               bs.ctypes.data), "rrin_subpixel_weights")
+            edge = (np.ascontiguousarray(w.transpose(1, 2, 3, 0)), b.copy())
+            w, b, cout = ws, bs, 4 * cout
+        out.append((w, b, cin, cout, level, perm, edge))
+    return out
+
+
+def geom_splits(records, prec: int, h, w) -> tuple:
+    """Per record conv: the geometry rule's split-K slices at image size h x w (exact fp32
+    Winograd; a tuple of 1s elsewhere or without a size)."""
+    if h is None or prec != _lib.PREC_F32R or not WINO:
+        return (1,) * len(records)
+    return tuple(geom_split(cin, cout, h >> level, w >> level) for (_, _, cin, cout, level, _, _) in records)
+
+
+def h8_cfgs(records, prec: int, size: str, geo) -> list:
+    """Per record conv: its tile config in size class ``size`` under the splits ``geo``."""
+    return [choose_cfg_h8(cin, cout, prec, level, size, g)
+            for (_, _, cin, cout, level, _, _), g in zip(records, geo)]
+
+
+def h8_splits(records, cfgs, geo, prec: int) -> list:
+    """Per record conv (ksplit, subpixel) of the ConvWeights table: the split-K slices (exact fp32
+    only, choose_split) and 0 (no sub-pixel conv), 1 (ring fix-up as its own launch) or 2 (ring
+    folded into the conv: RING_FOLD, where the conv can fold)."""
+    L = _lib.lib()
+    f32 = prec == _lib.PREC_F32R
+    out = []
+    for (_, _, _, _, level, _, edge), cfg, g in zip(records, cfgs, geo):
+        k = choose_split(level, cfg, g) if f32 else 0
+        fold = RING_FOLD and f32 and k <= 1 and L.rrin_conv_h8_cfg_wino(cfg) == 3
+        out.append((k, 0 if edge is None else 2 if fold else 1))
+    return out
+
+
+# one packed conv of pack_h8_host: offsets into the weight blob (wlo: the lo halves of split
+# fp16, else None) and the bias blob in elements, whether it has a ring edge, and fuse_next
+PackedConv = namedtuple("PackedConv", "whi wlo bias cfg inv_wscale edge fuse_next")
+
+
+def pack_conv_h8(rec, cfg: int, prec: int):
+    """One record conv packed for tile config ``cfg`` by the library packer of its form: ([weights]
+    or [hi, lo] arrays, padded bias array, inv_wscale).  fp32 records are unscaled fp32 in the
+    direct (r32), Winograd F(2x2,3x3) (wino_bm) or F(4,3)xF(2,3) (wino42, kind 14) layout; the fp16
+    precisions pack scaled halves, direct (h8: [cob][16-ch chunk][tap][half][bm][8], hi and for
+    split fp16 lo) or Winograd U = G g G^T in fp16 (wino_h8, conv_winoh.hip)."""
+    w, b, cin, cout, _, perm, _ = rec
+    L = _lib.lib()
+    bm, kind = L.rrin_conv_h8_cfg_bm(cfg), L.rrin_conv_h8_cfg_wino(cfg)
+    pa = perm.ctypes.data if perm is not None else None
+    bp = np.empty(L.rrin_pack_bias_floats(cout, bm), np.float32)
+    inv = C.c_float(1.0)
+    if prec == _lib.PREC_F32R:
+        if kind == 14:
+            name, size, args = "rrin_pack_conv3x3_wino42", L.rrin_pack_conv3x3_wino42_floats(cout, cin), (pa,)
+        elif kind > 0:
+            name, size, args = "rrin_pack_conv3x3_wino_bm", L.rrin_pack_conv3x3_wino_bm_floats(cout, cin, bm), (bm, pa)
+        else:
+            name, size, args = "rrin_pack_conv3x3_r32", L.rrin_pack_conv3x3_r32_floats(cout, cin, bm), (bm, pa)
+        ws = [np.empty(size, np.float32)]
+        args += (ws[0].ctypes.data, bp.ctypes.data)
+    elif kind > 0:
+        name = "rrin_pack_conv3x3_wino_h8"
+        ws = [np.empty(L.rrin_pack_conv3x3_wino_h8_halves(cout, cin, bm), np.uint16)]
+        args = (bm, pa, ws[0].ctypes.data, bp.ctypes.data, C.byref(inv))
+    else:
+        name = "rrin_pack_conv3x3_h8"
+        nh = L.rrin_pack_conv3x3_h8_halves(cout, cin, bm)
+        ws = [np.empty(nh, np.uint16) for _ in range(2 if prec == _lib.PREC_F16X3 else 1)]
+        args = (bm, pa, prec, ws[0].ctypes.data, ws[1].ctypes.data if len(ws) > 1 else None, bp.ctypes.data,
+                C.byref(inv))
+    _lib.check(getattr(L, name)(w.ctypes.data, b.ctypes.data, cout, cin, *args), name)
+    return ws, bp, inv.value
+
+
+def pack_h8_host(records, cfgs, prec: int):
+    """The record convs packed for the tile configs ``cfgs`` (the block of output channels BM of a
+    conv's config sets its packing): (weight blob -- fp32 for exact fp32, else uint16 halves --,
+    fp32 bias blob, [PackedConv])."""
+    L = _lib.lib()
+    fuse = set()
+    if FUSE_L0 and prec == _lib.PREC_F16:
+        for i in fused_pairs([(cin, cout, level, edge) for (_, _, cin, cout, level, _, edge) in records]):
+            if records[i][2] >= 32 and FUSE_L0 < 2:
+                continue  # the up block's conv_block (cat input): unfused below FUSE_L0 = 2
+            # both convs on direct-form packs (the fused kernel's weights)
+            if not (L.rrin_conv_h8_cfg_wino(cfgs[i]) or L.rrin_conv_h8_cfg_wino(cfgs[i + 1])):
+                fuse.add(i)
+    weights, biases, meta = [], [], []
+    woff = boff = 0
+    for i, (rec, cfg) in enumerate(zip(records, cfgs)):
+        ws, bp, inv = pack_conv_h8(rec, cfg, prec)
+        meta.append(PackedConv(woff, woff + ws[0].size if len(ws) > 1 else None, boff, cfg, inv,
+                               rec[6] is not None, int(i in fuse)))
+        weights += ws
+        woff += sum(a.size for a in ws)
+        biases.append(bp)
+        boff += bp.size
+    return np.concatenate(weights), np.concatenate(biases), meta
+
+
+# the buffers of one forward part, obtained before the fork (RRINEngine._run_parts): key = (pairs,
+# h, w, stream slot), its workspace, conv table, split-K / ring scratch (or None) and fp16 range
+# flag (None for the fp32 precisions)
+Part = namedtuple("Part", "key ws convs scratch status")
+
+
 class RRINEngine:
     # cached workspaces (one per forward part: (pairs, h, w, stream slot)): two shapes at the
     # largest default stream count stay resident together -- an fp16 4-stream forward alone fills 4
@@ -414,12 +584,9 @@ class RRINEngine:
         default the Net's four in execution order (UNET_ORDER, FIRST_CONV_PERM)."""
         self.lib = _lib.lib()
         self.subpixel_max_level = subpixel_max_level
-        if units is None:
-            units = [(name, getattr(net, name), FIRST_CONV_PERM[name]) for name in UNET_ORDER]
-        self.units = units
-        self.expected_convs = sum(2 * u.depth + 1 + 3 * (u.depth - 1) for _, u, _ in units)
-        params = list(net.parameters())
-        self.device = params[0].device
+        self.units = net_units(net) if units is None else units
+        self.expected_convs = sum(2 * u.depth + 1 + 3 * (u.depth - 1) for _, u, _ in self.units)
+        self.device = next(net.parameters()).device
         if self.device.type != "cuda":
             raise RuntimeError("rrin_amd.Net: move the model to a ROCm device (net.cuda()) before "
                                "forward — the HIP kernels are the only implementation")
@@ -427,259 +594,101 @@ class RRINEngine:
             raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}")
         self.precision = precision
         self.prec = _lib.PRECISIONS[precision]
-        L = self.lib
-        blobs, meta = [], []
-        off = 0
-        self.heads_t = []
-        if self.prec != _lib.PREC_F32:
-            self._init_h8(net)
+        convs, heads = unit_convs(self.units)
+        if len(convs) != self.expected_convs:
+            raise RuntimeError(f"packed {len(convs)} convs, expected {self.expected_convs}")
+        self.heads_t = [(self._upload(w), self._upload(b)) for w, b in heads]
+        self.head_table = (_lib.HeadWeights * len(heads))()
+        for i, (w, b) in enumerate(self.heads_t):
+            self.head_table[i].w = w.data_ptr()
+            self.head_table[i].bias = b.data_ptr()
+        self._reset_caches()
+        if self.prec == _lib.PREC_F32:
+            self._levels32 = [level for (_, _, _, _, _, level, _) in convs]  # grid level per body conv
+            self._table32_small = None  # small size class: TH 4 tiles at levels >= 1
+            blob, meta = pack_planar_host(convs)
+            self.blob = self._upload(blob)
+            base = self.blob.data_ptr()
+            self.conv_table = (_lib.ConvWeights * len(meta))()
+            for i, (wo, bo, cfg) in enumerate(meta):
+                self.conv_table[i].wpack = base + 4 * wo
+                self.conv_table[i].bias = base + 4 * bo
+                self.conv_table[i].cfg = cfg
+            self.cfgs = [m[2] for m in meta]
             return
-        self._levels32 = []         # grid level per body conv (fp32 path)
-        self._table32_small = None  # small size class: TH 4 tiles at levels >= 1
-        for name, unet, first_perm in self.units:
-            convs = unet.conv_list()
-            for idx, (tag, conv) in enumerate(convs):
-                w = conv.weight.detach().to("cpu", torch.float32).contiguous().numpy()
-                b = conv.bias.detach().to("cpu", torch.float32).contiguous().numpy()
-                cout, cin = w.shape[0], w.shape[1]
-                if tag == "last":
-                    self.heads_t.append((torch.from_numpy(w.copy()).to(self.device),
-                                         torch.from_numpy(b.copy()).to(self.device)))
-                    continue
-                cfg = choose_cfg(cin, cout, 0)
-                self._levels32.append(_level_of(unet, tag))
-                bm = L.rrin_conv_cfg_bm(cfg)
-                nw = L.rrin_pack_conv3x3_floats(cout, cin, bm)
-                nb = L.rrin_pack_bias_floats(cout, bm)
-                wp = np.empty(nw, np.float32)
-                bp = np.empty(nb, np.float32)
-                perm = first_perm if idx == 0 else None
-                perm_arr = np.asarray(perm, np.int32) if perm is not None else None
-                _lib.check(L.rrin_pack_conv3x3(w.ctypes.data, b.ctypes.data, cout, cin, bm,
-                                               perm_arr.ctypes.data if perm_arr is not None else None,
-                                               wp.ctypes.data, bp.ctypes.data), "rrin_pack_conv3x3")
-                meta.append((off, off + nw, cfg))
-                blobs += [wp, bp]
-                off += nw + nb
-                # keep 16-B alignment of every slab
-                pad = (-off) % 4
-                if pad:
-                    blobs.append(np.zeros(pad, np.float32))
-                    off += pad
-        if len(meta) != self.expected_convs:
-            raise RuntimeError(f"packed {len(meta)} convs, expected {self.expected_convs}")
-        self.blob = torch.from_numpy(np.concatenate(blobs)).to(self.device)
-        base = self.blob.data_ptr()
-        self.conv_table = (_lib.ConvWeights * len(meta))()
-        for i, (wo, bo, cfg) in enumerate(meta):
-            self.conv_table[i].wpack = base + 4 * wo
-            self.conv_table[i].bias = base + 4 * bo
-            self.conv_table[i].cfg = cfg
-        self.head_table = (_lib.HeadWeights * len(self.heads_t))()
-        for i, (w, b) in enumerate(self.heads_t):
-            self.head_table[i].w = w.data_ptr()
-            self.head_table[i].bias = b.data_ptr()
-        self.cfgs = [m[2] for m in meta]
-        self._scratch = {}
-        self._ws = OrderedDict()
-        self._flow_valid = {}
-        self._sides = []
-        self._status = {}
-        self._pending_status = []
-        self._graphs = {}
-        self.last_gate = None
-
-    def _init_h8(self, net):
-        """Pack for the split-fp16 (F16X3) or fp16 (F16) path: [cob][16-ch chunk][tap][half][bm][8]
-        halves (rrin_pack_conv3x3_h8), one device blob of halves + one of fp32 biases per
-        tile-table size class (the block of output channels BM of a conv's tile config sets
-        its packing); the "large" class is packed here, the others on first use."""
-        L = self.lib
-        self.edge_t = []  # device tensors referenced by the tables (sub-pixel convs)
-        self._h8_convs = []  # (w, b, cin, cout rows, grid level, first-conv perm, edge) per body conv
-        for name, unet, first_perm in self.units:
-            for idx, (tag, conv) in enumerate(unet.conv_list()):
-                w = conv.weight.detach().to("cpu", torch.float32).contiguous().numpy()
-                b = conv.bias.detach().to("cpu", torch.float32).contiguous().numpy()
-                cout, cin = w.shape[0], w.shape[1]
-                if tag == "last":
-                    self.heads_t.append((torch.from_numpy(w.copy()).to(self.device),
-                                         torch.from_numpy(b.copy()).to(self.device)))
-                    continue
-                edge = None
-                level = _level_of(unet, tag)
-                if tag.endswith(".up") and level <= self.subpixel_max_level:
-                    level += 1  # runs on the low-res grid
-                    # upsample folded into phase-combined weights (rrin_subpixel_weights)
-                    ws = np.empty((4 * cout, cin, 3, 3), np.float32)
-                    bs = np.empty(4 * cout, np.float32)
-                    _lib.check(L.rrin_subpixel_weights(w.ctypes.data, b.ctypes.data, cout, cin, ws.ctypes.data,
-                                                       bs.ctypes.data), "rrin_subpixel_weights")
-                    edge = (torch.from_numpy(np.ascontiguousarray(w.transpose(1, 2, 3, 0))).to(self.device),
-                            torch.from_numpy(b.copy()).to(self.device))
-                    self.edge_t.append(edge)
-                    w, b, cout = ws, bs, 4 * cout
-                perm = first_perm if idx == 0 else None
-                perm_arr = np.asarray(perm, np.int32) if perm is not None else None
-                self._h8_convs.append((w, b, cin, cout, level, perm_arr, edge))
-        if len(self._h8_convs) != self.expected_convs:
-            raise RuntimeError(f"packed {len(self._h8_convs)} convs, expected {self.expected_convs}")
-        self._block0 = fused_pairs([(cin, cout, level, edge) for (_, _, cin, cout, level, _, edge) in self._h8_convs])
-        self.head_table = (_lib.HeadWeights * len(self.heads_t))()
-        for i, (w, b) in enumerate(self.heads_t):
-            self.head_table[i].w = w.data_ptr()
-            self.head_table[i].bias = b.data_ptr()
-        self._packs = {}          # size class -> packing
+        # split fp16 (F16X3), fp16 (F16) and fp32 records (F32R): one device blob of packed weights
+        # and one of fp32 biases per set of tile configs; the "large" size class is packed here,
+        # the others on first use (_pack_h8)
+        self._h8_convs = h8_records(convs, subpixel_max_level)
+        # device tensors the tables point to: the raw weights and bias of every sub-pixel conv
+        self.edge_t = [None if r[6] is None else (self._upload(r[6][0]), self._upload(r[6][1]))
+                       for r in self._h8_convs]
+        self._packs = {}          # (size class, geometry splits, FUSE_L0) -> packing
         self._packs_by_cfgs = {}  # tuple of per-conv configs -> packing (shared between classes)
         _, _, self.conv_table, self.cfgs = self._pack_h8("large", None, None)
-        self._scratch = {}
-        self._ws = OrderedDict()
-        self._flow_valid = {}
-        self._sides = []
-        self._graphs = {}
+
+    def _upload(self, a: np.ndarray) -> torch.Tensor:
+        return torch.from_numpy(a).to(self.device)
+
+    def _reset_caches(self):
+        self._scratch = {}          # (part key, conv table address) -> scratch or None
+        self._ws = OrderedDict()    # part key -> workspace, least recently used first
+        self._flow_valid = {}       # part key -> tag of the path whose raw Flow the workspace keeps
+        self._sides = []            # side streams
+        self._graphs = {}           # (n, h, w, bounds) -> NetGraph
         self._status = {}           # slot -> device int32 range flag (fp16-stored precisions)
         self._pending_status = []   # (event, pinned host copy) of flags not checked yet
         self._gate_bufs = {}        # pairs -> (int64 sums, int32 codes) of the scene gate
-        self._sad_key = None        # (pairs, h0, w0, parts) whose sums the buffers hold
-        self.last_gate = None       # int32 device codes of the last gated forward_u8
-
-    def _geom_splits(self, h, w):
-        """Per body conv: the geometry rule's split-K slices at image size h x w (exact fp32
-        Winograd; a tuple of 1s elsewhere or without a size)."""
-        if h is None or self.prec != _lib.PREC_F32R or not WINO:
-            return (1,) * len(self._h8_convs)
-        return tuple(geom_split(cin, cout, h >> level, w >> level)
-                     for (_, _, cin, cout, level, _, _) in self._h8_convs)
+        self._sad_key = None        # (path, pairs, byte rows, byte columns, parts) whose sums the buffers hold
+        self.last_gate = None       # int32 device codes of the last gated forward_u8 / forward_yuv
 
     def _pack_h8(self, size: str, h: int = None, w: int = None):
-        """(halves blob, bias blob, ConvWeights table, cfgs) of size class ``size`` at image
+        """(weight blob, bias blob, ConvWeights table, cfgs) of size class ``size`` at image
         size h x w (the split-K geometry; None: no split), cached; classes / geometries
         whose tile configs agree share one packing."""
-        geo = self._geom_splits(h, w)
+        geo = geom_splits(self._h8_convs, self.prec, h, w)
         key = (size, geo, FUSE_L0)
         p = self._packs.get(key)
-        if p is not None:
-            return p
-        L = self.lib
-        cfgs = [choose_cfg_h8(cin, cout, self.prec, level, size, g)
-                for (_, _, cin, cout, level, _, _), g in zip(self._h8_convs, geo)]
-        ckey = (tuple(cfgs), FUSE_L0)
-        p = self._packs_by_cfgs.get(ckey)
-        if p is not None:
-            self._packs[key] = self._with_splits(p, geo)
-            return self._packs[key]
-        halves, biases, meta = [], [], []
-        hoff = boff = 0
-        f32 = self.prec == _lib.PREC_F32R
-        for (w, b, cin, cout, level, perm_arr, edge), cfg in zip(self._h8_convs, cfgs):
-            bm = L.rrin_conv_h8_cfg_bm(cfg)
-            if f32:  # fp32 records: unscaled fp32 weights (offsets in floats)
-                bp = np.empty(L.rrin_pack_bias_floats(cout, bm), np.float32)
-                pa = perm_arr.ctypes.data if perm_arr is not None else None
-                if L.rrin_conv_h8_cfg_wino(cfg) == 14:  # Winograd F(4,3) x F(2,3)
-                    wp = np.empty(L.rrin_pack_conv3x3_wino42_floats(cout, cin), np.float32)
-                    _lib.check(L.rrin_pack_conv3x3_wino42(w.ctypes.data, b.ctypes.data, cout, cin, pa,
-                                                          wp.ctypes.data, bp.ctypes.data), "rrin_pack_conv3x3_wino42")
-                elif L.rrin_conv_h8_cfg_wino(cfg) > 0:  # Winograd F(2x2,3x3): transformed weights
-                    wp = np.empty(L.rrin_pack_conv3x3_wino_bm_floats(cout, cin, bm), np.float32)
-                    _lib.check(L.rrin_pack_conv3x3_wino_bm(w.ctypes.data, b.ctypes.data, cout, cin, bm, pa,
-                                                           wp.ctypes.data, bp.ctypes.data), "rrin_pack_conv3x3_wino_bm")
-                else:
-                    wp = np.empty(L.rrin_pack_conv3x3_r32_floats(cout, cin, bm), np.float32)
-                    _lib.check(L.rrin_pack_conv3x3_r32(w.ctypes.data, b.ctypes.data, cout, cin, bm, pa,
-                                                       wp.ctypes.data, bp.ctypes.data), "rrin_pack_conv3x3_r32")
-                meta.append((hoff, None, boff, cfg, 1.0, edge))
-                halves.append(wp)
-                hoff += wp.size
-                biases.append(bp)
-                boff += bp.size
-                continue
-            if L.rrin_conv_h8_cfg_wino(cfg) > 0:  # fp16 Winograd: U = G g G^T in fp16 (conv_winoh.hip)
-                nh = L.rrin_pack_conv3x3_wino_h8_halves(cout, cin, bm)
-                whi = np.empty(nh, np.uint16)
-                bp = np.empty(L.rrin_pack_bias_floats(cout, bm), np.float32)
-                inv = C.c_float()
-                _lib.check(L.rrin_pack_conv3x3_wino_h8(
-                    w.ctypes.data, b.ctypes.data, cout, cin, bm,
-                    perm_arr.ctypes.data if perm_arr is not None else None, whi.ctypes.data, bp.ctypes.data,
-                    C.byref(inv)), "rrin_pack_conv3x3_wino_h8")
-                meta.append((hoff, None, boff, cfg, inv.value, edge))
-                halves.append(whi)
-                hoff += nh
-                biases.append(bp)
-                boff += bp.size
-                continue
-            nh = L.rrin_pack_conv3x3_h8_halves(cout, cin, bm)
-            whi = np.empty(nh, np.uint16)
-            wlo = np.empty(nh, np.uint16) if self.prec == _lib.PREC_F16X3 else None
-            bp = np.empty(L.rrin_pack_bias_floats(cout, bm), np.float32)
-            inv = C.c_float()
-            _lib.check(L.rrin_pack_conv3x3_h8(
-                w.ctypes.data, b.ctypes.data, cout, cin, bm,
-                perm_arr.ctypes.data if perm_arr is not None else None, self.prec, whi.ctypes.data,
-                wlo.ctypes.data if wlo is not None else None, bp.ctypes.data, C.byref(inv)),
-                "rrin_pack_conv3x3_h8")
-            meta.append((hoff, hoff + nh if wlo is not None else None, boff, cfg, inv.value, edge))
-            halves.append(whi)
-            hoff += nh
-            if wlo is not None:
-                halves.append(wlo)
-                hoff += nh
-            biases.append(bp)
-            boff += bp.size
-        elem = 4 if f32 else 2  # bytes per packed weight
-        cat = np.concatenate(halves)
-        blob = torch.from_numpy(cat if f32 else cat.view(np.int16)).to(self.device)
-        bias_blob = torch.from_numpy(np.concatenate(biases)).to(self.device)
-        hb, bb = blob.data_ptr(), bias_blob.data_ptr()
+        if p is None:
+            cfgs = h8_cfgs(self._h8_convs, self.prec, size, geo)
+            ckey = (tuple(cfgs), FUSE_L0)
+            base = self._packs_by_cfgs.get(ckey)
+            if base is None:
+                base = self._packs_by_cfgs[ckey] = self._upload_h8(cfgs)
+            p = self._packs[key] = self._with_splits(base, geo)
+        return p
+
+    def _upload_h8(self, cfgs):
+        """pack_h8_host on the device: the two blobs and the ConvWeights table that points into them."""
+        weights, biases, meta = pack_h8_host(self._h8_convs, cfgs, self.prec)
+        blob = self._upload(weights.view(np.int16) if weights.dtype == np.uint16 else weights)
+        bias_blob = self._upload(biases)
+        hb, bb, elem = blob.data_ptr(), bias_blob.data_ptr(), weights.itemsize
         table = (_lib.ConvWeights * len(meta))()
-        for i, (ho, lo, bo, cfg, inv, edge) in enumerate(meta):
+        for i, m in enumerate(meta):
             e = table[i]
-            e.whi = hb + elem * ho
-            e.wlo = hb + elem * lo if lo is not None else None
-            e.bias = bb + 4 * bo
-            e.cfg = cfg
-            e.inv_wscale = inv
-            if edge is not None:
+            e.whi = hb + elem * m.whi
+            e.wlo = hb + elem * m.wlo if m.wlo is not None else None
+            e.bias = bb + 4 * m.bias
+            e.cfg, e.inv_wscale, e.fuse_next = m.cfg, m.inv_wscale, m.fuse_next
+            if m.edge:
                 e.subpixel = 1
-                e.wedge = edge[0].data_ptr()
-                e.bias_raw = edge[1].data_ptr()
-        if FUSE_L0 and self.prec == _lib.PREC_F16:
-            for i in self._block0:  # both convs on direct-form packs (the fused kernel's weights)
-                if self._h8_convs[i][2] >= 32 and FUSE_L0 < 2:
-                    continue  # the up block's conv_block (cat input): unfused below FUSE_L0 = 2
-                if not (L.rrin_conv_h8_cfg_wino(cfgs[i]) or L.rrin_conv_h8_cfg_wino(cfgs[i + 1])):
-                    table[i].fuse_next = 1
-        p = (blob, bias_blob, table, cfgs)
-        self._packs_by_cfgs[ckey] = p
-        self._packs[key] = self._with_splits(p, geo)
-        return self._packs[key]
+                e.wedge, e.bias_raw = (t.data_ptr() for t in self.edge_t[i])
+        return blob, bias_blob, table, cfgs
 
     def _with_splits(self, p, geo):
-        """The packing p with the split-K slices of geometry ``geo`` (per conv) set in a
-        copy of its ConvWeights table (the weight blobs stay shared)."""
-        if self.prec != _lib.PREC_F32R:
-            return p
+        """The packing p with the split-K slices and ring-fold marks of geometry ``geo`` (h8_splits):
+        p itself where its table already says so, else a copy of the table (the weight blobs
+        stay shared)."""
         blob, bias_blob, table, cfgs = p
-        ks = [choose_split(level, cfg, g)
-              for (_, _, cin, cout, level, _, _), cfg, g in zip(self._h8_convs, cfgs, geo)]
-        if not any(ks):
-            self._set_fold(table, cfgs)
+        ks = h8_splits(self._h8_convs, cfgs, geo, self.prec)
+        if all((table[i].ksplit, table[i].subpixel) == s for i, s in enumerate(ks)):
             return p
         t2 = (_lib.ConvWeights * len(table))()
         C.memmove(t2, table, C.sizeof(table))
-        for i, k in enumerate(ks):
-            t2[i].ksplit = k
-        self._set_fold(t2, cfgs)
+        for i, (k, sub) in enumerate(ks):
+            t2[i].ksplit, t2[i].subpixel = k, sub
         return (blob, bias_blob, t2, cfgs)
-
-    def _set_fold(self, table, cfgs):
-        """subpixel = 2 (ring folded into the conv) where the conv can fold, else 1."""
-        for i, cfg in enumerate(cfgs):
-            if table[i].subpixel:
-                fold = (RING_FOLD and self.prec == _lib.PREC_F32R and table[i].ksplit <= 1
-                        and self.lib.rrin_conv_h8_cfg_wino(cfg) == 3)
-                table[i].subpixel = 2 if fold else 1
 
     force_size_class = None  # A/B knob: use this tile-table class for every forward part
 
@@ -749,12 +758,16 @@ class RRINEngine:
         self._scratch[sk] = sc
         return sc
 
-    def _net_scratch(self, n: int, h: int, w: int, slot: int):
+    def _net_scratch(self, n: int, h: int, w: int, slot: int, convs=None):
         """The scratch of Net forward part (n, h, w, slot) for its conv table (cached)."""
+        convs = self.conv_table_for(n, h, w) if convs is None else convs
+        sk = ((n, h, w, slot), C.addressof(convs))
+        if sk in self._scratch:
+            return self._scratch[sk]
         d = _lib.NetDesc()
         d.n, d.h, d.w, d.prec = n, h, w, self.prec
-        d.convs = self.conv_table_for(n, h, w)
-        return self.scratch((n, h, w, slot), d, self.lib.rrin_net_scratch_bytes)
+        d.convs = convs
+        return self.scratch(sk[0], d, self.lib.rrin_net_scratch_bytes)
 
     side_priority = 0  # torch.cuda.Stream priority of the side streams (-1: high)
 
@@ -790,15 +803,12 @@ class RRINEngine:
         if h % 16 or w % 16 or n < 1:
             raise RuntimeError(f"H and W must be multiples of 16 (the Flow U-Net pools 4 times); "
                                f"got {h}x{w} (reference fails at model.py:41)")
-        if streams is None:
-            streams = default_streams(self.precision, n)
         self._poll_range()
         i0 = i0.contiguous()
         i1 = i1.contiguous()
         out = torch.empty_like(i0)
         coef = t_coefficients(t, n).to(self.device, non_blocking=True)
         bounds = self._bounds(n, streams, split)
-        k = len(bounds)
         tapbuf = None
         if taps is not None:
             if len(bounds) != 1:
@@ -806,22 +816,14 @@ class RRINEngine:
             if reuse_flow:
                 raise ValueError("taps need the Flow U-Net to run (reuse_flow=False)")
             tapbuf = torch.full((13 * n * h * w,), float("nan"), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            main = torch.cuda.current_stream(self.device)
-            # workspaces and split scratch first: a new one is zero-filled on the main stream,
-            # before the fork (a side stream only waits for what main enqueued before it)
-            wss = [self.workspace(hi - lo, h, w, j) for j, (lo, hi) in enumerate(bounds)]
-            for j, (lo, hi) in enumerate(bounds):
-                self._net_scratch(hi - lo, h, w, j)
-            sides = self._side_streams(k - 1)
-            for s in sides:
-                s.wait_stream(main)
-            for j, (lo, hi) in enumerate(bounds):
-                st = main if j == 0 else sides[j - 1]
-                self._forward_part(i0[lo:hi], i1[lo:hi], out[lo:hi], coef[lo:hi], j, wss[j], st, prof, reuse_flow,
-                                   tapbuf)
-            for s in sides:
-                main.wait_stream(s)
+
+        def part(j, lo, hi, stream, p):
+            d = self._float_desc(p, i0[lo:hi], i1[lo:hi], out[lo:hi], coef[lo:hi])
+            d.prof = prof
+            d.taps = tapbuf.data_ptr() if tapbuf is not None else None
+            self._launch(self.lib.rrin_net_fwd, "rrin_net_fwd", d, d, p, "f32", reuse_flow, stream)
+
+        self._run_parts(h, w, bounds, part)
         if tapbuf is not None:
             off = 0
             for name, c in zip(UNET_ORDER, (4, 4, 2, 3)):
@@ -829,31 +831,99 @@ class RRINEngine:
                 off += n * c * h * w
         return out
 
-    def _u8_frames(self, f0, f1, what):
-        """Checks two uint8 [N,H0,W0,3] frame stacks of ``what`` and returns them with the bytes
-        between their frames: every frame dense, a uniform stride over dim 0 taken as it is
-        (``frames[:-1]`` / ``frames[1:]`` of one stack need no copy), anything else copied."""
+    def _frames(self, f0, f1, what: str, rgb: bool):
+        """Checks two uint8 frame stacks of ``what`` -- ``[N,H0,W0,3]`` (``rgb``) or 4:2:0
+        ``[N, 3*H0//2, W0]`` -- and returns them with (H0, W0) and the bytes between their frames:
+        every frame dense, a uniform stride over dim 0 taken as it is (``frames[:-1]`` /
+        ``frames[1:]`` of one stack need no copy), anything else copied."""
+        if not isinstance(f0, torch.Tensor) or not isinstance(f1, torch.Tensor):
+            raise TypeError(f"{what} takes two uint8 tensors")
         if f0.device != self.device or f1.device != self.device:
             raise RuntimeError(f"inputs on {f0.device}/{f1.device}, model on {self.device}")
         if f0.dtype != torch.uint8 or f1.dtype != torch.uint8:
             raise TypeError(f"{what} takes uint8 frames (forward takes float32)")
-        if f0.dim() != 4 or f0.shape != f1.shape or f0.shape[3] != 3:
-            raise ValueError(f"expected two [N,H0,W0,3] uint8 tensors, got {tuple(f0.shape)} / {tuple(f1.shape)}")
-        n, h0, w0, _ = f0.shape
+        if rgb:
+            if f0.dim() != 4 or f0.shape != f1.shape or f0.shape[3] != 3:
+                raise ValueError(f"expected two [N,H0,W0,3] uint8 tensors, got {tuple(f0.shape)} / {tuple(f1.shape)}")
+            h0, w0 = f0.shape[1:3]
+        else:
+            from . import yuv
+            if f0.shape != f1.shape:
+                raise ValueError(f"expected two equal [N, 3*H0//2, W0] stacks, got {tuple(f0.shape)} / "
+                                 f"{tuple(f1.shape)}")
+            h0, w0 = yuv.frame_size(f0)
+        n = f0.shape[0]
         if n < 1 or h0 < 1 or w0 < 1:
             raise ValueError(f"empty frames: {tuple(f0.shape)}")
-        frame = h0 * w0 * 3
+        frame = math.prod(f0.shape[1:])
 
         def stride_of(f):  # bytes between frames, or None if f needs a copy
-            if f.stride(3) != 1 or (w0 > 1 and f.stride(2) != 3) or (h0 > 1 and f.stride(1) != 3 * w0):
-                return None
+            dense = 1
+            for d in range(f.dim() - 1, 0, -1):  # the trailing dims: dense (a dim of 1 has no stride to check)
+                if f.shape[d] > 1 and f.stride(d) != dense:
+                    return None
+                dense *= f.shape[d]
             return frame if n == 1 else (f.stride(0) if f.stride(0) >= frame else None)
 
         s0, s1 = stride_of(f0), stride_of(f1)
         if s0 is None or s0 != s1:
             f0, f1 = f0.contiguous(), f1.contiguous()
             s0 = frame
-        return f0, f1, s0
+        return f0, f1, h0, w0, s0
+
+    def _scene_gate(self, path: str, n: int, rows: int, cols: int, t, bounds, reuse_flow, scene_threshold, gate):
+        """The scene gate of a byte-frame forward whose frames are ``rows x cols x 3`` bytes each
+        (RGB: H0 x W0; 4:2:0: H0/2 x W0).  Checks ``scene_threshold`` against ``gate`` and the gate
+        tensor, keeps :attr:`last_gate` and the key of the cached sums, and returns None (gate
+        off) or (sums or None, sums already there, limit, cut code, codes) for _enqueue_gate.
+        Changes state, so it runs after everything else that may refuse the call."""
+        if scene_threshold is not None and gate is not None:
+            raise ValueError("scene_threshold and gate exclude each other")
+        sad, have_sad, limit, cut_code = None, False, None, None
+        if scene_threshold is not None:
+            limit, cut_code = scene_limit(scene_threshold, rows, cols), scene_cut_code(t)
+            # the sums belong to the batch and its split: kept for the next t of the same pairs
+            skey = (path, n, rows, cols, tuple(bounds))
+            have_sad = bool(reuse_flow) and self._sad_key == skey
+            sad, gate = self._gate_buffers(n)
+            self._sad_key = skey
+        else:
+            if gate is not None:
+                if (not isinstance(gate, torch.Tensor) or gate.dtype != torch.int32 or gate.device != self.device
+                        or tuple(gate.shape) != (n,)):
+                    raise ValueError(f"gate must be an int32 tensor [{n}] on {self.device}")
+                gate = gate.contiguous()
+            self._sad_key = None  # the next call's pairs need not be these
+        if gate is None:
+            return None
+        self.last_gate = gate
+        return sad, have_sad, limit, cut_code, gate
+
+    def _enqueue_gate(self, g, p0: int, p1: int, img_stride: int, lo: int, hi: int, rows: int, cols: int, out: int,
+                      stream):
+        """The gate kernels of pairs [lo, hi) on ``stream``, behind the part's forward: the sums
+        (unless kept), the codes from the sums (unless given), the copy of the gated frames from
+        the frames at p0 / p1 (``rows x cols x 3`` bytes each) over those at ``out``."""
+        sad, have_sad, limit, cut_code, codes = g
+        sp, m = C.c_void_p(stream.cuda_stream), hi - lo
+        cp = codes[lo:hi].data_ptr()
+        if sad is not None:
+            sums = sad[lo:hi].data_ptr()
+            if not have_sad:
+                _lib.check(self.lib.rrin_pair_sad_u8(p0, p1, img_stride, m, rows, cols, sums, sp), "rrin_pair_sad_u8")
+            _lib.check(self.lib.rrin_gate_from_sad_u8(sums, m, limit, cut_code, cp, sp), "rrin_gate_from_sad_u8")
+        _lib.check(self.lib.rrin_gate_frames_u8(p0, p1, img_stride, m, rows, cols, cp, out, sp),
+                   "rrin_gate_frames_u8")
+
+    def _pair_sad(self, f0, f1, img_stride: int, rows: int, cols: int) -> torch.Tensor:
+        """rrin_pair_sad_u8 of two checked stacks on the current stream: a fresh int64 ``[N]``."""
+        n = f0.shape[0]
+        sad = torch.empty(n, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream(self.device)
+            _lib.check(self.lib.rrin_pair_sad_u8(f0.data_ptr(), f1.data_ptr(), img_stride, n, rows, cols,
+                                                 sad.data_ptr(), C.c_void_p(st.cuda_stream)), "rrin_pair_sad_u8")
+        return sad
 
     def forward_u8(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, reuse_flow: bool = False,
                    streams: int | None = None, split=None, scene_threshold=None, gate=None) -> torch.Tensor:
@@ -886,66 +956,35 @@ class RRINEngine:
         skipping it would need the codes on the host, a device-to-host sync per step.  The range
         guard does not look at the gate: a gated frame is the copied input even when its pair
         overflowed, and ``check_range`` still raises."""
-        if self.prec == _lib.PREC_F32:
-            raise RuntimeError("forward_u8 needs a record-layout precision: 'fp32', 'fp32_split16' or 'fp16' "
-                               "(not 'fp32_planar')")
-        f0, f1, s0 = self._u8_frames(f0, f1, "forward_u8")
-        n, h0, w0, _ = f0.shape
+        self._need_records("forward_u8")
+        f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_u8", rgb=True)
+        n = f0.shape[0]
         h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
-        if scene_threshold is not None and gate is not None:
-            raise ValueError("scene_threshold and gate exclude each other")
-        limit = cut_code = None
-        if scene_threshold is not None:
-            limit, cut_code = scene_limit(scene_threshold, h0, w0), scene_cut_code(t)
-        if gate is not None:
-            if (not isinstance(gate, torch.Tensor) or gate.dtype != torch.int32 or gate.device != self.device
-                    or tuple(gate.shape) != (n,)):
-                raise ValueError(f"gate must be an int32 tensor [{n}] on {self.device}")
-            gate = gate.contiguous()
-        if streams is None:
-            streams = default_streams(self.precision, n)
         self._poll_range()
-        out = torch.empty((n, h0, w0, 3), dtype=torch.uint8, device=self.device)
         coef = t_coefficients(t, n).to(self.device, non_blocking=True)
         bounds = self._bounds(n, streams, split)
-        sad = None
-        if limit is not None:
-            # the sums belong to the batch and its split: kept for the next t of the same pairs
-            skey = (n, h0, w0, tuple(bounds))
-            have_sad = bool(reuse_flow) and self._sad_key == skey
-            sad, gate = self._gate_buffers(n)
-            self._sad_key = skey
-        else:
-            self._sad_key = None  # the next call's pairs need not be these
-        if gate is not None:
-            self.last_gate = gate
-        with torch.cuda.device(self.device):
-            main = torch.cuda.current_stream(self.device)
-            wss = [self.workspace(hi - lo, h, w, j) for j, (lo, hi) in enumerate(bounds)]
-            for j, (lo, hi) in enumerate(bounds):
-                self._net_scratch(hi - lo, h, w, j)
-            sides = self._side_streams(len(bounds) - 1)
-            for s in sides:
-                s.wait_stream(main)
-            for j, (lo, hi) in enumerate(bounds):
-                st = main if j == 0 else sides[j - 1]
-                self._forward_part_u8(f0[lo:hi], f1[lo:hi], s0, out[lo:hi], coef[lo:hi], h, w, j, wss[j], st,
-                                      reuse_flow)
-                if gate is None:
-                    continue
-                sp = C.c_void_p(st.cuda_stream)
-                p0, p1, m = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), hi - lo
-                if sad is not None:
-                    if not have_sad:
-                        _lib.check(self.lib.rrin_pair_sad_u8(p0, p1, s0, m, h0, w0, sad[lo:hi].data_ptr(), sp),
-                                   "rrin_pair_sad_u8")
-                    _lib.check(self.lib.rrin_gate_from_sad_u8(sad[lo:hi].data_ptr(), m, limit, cut_code,
-                                                              gate[lo:hi].data_ptr(), sp), "rrin_gate_from_sad_u8")
-                _lib.check(self.lib.rrin_gate_frames_u8(p0, p1, s0, m, h0, w0, gate[lo:hi].data_ptr(),
-                                                        out[lo:hi].data_ptr(), sp), "rrin_gate_frames_u8")
-            for s in sides:
-                main.wait_stream(s)
+        g = self._scene_gate("u8", n, h0, w0, t, bounds, reuse_flow, scene_threshold, gate)
+        out = torch.empty((n, h0, w0, 3), dtype=torch.uint8, device=self.device)
+
+        def part(j, lo, hi, stream, p):
+            d = _lib.NetU8Desc()
+            self._fill_net(d.net, p, coef[lo:hi])
+            p0, p1, po = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), out[lo:hi].data_ptr()
+            d.f0, d.f1, d.img_stride, d.out_u8 = p0, p1, s0, po
+            d.h0, d.w0 = h0, w0
+            # the raw Flow kept in the workspace is that of 8-bit frames: forward(reuse_flow=True)
+            # must not take it for its own previous pair, nor forward_u8 the float path's
+            self._launch(self.lib.rrin_net_u8_fwd, "rrin_net_u8_fwd", d, d.net, p, "u8", reuse_flow, stream)
+            if g is not None:
+                self._enqueue_gate(g, p0, p1, s0, lo, hi, h0, w0, po, stream)
+
+        self._run_parts(h, w, bounds, part)
         return out
+
+    def _need_records(self, what: str):
+        if self.prec == _lib.PREC_F32:
+            raise RuntimeError(f"{what} needs a record-layout precision: 'fp32', 'fp32_split16' or 'fp16' "
+                               "(not 'fp32_planar')")
 
     def _gate_buffers(self, n: int):
         """The cached device buffers of the scene gate for a batch of n pairs: int64 sums of
@@ -963,75 +1002,10 @@ class RRINEngine:
         """The sum of absolute byte differences of every pair of two uint8 ``[N,H0,W0,3]`` stacks
         (as :meth:`forward_u8` takes them): a fresh int64 device tensor ``[N]``, exact, enqueued
         on the current stream (rrin_pair_sad_u8) -- for a caller with its own rule for ``gate``."""
-        f0, f1, s0 = self._u8_frames(f0, f1, "pair_stats_u8")
-        n, h0, w0, _ = f0.shape
-        sad = torch.empty(n, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            st = torch.cuda.current_stream(self.device)
-            _lib.check(self.lib.rrin_pair_sad_u8(f0.data_ptr(), f1.data_ptr(), s0, n, h0, w0, sad.data_ptr(),
-                                                 C.c_void_p(st.cuda_stream)), "rrin_pair_sad_u8")
-        return sad
-
-    def _forward_part_u8(self, f0, f1, img_stride, out, coef, h, w, slot, ws, stream, reuse_flow):
-        n, h0, w0, _ = f0.shape
-        key = (n, h, w, slot)
-        skip = bool(reuse_flow) and self._flow_valid.get(key, False) == "u8"
-        sc = self._net_scratch(n, h, w, slot)
-        st = self._status_of(slot) if self.prec in (_lib.PREC_F16X3, _lib.PREC_F16) else None
-        d = _lib.NetU8Desc()
-        nd = d.net
-        nd.n, nd.h, nd.w = n, h, w
-        nd.coef = coef.data_ptr()
-        nd.convs = self.conv_table_for(n, h, w)
-        nd.heads = self.head_table
-        nd.workspace, nd.workspace_bytes = ws.data_ptr(), ws.numel()
-        nd.skip_flow = 1 if skip else 0
-        nd.prec = self.prec
-        if sc is not None:
-            nd.scratch, nd.scratch_bytes = sc.data_ptr(), sc.numel()
-        nd.status = st.data_ptr() if st is not None else None
-        d.f0, d.f1, d.img_stride = f0.data_ptr(), f1.data_ptr(), img_stride
-        d.out_u8 = out.data_ptr()
-        d.h0, d.w0 = h0, w0
-        _lib.check(self.lib.rrin_net_u8_fwd(C.byref(d), C.c_void_p(stream.cuda_stream)), "rrin_net_u8_fwd")
-        # the raw Flow kept in this workspace is that of 8-bit frames: forward(reuse_flow=True)
-        # must not take it for its own previous pair, nor forward_u8 the float path's
-        self._flow_valid[key] = "u8"
-        if st is not None:
-            self._queue_status(slot, stream)
+        f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_u8", rgb=True)
+        return self._pair_sad(f0, f1, s0, h0, w0)
 
     # ---- 8-bit YUV 4:2:0 frames (NV12 / I420) ------------------------------------------
-    def _yuv_frames(self, f0, f1, what):
-        """Checks two uint8 [N, 3*H0//2, W0] 4:2:0 stacks of ``what`` and returns them with
-        (H0, W0) and the bytes between their frames: every frame dense, a uniform stride over dim
-        0 taken as it is (``frames[:-1]`` / ``frames[1:]`` of one stack need no copy), anything
-        else copied."""
-        from . import yuv
-        if not isinstance(f0, torch.Tensor) or not isinstance(f1, torch.Tensor):
-            raise TypeError(f"{what} takes two uint8 tensors")
-        if f0.device != self.device or f1.device != self.device:
-            raise RuntimeError(f"inputs on {f0.device}/{f1.device}, model on {self.device}")
-        if f0.dtype != torch.uint8 or f1.dtype != torch.uint8:
-            raise TypeError(f"{what} takes uint8 frames (forward takes float32)")
-        if f0.shape != f1.shape:
-            raise ValueError(f"expected two equal [N, 3*H0//2, W0] stacks, got {tuple(f0.shape)} / {tuple(f1.shape)}")
-        h0, w0 = yuv.frame_size(f0)
-        n, rows = f0.shape[0], f0.shape[1]
-        if n < 1:
-            raise ValueError(f"empty frames: {tuple(f0.shape)}")
-        frame = rows * w0
-
-        def stride_of(f):  # bytes between frames, or None if f needs a copy
-            if f.stride(2) != 1 or f.stride(1) != w0:
-                return None
-            return frame if n == 1 else (f.stride(0) if f.stride(0) >= frame else None)
-
-        s0, s1 = stride_of(f0), stride_of(f1)
-        if s0 is None or s0 != s1:
-            f0, f1 = f0.contiguous(), f1.contiguous()
-            s0 = frame
-        return f0, f1, h0, w0, s0
-
     @staticmethod
     def _yuv_stack(ptr: int, img_stride: int, h0: int, w0: int, layout: str) -> "_lib.Yuv420":
         """The rrin_yuv420 of a dense-frame stack at device address ``ptr``."""
@@ -1069,94 +1043,37 @@ class RRINEngine:
         ``floor(scene_threshold * H0*W0*3/2)``.  That is not the same number as the RGB path's
         threshold for the same footage, and like it no value has been validated on footage."""
         from . import yuv
-        if self.prec == _lib.PREC_F32:
-            raise RuntimeError("forward_yuv needs a record-layout precision: 'fp32', 'fp32_split16' or 'fp16' "
-                               "(not 'fp32_planar')")
+        self._need_records("forward_yuv")
         if layout not in yuv.LAYOUTS:
             raise ValueError(f"layout must be one of {yuv.LAYOUTS}, got {layout!r}")
         k = yuv.as_coef(coef)
-        f0, f1, h0, w0, s0 = self._yuv_frames(f0, f1, "forward_yuv")
+        f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_yuv", rgb=False)
         n = f0.shape[0]
         h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
-        if scene_threshold is not None and gate is not None:
-            raise ValueError("scene_threshold and gate exclude each other")
-        limit = cut_code = None
-        if scene_threshold is not None:
-            limit, cut_code = scene_limit(scene_threshold, h0 // 2, w0), scene_cut_code(t)
-        if gate is not None:
-            if (not isinstance(gate, torch.Tensor) or gate.dtype != torch.int32 or gate.device != self.device
-                    or tuple(gate.shape) != (n,)):
-                raise ValueError(f"gate must be an int32 tensor [{n}] on {self.device}")
-            gate = gate.contiguous()
-        if streams is None:
-            streams = default_streams(self.precision, n)
         self._poll_range()
-        out = torch.empty((n, 3 * h0 // 2, w0), dtype=torch.uint8, device=self.device)
         tcoef = t_coefficients(t, n).to(self.device, non_blocking=True)
         bounds = self._bounds(n, streams, split)
+        # the gate of forward_u8 on the frames' bytes: (H0/2) * W0 * 3 of them per frame
+        g = self._scene_gate("yuv", n, h0 // 2, w0, t, bounds, reuse_flow, scene_threshold, gate)
+        out = torch.empty((n, 3 * h0 // 2, w0), dtype=torch.uint8, device=self.device)
+        # the raw Flow kept in a workspace is that of these frames under this layout and matrix:
+        # no other path, layout or matrix may take it for its previous pair
         tag = "yuv:" + layout + ":" + ",".join(str(v) for v in k)
         kc = _lib.YuvCoef(*k)
-        sad = None
-        if limit is not None:
-            skey = ("yuv", n, h0, w0, tuple(bounds))
-            have_sad = bool(reuse_flow) and self._sad_key == skey
-            sad, gate = self._gate_buffers(n)
-            self._sad_key = skey
-        else:
-            self._sad_key = None
-        if gate is not None:
-            self.last_gate = gate
         frame = out.stride(0)
-        with torch.cuda.device(self.device):
-            main = torch.cuda.current_stream(self.device)
-            wss = [self.workspace(hi - lo, h, w, j) for j, (lo, hi) in enumerate(bounds)]
-            for j, (lo, hi) in enumerate(bounds):
-                self._net_scratch(hi - lo, h, w, j)
-            sides = self._side_streams(len(bounds) - 1)
-            for s in sides:
-                s.wait_stream(main)
-            for j, (lo, hi) in enumerate(bounds):
-                st = main if j == 0 else sides[j - 1]
-                m = hi - lo
-                p0, p1, po = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), out[lo:hi].data_ptr()
-                key = (m, h, w, j)
-                d = _lib.NetYuvDesc()
-                nd = d.net
-                nd.n, nd.h, nd.w = m, h, w
-                nd.coef = tcoef[lo:hi].data_ptr()
-                nd.convs = self.conv_table_for(m, h, w)
-                nd.heads = self.head_table
-                nd.workspace, nd.workspace_bytes = wss[j].data_ptr(), wss[j].numel()
-                nd.skip_flow = 1 if bool(reuse_flow) and self._flow_valid.get(key, False) == tag else 0
-                nd.prec = self.prec
-                sc = self._net_scratch(m, h, w, j)
-                if sc is not None:
-                    nd.scratch, nd.scratch_bytes = sc.data_ptr(), sc.numel()
-                status = self._status_of(j) if self.prec in (_lib.PREC_F16X3, _lib.PREC_F16) else None
-                nd.status = status.data_ptr() if status is not None else None
-                d.f0, d.f1 = self._yuv_stack(p0, s0, h0, w0, layout), self._yuv_stack(p1, s0, h0, w0, layout)
-                d.out = self._yuv_stack(po, frame, h0, w0, layout)
-                d.coef, d.h0, d.w0 = kc, h0, w0
-                sp = C.c_void_p(st.cuda_stream)
-                _lib.check(self.lib.rrin_net_yuv_fwd(C.byref(d), sp), "rrin_net_yuv_fwd")
-                # the raw Flow kept in this workspace is that of these frames under this layout
-                # and matrix: no other path, layout or matrix may take it for its previous pair
-                self._flow_valid[key] = tag
-                if status is not None:
-                    self._queue_status(j, st)
-                if gate is None:
-                    continue
-                # the gate of forward_u8 on the frames' bytes: (H0/2) * W0 * 3 of them per frame
-                if sad is not None:
-                    if not have_sad:
-                        _lib.check(self.lib.rrin_pair_sad_u8(p0, p1, s0, m, h0 // 2, w0, sad[lo:hi].data_ptr(), sp),
-                                   "rrin_pair_sad_u8")
-                    _lib.check(self.lib.rrin_gate_from_sad_u8(sad[lo:hi].data_ptr(), m, limit, cut_code,
-                                                              gate[lo:hi].data_ptr(), sp), "rrin_gate_from_sad_u8")
-                _lib.check(self.lib.rrin_gate_frames_u8(p0, p1, s0, m, h0 // 2, w0, gate[lo:hi].data_ptr(), po, sp),
-                           "rrin_gate_frames_u8")
-            for s in sides:
-                main.wait_stream(s)
+
+        def part(j, lo, hi, stream, p):
+            d = _lib.NetYuvDesc()
+            self._fill_net(d.net, p, tcoef[lo:hi])
+            p0, p1, po = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), out[lo:hi].data_ptr()
+            d.f0, d.f1 = self._yuv_stack(p0, s0, h0, w0, layout), self._yuv_stack(p1, s0, h0, w0, layout)
+            d.out = self._yuv_stack(po, frame, h0, w0, layout)
+            d.coef, d.h0, d.w0 = kc, h0, w0
+            self._launch(self.lib.rrin_net_yuv_fwd, "rrin_net_yuv_fwd", d, d.net, p, tag, reuse_flow, stream)
+            if g is not None:
+                self._enqueue_gate(g, p0, p1, s0, lo, hi, h0 // 2, w0, po, stream)
+
+        self._run_parts(h, w, bounds, part)
         return out
 
     def pair_stats_yuv(self, f0: torch.Tensor, f1: torch.Tensor) -> torch.Tensor:
@@ -1164,14 +1081,8 @@ class RRINEngine:
         stacks as :meth:`forward_yuv` takes them: a fresh int64 device tensor ``[N]``, exact
         (rrin_pair_sad_u8 on the frames' bytes) -- what its ``scene_threshold`` compares with
         ``floor(threshold * H0*W0*3/2)``."""
-        f0, f1, h0, w0, s0 = self._yuv_frames(f0, f1, "pair_stats_yuv")
-        n = f0.shape[0]
-        sad = torch.empty(n, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            st = torch.cuda.current_stream(self.device)
-            _lib.check(self.lib.rrin_pair_sad_u8(f0.data_ptr(), f1.data_ptr(), s0, n, h0 // 2, w0, sad.data_ptr(),
-                                                 C.c_void_p(st.cuda_stream)), "rrin_pair_sad_u8")
-        return sad
+        f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_yuv", rgb=False)
+        return self._pair_sad(f0, f1, s0, h0 // 2, w0)
 
     def unet_forward(self, x: torch.Tensor) -> torch.Tensor:
         """The single packed U-Net (engine built with one unit) on x [N,C,H,W]:
@@ -1201,16 +1112,12 @@ class RRINEngine:
         with torch.cuda.device(self.device):
             st = torch.cuda.current_stream(self.device)
             _lib.check(self.lib.rrin_unet_fwd(C.byref(d), C.c_void_p(st.cuda_stream)), "rrin_unet_fwd")
-            if status is not None:  # the range guard, checked as the Net's (_poll_range)
-                host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-                host.copy_(status, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(st)
-                self._pending_status.append((ev, host))
+            self._queue_status(100, st)  # the range guard, checked as the Net's (_poll_range)
         return y
 
     def _bounds(self, n: int, streams, split):
-        """Contiguous (lo, hi) pair ranges of the forward parts (one per HIP stream)."""
+        """Contiguous (lo, hi) pair ranges of the forward parts (one per HIP stream; ``streams``
+        None: the precision's default)."""
         if split is not None:  # explicit part sizes (pairs per stream)
             split = [int(c) for c in split]
             if sum(split) != n or min(split) < 1:
@@ -1219,6 +1126,8 @@ class RRINEngine:
             for c in split:
                 cuts.append(cuts[-1] + c)
             return list(zip(cuts[:-1], cuts[1:]))
+        if streams is None:
+            streams = default_streams(self.precision, n)
         k = max(1, min(int(streams), n))
         return [(n * j // k, n * (j + 1) // k) for j in range(k)]
 
@@ -1233,8 +1142,6 @@ class RRINEngine:
         ``tests/test_gpu_graph.py``).  reuse_flow and taps are eager-only."""
         if h % 16 or w % 16 or n < 1:
             raise RuntimeError(f"H and W must be multiples of 16, got {h}x{w}")
-        if streams is None:
-            streams = default_streams(self.precision, n)
         bounds = self._bounds(n, streams, split)
         key = (n, h, w, tuple(bounds))
         g = self._graphs.get(key)
@@ -1243,23 +1150,62 @@ class RRINEngine:
             self._graphs[key] = g
         return g
 
-    def _net_desc(self, i0, i1, out, coef, ws, sc, status, skip, prof, tapbuf):
-        n, _, h, w = i0.shape
+    def _run_parts(self, h: int, w: int, bounds, part):
+        """The forward parts ``bounds`` at h x w: part j on its own stream (main, then the side
+        streams), forked from and joined to the current stream.  ``part(j, lo, hi, stream, p)``
+        enqueues pairs [lo, hi) on ``stream`` with the buffers p (a Part).
+
+        The ordering that every caller relies on, kept here alone: each buffer that is zero-filled
+        when it is new -- workspace, scratch, fp16 range flag -- is obtained on the main stream
+        before the fork, because a side stream waits only for what main had enqueued by then.
+        Inside a graph capture (NetGraph) every one of them is a cache hit: nothing allocates."""
+        with torch.cuda.device(self.device):
+            main = torch.cuda.current_stream(self.device)
+            parts = [self._part(hi - lo, h, w, j) for j, (lo, hi) in enumerate(bounds)]
+            sides = self._side_streams(len(bounds) - 1)
+            for s in sides:
+                s.wait_stream(main)
+            for j, (lo, hi) in enumerate(bounds):
+                part(j, lo, hi, main if j == 0 else sides[j - 1], parts[j])
+            for s in sides:
+                main.wait_stream(s)
+
+    def _part(self, m: int, h: int, w: int, slot: int) -> Part:
+        """The buffers of the forward part of m pairs at h x w in stream slot ``slot``, cached; a
+        new one is zero-filled on the current stream."""
+        convs = self.conv_table_for(m, h, w)
+        prec16 = self.prec in (_lib.PREC_F16X3, _lib.PREC_F16)
+        return Part((m, h, w, slot), self.workspace(m, h, w, slot), convs, self._net_scratch(m, h, w, slot, convs),
+                    self._status_of(slot) if prec16 else None)
+
+    def _fill_net(self, nd, p: Part, coef):
+        """The rrin_net_desc fields every path shares (``nd``: a NetDesc or the ``net`` of a
+        NetU8Desc / NetYuvDesc) for part p with the coefficient rows ``coef``; skip_flow is _launch's."""
+        nd.n, nd.h, nd.w = p.key[:3]
+        nd.coef = coef.data_ptr()
+        nd.convs, nd.heads = p.convs, self.head_table
+        nd.workspace, nd.workspace_bytes = p.ws.data_ptr(), p.ws.numel()
+        nd.prec = self.prec
+        if p.scratch is not None:
+            nd.scratch, nd.scratch_bytes = p.scratch.data_ptr(), p.scratch.numel()
+        nd.status = p.status.data_ptr() if p.status is not None else None
+
+    def _float_desc(self, p: Part, i0, i1, out, coef):
         d = _lib.NetDesc()
-        d.n, d.h, d.w = n, h, w
-        d.i0, d.i1, d.out, d.coef = i0.data_ptr(), i1.data_ptr(), out.data_ptr(), coef.data_ptr()
-        d.convs = self.conv_table_for(n, h, w)
-        d.heads = self.head_table
-        d.workspace = ws.data_ptr()
-        d.workspace_bytes = ws.numel()
-        d.skip_flow = 1 if skip else 0
-        d.prec = self.prec
-        d.prof = prof
-        d.taps = tapbuf.data_ptr() if tapbuf is not None else None
-        if sc is not None:
-            d.scratch, d.scratch_bytes = sc.data_ptr(), sc.numel()
-        d.status = status.data_ptr() if status is not None else None
+        self._fill_net(d, p, coef)
+        d.i0, d.i1, d.out = i0.data_ptr(), i1.data_ptr(), out.data_ptr()
         return d
+
+    def _launch(self, fwd, name: str, d, nd, p: Part, tag: str, reuse_flow, stream):
+        """Library entry ``fwd`` on descriptor d (nd: its rrin_net_desc) for part p on ``stream``.
+        ``tag`` names the path -- and for YUV its layout and matrix -- whose raw Flow the part's
+        workspace keeps afterwards: the Flow U-Net is skipped only for ``reuse_flow`` with the
+        same tag, so no path takes another's pair for its own previous one."""
+        nd.skip_flow = 1 if reuse_flow and self._flow_valid.get(p.key) == tag else 0
+        _lib.check(fwd(C.byref(d), C.c_void_p(stream.cuda_stream)), name)
+        self._flow_valid[p.key] = tag
+        if p.status is not None:
+            self._queue_status(p.key[3], stream)
 
     def _queue_status(self, slot, stream):
         """Copy part `slot`'s fp16 range flag to the host behind the work enqueued on `stream`
@@ -1273,19 +1219,6 @@ class RRINEngine:
             ev = torch.cuda.Event()
             ev.record(stream)
         self._pending_status.append((ev, host))
-
-    def _forward_part(self, i0, i1, out, coef, slot, ws, stream, prof, reuse_flow, tapbuf=None):
-        n, _, h, w = i0.shape
-        key = (n, h, w, slot)
-        # True: the kept raw Flow is that of this path's previous pair ("u8": of forward_u8's)
-        skip = bool(reuse_flow) and self._flow_valid.get(key, False) is True
-        sc = self._net_scratch(n, h, w, slot)  # allocated (and zero-filled) before the fork
-        st = self._status_of(slot) if self.prec in (_lib.PREC_F16X3, _lib.PREC_F16) else None
-        d = self._net_desc(i0, i1, out, coef, ws, sc, st, skip, prof, tapbuf)
-        _lib.check(self.lib.rrin_net_fwd(C.byref(d), C.c_void_p(stream.cuda_stream)), "rrin_net_fwd")
-        self._flow_valid[key] = True
-        if st is not None:
-            self._queue_status(slot, stream)
 
     # ---- fp16 range guard (fp32_split16 / fp16) ---------------------------------
     # Activations of these precisions are stored as fp16; a value beyond 65504
@@ -1336,31 +1269,24 @@ class NetGraph:
         self._coef_host = torch.zeros((n, 8), dtype=torch.float32, pin_memory=True)
         self._coef_ev = None
         self._t = None
+        self.parts = []  # the captured parts' buffers, kept alive with the graph
         with torch.no_grad(), torch.cuda.device(dev):
             # an eager forward of the same parts first: workspaces, scratch, range flags, side
             # streams and the packing are allocated outside the capture (nothing allocates inside)
             eng.forward(self.i0, self.i1, 0.5, split=[hi - lo for lo, hi in bounds])
             eng._poll_range(wait=True)
             torch.cuda.synchronize(dev)
-            self.ws = [eng.workspace(hi - lo, h, w, j) for j, (lo, hi) in enumerate(bounds)]
-            self.sc = [eng._net_scratch(hi - lo, h, w, j) for j, (lo, hi) in enumerate(bounds)]
-            prec16 = eng.prec in (_lib.PREC_F16X3, _lib.PREC_F16)
-            self.status = [eng._status_of(j) if prec16 else None for j in range(len(bounds))]
-            sides = eng._side_streams(len(bounds) - 1)
+
+            def part(j, lo, hi, stream, p):
+                d = eng._float_desc(p, self.i0[lo:hi], self.i1[lo:hi], self.out[lo:hi], self.coef[lo:hi])
+                _lib.check(eng.lib.rrin_net_fwd(C.byref(d), C.c_void_p(stream.cuda_stream)), "rrin_net_fwd (capture)")
+                self.parts.append(p)
+
             self.graph = torch.cuda.CUDAGraph()
             cap = torch.cuda.Stream(dev)
             cap.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.graph(self.graph, stream=cap):
-                main = torch.cuda.current_stream(dev)
-                for s in sides:
-                    s.wait_stream(main)
-                for j, (lo, hi) in enumerate(bounds):
-                    st = main if j == 0 else sides[j - 1]
-                    d = eng._net_desc(self.i0[lo:hi], self.i1[lo:hi], self.out[lo:hi], self.coef[lo:hi],
-                                      self.ws[j], self.sc[j], self.status[j], False, None, None)
-                    _lib.check(eng.lib.rrin_net_fwd(C.byref(d), C.c_void_p(st.cuda_stream)), "rrin_net_fwd (capture)")
-                for s in sides:
-                    main.wait_stream(s)
+                eng._run_parts(h, w, bounds, part)
             torch.cuda.current_stream(dev).wait_stream(cap)
 
     def replay(self, t=0.5) -> torch.Tensor:
@@ -1377,7 +1303,7 @@ class NetGraph:
             self._coef_ev.record(st)
             self._t = key
         self.graph.replay()
-        for j, s in enumerate(self.status):
-            if s is not None:
-                eng._queue_status(j, st)
+        for p in self.parts:
+            if p.status is not None:
+                eng._queue_status(p.key[3], st)
         return self.out

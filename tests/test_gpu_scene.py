@@ -241,3 +241,53 @@ def test_folder_run_gates_on_gpu(tmp_path, gpu):
                 assert open(os.path.join(a, name), "rb").read() == open(os.path.join(b, name), "rb").read(), name
         name = f"{base + sf + 1:09d}.png"
         assert open(os.path.join(a, name), "rb").read() == open(os.path.join(b, name), "rb").read(), name
+
+
+def uneven_inputs(dev):
+    """f0 / f1 uint8 [3,30,44,3] (the net runs at 32x48: both paddings are non-zero): an ordinary pair (a
+    smooth ramp against itself rolled by one pixel), a duplicate pair, a cut pair (the ramp against noise)."""
+    yy, xx = np.mgrid[0:30, 0:44]
+    ramp = np.stack([60 + yy + 2 * xx, 40 + 2 * yy + xx, 80 + yy + xx], axis=-1).astype(np.uint8)
+    moved = np.roll(ramp, 2, axis=0)
+    f0 = np.stack([ramp, moved, ramp])
+    f1 = np.stack([np.roll(ramp, 1, axis=1), moved, stack_of(1, 30, 44, 8)[0]])
+    return torch.from_numpy(f0).to(dev), torch.from_numpy(f1).to(dev)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "fp16"])
+def test_uneven_split_equals_one_stream(gpu, precision):
+    """split=[1, 2] against streams=1, byte for byte in the frames and in last_gate: every part slices the
+    coefficient rows, the sums, the codes and the output by [lo:hi], and the other tests split evenly or
+    not at all.  Then reuse_flow=True at another t against a fresh call at that t.
+
+    The scene gate takes one t for the batch (scene_cut_code raises for a per-pair tensor), so the
+    per-pair t = (0.25, 0.5, 0.75) cannot go with scene_threshold.  Two legs cover the slices between
+    them: scene_threshold with a scalar t (the sums and the codes derived from them), and the per-pair t
+    with the same codes given as ``gate`` (the coefficient rows)."""
+    eng = net_of(gpu, precision).engine()
+    f0, f1 = uneven_inputs(gpu)
+    for t, want in ((0.75, [0, 1, 2]), (0.25, [0, 1, 1])):
+        assert cv.scene_gate_codes(f0.cpu(), f1.cpu(), 20, t).tolist() == want
+    with torch.no_grad():
+        one = eng.forward_u8(f0, f1, 0.75, streams=1, scene_threshold=20)
+        codes1 = eng.last_gate.clone()
+        two = eng.forward_u8(f0, f1, 0.75, split=[1, 2], scene_threshold=20)
+        assert torch.equal(two, one) and torch.equal(eng.last_gate, codes1)
+        assert codes1.cpu().tolist() == [0, 1, 2]
+        assert torch.equal(two[1], f0[1]) and torch.equal(two[2], f1[2]) and not torch.equal(two[0], f0[0])
+        again = eng.forward_u8(f0, f1, 0.25, split=[1, 2], reuse_flow=True, scene_threshold=20)   # kept Flow and sums
+        codes2 = eng.last_gate.clone()
+        fresh = eng.forward_u8(f0, f1, 0.25, streams=1, scene_threshold=20)
+        assert torch.equal(again, fresh) and torch.equal(codes2, eng.last_gate)
+        assert codes2.cpu().tolist() == [0, 1, 1] and torch.equal(again[2], f0[2])
+        # the per-pair t, each pair's code by the rule at its own t
+        t = torch.tensor([0.25, 0.5, 0.75])
+        g = torch.cat([cv.scene_gate_codes(f0[p:p + 1], f1[p:p + 1], 20, float(t[p])) for p in range(3)])
+        assert g.cpu().tolist() == [0, 1, 2]
+        one = eng.forward_u8(f0, f1, t, streams=1, gate=g)
+        two = eng.forward_u8(f0, f1, t, split=[1, 2], gate=g)
+        assert torch.equal(two, one) and eng.last_gate is g
+        again = eng.forward_u8(f0, f1, t.flip(0), split=[1, 2], reuse_flow=True, gate=g)
+        assert torch.equal(again, eng.forward_u8(f0, f1, t.flip(0), streams=1, gate=g))
+        assert not torch.equal(again[0], two[0])                         # another t: another frame
+    eng.check_range()

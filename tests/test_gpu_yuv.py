@@ -273,6 +273,54 @@ def test_forward_yuv_scene_gate(gpu):
         assert torch.equal(gated[0], f1[0]) and torch.equal(gated[1:3], plain[1:3]) and torch.equal(gated[3], f0[3])
 
 
+def byte_gate_codes(f0, f1, threshold, t):
+    """convert.scene_gate_codes on the bytes of 4:2:0 frames: H0/2 x W0 x 3 of them per frame."""
+    sad = torch_sad(f0, f1)
+    limit = cv.scene_limit(threshold, f0.shape[1] // 3, f0.shape[2])
+    codes = torch.where(sad > limit, cv.scene_cut_code(t), 0)
+    return torch.where(sad == 0, 1, codes).to(torch.int32)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "fp16"])
+def test_uneven_split_equals_one_stream(gpu, precision):
+    """test_gpu_scene.py::test_uneven_split_equals_one_stream on 30x44 NV12 frames ([3,45,44]; the net
+    runs at 32x48): split=[1, 2] against streams=1 byte for byte in the frames and in last_gate, then
+    reuse_flow=True at another t against a fresh call.  As there, the gate takes one t for the batch: one
+    leg has scene_threshold and a scalar t, the other the per-pair t = (0.25, 0.5, 0.75) and the codes
+    of the same rule as ``gate``."""
+    eng = net_of(gpu, precision).engine()
+    yy, xx = np.mgrid[0:45, 0:44]
+    ramp = (60 + yy + 2 * xx).astype(np.uint8)
+    moved = np.roll(ramp, 2, axis=0)
+    noise = np.random.default_rng(8).integers(0, 256, (45, 44), dtype=np.uint8)
+    f0 = torch.from_numpy(np.stack([ramp, moved, ramp])).to(gpu)
+    f1 = torch.from_numpy(np.stack([np.roll(ramp, 1, axis=1), moved, noise])).to(gpu)
+    assert byte_gate_codes(f0, f1, 20, 0.75).tolist() == [0, 1, 2]
+    assert byte_gate_codes(f0, f1, 20, 0.25).tolist() == [0, 1, 1]
+    with torch.no_grad():
+        one = eng.forward_yuv(f0, f1, 0.75, streams=1, scene_threshold=20)
+        codes1 = eng.last_gate.clone()
+        two = eng.forward_yuv(f0, f1, 0.75, split=[1, 2], scene_threshold=20)
+        assert torch.equal(two, one) and torch.equal(eng.last_gate, codes1)
+        assert codes1.cpu().tolist() == [0, 1, 2]
+        assert torch.equal(two[1], f0[1]) and torch.equal(two[2], f1[2]) and not torch.equal(two[0], f0[0])
+        again = eng.forward_yuv(f0, f1, 0.25, split=[1, 2], reuse_flow=True, scene_threshold=20)   # kept Flow and sums
+        codes2 = eng.last_gate.clone()
+        fresh = eng.forward_yuv(f0, f1, 0.25, streams=1, scene_threshold=20)
+        assert torch.equal(again, fresh) and torch.equal(codes2, eng.last_gate)
+        assert codes2.cpu().tolist() == [0, 1, 1] and torch.equal(again[2], f0[2])
+        t = torch.tensor([0.25, 0.5, 0.75])
+        g = torch.cat([byte_gate_codes(f0[p:p + 1], f1[p:p + 1], 20, float(t[p])) for p in range(3)])
+        assert g.cpu().tolist() == [0, 1, 2]
+        one = eng.forward_yuv(f0, f1, t, streams=1, gate=g)
+        two = eng.forward_yuv(f0, f1, t, split=[1, 2], gate=g)
+        assert torch.equal(two, one) and eng.last_gate is g
+        again = eng.forward_yuv(f0, f1, t.flip(0), split=[1, 2], reuse_flow=True, gate=g)
+        assert torch.equal(again, eng.forward_yuv(f0, f1, t.flip(0), streams=1, gate=g))
+        assert not torch.equal(again[0], two[0])                         # another t: another frame
+    eng.check_range()
+
+
 def test_range_guard_writes_black_and_check_range_raises(gpu):
     """An fp16 overflow (the recipe of test_range_guard_writes_zeros_and_check_range_raises): the output
     is rgb_to_yuv420 of zeros, and check_range raises."""

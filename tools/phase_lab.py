@@ -27,7 +27,7 @@ def main():
     out = torch.empty_like(i0)
     coef = t_coefficients(0.5, B).to(dev)
     parts = [(0, 2), (2, 4)]
-    wss = [eng.workspace(2, H, W, j) for j in range(2)]
+    ps = [eng._part(2, H, W, j) for j in range(2)]
     main_s = torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(dev)
     # cycles per ms of the spin kernel (measured)
@@ -53,7 +53,8 @@ def main():
                 for j, (lo, hi) in enumerate(parts):
                     st = main_s if j == 0 else side
                     ev[j][k].record(st)
-                    eng._forward_part(i0[lo:hi], i1[lo:hi], out[lo:hi], coef[lo:hi], j, wss[j], st, None, False)
+                    d = eng._float_desc(ps[j], i0[lo:hi], i1[lo:hi], out[lo:hi], coef[lo:hi])
+                    eng._launch(eng.lib.rrin_net_fwd, "rrin_net_fwd", d, d, ps[j], "f32", False, st)
         torch.cuda.synchronize()
         return sum(2 * (b - a) / (ev[j][a].elapsed_time(ev[j][b]) * 1e-3) for j in range(2))
 
