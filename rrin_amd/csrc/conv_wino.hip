@@ -33,20 +33,13 @@
 //   U slab [xi][half][co] 16 x 2 x 32 records
 // The output transform's two halves (xi_y 0-1, 2-3) meet through LDS: wave
 // xh = 0 finishes output row 0 of each patch, xh = 1 row 1.
-#include "common.hpp"
+#include "wino_tile.hpp"
 
 namespace rrin {
-
-typedef float wfloatx16 __attribute__((ext_vector_type(16)));
-typedef float wfloatx4 __attribute__((ext_vector_type(4)));
-typedef float wfloatx2 __attribute__((ext_vector_type(2)));
 
 constexpr int kWnRawCols = 34, kWnRawG = 10 * kWnRawCols, kWnRaw = 2 * kWnRawG, kWnRawStride = 704;
 constexpr int kWnU = 16 * 2 * 32;  // records per U buffer: [xi][half][co]
 static_assert(kWinoLds == (size_t)(2 * kWnRawStride + 2 * kWnU) * 16, "LDS size");
-// LDS position of raw column col (0..33) within its row: even columns first
-__device__ inline int wn_col(int col) { return (col & 1) * 17 + (col >> 1); }
-
 // ABL: kernel-lab ablations only (built into librrin_lab.so under RRIN_LAB; the
 // product library instantiates ABL = 0): 1 no weight DMA after chunk 1, 2 no raw
 // DMA after chunk 1, 4 no MFMAs (operands kept live), 8 no transform arithmetic.
@@ -63,17 +56,12 @@ __device__ inline int wn_col(int col) { return (col & 1) * 17 + (col >> 1); }
 template <int EPI, int ABL = 0>
 __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvH8Args a) {
   extern __shared__ __attribute__((aligned(16))) uint4 smem4[];
-  uint4* s_raw = smem4;                      // [2][kWnRawStride]: [group][row][wn_col]
+  uint4* s_raw = smem4;                      // [2][kWnRawStride]: [group][row][wino_col]
   uint4* s_u = smem4 + 2 * kWnRawStride;     // [2][16][2][32]
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int xh = wv & 1, ph = wv >> 1, j = lane & 31, hh = lane >> 5;
-  int bid;
-  {  // XCD-aware bijective remap (see conv_mfma.hip)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  const int bid = wino_xcd_bid();
   const int ntiles = a.co_blocks * a.tiles_x * a.tiles_y * a.n;
   if (bid >= ntiles) return;
   const int nch = a.nchunks;
@@ -142,29 +130,29 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvH8Args a) {
   const int rw0 = hh * kWnRawG + (2 * pr) * kWnRawCols;
   int pc[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) pc[k] = wn_col(2 * jx + k);
+  for (int k = 0; k < 4; ++k) pc[k] = wino_col(2 * jx + k);
   const int r0a = (ra)*kWnRawCols, r0b = (rb)*kWnRawCols, r1a = kWnRawCols, r1b = (rd)*kWnRawCols;
 
-  wfloatx16 acc[8];
-  wfloatx4 u[4], v[4];  // operands of the half being issued; point x recycled after its MFMAs
+  floatx16 acc[8];
+  floatx4 u[4], v[4];  // operands of the half being issued; point x recycled after its MFMAs
   // U record of point (8 xh + 4 yl + x) of the chunk in buffer b
   auto read_u = [&](int b, int yl, int x) {
-    return __builtin_bit_cast(wfloatx4, smem4[su0 + b * kWnU + yl * 256 + x * 64]);
+    return __builtin_bit_cast(floatx4, smem4[su0 + b * kWnU + yl * 256 + x * 64]);
   };
   // the 8 window records of B^T row yl (rows o0 / o1, 4 columns)
-  auto read_raw = [&](int b, int yl, wfloatx4* d) {
+  auto read_raw = [&](int b, int yl, floatx4* d) {
     const uint4* rw = s_raw + b * kWnRawStride + rw0;
     const int o0 = yl ? r1a : r0a, o1 = yl ? r1b : r0b;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      d[2 * k] = __builtin_bit_cast(wfloatx4, rw[o0 + pc[k]]);
-      d[2 * k + 1] = __builtin_bit_cast(wfloatx4, rw[o1 + pc[k]]);
+      d[2 * k] = __builtin_bit_cast(floatx4, rw[o0 + pc[k]]);
+      d[2 * k + 1] = __builtin_bit_cast(floatx4, rw[o1 + pc[k]]);
     }
   };
   // column k of B^T row yl: t = d[ra] - d[rb] (yl 0) or d[1] + sgn d[rd] (yl 1)
-  auto row_t = [&](int yl, const wfloatx4* d, int k) {
+  auto row_t = [&](int yl, const floatx4* d, int k) {
     if constexpr ((ABL & 8) != 0) return d[2 * k];
-    wfloatx4 t;
+    floatx4 t;
     if (yl == 0) {
       t = d[2 * k] - d[2 * k + 1];
     } else {
@@ -180,7 +168,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvH8Args a) {
       if constexpr ((ABL & 4) != 0) {
         asm volatile("" ::"v"(u[x][e]), "v"(v[x][e]));
       } else {
-        const wfloatx16 c = (first && e == 0) ? wfloatx16{} : acc[4 * yl + x];
+        const floatx16 c = (first && e == 0) ? floatx16{} : acc[4 * yl + x];
         acc[4 * yl + x] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[x][e], v[x][e], c, 0, 0, 0);
       }
     }
@@ -199,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvH8Args a) {
     if constexpr (RRIN_WINO_FENCE) __builtin_amdgcn_sched_barrier(0);
   };
   auto half = [&](int yl, int bn, int yn, bool first) {
-    wfloatx4 d[8], t[4];
+    floatx4 d[8], t[4];
     read_raw(bn, yn, d);
     fence();
     mfma_point(yl, 0, first);
@@ -255,7 +243,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvH8Args a) {
   __syncthreads();
   if (nch > 1) issue(1, 1);
   {
-    wfloatx4 d[8], t[4];
+    floatx4 d[8], t[4];
     read_raw(0, 0, d);
 #pragma unroll
     for (int k = 0; k < 4; ++k) t[k] = row_t(0, d, k);
@@ -301,12 +289,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvH8Args a) {
     // wave xh 0 hands its Q1 (yl 1) to its partner, wave xh 1 its Q2 (yl 0): records
     // k 0-3 / 4-7 in the two U buffers (no DMA in flight and every read of them
     // consumed since the last chunk's barrier)
-    wfloatx4* xlo = reinterpret_cast<wfloatx4*>(s_u);
-    wfloatx4* xhi = reinterpret_cast<wfloatx4*>(s_u + kWnU);
+    floatx4* xlo = reinterpret_cast<floatx4*>(s_u);
+    floatx4* xhi = reinterpret_cast<floatx4*>(s_u + kWnU);
     auto xslot = [&](int w, int k) { return (k < 4 ? xlo : xhi) + (w * 4 + (k & 3)) * 64 + lane; };
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      wfloatx4 g;
+      floatx4 g;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int v = 4 * k + e, c = v >> 4, i = v & 15;
@@ -318,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvH8Args a) {
     float yv[2][16];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const wfloatx4 pv = *xslot(wv ^ 1, k);
+      const floatx4 pv = *xslot(wv ^ 1, k);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int v = 4 * k + e, c = v >> 4, i = v & 15;
@@ -390,12 +378,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvH8Args a) {
       if constexpr (EPI == RRIN_EPI_LEAKY_POOL) {
         // row 1 of each patch (wave xh 1) meets row 0 (wave xh 0) in LDS, in the raw
         // buffers (idle now); avg = 0.25 ((v00 + v10) + (v01 + v11))
-        wfloatx4* xp = reinterpret_cast<wfloatx4*>(s_raw);
+        floatx4* xp = reinterpret_cast<floatx4*>(s_raw);
         auto pslot = [&](int k) { return xp + (ph * 8 + k) * 64 + lane; };
         if (xh) {
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
-            wfloatx4 g;
+            floatx4 g;
 #pragma unroll
             for (int e = 0; e < 4; ++e) g[e] = v[(4 * k + e) >> 4][(4 * k + e) & 15];
             *pslot(k) = g;
@@ -406,7 +394,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvH8Args a) {
           float v1[2][16];
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
-            const wfloatx4 g = *pslot(k);
+            const floatx4 g = *pslot(k);
 #pragma unroll
             for (int e = 0; e < 4; ++e) v1[(4 * k + e) >> 4][(4 * k + e) & 15] = g[e];
           }
@@ -444,18 +432,8 @@ static int launch_wino_k(const ConvH8Args& a, hipStream_t st) {
 
 
 int launch_wino(const ConvH8Args& a, int epi, hipStream_t st) {
-  switch (epi) {
-    case RRIN_EPI_LINEAR: return launch_wino_k<RRIN_EPI_LINEAR>(a, st);
-    case RRIN_EPI_LEAKY: return launch_wino_k<RRIN_EPI_LEAKY>(a, st);
-    case RRIN_EPI_LEAKY_POOL: return launch_wino_k<RRIN_EPI_LEAKY_POOL>(a, st);
-    case RRIN_EPI_LEAKY_REP: return launch_wino_k<RRIN_EPI_LEAKY_REP>(a, st);
-    case RRIN_EPI_SUBPIXEL: return launch_wino_k<RRIN_EPI_SUBPIXEL>(a, st);
-  }
-  return RRIN_E_ARG;
+  return wino_dispatch_epi(epi, [&](auto e) { return launch_wino_k<decltype(e)::value>(a, st); });
 }
-
-
-
 
 // ============================================================================
 // 4-waves-per-SIMD tile (config kWinoQCfg): the 32-channel tile of cfg 18 (same
@@ -713,12 +691,7 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
     }
     cidx -= 8 * min(g + 1, ng);
   }
-  int bid;
-  {
-    const int nwg = gridDim.x - (RF ? a.nring : 0), q = nwg >> 3, r = nwg & 7;
-    const int xcd = cidx & 7, slot = cidx >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  const int bid = wino_xcd_bid((int)gridDim.x - (RF ? a.nring : 0), cidx);
   const int ntiles = a.co_blocks * a.tiles_x * a.tiles_y * a.n;
   const int ksn = SK ? a.ksplit : 1;  // K slices per tile
   if (bid >= ntiles * ksn) return;
@@ -748,23 +721,17 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
     cob = t % a.co_blocks;
     t /= a.co_blocks;
     t = t * a.tiles_y + ty_;
-#else  // groups of a.cob_group co blocks (0: one group of all), tile positions within a group,
-       // the group's co blocks of a tile position on consecutive workgroups (they share its raw
-       // tile); an XCD runs consecutive workgroups, so with groups it streams one group's U
+#else  // co-block groups (wino_tile_pos); an XCD runs consecutive workgroups, so with groups it
+       // streams one group's U
     {
-      const int cpg = a.cob_group > 0 ? a.cob_group : a.co_blocks;
-      const int gsz = cpg * (ntiles / a.co_blocks);
-      const int g = t / gsz;
-      const int r = t - g * gsz;
-      const int cg = min(cpg, a.co_blocks - g * cpg);
-      cob = g * cpg + r % cg;
-      t = r / cg;
+      const WinoTile p = wino_tile_pos(a, ntiles, t, 32, TH);
+      cob = p.cob, x0 = p.x0, y0 = p.y0, img = p.img;
     }
-    x0 = (t % a.tiles_x) * 32;
-    t /= a.tiles_x;
 #endif
+#if RRIN_WINOQ_ORDER
     y0 = (t % a.tiles_y) * TH;
     img = t / a.tiles_y;
+#endif
   }
   const uint4* tsrc =
       a.src_hi + (int64_t)img * a.src_img + (int64_t)(2 * c0) * a.src_gp + (int64_t)y0 * a.src_wp + x0 + (kH8PadLeft - 1);
@@ -815,9 +782,9 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
                                                      0, 0x7fffffff, 0x00020000);
   auto load_u = [&](int c, int x) {
     const unsigned voff = (unsigned)(((4 * yw + x) * 64 + hh * 32 + j) * 16);
-    return __builtin_bit_cast(wfloatx4, __builtin_amdgcn_raw_buffer_load_b128(urs, voff, c * kWnU * 16, 0));
+    return __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(urs, voff, c * kWnU * 16, 0));
   };
-  wfloatx4 ur[4];  // RU: U of the chunk being computed (point x reloaded after its MFMAs)
+  floatx4 ur[4];  // RU: U of the chunk being computed (point x reloaded after its MFMAs)
   const int pr = 2 * pt + (j >> 4), jx = (j + 12 * (j >> 4)) & 15;
   const int ra = yw == 0 ? 0 : (yw == 2 ? 2 : 1);
   const int rb = yw == 0 ? 2 : (yw == 1 ? 2 : (yw == 2 ? 1 : 3));
@@ -826,22 +793,22 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
   const int oa = ra * kWnRawCols, ob = rb * kWnRawCols;
   int pc[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) pc[k] = wn_col(2 * jx + k);
+  for (int k = 0; k < 4; ++k) pc[k] = wino_col(2 * jx + k);
   const int su0 = (4 * yw) * 64 + hh * 32 + j;  // U of point 4 yw + x: + x * 64 (layout [xi][half][32 co])
 
-  wfloatx16 acc[4];
-  wfloatx4 dk[8], uk[4];  // ABL 16 / 32: chunk 0's reads kept
+  floatx16 acc[4];
+  floatx4 dk[8], uk[4];  // ABL 16 / 32: chunk 0's reads kept
   // one chunk in buffer b: window reads -> B^T row -> 4 points, then per point
   // its U record and 4 MFMAs (point-major, the cfg 18 accumulation order)
   auto chunk = [&](bool first, int c) {
     const uint4* rw = raw_stage(c) + rw0;
-    wfloatx4 t[4];
+    floatx4 t[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      wfloatx4 d0, d1;
+      floatx4 d0, d1;
       if (!(ABL & 16) || first) {
-        d0 = __builtin_bit_cast(wfloatx4, rw[oa + pc[k]]);
-        d1 = __builtin_bit_cast(wfloatx4, rw[ob + pc[k]]);
+        d0 = __builtin_bit_cast(floatx4, rw[oa + pc[k]]);
+        d1 = __builtin_bit_cast(floatx4, rw[ob + pc[k]]);
         if constexpr ((ABL & 16) != 0) dk[2 * k] = d0, dk[2 * k + 1] = d1;
       } else {
         d0 = dk[2 * k];
@@ -855,7 +822,7 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
         for (int e = 0; e < 4; ++e) t[k][e] = fmaf(sg, d1[e], d0[e]);
       }
     }
-    wfloatx4 v[4];
+    floatx4 v[4];
     if constexpr ((ABL & 8) != 0) {
 #pragma unroll
       for (int x = 0; x < 4; ++x) v[x] = t[x];
@@ -871,11 +838,11 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
 #endif
 #pragma unroll
     for (int x = 0; x < 4; ++x) {
-      wfloatx4 u;
+      floatx4 u;
       if constexpr (RU) {
         u = ur[x];
       } else if (!(ABL & 32) || first) {
-        u = __builtin_bit_cast(wfloatx4, su[x * 64]);
+        u = __builtin_bit_cast(floatx4, su[x * 64]);
         if constexpr ((ABL & 32) != 0) uk[x] = u;
       } else {
         u = uk[x];
@@ -885,7 +852,7 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
         if constexpr ((ABL & 4) != 0) {
           asm volatile("" ::"v"(u[e]), "v"(v[x][e]));
         } else {
-          const wfloatx16 cin_acc = (first && e == 0) ? wfloatx16{} : acc[x];
+          const floatx16 cin_acc = (first && e == 0) ? floatx16{} : acc[x];
           acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[e], v[x][e], cin_acc, 0, 0, 0);
         }
       }
@@ -920,7 +887,7 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
   };
   if constexpr ((ABL & 4) != 0) {
 #pragma unroll
-    for (int x = 0; x < 4; ++x) acc[x] = wfloatx16{};
+    for (int x = 0; x < 4; ++x) acc[x] = floatx16{};
   }
   {
   if constexpr (NS == 3) {
@@ -976,7 +943,7 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
   // patch-row pair exchange their Q[c] = sum_x M[x] A[x][c] through LDS, one
   // column c per pass; wave (yw, pt) finishes output row r = yw & 1 of column
   // cc = yw >> 1, Y[0] = (Q0 + Q1) + Q2, Y[1] = (Q1 - Q2) - Q3 (cfg 18's order)
-  wfloatx4* X = reinterpret_cast<wfloatx4*>(smem4);
+  floatx4* X = reinterpret_cast<floatx4*>(smem4);
   const int r = yw & 1, cc = yw >> 1;
   const int y = y0 + 2 * pr + r, x = x0 + 2 * jx + cc;
   uint4* dst = a.dst_hi + (int64_t)img * a.dst_img;
@@ -993,7 +960,7 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
   for (int p = 0; p < 2; ++p) {
 #pragma unroll
     for (int k4 = 0; k4 < 4; ++k4) {
-      wfloatx4 g;
+      floatx4 g;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int i = 4 * k4 + e;
@@ -1006,10 +973,10 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
     if (cc == p) {
 #pragma unroll
       for (int k4 = 0; k4 < 4; ++k4) {
-        const wfloatx4 q0 = X[((pt * 4 + 0) * 4 + k4) * 64 + lane];
-        const wfloatx4 q1 = X[((pt * 4 + 1) * 4 + k4) * 64 + lane];
-        const wfloatx4 q2 = X[((pt * 4 + 2) * 4 + k4) * 64 + lane];
-        const wfloatx4 q3 = X[((pt * 4 + 3) * 4 + k4) * 64 + lane];
+        const floatx4 q0 = X[((pt * 4 + 0) * 4 + k4) * 64 + lane];
+        const floatx4 q1 = X[((pt * 4 + 1) * 4 + k4) * 64 + lane];
+        const floatx4 q2 = X[((pt * 4 + 2) * 4 + k4) * 64 + lane];
+        const floatx4 q3 = X[((pt * 4 + 3) * 4 + k4) * 64 + lane];
 #pragma unroll
         for (int e = 0; e < 4; ++e) yv[4 * k4 + e] = r == 0 ? (q0[e] + q1[e]) + q2[e] : (q1[e] - q2[e]) - q3[e];
       }
@@ -1142,7 +1109,7 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
     if constexpr (EPI == RRIN_EPI_LEAKY_POOL) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        wfloatx4 g;
+        floatx4 g;
 #pragma unroll
         for (int e = 0; e < 4; ++e) g[e] = vv[4 * k + e];
         X[((pt * 4 + yw) * 4 + k) * 64 + lane] = g;
@@ -1153,10 +1120,10 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
         uint4* pdst = a.pool_hi + (int64_t)img * a.pool_img;
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) {
-          const wfloatx4 y00 = X[((pt * 4 + 0) * 4 + qq) * 64 + lane];
-          const wfloatx4 y10 = X[((pt * 4 + 1) * 4 + qq) * 64 + lane];
-          const wfloatx4 y01 = X[((pt * 4 + 2) * 4 + qq) * 64 + lane];
-          const wfloatx4 y11 = X[((pt * 4 + 3) * 4 + qq) * 64 + lane];
+          const floatx4 y00 = X[((pt * 4 + 0) * 4 + qq) * 64 + lane];
+          const floatx4 y10 = X[((pt * 4 + 1) * 4 + qq) * 64 + lane];
+          const floatx4 y01 = X[((pt * 4 + 2) * 4 + qq) * 64 + lane];
+          const floatx4 y11 = X[((pt * 4 + 3) * 4 + qq) * 64 + lane];
           if (cob * 32 + 8 * qq < a.cout && yp < a.h && xp < a.w) {
             float s4[4];
 #pragma unroll
@@ -1197,61 +1164,28 @@ static int launch_winoq_k(const ConvH8Args& a, hipStream_t st) {
   return hip_code(hipGetLastError());
 }
 
-template <int PT>
-static int launch_winoq_sk(const ConvH8Args& a, int epi, hipStream_t st) {
-  switch (epi) {
-    case RRIN_EPI_LINEAR: return launch_winoq_k<RRIN_EPI_LINEAR, 0, PT, 1>(a, st);
-    case RRIN_EPI_LEAKY: return launch_winoq_k<RRIN_EPI_LEAKY, 0, PT, 1>(a, st);
-    case RRIN_EPI_LEAKY_POOL: return launch_winoq_k<RRIN_EPI_LEAKY_POOL, 0, PT, 1>(a, st);
-    case RRIN_EPI_LEAKY_REP: return launch_winoq_k<RRIN_EPI_LEAKY_REP, 0, PT, 1>(a, st);
-    case RRIN_EPI_SUBPIXEL: return launch_winoq_k<RRIN_EPI_SUBPIXEL, 0, PT, 1>(a, st);
-  }
-  return RRIN_E_ARG;
-}
-
-// Workgroup order of kinds 3 / 4 (as kind 6's, conv_winoc.hip::winoc_cob_group): when the co
-// blocks' U (nchunks x 16 KB each) exceeds RRIN_WINOQ_UGROUP_KB, groups of co blocks whose U fits
-// it, each group's workgroups consecutive -- an XCD then streams one group's U instead of every
-// co block's (the deep split-K convs of small images read each U once per XCD otherwise).  The
-// order changes no result.  Ring-folding launches keep their own index space.
+// Workgroup order of kinds 3 / 4: co-block groups (wino_cob_group) when the co blocks' U (nchunks x
+// 16 KB each) exceeds RRIN_WINOQ_UGROUP_KB -- the deep split-K convs of small images read each U
+// once per XCD otherwise.  Ring-folding launches keep their own index space.
 #ifndef RRIN_WINOQ_UGROUP_KB
 #define RRIN_WINOQ_UGROUP_KB 2048
 #endif
-static int winoq_cob_group(const ConvH8Args& a) {
-  const int64_t per_cob = (int64_t)a.nchunks * kWnU * 16;
-  const int64_t cap = (int64_t)RRIN_WINOQ_UGROUP_KB * 1024;
-  if (RRIN_WINOQ_UGROUP_KB <= 0 || a.nring > 0 || (int64_t)a.co_blocks * per_cob <= cap) return 0;
-  int g = 1;
-  while (2 * g < a.co_blocks && 2 * g * per_cob <= cap) g *= 2;
-  return g;
+
+template <int PT, int SK>
+static int launch_winoq_e(const ConvH8Args& a, int epi, hipStream_t st) {
+  return wino_dispatch_epi(epi, [&](auto e) { return launch_winoq_k<decltype(e)::value, 0, PT, SK>(a, st); });
 }
 
 int launch_winoq(const ConvH8Args& a0, int epi, int th, hipStream_t st) {
   ConvH8Args a = a0;
-  a.cob_group = winoq_cob_group(a0);
-  if (a.ksplit > 1) return th == 4 ? launch_winoq_sk<1>(a, epi, st) : launch_winoq_sk<2>(a, epi, st);
+  a.cob_group =
+      a.nring > 0 ? 0 : wino_cob_group(a.co_blocks, (int64_t)a.nchunks * kWnU * 16, RRIN_WINOQ_UGROUP_KB);
+  if (a.ksplit > 1) return th == 4 ? launch_winoq_e<1, 1>(a, epi, st) : launch_winoq_e<2, 1>(a, epi, st);
   if (a.nring > 0) {
     if (th != 8 || epi != RRIN_EPI_SUBPIXEL) return RRIN_E_CONFIG;
     return launch_winoq_k<RRIN_EPI_SUBPIXEL, 0, 2, 0, 1>(a, st);
   }
-  if (th == 4) {
-    switch (epi) {
-      case RRIN_EPI_LINEAR: return launch_winoq_k<RRIN_EPI_LINEAR, 0, 1>(a, st);
-      case RRIN_EPI_LEAKY: return launch_winoq_k<RRIN_EPI_LEAKY, 0, 1>(a, st);
-      case RRIN_EPI_LEAKY_POOL: return launch_winoq_k<RRIN_EPI_LEAKY_POOL, 0, 1>(a, st);
-      case RRIN_EPI_LEAKY_REP: return launch_winoq_k<RRIN_EPI_LEAKY_REP, 0, 1>(a, st);
-      case RRIN_EPI_SUBPIXEL: return launch_winoq_k<RRIN_EPI_SUBPIXEL, 0, 1>(a, st);
-    }
-    return RRIN_E_ARG;
-  }
-  switch (epi) {
-    case RRIN_EPI_LINEAR: return launch_winoq_k<RRIN_EPI_LINEAR>(a, st);
-    case RRIN_EPI_LEAKY: return launch_winoq_k<RRIN_EPI_LEAKY>(a, st);
-    case RRIN_EPI_LEAKY_POOL: return launch_winoq_k<RRIN_EPI_LEAKY_POOL>(a, st);
-    case RRIN_EPI_LEAKY_REP: return launch_winoq_k<RRIN_EPI_LEAKY_REP>(a, st);
-    case RRIN_EPI_SUBPIXEL: return launch_winoq_k<RRIN_EPI_SUBPIXEL>(a, st);
-  }
-  return RRIN_E_ARG;
+  return th == 4 ? launch_winoq_e<1, 0>(a, epi, st) : launch_winoq_e<2, 0>(a, epi, st);
 }
 
 #ifdef RRIN_LAB
@@ -1294,47 +1228,3 @@ extern "C" int rrin_winoq_clock_read(unsigned long long* host, int n) {
                                             hipMemcpyDeviceToHost));
 }
 #endif
-
-extern "C" int64_t rrin_pack_conv3x3_wino_floats(int32_t cout, int32_t cin) {
-  return rrin_pack_conv3x3_wino_bm_floats(cout, cin, 32);
-}
-
-extern "C" int64_t rrin_pack_conv3x3_wino_bm_floats(int32_t cout, int32_t cin, int32_t bm) {
-  if (cout < 1 || cin < 1 || (bm != 32 && bm != 64)) return RRIN_E_ARG;
-  const int64_t cob = (cout + bm - 1) / bm, nch = (cin + 7) / 8;
-  return cob * nch * 16 * 2 * bm * 4;
-}
-
-extern "C" int rrin_pack_conv3x3_wino(const float* w, const float* b, int32_t cout, int32_t cin, const int32_t* perm,
-                                      float* wpack, float* bpack) {
-  return rrin_pack_conv3x3_wino_bm(w, b, cout, cin, 32, perm, wpack, bpack);
-}
-
-// [co block of bm][8-channel chunk][transform point xi][record half][bm co][4 channels]
-extern "C" int rrin_pack_conv3x3_wino_bm(const float* w, const float* b, int32_t cout, int32_t cin, int32_t bm,
-                                         const int32_t* perm, float* wpack, float* bpack) {
-  if (!w || !b || !wpack || !bpack || cout < 1 || cin < 1 || (bm != 32 && bm != 64)) return RRIN_E_ARG;
-  if (perm)
-    for (int c = 0; c < cin; ++c)
-      if (perm[c] < 0 || perm[c] >= cin) return RRIN_E_ARG;
-  static const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
-  const int cob_n = (cout + bm - 1) / bm, nch = (cin + 7) / 8;
-  int64_t o = 0;
-  for (int cob = 0; cob < cob_n; ++cob)
-    for (int c = 0; c < nch; ++c)
-      for (int xi = 0; xi < 16; ++xi)
-        for (int hh = 0; hh < 2; ++hh)
-          for (int col = 0; col < bm; ++col)
-            for (int e = 0; e < 4; ++e) {
-              const int co = cob * bm + col, ch = c * 8 + hh * 4 + e;
-              double u = 0.0;
-              if (co < cout && ch < cin) {
-                const float* g = w + ((int64_t)co * cin + (perm ? perm[ch] : ch)) * 9;
-                for (int ky = 0; ky < 3; ++ky)
-                  for (int kx = 0; kx < 3; ++kx) u += G[xi >> 2][ky] * G[xi & 3][kx] * (double)g[ky * 3 + kx];
-              }
-              wpack[o++] = (float)u;
-            }
-  for (int co = 0; co < cob_n * bm; ++co) bpack[co] = co < cout ? b[co] : 0.f;
-  return 0;
-}

@@ -30,8 +30,8 @@
 // Wave yw (0-3) owns B^T row yw (points 4 yw .. 4 yw + 3) of every patch; lane
 // (j, hh): patch j of a 32-patch MFMA tile, record half hh (channels 4 hh .. + 3
 // of the chunk; MFMA product e contracts channels e and 4 + e).
-#include "common.hpp"
 #include "edge_fix.hpp"
+#include "wino_tile.hpp"
 
 #ifndef RRIN_WINOC_AGPR
 #define RRIN_WINOC_AGPR 0
@@ -56,27 +56,6 @@ namespace rrin {
 constexpr int kClkSlots = 1 << 16;
 __device__ unsigned long long g_winoc_clk[kClkSlots * 4];
 #endif
-
-typedef float cfloatx16 __attribute__((ext_vector_type(16)));
-typedef float cfloatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int cu32x4 __attribute__((ext_vector_type(4)));
-
-// LDS position of raw column col (0..33) within its row: even columns first (the
-// stride-2 window reads of 16 lanes fall on distinct banks), as kinds 1-4
-__device__ inline int wc_col(int col) { return (col & 1) * 17 + (col >> 1); }
-
-// buffer_load_dwordx4 ... lds: one 16-B record per lane at byte offset voff of rsrc into
-// the lane-linear LDS image at the wave-uniform base
-__device__ inline void buf_dma16(__amdgpu_buffer_rsrc_t rs, uint4* lds_wave_base, uint32_t voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, 0, 0,
-                                           0);
-}
-__device__ inline __amdgpu_buffer_rsrc_t buf_rsrc(const void* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
-__device__ inline cfloatx4 buf_load16(__amdgpu_buffer_rsrc_t rs, uint32_t voff, int soff) {
-  return __builtin_bit_cast(cfloatx4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
-}
 
 template <int NT>
 struct WinoC {
@@ -110,35 +89,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
       return;
     }
   }
-  int bid;
-  {  // XCD-aware bijective remap (conv_mfma.hip): an XCD's workgroups are consecutive tiles
-     // (nfix, a multiple of 8, keeps each conv workgroup's XCD)
-    const int nwg = (int)gridDim.x - a.nfix, q = nwg >> 3, r = nwg & 7;
-    const int cb = (int)blockIdx.x - a.nfix;
-    const int xcd = cb & 7, slot = cb >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  // (nfix, a multiple of 8, keeps each conv workgroup's XCD)
+  const int bid = wino_xcd_bid(a.nfix);
   const int ntiles = a.co_blocks * a.tiles_x * a.tiles_y * a.n;
   if (bid >= ntiles) return;
 #if RRIN_WINOC_CLOCK
   const unsigned long long clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
   const int nch = a.nchunks;
-  int cob, x0, y0, img;
-  {  // groups of cob_group co blocks, tile positions within a group, the group's co blocks
-     // of a tile position on consecutive workgroups (they share its raw tile)
-    const int cpg = a.cob_group > 0 ? a.cob_group : a.co_blocks;
-    const int gsz = cpg * (ntiles / a.co_blocks);  // workgroups of a full group
-    const int g = bid / gsz;
-    const int r = bid - g * gsz;
-    const int cg = min(cpg, a.co_blocks - g * cpg);  // co blocks of this group (the last may be short)
-    cob = g * cpg + r % cg;
-    int t = r / cg;
-    x0 = (t % a.tiles_x) * 32;
-    t /= a.tiles_x;
-    y0 = (t % a.tiles_y) * TH;
-    img = t / a.tiles_y;
-  }
+  const WinoTile tp = wino_tile_pos(a, ntiles, bid, 32, TH);
+  const int cob = tp.cob, x0 = tp.x0, y0 = tp.y0, img = tp.img;
 
   // ---- raw tile: rows y0 - 1 .. y0 + TH, cols x0 - 1 .. x0 + 32 of the chunk's two
   // record groups, by buffer_load ... lds from a per-chunk base (byte offsets per lane
@@ -183,14 +143,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
   const float sg = yw == 1 ? 1.f : -1.f;
   int pcol[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) pcol[k] = hh * RG + (2 * (j >> 4)) * 34 + wc_col(2 * jx + k);
+  for (int k = 0; k < 4; ++k) pcol[k] = hh * RG + (2 * (j >> 4)) * 34 + wino_col(2 * jx + k);
   const int oa = ra * 34, ob = rb * 34;
 
-  cfloatx16 acc[CT][NT][4];
+  floatx16 acc[CT][NT][4];
   // (set by chunk 0's first MFMA of each accumulator: C = 0, no zeroing per tile)
-  cfloatx4 u[CT][4];              // U of the chunk being computed (point x reloaded after its MFMAs)
-  cfloatx4 v[NT][4];              // B operands of the chunk being computed
-  cfloatx4 d[8];                  // window records of one N tile of the next chunk
+  floatx4 u[CT][4];              // U of the chunk being computed (point x reloaded after its MFMAs)
+  floatx4 v[NT][4];              // B operands of the chunk being computed
+  floatx4 d[8];                  // window records of one N tile of the next chunk
 
   // window records of N tile nt of the chunk in stage s -> d; B^T row yw -> its 4
   // points' B operands v[nt]
@@ -198,8 +158,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
     const uint4* rw = smem4 + s * STAGE + nt * 4 * 34;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      d[2 * k] = __builtin_bit_cast(cfloatx4, rw[oa + pcol[k]]);
-      d[2 * k + 1] = __builtin_bit_cast(cfloatx4, rw[ob + pcol[k]]);
+      d[2 * k] = __builtin_bit_cast(floatx4, rw[oa + pcol[k]]);
+      d[2 * k + 1] = __builtin_bit_cast(floatx4, rw[ob + pcol[k]]);
     }
   };
   auto transform = [&](int nt) {
@@ -207,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
       v[nt][0] = d[0], v[nt][1] = d[2], v[nt][2] = d[4], v[nt][3] = d[6];
       return;
     }
-    cfloatx4 tr[4];
+    floatx4 tr[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -223,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         acc[t][nt][x] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[t][x][e], v[nt][x][e],
-                                                                first && e == 0 ? cfloatx16{} : acc[t][nt][x], 0, 0, 0);
+                                                                first && e == 0 ? floatx16{} : acc[t][nt][x], 0, 0, 0);
   };
   auto reload_u = [&](int c, int x) {
 #pragma unroll
@@ -321,11 +281,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
 #endif
   __syncthreads();  // every read of the stages done before the exchange reuses the LDS
 
-  // ---- output transform (kinds 1-4's order): Q[c] = sum_x M[x] A[x][c] of this wave's
+  // ---- output transform (kind 3's order): Q[c] = sum_x M[x] A[x][c] of this wave's
   // B^T row, Y[0][c] = (Q0 + Q1) + Q2, Y[1][c] = (Q1 - Q2) - Q3 over the four waves,
   // exchanged through LDS one co tile at a time; wave yw then finishes output row
   // r = yw & 1, column cc = yw >> 1 of its patches
-  cfloatx4* X = reinterpret_cast<cfloatx4*>(smem4);
+  floatx4* X = reinterpret_cast<floatx4*>(smem4);
   const int r = yw & 1, cc = yw >> 1;
   uint4* dst = a.dst_hi + (int64_t)img * a.dst_img;
   auto store4 = [&](int64_t rec, const float* vv) {
@@ -338,7 +298,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        cfloatx4 g;
+        floatx4 g;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int vi = 4 * k + e, c2 = vi >> 4, i = vi & 15;
@@ -354,10 +314,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
 #pragma unroll
       for (int k4 = 0; k4 < 4; ++k4) {
         const int k = 4 * cc + k4;
-        const cfloatx4 q0 = X[((nt * 4 + 0) * 8 + k) * 64 + lane];
-        const cfloatx4 q1 = X[((nt * 4 + 1) * 8 + k) * 64 + lane];
-        const cfloatx4 q2 = X[((nt * 4 + 2) * 8 + k) * 64 + lane];
-        const cfloatx4 q3 = X[((nt * 4 + 3) * 8 + k) * 64 + lane];
+        const floatx4 q0 = X[((nt * 4 + 0) * 8 + k) * 64 + lane];
+        const floatx4 q1 = X[((nt * 4 + 1) * 8 + k) * 64 + lane];
+        const floatx4 q2 = X[((nt * 4 + 2) * 8 + k) * 64 + lane];
+        const floatx4 q3 = X[((nt * 4 + 3) * 8 + k) * 64 + lane];
 #pragma unroll
         for (int e = 0; e < 4; ++e) yv[nt][4 * k4 + e] = r == 0 ? (q0[e] + q1[e]) + q2[e] : (q1[e] - q2[e]) - q3[e];
       }
@@ -410,10 +370,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
         }
         if constexpr (EPI == RRIN_EPI_LEAKY_POOL) {
           // the patch's four outputs (yw = (r, c)) meet in LDS; wave 0 writes
-          // avg = 0.25 ((Y00 + Y10) + (Y01 + Y11)), kinds 1-4's order
+          // avg = 0.25 ((Y00 + Y10) + (Y01 + Y11)), kind 3's order (conv_wino.hip)
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            cfloatx4 g;
+            floatx4 g;
 #pragma unroll
             for (int e = 0; e < 4; ++e) g[e] = vv[4 * k + e];
             X[(yw * 4 + k) * 64 + lane] = g;
@@ -424,10 +384,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
             uint4* pdst = a.pool_hi + (int64_t)img * a.pool_img;
 #pragma unroll
             for (int qq = 0; qq < 4; ++qq) {
-              const cfloatx4 y00 = X[(0 * 4 + qq) * 64 + lane];
-              const cfloatx4 y10 = X[(1 * 4 + qq) * 64 + lane];
-              const cfloatx4 y01 = X[(2 * 4 + qq) * 64 + lane];
-              const cfloatx4 y11 = X[(3 * 4 + qq) * 64 + lane];
+              const floatx4 y00 = X[(0 * 4 + qq) * 64 + lane];
+              const floatx4 y10 = X[(1 * 4 + qq) * 64 + lane];
+              const floatx4 y01 = X[(2 * 4 + qq) * 64 + lane];
+              const floatx4 y11 = X[(3 * 4 + qq) * 64 + lane];
               if (cobe * 32 + 8 * qq < a.cout && yp < a.h && xp < a.w) {
                 float s4[4];
 #pragma unroll
@@ -481,37 +441,17 @@ static int launch_winoc_k(const ConvH8Args& a, hipStream_t st) {
 
 template <int CT, int NT>
 static int launch_winoc_e(const ConvH8Args& a, int epi, hipStream_t st) {
-  switch (epi) {
-    case RRIN_EPI_LINEAR: return launch_winoc_k<RRIN_EPI_LINEAR, CT, NT>(a, st);
-    case RRIN_EPI_LEAKY: return launch_winoc_k<RRIN_EPI_LEAKY, CT, NT>(a, st);
-    case RRIN_EPI_LEAKY_POOL: return launch_winoc_k<RRIN_EPI_LEAKY_POOL, CT, NT>(a, st);
-    case RRIN_EPI_LEAKY_REP: return launch_winoc_k<RRIN_EPI_LEAKY_REP, CT, NT>(a, st);
-    case RRIN_EPI_SUBPIXEL: return launch_winoc_k<RRIN_EPI_SUBPIXEL, CT, NT>(a, st);
-  }
-  return RRIN_E_ARG;
+  return wino_dispatch_epi(epi, [&](auto e) { return launch_winoc_k<decltype(e)::value, CT, NT>(a, st); });
 }
 
-// Workgroup order (XCD-aware remap: an XCD runs a contiguous range of workgroups): a
-// workgroup streams its co block's whole U (nchunks x 32 BM records); when the co blocks'
-// U does not fit an XCD's 4 MB L2, co blocks of one tile position that started at
-// different times each stream U from HBM (PMC: up to 11x the algorithmic bytes on the
-// deep convs).  Groups of co blocks whose U fits kWinoCUGroupBytes put each XCD on one
-// group (its U read once per XCD, L2-resident) at the price of reading each raw tile
-// once per group.  The order does not change any result.
+// co-block groups (wino_cob_group): U of a group within this many KB
 #ifndef RRIN_WINOC_UGROUP_KB
 #define RRIN_WINOC_UGROUP_KB 2048
 #endif
-static int winoc_cob_group(const ConvH8Args& a, int bm) {
-  const int64_t per_cob = (int64_t)a.nchunks * 32 * bm * 16;  // U bytes of one co block
-  if (RRIN_WINOC_UGROUP_KB <= 0 || (int64_t)a.co_blocks * per_cob <= (int64_t)RRIN_WINOC_UGROUP_KB * 1024) return 0;
-  int g = 1;  // the largest power of two of co blocks whose U fits (at least one)
-  while (2 * g < a.co_blocks && 2 * g * per_cob <= (int64_t)RRIN_WINOC_UGROUP_KB * 1024) g *= 2;
-  return g;
-}
-
 int launch_winoc(const ConvH8Args& a, int epi, int ct, hipStream_t st) {
   ConvH8Args b = a;
-  b.cob_group = winoc_cob_group(a, 32 * ct);
+  // U of one co block: nchunks x 32 BM records
+  b.cob_group = wino_cob_group(a.co_blocks, (int64_t)a.nchunks * 32 * (32 * ct) * 16, RRIN_WINOC_UGROUP_KB);
   return ct == 2 ? launch_winoc_e<2, 1>(b, epi, st) : launch_winoc_e<1, 2>(b, epi, st);
 }
 

@@ -27,17 +27,12 @@
 // the next tile's raw(0), raw(1), U(0) before this tile's epilogue (W42P: the exchange in two
 // halves, the stages past it).
 // U: rrin_pack_conv3x3_wino_cfg for this kind, [cob][chunk][xi 24][hh][32 co][4 ch].
-#include <type_traits>
-
-#include "common.hpp"
+#include "wino_tile.hpp"
 
 #ifndef RRIN_WINO42_AGPR
 #define RRIN_WINO42_AGPR 0
 #endif
 namespace rrin {
-
-typedef float w42f16 __attribute__((ext_vector_type(16)));
-typedef float w42f4 __attribute__((ext_vector_type(4)));
 
 // Tile geometry PCW: 8 -> 32 px x 8 rows (8 x 4 patches), 4 -> 16 px x 16 rows (4 x 8 patches).
 // Every output comes from the same patch, transforms and MFMA column arithmetic in both, so the
@@ -103,29 +98,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc42_kernel(ConvH8Args a) {
   const int yw = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 31, hh = lane >> 5;
   const int pc = j % PCW, pr = j / PCW;
-  int bid;
-  {  // XCD-aware bijective remap (conv_mfma.hip): an XCD's workgroups are consecutive tiles
-    const int nwg = (int)gridDim.x, q = nwg >> 3, r = nwg & 7;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  const int bid = wino_xcd_bid();
   const int ntiles = a.co_blocks * a.tiles_x * a.tiles_y * a.n;
   if (bid >= ntiles) return;
   const int nch = a.nchunks;
   // tile -> (co block, x0, y0, image); co-block groups as kind 6 (launch_winoc42: U of a group
   // fits an XCD's L2).  PERSIST: workgroup b runs tiles b, b + grid, ...
   auto decode = [&](int tile, int& cob_, int& x0_, int& y0_, int& img_) {
-    const int cpg = a.cob_group > 0 ? a.cob_group : a.co_blocks;
-    const int gsz = cpg * (ntiles / a.co_blocks);
-    const int g = tile / gsz;
-    const int r = tile - g * gsz;
-    const int cg = min(cpg, a.co_blocks - g * cpg);
-    cob_ = g * cpg + r % cg;
-    int t = r / cg;
-    x0_ = (t % a.tiles_x) * TW;
-    t /= a.tiles_x;
-    y0_ = (t % a.tiles_y) * TH;
-    img_ = t / a.tiles_y;
+    const WinoTile p = wino_tile_pos(a, ntiles, tile, TW, TH);
+    cob_ = p.cob, x0_ = p.x0, y0_ = p.y0, img_ = p.img;
   };
   int tile = bid, cob, x0, y0, img;
   decode(tile, cob, x0, y0, img);
@@ -171,7 +152,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc42_kernel(ConvH8Args a) {
   const uint32_t uvoff = (uint32_t)(hh * 32 + j) * 16u;
   auto load_u = [&](int c, int x) {
     const int soff = c * (1536 * 16) + (6 * yw + (x & 4)) * 1024;
-    return __builtin_bit_cast(w42f4,
+    return __builtin_bit_cast(floatx4,
                               __builtin_amdgcn_raw_buffer_load_b128(w42_rsrc(ub), uvoff + (x & 3) * 1024, soff, 0));
   };
 
@@ -182,22 +163,22 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc42_kernel(ConvH8Args a) {
   const int lbase = hh * RG + 2 * pr * RW + pc;
   const int oa = lbase + ra * RW, ob = lbase + rb * RW;
 
-  w42f16 acc[6];  // set by chunk 0's first MFMA of each point (C = 0: no 96 zeroing moves per tile)
+  floatx16 acc[6];  // set by chunk 0's first MFMA of each point (C = 0: no 96 zeroing moves per tile)
   // U of the chunk being computed (point x reloaded for the next chunk after its MFMAs; a
   // prefetch distance of two chunks needs a second set: 256 VGPRs and spills)
-  w42f4 ua[6];
-  w42f4 v[6];   // B operands of the chunk being computed
-  w42f4 d[12];  // window records of the next chunk: rows ra / rb, columns 0-5
+  floatx4 ua[6];
+  floatx4 v[6];   // B operands of the chunk being computed
+  floatx4 d[12];  // window records of the next chunk: rows ra / rb, columns 0-5
 
   auto read_raw = [&](int s) {
     const uint4* rw = smem4 + SB + s * STAGE;
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
-      d[2 * k] = __builtin_bit_cast(w42f4, rw[oa + w42_slot<WM>(k)]);
-      d[2 * k + 1] = __builtin_bit_cast(w42f4, rw[ob + w42_slot<WM>(k)]);
+      d[2 * k] = __builtin_bit_cast(floatx4, rw[oa + w42_slot<WM>(k)]);
+      d[2 * k + 1] = __builtin_bit_cast(floatx4, rw[ob + w42_slot<WM>(k)]);
     }
   };
-  w42f4 t[6];
+  floatx4 t[6];
   auto rows = [&]() {
 #pragma unroll
     for (int k = 0; k < 6; ++k)
@@ -221,10 +202,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc42_kernel(ConvH8Args a) {
       v[5][e] = fmaf(4.f, t[1][e], fmaf(-5.f, t[3][e], t[5][e]));
     }
   };
-  auto mfma_point = [&](const w42f4(&u)[6], int x, const bool first) {
+  auto mfma_point = [&](const floatx4(&u)[6], int x, const bool first) {
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[x][e], v[x][e], first && e == 0 ? w42f16{} : acc[x], 0, 0, 0);
+      acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[x][e], v[x][e], first && e == 0 ? floatx16{} : acc[x], 0, 0, 0);
   };
   auto bar = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   auto fence = [&]() { __builtin_amdgcn_sched_barrier(0); };
@@ -237,7 +218,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc42_kernel(ConvH8Args a) {
   // per chunk: U pts 0-2, raw(c + 2), U pts 3-5 -- the same every chunk.  The prologue issues
   // raw(0), raw(1), U(0) (also when it is the previous tile's prefetch), so chunk 0's wait for
   // raw(1) leaves 9 loads in flight: U(0) and U(1) pts 0-2.
-  auto chunk = [&](int c, int s, const bool more, const bool first, w42f4(&u)[6]) {
+  auto chunk = [&](int c, int s, const bool more, const bool first, floatx4(&u)[6]) {
     const int cu = c + 1;
 #pragma unroll
     for (int x = 0; x < 3; ++x) {
@@ -301,7 +282,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc42_kernel(ConvH8Args a) {
   const int prw = yw * NPR + (NPR == 1 ? 0 : (lane >> 4) & 1);
   const int src = (xo >> 2) + PCW * prw + 32 * hh;  // the lane of the MFMA layout holding this patch
   auto qrec = [&](int k) {
-    w42f4 g;
+    floatx4 g;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int vi = 4 * k + e, c = vi >> 4, i = vi & 15;
@@ -313,7 +294,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc42_kernel(ConvH8Args a) {
     }
     return g;
   };
-  w42f4* X = reinterpret_cast<w42f4*>(smem4);
+  floatx4* X = reinterpret_cast<floatx4*>(smem4);
   float bsv[16];
   int ncob = 0;
   // the epilogue of the current tile; PF: the next tile's raw(0), raw(1) are in flight, its U(0)
@@ -328,10 +309,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc42_kernel(ConvH8Args a) {
 #pragma unroll
       for (int k4 = 0; k4 < 4; ++k4) {
         const int k = 4 * cx + k4;
-        const w42f4 q0 = X[(0 * 16 + k) * XP + src];
-        const w42f4 q1 = X[(1 * 16 + k) * XP + src];
-        const w42f4 q2 = X[(2 * 16 + k) * XP + src];
-        const w42f4 q3 = X[(3 * 16 + k) * XP + src];
+        const floatx4 q0 = X[(0 * 16 + k) * XP + src];
+        const floatx4 q1 = X[(1 * 16 + k) * XP + src];
+        const floatx4 q2 = X[(2 * 16 + k) * XP + src];
+        const floatx4 q3 = X[(3 * 16 + k) * XP + src];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           yv[0][4 * k4 + e] = (q0[e] + q1[e]) + q2[e];
@@ -348,10 +329,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc42_kernel(ConvH8Args a) {
 #pragma unroll
         for (int k4h = 0; k4h < 2; ++k4h) {
           const int kk = 2 * cx + k4h, k4 = 2 * h + k4h;
-          const w42f4 q0 = X[(0 * 8 + kk) * XP + src];
-          const w42f4 q1 = X[(1 * 8 + kk) * XP + src];
-          const w42f4 q2 = X[(2 * 8 + kk) * XP + src];
-          const w42f4 q3 = X[(3 * 8 + kk) * XP + src];
+          const floatx4 q0 = X[(0 * 8 + kk) * XP + src];
+          const floatx4 q1 = X[(1 * 8 + kk) * XP + src];
+          const floatx4 q2 = X[(2 * 8 + kk) * XP + src];
+          const floatx4 q3 = X[(3 * 8 + kk) * XP + src];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             yv[0][4 * k4 + e] = (q0[e] + q1[e]) + q2[e];
@@ -524,19 +505,13 @@ static std::atomic<int> g_wino42_geom{RRIN_WINO42_GEOM_DEFAULT};
 #define RRIN_WINO42_PERSIST_MINT 768
 #endif
 
-// co-block groups whose U fits kWinoCUGroupBytes of an XCD's L2 (as launch_winoc)
+// co-block groups (wino_cob_group): U of a group within this many KB
 #ifndef RRIN_WINO42_UGROUP_KB
 #define RRIN_WINO42_UGROUP_KB 2048
 #endif
 int launch_winoc42(const ConvH8Args& a, int epi, hipStream_t st) {
   ConvH8Args b = a;
-  const int64_t per_cob = (int64_t)a.nchunks * 1536 * 16;
-  b.cob_group = 0;
-  if (RRIN_WINO42_UGROUP_KB > 0 && (int64_t)a.co_blocks * per_cob > (int64_t)RRIN_WINO42_UGROUP_KB * 1024) {
-    int g = 1;
-    while (2 * g < a.co_blocks && 2 * g * per_cob <= (int64_t)RRIN_WINO42_UGROUP_KB * 1024) g *= 2;
-    b.cob_group = g;
-  }
+  b.cob_group = wino_cob_group(a.co_blocks, (int64_t)a.nchunks * 1536 * 16, RRIN_WINO42_UGROUP_KB);
   // the 16 x 16 tile when it needs fewer rounds of the 512 resident workgroups (two per CU):
   // 1280 x 720's level 4 (80 x 45) is 576 tiles of 32 x 8 (1.1 rounds, 28 % of the area past
   // the image) but 480 of 16 x 16; elsewhere the 32 x 8 tile (10 raw rows per 8, not 18 per 16)
@@ -554,20 +529,12 @@ int launch_winoc42(const ConvH8Args& a, int epi, hipStream_t st) {
   const bool persist = !use_tall && mode != 3 && RRIN_WINO42_PERSIST_MAXCH > 0 &&
                        a.nchunks <= RRIN_WINO42_PERSIST_MAXCH && wide >= RRIN_WINO42_PERSIST_MINT;
   const int64_t grid = persist ? std::min<int64_t>(RRIN_WINO42_PERSIST_WG, wide / 2) : use_tall ? tall : wide;
-#define RRIN_W42_CASE(E)                                                       \
-  case E:                                                                      \
-    return use_tall  ? launch_winoc42_k<E, 4, false>(b, grid, st)              \
-           : persist ? launch_winoc42_k<E, 8, true>(b, grid, st)               \
+  return wino_dispatch_epi(epi, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    return use_tall  ? launch_winoc42_k<E, 4, false>(b, grid, st)
+           : persist ? launch_winoc42_k<E, 8, true>(b, grid, st)
                      : launch_winoc42_k<E, 8, false>(b, grid, st);
-  switch (epi) {
-    RRIN_W42_CASE(RRIN_EPI_LINEAR)
-    RRIN_W42_CASE(RRIN_EPI_LEAKY)
-    RRIN_W42_CASE(RRIN_EPI_LEAKY_POOL)
-    RRIN_W42_CASE(RRIN_EPI_LEAKY_REP)
-    RRIN_W42_CASE(RRIN_EPI_SUBPIXEL)
-  }
-#undef RRIN_W42_CASE
-  return RRIN_E_ARG;
+  });
 }
 
 }  // namespace rrin
@@ -580,45 +547,4 @@ using namespace rrin;
 extern "C" int rrin_conv_h8_set_wino42_geom(int32_t mode) {
   if (mode < 0 || mode > 3) return RRIN_E_ARG;
   return g_wino42_geom.exchange(mode);
-}
-
-// Kind-14 packing: [co block of 32][8-channel chunk][point xi = 6 eta + xi_x][record half][32 co][4 ch],
-// U(eta, xi_x) = sum G2[eta][ky] G4[xi_x][kx] g[ky][kx] in double, rounded once to fp32
-extern "C" int64_t rrin_pack_conv3x3_wino42_floats(int32_t cout, int32_t cin) {
-  if (cout < 1 || cin < 1) return RRIN_E_ARG;
-  return (int64_t)((cout + 31) / 32) * ((cin + 7) / 8) * 24 * 2 * 32 * 4;
-}
-
-extern "C" int rrin_pack_conv3x3_wino42(const float* w, const float* b, int32_t cout, int32_t cin, const int32_t* perm,
-                                        float* wpack, float* bpack) {
-  if (!w || !b || !wpack || !bpack || cout < 1 || cin < 1) return RRIN_E_ARG;
-  if (perm)
-    for (int c = 0; c < cin; ++c)
-      if (perm[c] < 0 || perm[c] >= cin) return RRIN_E_ARG;
-  static const double G2[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
-  static const double G4[6][3] = {{0.25, 0.0, 0.0},
-                                  {-1.0 / 6, -1.0 / 6, -1.0 / 6},
-                                  {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                  {1.0 / 24, 1.0 / 12, 1.0 / 6},
-                                  {1.0 / 24, -1.0 / 12, 1.0 / 6},
-                                  {0.0, 0.0, 1.0}};
-  const int cob_n = (cout + 31) / 32, nch = (cin + 7) / 8;
-  int64_t o = 0;
-  for (int cob = 0; cob < cob_n; ++cob)
-    for (int c = 0; c < nch; ++c)
-      for (int xi = 0; xi < 24; ++xi)
-        for (int hh = 0; hh < 2; ++hh)
-          for (int col = 0; col < 32; ++col)
-            for (int e = 0; e < 4; ++e) {
-              const int co = cob * 32 + col, ch = c * 8 + hh * 4 + e;
-              double u = 0.0;
-              if (co < cout && ch < cin) {
-                const float* g = w + ((int64_t)co * cin + (perm ? perm[ch] : ch)) * 9;
-                for (int ky = 0; ky < 3; ++ky)
-                  for (int kx = 0; kx < 3; ++kx) u += G2[xi / 6][ky] * G4[xi % 6][kx] * (double)g[ky * 3 + kx];
-              }
-              wpack[o++] = (float)u;
-            }
-  for (int co = 0; co < cob_n * 32; ++co) bpack[co] = co < cout ? b[co] : 0.f;
-  return 0;
 }

@@ -627,7 +627,7 @@ extern "C" int rrin_twarp_bwd(const float* img, const float* flow, const float* 
 }
 
 // ---- Winograd weight pack on the device (training: the weights change every optimizer
-// step).  The layout and arithmetic of rrin_pack_conv3x3_wino_bm (conv_wino.hip): per
+// step).  The layout and arithmetic of rrin_pack_conv3x3_wino_bm (pack_wino.hip): per
 // output row o, input channel i and point xi, u = sum_ky sum_kx G[xi/4][ky] G[xi%4][kx] g,
 // in double, that order, no contraction, rounded once -- the host packing's bits.
 // mode 0: g = W[o][i] (the forward conv); mode 1: g = W[i][o] flipped in y and x (the

@@ -210,6 +210,29 @@ def test_h8_conv_pool(gpu, prec, n, cin, cout, h, w):
                                    err_msg=f"cfg {cfg}")
 
 
+# U of the co blocks past the 2 MB group budget, with a group size (the largest power of two whose U
+# fits) that does not divide the co blocks: the last co-block group is short.  Co blocks of BM
+# channels, U per co block = cin / chunk channels x records x 16 B:
+#   kinds 3, 4 (BM 32, 512 KB): 5 co blocks, groups 4 + 1     kind 6 R32 (BM 64, 1 MB): 3, 2 + 1
+#   kind 14 (BM 32, 768 KB): 3, 2 + 1                          kind 6 F16 (BM 64, 1 MB): 5, 2 + 2 + 1
+# on a 2 x 2-3 tile grid that is partial in both directions.
+@pytest.mark.parametrize("prec,kinds,n,cin,cout,h,w", [(R32, (3, 4), 1, 256, 160, 9, 40), (R32, (6,), 1, 256, 192, 9, 40),
+                                                       (F16, (6,), 1, 512, 320, 9, 40), (R32, (14,), 1, 256, 96, 9, 40)])
+def test_h8_wino_short_last_cob_group(gpu, prec, kinds, n, cin, cout, h, w):
+    lib = _lib.lib()
+    x = torch.rand(n, cin, h, w, device=gpu) * 2 - 1
+    wt, b = keyed_conv(cin, cout)
+    ref = ref_conv(x, wt, b, 0.1).numpy()
+    ran = []
+    for cfg in cfgs(prec, cout, cin):
+        if lib.rrin_conv_h8_cfg_wino(cfg) not in kinds:
+            continue
+        dst, _ = conv_h8(H8Tensor.from_nchw(x, prec), wt, b, cfg, prec, epi=_lib.EPI_LEAKY)
+        np.testing.assert_allclose(dst.to_nchw().cpu().double().numpy(), ref, **tol(prec, cfg), err_msg=f"cfg {cfg}")
+        ran.append(lib.rrin_conv_h8_cfg_wino(cfg))
+    assert sorted(set(ran)) == sorted(kinds), ran
+
+
 @pytest.mark.parametrize("prec", PRECS)
 def test_h8_conv_partial_channels_and_perm(gpu, prec):
     x = torch.rand(2, 16, 32, 48, device=gpu)
