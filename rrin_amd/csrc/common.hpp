@@ -197,11 +197,11 @@ __device__ inline float warp_apply_f(const WarpTaps& t, F get) {
 }
 #pragma clang fp contract(on)
 
-// ---- record-layout conv kernels (conv_h8.hip, conv_wino.hip) --------------
+// ---- record-layout conv kernels (conv_h8.hip, conv_wino*.hip; front end conv_rec.hip) ----
 // LeakyReLU for 0 <= slope <= 1 (h8_prepare checks): one mul + one max
 __device__ inline float leaky(float t, float slope) { return fmaxf(t, t * slope); }
 
-// sub-pixel ring fix-up (conv_h8.hip edge_fix_*): tiles of kFixPx line pixels x kFixCo output
+// sub-pixel ring fix-up (edge_fix.hip, edge_fix.hpp): tiles of kFixPx line pixels x kFixCo output
 // channels, input channels staged kFixCi at a time
 constexpr int kFixPx = 32, kFixCo = 32, kFixCi = 32;
 
@@ -302,7 +302,17 @@ __device__ inline void dma16(const uint4* src, uint4* lds_wave_base) {
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-// Winograd F(2x2,3x3) exact-fp32 conv (conv_wino.hip): tile config kWinoCfg of
+// The direct-form tiles (conv_h8.hip): tile config cfg (kind 0 of the table in h8_cfg.hpp) at
+// record precision prec with epilogue epi.
+int launch_h8(const ConvH8Args& a, int cfg, int prec, int epi, hipStream_t st);
+// The ring fix-up as its own launch (edge_fix.hip): validate d and fill a (everything but the K
+// split) and its grid (ring tiles x co blocks x images); launch it with the K split of cin and
+// prec (d: the caller's cross-workgroup scratch, may be null; one_group: one K group, fp32 runs of
+// one chunk -- the summation order of the fix-up inside a conv's launch).
+int edge_fix_prepare(const rrin_edge_fix_desc* d, EdgeFixArgs& a, dim3& grid);
+int edge_fix_run(EdgeFixArgs a, dim3 grid, int prec, bool full, const rrin_edge_fix_desc* d, hipStream_t st,
+                 bool one_group = false);
+// Winograd F(2x2,3x3) exact-fp32 conv (conv_wino.hip): tile config 18 of
 // the record-layout table (F32R only), its LDS bytes per block and launcher.
 constexpr size_t kWinoLds = (size_t)(2 * 704 + 2 * 16 * 2 * 32) * 16;
 int launch_wino(const ConvH8Args& a, int epi, hipStream_t st);
@@ -325,7 +335,7 @@ int launch_winoc(const ConvH8Args& a, int epi, int ct, hipStream_t st);
 constexpr size_t kWinoC42Lds = (size_t)4160 * 16;
 int launch_winoc42(const ConvH8Args& a, int epi, hipStream_t st);
 // whether rrin_conv3x3_h8_fwd runs a ring_full fix-up inside the conv's launch for tile config
-// cfg, cin input channels and precision prec (else it launches it after the conv) -- conv_h8.hip
+// cfg, cin input channels and precision prec (else it launches it after the conv) -- conv_rec.hip
 bool ring_in_launch_ok(int cfg, int cin, int prec);
 // the kind-6 tile at fp16 (conv_winoh.hip): H8 records, v_mfma_f32_32x32x16_f16, packed-f16
 // input transform; same LDS as kWinoCLds1
@@ -367,9 +377,11 @@ constexpr int kB0Mid = 4 * kB0MR * kB0MC;            // conv-a tile records (ali
 constexpr size_t kB0Lds = (size_t)(kB0Mid + kB0Stage + 16) * 16;
 static_assert(kB0Stage <= kB0Mid, "stage Y inside the conv-a tile");
 static_assert(2 * kB0Lds <= 160 * 1024, "two fused-block workgroups per CU");
-int launch_block0(const Block0Args& a, hipStream_t st);
 #ifdef RRIN_LAB
 int launch_wino_lab(const ConvH8Args& a, int abl, hipStream_t st);  // ablation bits (conv_wino.hip)
+// one LEAKY conv of a direct-form tile at F16X3 (cfg 0, 1, 6) or F32R (cfg 0, 1, 3, 4, 5, 6, 16)
+// with schedule knobs sched (SCHED_*, ablations included) and grid persist (conv_h8.hip)
+int launch_h8_lab(const ConvH8Args& a, int cfg, int prec, int sched, int persist, hipStream_t st);
 #endif
 
 }  // namespace rrin

@@ -1,9 +1,8 @@
 // Direct-form 3x3 conv on the record layouts (h8.hpp) at all three record precisions, on the
 // gfx950 matrix cores: split-fp16 ("F16X3") and fp16 ("F16") on v_mfma_f32_32x32x16_f16, exact
-// fp32 ("F32R") on v_mfma_f32_32x32x2_f32, fp32 accumulate.  Also the tile-config table of every
-// record conv (the Winograd tiles of conv_wino*.hip included) with its queries, the entry points
-// rrin_conv3x3_h8_fwd / rrin_conv_block0_h8_fwd, and the sub-pixel ring fix-up's standalone
-// kernel and host side (edge_fix_*; device side in edge_fix.hpp).
+// fp32 ("F32R") on v_mfma_f32_32x32x2_f32, fp32 accumulate: the kernel, its launch templates and
+// the host entry launch_h8.  The tiles are the direct-form rows of the config table (h8_cfg.hpp);
+// descriptor validation and rrin_conv3x3_h8_fwd are in conv_rec.hip.
 //
 // Numerics (F16X3): every fp32 value v lives as hi = f16(v) and a pre-scaled
 // lo' = f16((v - hi) * 2^11), so v = hi + lo' 2^-11 to ~2^-22 |v| and lo' stays
@@ -18,31 +17,15 @@
 // (unet.py:29,59-63,78), F.avg_pool2d (unet.py:46, fused second output), torch.cat (unet.py:93, channel-offset views).  The non-conv passes of the record
 // path (upsample, layout, heads + model.py glue) are in glue_h8.hip, the host-side weight
 // packing in pack_h8.hip.
-#include <string.h>
-
 #include <type_traits>
 
 #include "edge_fix.hpp"
-#include "h8.hpp"
+#include "h8_cfg.hpp"
 
 namespace rrin {
 
-template <int NW, int WM, int WN, int PLANES>
-struct TileH8 {
-  static constexpr int NT = 64 * NW;
-  static constexpr int BM = 32 * WM;
-  static constexpr int TH = WN * NW;
-  static constexpr int ROWS = TH + 2;
-  static constexpr int IN_REC = 2 * ROWS * H8_LC;  // per plane: 2 groups x rows x cols
-  static constexpr int W_REC = 9 * 2 * BM;          // per plane: taps x halves x co
-  static constexpr int IN_IT = (IN_REC + NT - 1) / NT;
-  static constexpr int W_IT = (W_REC + NT - 1) / NT;
-  static constexpr size_t LDS = 2 * (size_t)PLANES * (IN_REC + W_REC) * 16;
-  static_assert(16 % TH == 0, "TH must divide the 16-row plane padding");
-};
-
-// Schedule knobs of the kernel (template SCHED; the cfg table picks them per
-// layer, tools/conv_lab.py ablate times them).  SPREAD issues the next chunk's
+// Schedule knobs of the kernel (template SCHED, the SCHED_* bits of h8_cfg.hpp; the cfg table picks
+// them per layer, tools/conv_lab.py ablate times them).  SPREAD issues the next chunk's
 // DMA pieces between the first kSpreadTaps taps of the current chunk instead
 // of in one burst before it; STAGGER lets waves NW/2.. issue theirs after tap
 // kStaggerTap instead (the two wave halves of a SIMD then load at different
@@ -68,10 +51,6 @@ struct TileH8 {
 #define RRIN_H8_BIAS -1
 #endif
 
-enum : int {
-  SCHED_NO_WDMA = 1, SCHED_NO_IDMA = 2, SCHED_NO_MFMA = 4, SCHED_NO_EPI = 8,
-  SCHED_SPREAD = 16, SCHED_WRES = 32, SCHED_STAGGER = 64, SCHED_MFMA16 = 128
-};
 constexpr int kSpreadTaps = 6, kStaggerTap = 3;
 
 // DMA = true: stage with LDS-DMA (requires cin % 8 == 0: no partial channel
@@ -740,95 +719,6 @@ __global__ void RRIN_PK_CONV_ATTR __launch_bounds__(64 * NW) conv3x3_h8_kernel(C
   if (bad && a.status) *a.status = 1;
 }
 
-// Config table: cfg -> (NW waves along rows, WM co-tiles, WN rows per wave,
-// SC schedule knobs SCHED_*, PE grid: 0 = one tile per block, k = k x the
-// blocks a CU holds at once, persistent).  16-17 (BM 32 x TH 4) are for the
-// few-tile deep levels of small workloads (engine size classes).
-#define RRIN_H8_CFGS(X)  \
-  X(0, 8, 2, 2, 0, 0)    \
-  X(1, 8, 1, 2, 0, 0)    \
-  X(2, 4, 2, 2, 0, 0)    \
-  X(3, 4, 1, 4, 0, 0)    \
-  X(4, 4, 2, 1, 0, 0)    \
-  X(5, 8, 4, 2, 0, 0)    \
-  X(6, 4, 1, 2, 0, 0)    \
-  X(7, 2, 1, 4, 0, 0)    \
-  X(8, 4, 1, 2, 32, 1)   \
-  X(9, 8, 1, 2, 32, 1)   \
-  X(10, 8, 2, 2, 16, 1)  \
-  X(11, 8, 2, 2, 16, 0)  \
-  X(12, 4, 1, 2, 16, 1)  \
-  X(13, 8, 1, 2, 16, 1)  \
-  X(14, 4, 1, 2, 48, 1)  \
-  X(15, 8, 1, 2, 48, 1)  \
-  X(16, 4, 1, 1, 16, 1)  \
-  X(17, 2, 1, 2, 16, 1)
-
-// Shared memory of one block: double-buffered input tile and weight slab, or
-// with WRES every chunk's weight slab resident.
-template <int NW, int WM, int WN, int PLANES>
-constexpr size_t h8_lds_bytes(bool wres, int nchunks) {
-  using T = TileH8<NW, WM, WN, PLANES>;
-  return ((size_t)2 * T::IN_REC + (size_t)(wres && nchunks > 2 ? nchunks : 2) * T::W_REC) * PLANES * 16;
-}
-
-struct CfgH8 {
-  int bm, th;
-  size_t lds1, lds2;  // at two weight slabs (WRES: at <= 2 chunks)
-  size_t wslab;       // bytes of one weight slab per plane (WRES: one more per chunk past 2)
-  bool pool_ok;
-  int sched, persist;
-  int nt;  // threads per workgroup (the direct-form tiles; 0: Winograd configs)
-};
-static constexpr size_t kRetiredLds = (size_t)1 << 30;  // > kMaxLds: never usable
-static const CfgH8 kCfgH8[] = {
-#define X(id, nw, wm, wn, sc, pe)                                                                               \
-  {TileH8<nw, wm, wn, 1>::BM, TileH8<nw, wm, wn, 1>::TH, h8_lds_bytes<nw, wm, wn, 1>((sc & SCHED_WRES) != 0, 2), \
-   h8_lds_bytes<nw, wm, wn, 2>((sc & SCHED_WRES) != 0, 2), (size_t)TileH8<nw, wm, wn, 1>::W_REC * 16,     \
-   (wn % 2) == 0, sc, pe, 64 * nw},
-    RRIN_H8_CFGS(X)
-#undef X
-    // kWinoCfg: Winograd F(2x2,3x3) on fp32 records (conv_wino.hip), BM 32 x TH 8
-    {32, 8, kWinoLds, (size_t)1 << 30, 0, true, 0, 0},
-    // config 19, retired in round 6: the kind-2 Winograd tile (BM 64, 8 waves, one block per CU)
-    // lost to kinds 3 and 6 and was removed; the id stays reserved so ids 20-24 keep their meaning
-    {64, 8, kRetiredLds, kRetiredLds, 0, true, 0, 0},
-    // kWinoQCfg: cfg 18's tile and packing, 8 waves of 4 accumulators (conv3x3_winoq_kernel)
-    {32, 8, (size_t)2 * (680 + 1024) * 16, (size_t)1 << 30, 0, true, 0, 0},
-    // kWinoQ4Cfg: the same on half-height tiles (TH 4, 4 waves): twice the tiles
-    {32, 4, (size_t)2 * (408 + 1024) * 16, (size_t)1 << 30, 0, true, 0, 0},
-    // config 22, retired in round 6: Winograd F(4x4,3x3) (kind 5), 1.28-1.58x kind 3's time
-    {32, 16, kRetiredLds, kRetiredLds, 0, true, 0, 0},
-    // kWinoC2Cfg: register-U tile, BM 64 x TH 4, 4 waves of 2 co tiles (conv_winoc.hip); at fp16
-    // the same tile with f16 MFMAs (conv_winoh.hip)
-    {64, 4, kWinoCLds1, (size_t)1 << 30, 0, true, 0, 0},
-    // kWinoC1Cfg: register-U tile, BM 32 x TH 8, 4 waves of 2 patch tiles
-    {32, 8, kWinoCLds2, (size_t)1 << 30, 0, true, 0, 0},
-    // kWinoC42Cfg (round 6): register-U tile in F(4,3) x F(2,3), BM 32 x TH 8 (conv_winoc42.hip)
-    {32, 8, kWinoC42Lds, (size_t)1 << 30, 0, true, 0, 0},
-};
-static constexpr int kNumCfgH8 = sizeof(kCfgH8) / sizeof(kCfgH8[0]);
-static constexpr int kWinoCfg = 18;
-static constexpr int kRetired19Cfg = 19;
-static constexpr int kWinoQCfg = 20;
-static constexpr int kWinoQ4Cfg = 21;
-static constexpr int kRetired22Cfg = 22;
-static constexpr int kWinoC2Cfg = 23;
-static constexpr int kWinoC1Cfg = 24;
-static constexpr int kWinoC42Cfg = 25;
-static_assert(kNumCfgH8 == 26, "config ids (engine tables, rrin_hip.h)");
-static inline bool is_winoc(int cfg) { return cfg == kWinoC2Cfg || cfg == kWinoC1Cfg; }
-// Round 6 removed the rejected Winograd tiles (kinds 2, 5, 8-13; DESIGN.md §5b-§5e keep their
-// measurements): ids 19 and 22 stay reserved (rrin_conv_h8_cfg_ok 0, RRIN_E_CONFIG), 25-30 are gone.
-static inline bool retired(int cfg) { return cfg == kRetired19Cfg || cfg == kRetired22Cfg; }
-static inline bool is_wino(int cfg) {
-  return cfg == kWinoCfg || cfg == kWinoQCfg || cfg == kWinoQ4Cfg || is_winoc(cfg) || cfg == kWinoC42Cfg;
-}
-// the fp16 Winograd tile (conv_winoh.hip): kind 6
-static inline bool is_winoh(int cfg) { return cfg == kWinoC2Cfg; }
-static constexpr size_t kMaxLds = 160 * 1024;
-static constexpr int kMaxKSplit = 16;
-
 static int num_cus(int dev) {
   static std::atomic<int> n[kMaxDevices] = {};
   int v = n[dev].load(std::memory_order_relaxed);
@@ -919,431 +809,21 @@ static int launch_h8_cfg(const ConvH8Args& args, int prec, int epi, int persist,
   return launch_h8_epi<NW, WM, WN, 1, SCHED, false>(args, epi, persist, st);
 }
 
-// ---- the ring fix-up as its own launch: kernel and host side -----------------------
-template <int PLANES, int KS, bool F32 = false, bool FULL = false>
-__global__ void RRIN_PK_EDGE_ATTR __launch_bounds__(256 * KS) edge_fix_h8_kernel(EdgeFixArgs a) {
-  edge_fix_body<PLANES, KS, F32, FULL>(a, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-
-template <int PLANES, int KS, bool F32, bool FULL>
-static int edge_fix_launch_m(const EdgeFixArgs& a, dim3 grid, hipStream_t st) {
-  constexpr size_t lds = (size_t)KS * kFixSubFloats * sizeof(float);
-  static_assert(lds <= 160 * 1024, "edge fix LDS");
-  static_assert(kFixSubFloats >= 4 * 256, "K-group sums fit a staging region");
-  static LdsAttr attr;
-  if (int e = attr.ensure((const void*)edge_fix_h8_kernel<PLANES, KS, F32, FULL>, (int)lds, st)) return e;
-  hipLaunchKernelGGL((edge_fix_h8_kernel<PLANES, KS, F32, FULL>), grid, dim3(256 * KS), lds, st, a);
-  return hip_code(hipGetLastError());
-}
-
-template <int PLANES, int KS, bool F32 = false>
-static int edge_fix_launch(const EdgeFixArgs& a, dim3 grid, hipStream_t st, bool full) {
-  return full ? edge_fix_launch_m<PLANES, KS, F32, true>(a, grid, st)
-              : edge_fix_launch_m<PLANES, KS, F32, false>(a, grid, st);
-}
-
-// K groups and K runs of the ring fix-up, by cin and precision only (the
-// summation order never depends on batch, size or scratch).  fp32 records: 2
-// groups from cin 64 on, never 4 (4 x 256 threads cap a thread at 128 VGPRs and
-// the fp32 kernel spills there: 31.6 vs 15.7 us per launch), runs of one chunk per
-// group (cin / 64 runs).  fp16: split16 stops at 2 groups (the two-plane kernel
-// spills at 4), one run.
-static void edge_fix_split(int cin, int prec, int* ks, int* nsl) {
-  *nsl = 1;
-  if (prec == RRIN_PREC_F32R) {
-    *ks = cin % (2 * kFixCi) == 0 ? 2 : 1;
-    if (cin % (*ks * kFixCi) == 0) *nsl = cin / (*ks * kFixCi);
-    return;
-  }
-  *ks = cin % (2 * kFixCi) == 0 && cin >= 4 * kFixCi ? 2 : 1;
-  if (planes_of(prec) == 1 && cin % (4 * kFixCi) == 0 && cin >= 8 * kFixCi) *ks = 4;
-}
-
-// validate d and fill a (everything but the K split); grid: ring tiles x co blocks x images
-static int edge_fix_prepare(const rrin_edge_fix_desc* d, EdgeFixArgs& a, dim3& grid) {
-  if (!d || (!d->edge && !d->full) || !d->wedge || !d->bias || (d->full != 0 && d->full != 1)) return RRIN_E_ARG;
-  if (!rec_prec(d->prec)) return RRIN_E_ARG;
-  if (d->n < 1 || d->cin < 8 || (d->cin & 7) || d->cout < 8 || (d->cout & 7)) return RRIN_E_ARG;
-  if (d->epi_mode != RRIN_EPI_LINEAR && d->epi_mode != RRIN_EPI_LEAKY) return RRIN_E_ARG;
-  if (!h8_ok(d->src, d->prec) || !h8_ok(d->dst, d->prec)) return RRIN_E_SHAPE;
-  if (d->dst.g.h != 2 * d->src.g.h || d->dst.g.w != 2 * d->src.g.w) return RRIN_E_SHAPE;
-  const int cpr = chans_per_rec(d->prec);
-  if (d->cin > cpr * d->src.groups || d->cout > cpr * d->dst.groups) return RRIN_E_ARG;
-  const int planes = planes_of(d->prec);
-  memset(&a, 0, sizeof(a));
-  const int64_t sg = (int64_t)d->src.g_off * d->src.g.plane, dg = (int64_t)d->dst.g_off * d->dst.g.plane;
-  a.s_hi = static_cast<const uint4*>(d->src.hi) + sg;
-  a.s_lo = planes == 2 ? static_cast<const uint4*>(d->src.lo) + sg : nullptr;
-  a.s_img = d->src.img_stride;
-  a.s_gp = d->src.g.plane;
-  a.s_wp = d->src.g.wp;
-  a.sh = d->src.g.h;
-  a.sw = d->src.g.w;
-  a.cin = d->cin;
-  if (d->prec == RRIN_PREC_F32R) {
-    a.d_f32 = static_cast<float*>(d->dst.hi) + dg * 4;
-  } else {
-    a.d_hi = static_cast<_Float16*>(d->dst.hi) + dg * 8;
-    a.d_lo = planes == 2 ? static_cast<_Float16*>(d->dst.lo) + dg * 8 : nullptr;
-  }
-  a.d_img = d->dst.img_stride;
-  a.d_gp = d->dst.g.plane;
-  a.d_wp = d->dst.g.wp;
-  a.cout = d->cout;
-  a.edge = d->edge;
-  a.wedge = d->wedge;
-  a.bias = d->bias;
-  a.ring = ring_pixels(d->dst.g.h, d->dst.g.w);
-  a.slope = d->slope;
-  a.leaky = d->epi_mode == RRIN_EPI_LEAKY;
-  a.status = d->status;
-  const int H = d->dst.g.h, W = d->dst.g.w;
-  a.tiles_row = (W + kFixPx - 1) / kFixPx;
-  a.tiles_col = (H - 2 + kFixPx - 1) / kFixPx;
-  grid = dim3((unsigned)(2 * a.tiles_row + 2 * a.tiles_col), (unsigned)((d->cout + kFixCo - 1) / kFixCo),
-              (unsigned)d->n);
-  a.nslices = 1;
-  a.cross = 0;
-  return 0;
-}
-
-// the fix-up as its own launch: K groups / runs by edge_fix_split; the cross-workgroup K split
-// where the caller passed its scratch (fp32 records)
-// (one_group: one K group, fp32 runs of one chunk -- the order of the in-launch fix-up)
-static int edge_fix_run(EdgeFixArgs a, dim3 grid, int prec, bool full, const rrin_edge_fix_desc* d,
-                        hipStream_t st, bool one_group = false) {
-  int ks, nsl;
-  edge_fix_split(a.cin, prec, &ks, &nsl);
-  if (one_group) {
-    ks = 1;
-    nsl = prec == RRIN_PREC_F32R ? a.cin / kFixCi : 1;
-    d = nullptr;
-  }
-  a.nslices = nsl;
-  a.cross = 0;
-  dim3 g = grid;
-  const int n = (int)grid.z;
-  const int64_t tiles = (int64_t)grid.x * grid.y * n;
-  if (d && nsl > 1 && d->part && d->cnt && tiles * nsl * 1024 <= d->part_floats && tiles <= d->cnt_len) {
-    a.cross = 1;  // one workgroup per K run (same arithmetic as the loop over runs)
-    a.part = d->part;
-    a.cnt = d->cnt;
-    g.z = (unsigned)(n * nsl);
-  }
-  if (prec == RRIN_PREC_F32R) {
-    return ks == 2 ? edge_fix_launch<1, 2, true>(a, g, st, full) : edge_fix_launch<1, 1, true>(a, g, st, full);
-  }
-  switch (planes_of(prec) * 8 + ks) {
-    case 2 * 8 + 2: return edge_fix_launch<2, 2>(a, g, st, full);
-    case 2 * 8 + 1: return edge_fix_launch<2, 1>(a, g, st, full);
-    case 1 * 8 + 4: return edge_fix_launch<1, 4>(a, g, st, full);
-    case 1 * 8 + 2: return edge_fix_launch<1, 2>(a, g, st, full);
-    default: return edge_fix_launch<1, 1>(a, g, st, full);
-  }
-}
-
-// Validate a conv descriptor and turn it into kernel arguments.
-static int h8_prepare(const rrin_conv_h8_desc* d, ConvH8Args& a, bool need_scratch = true) {
-  if (!d || !d->whi || !d->bias) return RRIN_E_ARG;
-  if (!rec_prec(d->prec)) return RRIN_E_ARG;
-  if (d->prec == RRIN_PREC_F16X3 && !d->wlo) return RRIN_E_ARG;
-  if (d->cfg < 0 || d->cfg >= kNumCfgH8 || retired(d->cfg) ||
-      (planes_of(d->prec) == 2 ? kCfgH8[d->cfg].lds2 : kCfgH8[d->cfg].lds1) > kMaxLds)
-    return RRIN_E_CONFIG;
-  if (d->n < 1 || d->cin < 1 || d->cout < 8 || (d->cout & 7)) return RRIN_E_ARG;
-  if (d->epi_mode < RRIN_EPI_LINEAR || d->epi_mode > RRIN_EPI_SUBPIXEL) return RRIN_E_ARG;
-  if (!h8_ok(d->src, d->prec) || !h8_ok(d->dst, d->prec)) return RRIN_E_SHAPE;
-  const bool sub = d->epi_mode == RRIN_EPI_SUBPIXEL;
-  const int h = d->src.g.h, w = d->src.g.w;  // the grid the conv runs on
-  if (d->dst.g.h != (sub ? 2 * h : h) || d->dst.g.w != (sub ? 2 * w : w)) return RRIN_E_SHAPE;
-  const int cpr = chans_per_rec(d->prec);
-  if (d->cin > cpr * d->src.groups || (sub ? d->cout / 4 : d->cout) > cpr * d->dst.groups) return RRIN_E_ARG;
-  if (sub && ((d->cout & 31) || !d->edge)) return RRIN_E_ARG;
-  if (!(d->slope >= 0.f && d->slope <= 1.f)) return RRIN_E_ARG;  // leaky() as max(t, slope t)
-  if (d->epi_mode == RRIN_EPI_LEAKY_POOL) {
-    if (!kCfgH8[d->cfg].pool_ok) return RRIN_E_CONFIG;  // a wave must own both rows of a pool pair
-    if (!h8_ok(d->pool, d->prec) || (h & 1) || (w & 1) || d->pool.g.h * 2 != h || d->pool.g.w * 2 != w ||
-        d->cout > cpr * d->pool.groups)
-      return RRIN_E_SHAPE;
-  }
-  const int planes = planes_of(d->prec);
-  const CfgH8& ci = kCfgH8[d->cfg];
-  memset(&a, 0, sizeof(a));
-  const int64_t sg = (int64_t)d->src.g_off * d->src.g.plane;
-  a.src_hi = static_cast<const uint4*>(d->src.hi) + sg;
-  a.src_lo = planes == 2 ? static_cast<const uint4*>(d->src.lo) + sg : nullptr;
-  a.src_img = d->src.img_stride;
-  a.src_gp = d->src.g.plane;
-  a.src_wp = d->src.g.wp;
-  a.cin = d->cin;
-  a.nchunks = (d->cin + 2 * cpr - 1) / (2 * cpr);  // 2 record groups per chunk
-  const int64_t dg = (int64_t)d->dst.g_off * d->dst.g.plane;
-  a.dst_hi = static_cast<uint4*>(d->dst.hi) + dg;
-  a.dst_lo = planes == 2 ? static_cast<uint4*>(d->dst.lo) + dg : nullptr;
-  a.dst_img = d->dst.img_stride;
-  a.dst_gp = d->dst.g.plane;
-  a.dst_wp = d->dst.g.wp;
-  a.cout = d->cout;
-  if (d->epi_mode == RRIN_EPI_LEAKY_POOL) {
-    const int64_t pg = (int64_t)d->pool.g_off * d->pool.g.plane;
-    a.pool_hi = static_cast<uint4*>(d->pool.hi) + pg;
-    a.pool_lo = planes == 2 ? static_cast<uint4*>(d->pool.lo) + pg : nullptr;
-    a.pool_img = d->pool.img_stride;
-    a.pool_gp = d->pool.g.plane;
-    a.pool_wp = d->pool.g.wp;
-  }
-  a.w_hi = static_cast<const uint4*>(d->whi);
-  a.w_lo = planes == 2 ? static_cast<const uint4*>(d->wlo) : nullptr;
-  a.bias = d->bias;
-  a.inv_wscale = d->prec == RRIN_PREC_F32R ? 1.0f : d->inv_wscale;
-  a.slope = d->slope;
-  a.tail_finite = d->tail_finite;
-  a.status = d->status;
-  a.h = h;
-  a.w = w;
-  if (sub) {
-    a.edge = d->edge;
-    a.ring = ring_pixels(2 * h, 2 * w);
-  }
-  a.co_blocks = (d->cout + ci.bm - 1) / ci.bm;
-  a.tiles_x = (w + 31) / 32;
-  a.tiles_y = (h + ci.th - 1) / ci.th;
-  if (is_wino(d->cfg) && d->prec == RRIN_PREC_F16) {
-    // fp16 Winograd (kind 6 only): 16-channel chunks of both record groups, no split / fold
-    if (!is_winoh(d->cfg) || d->ksplit > 1 || d->ring_w) return RRIN_E_CONFIG;
-    if ((d->cin & 15) && !d->tail_finite) return RRIN_E_CONFIG;
-  } else if (is_wino(d->cfg)) {
-    if (d->prec != RRIN_PREC_F32R) return RRIN_E_CONFIG;
-    if ((d->cin & 3) && !d->tail_finite) return RRIN_E_CONFIG;  // stages whole records only
-    // the register-U tiles stage both record groups of every chunk: they must exist
-    if ((is_winoc(d->cfg) || d->cfg == kWinoC42Cfg) && (d->cin & 7) && !d->tail_finite) return RRIN_E_CONFIG;
-    a.nchunks = (d->cin + 7) / 8;  // two record groups per K chunk
-  }
-  // the Winograd tiles stage every record group of every chunk (past cin against zero
-  // weights): the source view must hold them, or the staging reads past the tensor
-  if (is_wino(d->cfg) && 2 * a.nchunks > d->src.groups) return RRIN_E_SHAPE;
-  {
-    // LDS-DMA staging addresses the source through buffer resources (num_records 2^31 - 1) with
-    // 32-bit byte offsets: the direct-form tiles from one base per image (every staged record
-    // group of the image), the Winograd tiles from one base per tile and chunk (two groups).  A
-    // larger span would stage zeros past the range -- a wrong result with no error -- so it is
-    // rejected (a 64-channel fp16 view passes 2 GB near 6144x3456).
-    const bool dma = is_wino(d->cfg) || d->cin % 8 == 0 || d->tail_finite;
-    const int64_t span_groups = is_wino(d->cfg) ? 3 : 2 * (int64_t)a.nchunks;
-    if (dma && span_groups * d->src.g.plane * 16 >= ((int64_t)1 << 31)) return RRIN_E_SHAPE;
-  }
-  a.n = d->n;
-  if ((int64_t)a.co_blocks * a.tiles_x * a.tiles_y * a.n > 0x7fffffff) return RRIN_E_SHAPE;
-  a.ksplit = 1;
-  if (d->ksplit > 1) {  // Winograd split-K: kinds 3 and 4 only
-    if (d->cfg != kWinoQCfg && d->cfg != kWinoQ4Cfg) return RRIN_E_CONFIG;
-    if (d->ksplit > kMaxKSplit || (need_scratch && (!d->part || !d->cnt))) return RRIN_E_ARG;
-    a.kper = (a.nchunks + d->ksplit - 1) / d->ksplit;
-    a.ksplit = (a.nchunks + a.kper - 1) / a.kper;  // every slice non-empty
-    if ((int64_t)a.co_blocks * a.tiles_x * a.tiles_y * a.n * a.ksplit > 0x7fffffff) return RRIN_E_SHAPE;
-    a.part = d->part;
-    a.cnt = d->cnt;
-  }
-  if (d->ring_w) {  // sub-pixel ring fold (kind 3, unsplit): no separate edge fix-up launch
-    if (!sub || d->cfg != kWinoQCfg || a.ksplit > 1) return RRIN_E_CONFIG;
-    if ((d->cin & 7) || !d->ring_bias || (need_scratch && (!d->ring_corr || !d->ring_cnt))) return RRIN_E_ARG;
-    a.nseg = 2 * a.tiles_x + 2 * a.tiles_y;
-    const int64_t rb = (int64_t)a.n * a.co_blocks * a.nseg;
-    if (rb + (int64_t)a.co_blocks * a.tiles_x * a.tiles_y * a.n > 0x7fffffff) return RRIN_E_SHAPE;
-    a.nring = (int)((rb + 7) & ~(int64_t)7);  // keeps the tiles' XCD remap aligned
-    const int64_t grid = (int64_t)a.co_blocks * a.tiles_x * a.tiles_y * a.n + a.nring;
-    a.rstride = 8 * (int)(grid / a.nring);    // ring groups spread over the whole grid
-    a.wedge = d->ring_w;
-    a.bias_raw = d->ring_bias;
-    a.corr = d->ring_corr;
-    a.rcnt = d->ring_cnt;
-  }
-  if (d->ring_full) {  // the ring from scratch with this conv (ABI 17)
-    const rrin_edge_fix_desc* e = d->ring_full;
-    if (!sub || d->ring_w || e->full != 1 || e->prec != d->prec || e->n != d->n || e->cout * 4 != d->cout)
-      return RRIN_E_ARG;
-    dim3 g;
-    if (int rc = edge_fix_prepare(e, a.fix, g)) return rc;
-    if (a.fix.s_hi != a.src_hi || a.fix.sh != h || a.fix.sw != w) return RRIN_E_ARG;  // this conv's input
-    a.fix_gx = (int)g.x;
-    a.fix_gy = (int)g.y;
-    const int64_t nf = (int64_t)g.x * g.y * g.z;
-    if (nf + (int64_t)a.co_blocks * a.tiles_x * a.tiles_y * a.n + 8 > 0x7fffffff) return RRIN_E_SHAPE;
-    a.fix_real = (int)nf;
-  }
-  return 0;
-}
-
-// floats of rrin_conv_h8_desc.ring_corr and ints of .ring_cnt a ring-folding sub-pixel conv
-// needs (0 and 0 when d->ring_w is NULL)
-extern "C" int64_t rrin_conv_h8_ring_floats(const rrin_conv_h8_desc* d, int64_t* cnt_ints) {
-  ConvH8Args a;
-  const int rc = h8_prepare(d, a, false);
-  if (rc) return rc;
-  const int64_t segs = a.nring > 0 ? (int64_t)a.n * a.co_blocks * a.nseg : 0;
-  if (cnt_ints) *cnt_ints = segs;
-  return segs * 512;
-}
-
-// floats of rrin_conv_h8_desc.part and ints of .cnt a split-K conv needs (0 without a split)
-extern "C" int64_t rrin_conv_h8_split_floats(const rrin_conv_h8_desc* d, int64_t* cnt_ints) {
-  ConvH8Args a;
-  const int rc = h8_prepare(d, a, false);
-  if (rc) return rc;
-  const int64_t tiles = (int64_t)a.co_blocks * a.tiles_x * a.tiles_y * a.n;
-  if (cnt_ints) *cnt_ints = a.ksplit > 1 ? tiles : 0;
-  return a.ksplit > 1 ? tiles * a.ksplit * 32 * 32 * kCfgH8[d->cfg].th : 0;  // 16 floats per thread of 64 x th threads
-}
-
-}  // namespace rrin
-
-using namespace rrin;
-
-extern "C" int rrin_conv_h8_cfg_count(void) { return kNumCfgH8; }
-extern "C" int rrin_conv_h8_cfg_bm(int32_t cfg) {
-  return (cfg >= 0 && cfg < kNumCfgH8) ? kCfgH8[cfg].bm : RRIN_E_CONFIG;
-}
-extern "C" int rrin_conv_h8_cfg_th(int32_t cfg) {
-  return (cfg >= 0 && cfg < kNumCfgH8) ? kCfgH8[cfg].th : RRIN_E_CONFIG;
-}
-// 0: direct form; Winograd tile kind: 1 BM 32 / 4 waves, 3 BM 32 / 8 waves, 4 BM 32 x TH 4 / 4 waves;
-// 6 BM 64 x TH 4 and 7 BM 32 x TH 8, register-U tiles (conv_winoc.hip; kind 6 also at fp16,
-// conv_winoh.hip); 14 BM 32 x TH 8, the register-U tile in F(4,3) x F(2,3) (conv_winoc42.hip,
-// packed by rrin_pack_conv3x3_wino42).  The retired ids (19, 22) report -1.
-extern "C" int rrin_conv_h8_cfg_wino(int32_t cfg) {
-  return cfg == kWinoCfg      ? 1
-         : cfg == kWinoQCfg   ? 3
-         : cfg == kWinoQ4Cfg  ? 4
-         : cfg == kWinoC2Cfg  ? 6
-         : cfg == kWinoC1Cfg  ? 7
-         : cfg == kWinoC42Cfg ? 14
-         : retired(cfg)       ? -1
-                              : 0;
-}
-// Fused level-0 UNetConvBlock (conv_block0.hip): validate and launch.
-extern "C" int rrin_conv_block0_h8_fwd(const rrin_block0_h8_desc* d, void* stream) {
-  if (!d || !d->whi_a || !d->bias_a || !d->whi_b || !d->bias_b) return RRIN_E_ARG;
-  for (int cfg : {d->cfg_a, d->cfg_b})
-    if (cfg < 0 || cfg >= kNumCfgH8 || is_wino(cfg)) return RRIN_E_CONFIG;  // direct-form packs only
-  if (d->n < 1 || d->cin < 1 || ((d->cin & 7) && !d->tail_finite)) return RRIN_E_ARG;
-  if (!(d->slope >= 0.f && d->slope <= 1.f)) return RRIN_E_ARG;
-  const int prec = RRIN_PREC_F16;
-  if (!h8_ok(d->src, prec) || !h8_ok(d->dst, prec) || d->src.lo || d->dst.lo) return RRIN_E_SHAPE;
-  const int h = d->src.g.h, w = d->src.g.w;
-  if (d->dst.g.h != h || d->dst.g.w != w || d->dst.groups < 4 || d->cin > 8 * d->src.groups) return RRIN_E_SHAPE;
-  const bool pool = d->pool.hi != nullptr;
-  if (pool && (!h8_ok(d->pool, prec) || d->pool.lo || (h & 1) || (w & 1) || d->pool.g.h * 2 != h ||
-               d->pool.g.w * 2 != w || d->pool.groups < 4))
-    return RRIN_E_SHAPE;
-  // 32-bit byte offsets within an image (buffer loads and stores)
-  const int64_t lim = (int64_t)1 << 31;
-  if (d->src.img_stride * 16 >= lim || d->dst.img_stride * 16 >= lim || (pool && d->pool.img_stride * 16 >= lim))
-    return RRIN_E_SHAPE;
-  Block0Args a;
-  memset(&a, 0, sizeof(a));
-  a.src = static_cast<const uint4*>(d->src.hi) + (int64_t)d->src.g_off * d->src.g.plane;
-  a.src_img = (int)d->src.img_stride;
-  a.src_gp = (int)d->src.g.plane;
-  a.src_wp = d->src.g.wp;
-  a.src_hp = d->src.g.hp;
-  a.cin = d->cin;
-  a.ngroups = (d->cin + 7) / 8;
-  a.nch = (d->cin + 15) / 16;
-  a.wa = static_cast<const uint4*>(d->whi_a);
-  a.bma = kCfgH8[d->cfg_a].bm;
-  a.ba = d->bias_a;
-  a.isa = d->inv_wscale_a;
-  a.wb = static_cast<const uint4*>(d->whi_b);
-  a.bmb = kCfgH8[d->cfg_b].bm;
-  a.bb = d->bias_b;
-  a.isb = d->inv_wscale_b;
-  a.dst = static_cast<uint4*>(d->dst.hi) + (int64_t)d->dst.g_off * d->dst.g.plane;
-  a.dst_img = (int)d->dst.img_stride;
-  a.dst_gp = (int)d->dst.g.plane;
-  a.dst_wp = d->dst.g.wp;
-  if (pool) {
-    a.pool = static_cast<uint4*>(d->pool.hi) + (int64_t)d->pool.g_off * d->pool.g.plane;
-    a.pool_img = (int)d->pool.img_stride;
-    a.pool_gp = (int)d->pool.g.plane;
-    a.pool_wp = d->pool.g.wp;
-  }
-  a.slope = d->slope;
-  a.h = h;
-  a.w = w;
-  a.n = d->n;
-  a.tiles_x = (w + kB0TW - 1) / kB0TW;
-  a.tiles_y = (h + kB0TH - 1) / kB0TH;
-  a.status = d->status;
-  if ((int64_t)a.tiles_x * a.tiles_y * a.n > 0x7fffffff) return RRIN_E_SHAPE;
-  return launch_block0(a, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int rrin_conv_h8_cfg_ok(int32_t cfg, int32_t prec) {
-  if (cfg < 0 || cfg >= kNumCfgH8) return 0;
-  if (!rec_prec(prec) || retired(cfg)) return 0;
-  // Winograd tiles: exact fp32 records; the register-U kind 6 also at fp16 (conv_winoh.hip)
-  if (is_wino(cfg) && (prec == RRIN_PREC_F16 ? !is_winoh(cfg) : prec != RRIN_PREC_F32R)) return 0;
-  return (planes_of(prec) == 2 ? kCfgH8[cfg].lds2 : kCfgH8[cfg].lds1) <= kMaxLds ? 1 : 0;
-}
-
-extern "C" int rrin_conv_h8_cfg_fits(int32_t cfg, int32_t prec, int32_t cin) {
-  if (!rrin_conv_h8_cfg_ok(cfg, prec) || cin < 1) return 0;
-  const CfgH8& c = kCfgH8[cfg];
-  const int nch = (cin + 2 * chans_per_rec(prec) - 1) / (2 * chans_per_rec(prec));
-  if (!(c.sched & SCHED_WRES) || nch <= 2) return 1;
-  const int planes = planes_of(prec);
-  const size_t lds = (planes == 2 ? c.lds2 : c.lds1) + (size_t)(nch - 2) * c.wslab * planes;
-  return lds <= kMaxLds ? 1 : 0;
-}
-
-static int conv3x3_h8_launch(const rrin_conv_h8_desc* d, const ConvH8Args& a, hipStream_t st) {
-  if (d->cfg == kWinoCfg) return launch_wino(a, d->epi_mode, st);
-  if (d->cfg == kWinoQCfg) return launch_winoq(a, d->epi_mode, 8, st);
-  if (d->cfg == kWinoQ4Cfg) return launch_winoq(a, d->epi_mode, 4, st);
-  if (is_winoh(d->cfg) && d->prec == RRIN_PREC_F16) return launch_winoh(a, d->epi_mode, st);
-  if (d->cfg == kWinoC2Cfg) return launch_winoc(a, d->epi_mode, 2, st);
-  if (d->cfg == kWinoC1Cfg) return launch_winoc(a, d->epi_mode, 1, st);
-  if (d->cfg == kWinoC42Cfg) return launch_winoc42(a, d->epi_mode, st);
-  switch (d->cfg) {
+int launch_h8(const ConvH8Args& a, int cfg, int prec, int epi, hipStream_t st) {
+  switch (cfg) {
 #define X(id, nw, wm, wn, sc, pe) \
   case id:                        \
-    return launch_h8_cfg<nw, wm, wn, sc>(a, d->prec, d->epi_mode, pe, st);
+    return launch_h8_cfg<nw, wm, wn, sc>(a, prec, epi, pe, st);
     RRIN_H8_CFGS(X)
 #undef X
   }
   return RRIN_E_CONFIG;
 }
 
-bool rrin::ring_in_launch_ok(int cfg, int cin, int prec) {
-  if (cfg < 0 || cfg >= kNumCfgH8 || retired(cfg) || cin % kFixCi) return false;
-  if (is_winoc(cfg)) return prec == RRIN_PREC_F32R;  // kinds 6 / 7 (exact fp32): 256 threads
-  if (is_wino(cfg)) return false;                    // kinds 1, 3, 4: the fix-up as a second launch
-  return kCfgH8[cfg].nt >= 256;                      // direct-form tiles of 256 / 512 threads
-}
-
-extern "C" int rrin_conv3x3_h8_fwd(const rrin_conv_h8_desc* d, void* stream) {
-  ConvH8Args a;
-  const int rc = h8_prepare(d, a);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (a.fix_real > 0) {
-    // in the conv's launch (a tile of 256 or 512 threads); otherwise the conv, then the FULL
-    // fix-up as its own launch in the same summation order
-    if (!ring_in_launch_ok(d->cfg, a.fix.cin, d->prec)) {
-      ConvH8Args b = a;
-      b.fix_real = 0;
-      if (int e = conv3x3_h8_launch(d, b, st)) return e;
-      dim3 g((unsigned)a.fix_gx, (unsigned)a.fix_gy, (unsigned)d->n);
-      return edge_fix_run(a.fix, g, d->prec, true, nullptr, st, true);  // the in-launch summation order
-    }
-  }
-  return conv3x3_h8_launch(d, a, st);
-}
-
 #ifdef RRIN_LAB
-// Kernel lab (tools/conv_lab.py ablate; built only into librrin_lab.so, `make
-// lab`): one F16X3 LEAKY conv of tile config cfg 0, 1 or 6 with the schedule
-// knobs `sched` (SCHED_*, ablations included) and grid `persist` (as PE).
+// Kernel lab (tools/conv_lab.py ablate; built only into librrin_lab.so, `make lab`): one LEAKY
+// conv of a direct-form tile with the schedule knobs `sched` (SCHED_*, ablations included) and
+// grid `persist` (as PE), at F16X3 (cfg 0, 1, 6) or F32R (cfg 0, 1, 3, 4, 5, 6, 16).
 template <int NW, int WM, int WN, bool F32>
 static int lab_cfg(const ConvH8Args& a, int sched, int persist, hipStream_t st) {
   constexpr int P = F32 ? 1 : 2;
@@ -1357,24 +837,9 @@ static int lab_cfg(const ConvH8Args& a, int sched, int persist, hipStream_t st) 
   return RRIN_E_CONFIG;
 }
 
-// F16X3 (cfg 0, 1, 6) or F32R (cfg 0, 1, 3, 4, 5, 6, 16) LEAKY conv with schedule bits
-extern "C" int rrin_conv3x3_h8_lab(const rrin_conv_h8_desc* d, int32_t sched, int32_t persist, void* stream) {
-  if (d && is_wino(d->cfg) && d->epi_mode == RRIN_EPI_LEAKY) {  // Winograd: sched = ablation bits
-    ConvH8Args a;
-    const int rc = h8_prepare(d, a);
-    if (rc) return rc;
-    return launch_wino_lab(a, sched, (hipStream_t)stream);
-  }
-  if (!d || (d->prec != RRIN_PREC_F16X3 && d->prec != RRIN_PREC_F32R) || d->epi_mode != RRIN_EPI_LEAKY ||
-      (d->cin % 8))
-    return RRIN_E_ARG;
-  if (d->prec == RRIN_PREC_F32R && (sched & SCHED_MFMA16)) return RRIN_E_CONFIG;
-  ConvH8Args a;
-  const int rc = h8_prepare(d, a);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->prec == RRIN_PREC_F32R) {
-    switch (d->cfg) {
+int launch_h8_lab(const ConvH8Args& a, int cfg, int prec, int sched, int persist, hipStream_t st) {
+  if (prec == RRIN_PREC_F32R) {
+    switch (cfg) {
       case 0: return lab_cfg<8, 2, 2, true>(a, sched, persist, st);
       case 1: return lab_cfg<8, 1, 2, true>(a, sched, persist, st);
       case 3: return lab_cfg<4, 1, 4, true>(a, sched, persist, st);
@@ -1385,7 +850,7 @@ extern "C" int rrin_conv3x3_h8_lab(const rrin_conv_h8_desc* d, int32_t sched, in
     }
     return RRIN_E_CONFIG;
   }
-  switch (d->cfg) {
+  switch (cfg) {
     case 0: return lab_cfg<8, 2, 2, false>(a, sched, persist, st);
     case 1: return lab_cfg<8, 1, 2, false>(a, sched, persist, st);
     case 6: return lab_cfg<4, 1, 2, false>(a, sched, persist, st);
@@ -1394,21 +859,4 @@ extern "C" int rrin_conv3x3_h8_lab(const rrin_conv_h8_desc* d, int32_t sched, in
 }
 #endif
 
-extern "C" int rrin_subpixel_edge_fix_h8(const rrin_edge_fix_desc* d, void* stream) {
-  EdgeFixArgs a;
-  dim3 grid;
-  if (int e = edge_fix_prepare(d, a, grid)) return e;
-  return edge_fix_run(a, grid, d->prec, d->full == 1, d, (hipStream_t)stream);
-}
-
-extern "C" int64_t rrin_edge_fix_split_floats(const rrin_edge_fix_desc* d, int64_t* cnt) {
-  if (!d || d->n < 1 || d->cin < 8 || (d->cin & 7) || d->cout < 8 || !rec_prec(d->prec)) return RRIN_E_ARG;
-  int ks, nsl;
-  edge_fix_split(d->cin, d->prec, &ks, &nsl);
-  const int H = d->dst.g.h, W = d->dst.g.w;
-  if (H < 2 || W < 1) return RRIN_E_SHAPE;
-  const int64_t tiles = (int64_t)(2 * ((W + kFixPx - 1) / kFixPx) + 2 * ((H - 2 + kFixPx - 1) / kFixPx)) *
-                        ((d->cout + kFixCo - 1) / kFixCo) * d->n;
-  if (cnt) *cnt = nsl > 1 ? tiles : 0;
-  return nsl > 1 ? tiles * nsl * 1024 : 0;
-}
+}  // namespace rrin

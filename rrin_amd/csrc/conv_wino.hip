@@ -1,5 +1,5 @@
 // Exact-fp32 3x3 conv as Winograd F(2x2, 3x3) on fp32 records (R32) with the
-// f32-input matrix cores (v_mfma_f32_32x32x2_f32).  Tile config kWinoCfg of
+// f32-input matrix cores (v_mfma_f32_32x32x2_f32).  Tile config 18 (kind 1) of
 // the record-layout conv table (rrin_conv3x3_h8_fwd, precision F32R).
 //
 // Replaces the same reference ops as conv3x3_h8_kernel: nn.Conv2d(3, pad=1) +
@@ -492,7 +492,7 @@ static_assert(2 * kWinoQLds <= 160 * 1024, "two blocks per CU");
 // reads zero padding where the phase form read the clamped upsample, so the ring
 // pixels take  y = (phase value - corr) + bias  with corr = sum over ci of the
 // out-of-image taps w[c][ci][ky][kx] * up(ci, clamp(Y + ky - 1), clamp(X + kx - 1))
-// (the arithmetic of edge_fix_h8_kernel, conv_h8.hip, which runs as a separate
+// (the arithmetic of edge_fix_h8_kernel, edge_fix.hip, which runs as a separate
 // launch for the other configs).  Ring segment seg of (image, co block): top / bottom
 // row under tile column tx (seg tx / tiles_x + tx: X in [64 tx, 64 tx + 64)), left /
 // right column beside tile row ty (2 tiles_x + ty / 2 tiles_x + tiles_y + ty:

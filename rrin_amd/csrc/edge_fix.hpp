@@ -1,5 +1,5 @@
 // Device side of the sub-pixel up conv's ring fix-up, shared by the standalone fix-up kernel
-// (conv_h8.hip edge_fix_h8_kernel) and the conv tiles that run it in extra workgroups of their
+// (edge_fix.hip edge_fix_h8_kernel) and the conv tiles that run it in extra workgroups of their
 // own launch (rrin_conv_h8_desc.ring_full: conv3x3_h8_kernel, conv3x3_winoc_kernel), plus the
 // packed-FP32 experiment switches both need.
 #pragma once

@@ -352,7 +352,7 @@ def wino_f16_ok(cin: int, cout: int, level: int) -> bool:
 
 
 def choose_cfg_h8(cin: int, cout: int, prec: int, level: int = 0, size: str = "large", split: int = 1) -> int:
-    """Tile config of the record-layout conv (conv_h8.hip table) for a conv
+    """Tile config of the record-layout conv (h8_cfg.hpp table) for a conv
     running on the grid of U-Net level ``level`` (a sub-pixel up conv runs on the
     low-res grid with 4x the output rows) in a forward part of size class
     ``size``: exact fp32 takes the Winograd config (WINO_SIZES; kind 4 where the

@@ -89,7 +89,7 @@ class H8Tensor:
 
     def chunk_view(self, ch_off: int = 0, channels: int | None = None) -> _lib.H8:
         """``view`` widened to whole 2-group chunks (within the allocation): the source
-        view of a conv, which may stage groups past ``channels`` (conv_h8.hip h8_prepare)."""
+        view of a conv, which may stage groups past ``channels`` (conv_rec.hip h8_prepare)."""
         v = self.view(ch_off, channels)
         v.groups = min((v.groups + 1) // 2 * 2, self.groups - v.g_off)
         return v

@@ -50,7 +50,7 @@ def keyed_conv(cin, cout, key="h8"):
             keyed_tensor(f"{key}.{cin}.{cout}.b", (cout,), cin * 9))
 
 
-# configs with one output row per wave (WN == 1 in conv_h8.hip's table): a
+# configs with one output row per wave (WN == 1 in h8_cfg.hpp's table): a
 # wave must own both rows of a pool pair, so they reject the pool epilogue
 NO_POOL_CFGS = (4, 16)
 

@@ -329,7 +329,7 @@ def single(args):
           f"{2 * 9 * cin * cout * h * w * n / (ms * 1e-3) / 1e12:.1f} TF")
 
 
-# (name, SCHED_* knobs of conv_h8.hip, persistent grid) -- the lab build's variants
+# (name, SCHED_* knobs of h8_cfg.hpp, persistent grid) -- the lab build's variants
 LAB_VARIANTS = [("base", 0, 0), ("persist", 0, 1), ("spread", 16, 0), ("persist+spread", 16, 1),
                 ("stagger", 64, 0), ("persist+stagger", 64, 1), ("wres", 32, 0), ("persist+wres", 32, 1),
                 ("persist+wres+spread", 48, 1), ("persist+wres+stagger", 96, 1),
