@@ -439,7 +439,9 @@ int rrin_yuv_coef_std(int32_t standard, int32_t full_range, rrin_yuv_coef* c);
  * is not round_up(h0,16) x round_up(w0,16): RRIN_E_SHAPE.  Validated before any HIP call. */
 int rrin_pack_g16_yuv_h8(const rrin_yuv420* f0, const rrin_yuv420* f1, const rrin_yuv_coef* coef, int32_t n,
                          int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec, void* stream);
-/* NCHW fp32 <-> H8 view (c channels starting at channel ch_off of the view). */
+/* NCHW fp32 <-> H8 view (c channels starting at channel ch_off of the view).  rrin_nchw_to_h8
+ * stores one element per value: the other channels of a record that [ch_off, ch_off + c) covers
+ * only partly keep their contents, as do the padding and every other group. */
 int rrin_nchw_to_h8(const float* src, int32_t n, int32_t c, int32_t ch_off, const rrin_h8* dst,
                     int32_t prec, void* stream);
 int rrin_h8_to_nchw(const rrin_h8* src, int32_t n, int32_t c, int32_t ch_off, float* dst, int32_t prec,

@@ -110,7 +110,9 @@ int edge_fix_run(EdgeFixArgs a, dim3 grid, int prec, bool full, const rrin_edge_
   edge_fix_split(a.cin, prec, &ks, &nsl);
   if (one_group) {
     ks = 1;
-    nsl = prec == RRIN_PREC_F32R ? a.cin / kFixCi : 1;
+    // runs of whole chunks only: a cin that is no multiple of kFixCi is one run whose last chunk is
+    // masked (cin / kFixCi would be no run at all below kFixCi, and runs that overlap above it)
+    nsl = prec == RRIN_PREC_F32R && a.cin % kFixCi == 0 ? a.cin / kFixCi : 1;
     d = nullptr;
   }
   a.nslices = nsl;

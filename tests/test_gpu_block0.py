@@ -37,12 +37,15 @@ def direct_cfg(cin, cout, bm=None):
                 and lib.rrin_conv_h8_cfg_bm(c) == bm and c not in NO_POOL_CFGS)
 
 
-def block0(src, cin, wa, ba, cfg_a, wb, bb, cfg_b, pool, dst=None, dst_off=0, status=None, tail_finite=0):
+def block0(src, cin, wa, ba, cfg_a, wb, bb, cfg_b, pool, dst=None, dst_off=0, status=None, tail_finite=0, pl=None,
+           pool_off=0):
+    """pl / pool_off: a caller-allocated pool tensor and the first channel of its view."""
     dev = src.hi.device
     n, h, w = src.n, src.h, src.w
     if dst is None:
         dst = H8Tensor(n, 32 + dst_off, h, w, dev, F16)
-    pl = H8Tensor(n, 32, h // 2, w // 2, dev, F16) if pool else None
+    if pl is None:
+        pl = H8Tensor(n, 32, h // 2, w // 2, dev, F16) if pool else None
     wha, _, bpa, inva = pack_h8(wa, ba, cfg_a, F16, dev)
     whb, _, bpb, invb = pack_h8(wb, bb, cfg_b, F16, dev)
     d = _lib.Block0Desc()
@@ -51,7 +54,7 @@ def block0(src, cin, wa, ba, cfg_a, wb, bb, cfg_b, pool, dst=None, dst_off=0, st
     d.src = src.chunk_view(0, cin)
     d.dst = dst.view(dst_off, 32)
     if pl is not None:
-        d.pool = pl.view(0, 32)
+        d.pool = pl.view(pool_off, 32)
     d.whi_a, d.bias_a, d.whi_b, d.bias_b = wha.data_ptr(), bpa.data_ptr(), whb.data_ptr(), bpb.data_ptr()
     d.status = status.data_ptr() if status is not None else None
     _lib.check(_lib.lib().rrin_conv_block0_h8_fwd(C.byref(d), H.stream(dev)), "rrin_conv_block0_h8_fwd")

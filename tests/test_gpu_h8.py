@@ -126,7 +126,16 @@ def pack_h8(w, b, cfg, prec, dev, perm=None):
     return t(whi), t(wlo), torch.from_numpy(bp).to(dev), inv.value
 
 
-def set_split(d, ksplit, dev, keep):
+def scratch(name, numel, dtype, dev):
+    """Default scratch of the helpers below: NaN floats, zero tickets.  A caller's own `alloc`
+    (tests/test_gpu_h8_storage.py: guard bands around each array) has the same signature and
+    returns anything with data_ptr()."""
+    if dtype == torch.int32:
+        return torch.zeros(numel, dtype=torch.int32, device=dev)
+    return torch.full((numel,), float("nan"), device=dev)
+
+
+def set_split(d, ksplit, dev, keep, alloc=scratch):
     """Give desc d a split-K of ksplit slices (Winograd kinds 3, 4) with fresh scratch;
     keep collects the scratch tensors (the counters are checked by test_gpu_split)."""
     if not ksplit:
@@ -135,14 +144,17 @@ def set_split(d, ksplit, dev, keep):
     nc = C.c_int64()
     nf = _lib.lib().rrin_conv_h8_split_floats(C.byref(d), C.byref(nc))
     assert nf > 0 and nc.value > 0, nf
-    part = torch.full((nf,), float("nan"), device=dev)
-    cnt = torch.zeros(nc.value, dtype=torch.int32, device=dev)
+    part = alloc("part", nf, torch.float32, dev)
+    cnt = alloc("cnt", nc.value, torch.int32, dev)
     d.part, d.cnt = part.data_ptr(), cnt.data_ptr()
     keep.extend([part, cnt])
 
 
 def conv_h8(src: H8Tensor, w, b, cfg, prec, epi=_lib.EPI_LINEAR, dst=None, dst_off=0, pool=None, perm=None,
-            cin=None, tail_finite=0, ksplit=0, keep=None):
+            cin=None, tail_finite=0, ksplit=0, keep=None, src_off=0, status=None, alloc=scratch, packed=None,
+            pool_off=0):
+    """src_off: first channel of the source view; status: the fp16 range flag (an int32 tensor);
+    alloc: see scratch(); packed: pack_h8's result for (w, b, cfg, prec), to pack once per config."""
     dev = src.hi.device
     cout, cin_w = w.shape[:2]
     cin = cin or cin_w
@@ -150,16 +162,17 @@ def conv_h8(src: H8Tensor, w, b, cfg, prec, epi=_lib.EPI_LINEAR, dst=None, dst_o
         dst = H8Tensor(src.n, cout + dst_off, src.h, src.w, dev, prec)
     if epi == _lib.EPI_LEAKY_POOL and pool is None:
         pool = H8Tensor(src.n, cout, src.h // 2, src.w // 2, dev, prec)
-    whi, wlo, bp, inv = pack_h8(w, b, cfg, prec, dev, perm)
+    whi, wlo, bp, inv = packed if packed is not None else pack_h8(w, b, cfg, prec, dev, perm)
     d = _lib.ConvH8Desc()
     d.n, d.cin, d.cout, d.cfg, d.prec, d.epi_mode, d.slope, d.inv_wscale = src.n, cin, cout, cfg, prec, epi, 0.1, inv
     d.tail_finite = tail_finite
-    d.src = src.chunk_view(0, cin)
+    d.status = status.data_ptr() if status is not None else None
+    d.src = src.chunk_view(src_off, cin)
     d.dst = dst.view(dst_off, cout)
     if pool is not None:
-        d.pool = pool.view(0, cout)
+        d.pool = pool.view(pool_off, cout)
     d.whi, d.wlo, d.bias = whi.data_ptr(), wlo.data_ptr() if prec == X3 else None, bp.data_ptr()
-    set_split(d, ksplit, dev, keep if keep is not None else [])
+    set_split(d, ksplit, dev, keep if keep is not None else [], alloc)
     _lib.check(_lib.lib().rrin_conv3x3_h8_fwd(C.byref(d), H.stream(dev)), "rrin_conv3x3_h8_fwd")
     torch.cuda.synchronize(dev)
     return dst, pool
@@ -368,12 +381,17 @@ def test_h8_leaky_rep_writes_replicated_ring(gpu, prec):
 
 
 def subpixel_upconv(src: H8Tensor, w, b, cfg, prec, dst=None, ksplit=0, keep=None, fold=False, edge_split=False,
-                    full=False, inlaunch=False):
+                    full=False, inlaunch=False, src_off=0, dst_off=0, status=None, fix_status=None, alloc=scratch,
+                    conv=True, fix=True):
     """EPI_SUBPIXEL conv + ring fix-up through the C ABI (the Net's up.1 conv); fold: the
     ring in the conv launch (rrin_conv_h8_desc.ring_w, Winograd kind 3) instead of
     rrin_subpixel_edge_fix_h8; full: the fix-up's from-scratch mode (rrin_edge_fix_desc.full,
     no edge buffer), launched BEFORE the conv -- it must read nothing the conv writes, and the
-    conv must write no ring pixel."""
+    conv must write no ring pixel.  src_off / dst_off: first channel of the source / destination
+    view; status / fix_status: the range flags of the conv and of the fix-up; alloc: see scratch()
+    (names "edge", "part", "cnt", "ring_corr", "ring_cnt", "fix_part", "fix_cnt"; keep receives
+    them in that order of use, the edge buffer first); conv / fix False: leave that launch of the
+    separate pair out."""
     lib = _lib.lib()
     dev = src.hi.device
     cout, cin = w.shape[:2]
@@ -386,15 +404,18 @@ def subpixel_upconv(src: H8Tensor, w, b, cfg, prec, dst=None, ksplit=0, keep=Non
     H_, W_ = 2 * src.h, 2 * src.w
     if dst is None:
         dst = H8Tensor(src.n, cout, H_, W_, dev, prec)
-    edge = torch.full((src.n, cout, lib.rrin_ring_pixels(H_, W_)), float("nan"), device=dev)
+    edge = alloc("edge", src.n * cout * lib.rrin_ring_pixels(H_, W_), torch.float32, dev)
     d = _lib.ConvH8Desc()
     d.n, d.cin, d.cout, d.cfg, d.prec, d.epi_mode, d.slope, d.inv_wscale = (src.n, cin, 4 * cout, cfg, prec,
                                                                             _lib.EPI_SUBPIXEL, 0.1, inv)
-    d.src, d.dst = src.chunk_view(0, cin), dst.view(0, cout)
+    d.src, d.dst = src.chunk_view(src_off, cin), dst.view(dst_off, cout)
     d.whi, d.wlo, d.bias = whi.data_ptr(), wlo.data_ptr() if prec == X3 else None, bp.data_ptr()
     d.edge = edge.data_ptr()
+    d.status = status.data_ptr() if status is not None else None
     keep = keep if keep is not None else []
-    set_split(d, ksplit, dev, keep)
+    if alloc is not scratch:
+        keep.append(edge)
+    set_split(d, ksplit, dev, keep, alloc)
     wedge = torch.from_numpy(np.ascontiguousarray(wn.transpose(1, 2, 3, 0))).to(dev)
     braw = torch.from_numpy(bn.copy()).to(dev)
     if fold:
@@ -402,8 +423,8 @@ def subpixel_upconv(src: H8Tensor, w, b, cfg, prec, dst=None, ksplit=0, keep=Non
         nc = C.c_int64()
         nf = lib.rrin_conv_h8_ring_floats(C.byref(d), C.byref(nc))
         assert nf > 0 and nc.value > 0, nf
-        corr = torch.full((nf,), float("nan"), device=dev)
-        cnt = torch.zeros(nc.value, dtype=torch.int32, device=dev)
+        corr = alloc("ring_corr", nf, torch.float32, dev)
+        cnt = alloc("ring_cnt", nc.value, torch.int32, dev)
         d.ring_corr, d.ring_cnt = corr.data_ptr(), cnt.data_ptr()
         keep.extend([corr, cnt])
         _lib.check(lib.rrin_conv3x3_h8_fwd(C.byref(d), H.stream(dev)), "rrin_conv3x3_h8_fwd(subpixel, fold)")
@@ -411,27 +432,31 @@ def subpixel_upconv(src: H8Tensor, w, b, cfg, prec, dst=None, ksplit=0, keep=Non
         return dst
     e = _lib.EdgeFixDesc()
     e.n, e.cin, e.cout, e.prec, e.epi_mode, e.slope = src.n, cin, cout, prec, _lib.EPI_LINEAR, 0.1
-    e.src, e.dst = src.chunk_view(0, cin), dst.view(0, cout)
+    e.src, e.dst = src.chunk_view(src_off, cin), dst.view(dst_off, cout)
     e.edge, e.wedge, e.bias = (None if full or inlaunch else edge.data_ptr()), wedge.data_ptr(), braw.data_ptr()
     e.full = int(full or inlaunch)
+    e.status = fix_status.data_ptr() if fix_status is not None else None
     if inlaunch:  # ABI 17: the ring from scratch with the conv (rrin_conv_h8_desc.ring_full)
         d.ring_full = C.addressof(e)
         _lib.check(lib.rrin_conv3x3_h8_fwd(C.byref(d), H.stream(dev)), "rrin_conv3x3_h8_fwd(subpixel, ring_full)")
         torch.cuda.synchronize(dev)
         return dst
-    if not full:
+    if not full and conv:
         _lib.check(lib.rrin_conv3x3_h8_fwd(C.byref(d), H.stream(dev)), "rrin_conv3x3_h8_fwd(subpixel)")
+        if not fix:
+            torch.cuda.synchronize(dev)
+            return dst
     if edge_split:  # cross-workgroup K split of the fix-up (fp32 records)
         nc = C.c_int64(-1)
         nf = lib.rrin_edge_fix_split_floats(C.byref(e), C.byref(nc))
         assert nf >= 0 and nc.value >= 0, nf
         if nf:
-            part = torch.full((nf,), float("nan"), device=dev)
-            cnt = torch.zeros(nc.value, dtype=torch.int32, device=dev)
+            part = alloc("fix_part", nf, torch.float32, dev)
+            cnt = alloc("fix_cnt", nc.value, torch.int32, dev)
             e.part, e.cnt, e.part_floats, e.cnt_len = part.data_ptr(), cnt.data_ptr(), nf, nc.value
             keep.extend([part, cnt])
     _lib.check(lib.rrin_subpixel_edge_fix_h8(C.byref(e), H.stream(dev)), "rrin_subpixel_edge_fix_h8")
-    if full:
+    if full and conv:
         _lib.check(lib.rrin_conv3x3_h8_fwd(C.byref(d), H.stream(dev)), "rrin_conv3x3_h8_fwd(subpixel)")
     torch.cuda.synchronize(dev)
     return dst
