@@ -47,7 +47,7 @@ __device__ inline void pk_fma4(f32x2& a01, f32x2& a23, float4 w, float u) {
 // kernel row (top/bottom line) or column (left/right line) applied to U on that
 // line: a 1-D conv, done here as a small GEMM per tile of 64 line pixels x 32
 // output channels with U (recomputed from the low-res source exactly as
-// up2x_h8_kernel does) and the weights staged in LDS.  A corner also has the
+// up2x_kernel does) and the weights staged in LDS.  A corner also has the
 // two other taps of its outside column ("extra" slots).  Lines: top row and
 // bottom row (corners included), left and right columns without the corners.
 

@@ -1,5 +1,5 @@
 """GPU: the record-path Net glue kernel by kernel -- the FLOW / REFINE / MASK / FINAL epilogues of
-rrin_head_h8_fwd (head_h8_kernel at fp32_split16 and fp16, head_r32_kernel at fp32) and the t-blend
+rrin_head_h8_fwd (head_kernel over RecH8<2> at fp32_split16, RecH8<1> at fp16, RecR32 at fp32) and the t-blend
 kernels rrin_flow_tblend_h8 / rrin_flow_tblend_fwd -- against tests/glue_ref.py.
 
 Every call runs on a Net buffer whose whole raw storage (both planes, padding ring, groups past

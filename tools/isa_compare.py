@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Text diff of two `make check-isa` trees (build/isa/*.s), kernel by kernel.
 
-    python3 tools/isa_compare.py PARENT/build/isa build/isa [--rename REGEX REPL] [--only REGEX]
+    python3 tools/isa_compare.py PARENT/build/isa build/isa [--rename REGEX REPL] [--only REGEX] [--table REGEX]
 
 The method of DESIGN.md's refactor entries: both trees come from the same compiler and flags;
 comments, label numbers and debug lines are stripped, and every function's body and its kernel
@@ -75,6 +75,7 @@ def main():
     ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("REGEX", "REPL"))
     ap.add_argument("--only", default="", help="report only functions matching this regex")
     ap.add_argument("--context", type=int, default=40, help="diff lines shown per function")
+    ap.add_argument("--table", default="", help="also print a resource table of the functions matching this regex")
     a = ap.parse_args()
     old, new = tree(a.parent, a.rename), tree(a.new, [])
     keep = (lambda k: re.search(a.only, k)) if a.only else (lambda k: True)
@@ -101,6 +102,18 @@ def main():
             print(ln)
     print(f"compared {same + len(differ)}: identical {same}, differing {len(differ)}, "
           f"descriptor differs {len(worse)}")
+    if a.table:
+        # parent / new per kernel: registers, scratch, LDS, occupancy, global loads and stores
+        cols = ("TotalNumSgprs", "NumVgprs", "ScratchSize", "LDSByteSize", "Occupancy")
+        count = lambda b, op: sum(1 for ln in b if ln.startswith(op))  # noqa: E731
+        print("\n" + "  ".join(("sgpr", "vgpr", "scratch", "lds", "occ", "gload", "gstore")) + "  kernel (parent/new)")
+        for k in sorted(new):
+            if not re.search(a.table, k):
+                continue
+            b0, d0 = (old[k][1], old[k][2]) if k in old else ([], {})
+            cells = [f"{d0.get(c, '-')}/{new[k][2].get(c, '-')}" for c in cols]
+            cells += [f"{count(b0, op) if k in old else '-'}/{count(new[k][1], op)}" for op in ("global_load", "global_store")]
+            print("  ".join(cells) + "  " + k)
     return 1 if worse else 0
 
 

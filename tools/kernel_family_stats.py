@@ -9,7 +9,7 @@ launch duration with the one bench.py measures with HIP events.
 With a kernel_trace.csv, also each FAMILY's busy time per step = the union of its
 dispatch spans (the quantity bench.py's roofline divides by when the batch is split
 over several streams).  STEPS is the number of bench steps the trace holds, or
-"auto": the dispatches of the once-per-forward-part kernel (pack_g16_*: one per
+"auto": the dispatches of the once-per-forward-part kernel (pack_g16_kernel: one per
 stream part) / P (= bench --streams, default 2).  A profiled `bench.py --steps K
 --warmup W` runs W + K steps, with `--full` plus bench's unprofiled re-run of the K
 steps: "auto" counts them all.  With --ms-per-step (the bench line's own ms_per_step), a family
@@ -31,7 +31,7 @@ import re
 import sys
 from collections import defaultdict
 
-MARKER = re.compile(r"^pack_g16_(r32|h8)_kernel$")
+MARKER = re.compile(r"^pack_g16_((r32|h8)_)?kernel$")  # (r32|h8): traces from before the kernels were one template
 
 
 def family(name):

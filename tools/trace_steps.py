@@ -1,5 +1,5 @@
 # Per-family durations, inter-kernel gaps and one step's launch list from a rocprofv3
-# --kernel-trace CSV of a one-stream bench run (steps delimited by pack_g16_r32_kernel).
+# --kernel-trace CSV of a one-stream bench run (steps delimited by pack_g16_kernel).
 # usage: python3 tools/trace_steps.py <run_kernel_trace.csv>
 import csv, collections, sys
 rows=list(csv.DictReader(open(sys.argv[1])))
