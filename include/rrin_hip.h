@@ -521,7 +521,14 @@ int rrin_prof_create(int32_t capacity, rrin_prof** out);
 int rrin_prof_destroy(rrin_prof* p);
 int rrin_prof_reset(rrin_prof* p);
 /* After the stream has synchronised: per recorded launch its kind, elapsed
- * milliseconds and algorithmic FLOPs (2*MAC of the conv; 0 for layout). */
+ * milliseconds and FLOPs: 2 x the multiply-adds of the form the launch runs.  Planar fp32 convs
+ * and every head: the direct form, 2*9*cin*cout per output pixel.  Record-layout convs, by the
+ * tile kind of their config (rrin_conv_h8_cfg_wino): 9 multiply-adds per output and input channel
+ * in the direct form (kind 0), 4 in Winograd F(2x2,3x3), 3 in F(4,3) x F(2,3) (kind 14); a
+ * sub-pixel up conv counts its 4*cout phase rows on the low-res grid, a fused level-0 block both
+ * convs' direct form.  So a Winograd launch reports 4/9 or 1/3 of the conv's direct-form FLOPs.
+ * 0 for LAYOUT and EDGE launches.  At most the profiler's capacity of launches is recorded; the
+ * rest of the call runs unrecorded. */
 int rrin_prof_read(rrin_prof* p, int32_t* kinds, float* ms, double* flops, int32_t cap, int32_t* count);
 /* Start / end of every recorded launch in ms after the first recorded event
  * (launches on several streams: the union of their spans is the busy time). */
