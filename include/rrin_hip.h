@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define RRIN_ABI_VERSION 22
+#define RRIN_ABI_VERSION 23
 
 #define RRIN_OK 0
 #define RRIN_E_SHAPE (-1)     /* H or W not a multiple of 16, or N < 1          */
@@ -439,6 +439,44 @@ int rrin_yuv_coef_std(int32_t standard, int32_t full_range, rrin_yuv_coef* c);
  * is not round_up(h0,16) x round_up(w0,16): RRIN_E_SHAPE.  Validated before any HIP call. */
 int rrin_pack_g16_yuv_h8(const rrin_yuv420* f0, const rrin_yuv420* f1, const rrin_yuv_coef* coef, int32_t n,
                          int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec, void* stream);
+
+/* ---- 10- to 16-bit frames in 16-bit words (ABI 23) -------------------------------------------
+ * The 8-bit frame paths with uint16 words: a sample of depth d (maxval = 2^d - 1) is
+ * min(word >> shift, maxval) and becomes float(sample) / float(maxval), correctly rounded (the
+ * IEEE fp32 division, no reciprocal multiply).  Strides and pitches count samples, so a frame of
+ * an [n+1] stack starts at any even address.
+ *
+ * rrin_pack_g16_u16_h8: rrin_pack_g16_u8_h8 from uint16 [n][h0][w0][3] RGB frames of depth 9..16
+ * (RRIN_E_ARG otherwise), the sample in the word's low bits; the records are bitwise those
+ * rrin_pack_g16_h8 writes from the padded fp32 frames. */
+int rrin_pack_g16_u16_h8(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int32_t h0,
+                         int32_t w0, int32_t depth, const rrin_h8* g16, int32_t prec, void* stream);
+
+/* One stack of 4:2:0 frames of 16-bit words: rrin_yuv420 with every pitch, step and stride in
+ * samples.  depth is 10 or 12 (RRIN_E_ARG otherwise: with |coefficient| < 2^16 the Q14 sums stay
+ * inside int32 up to 14 bits, not at 16); shift is 0 (the sample in the low bits: yuv420p10le, Y4M
+ * C420p10) or 16 - depth (in the high bits: P010 / P012).  Samples are read as
+ * min(word >> shift, maxval) and written as sample << shift. */
+typedef struct rrin_yuv420_16 {
+  const uint16_t *y, *u, *v;   /* frame 0; NV12 order: v == u + 1 */
+  int64_t img_stride;          /* samples between frames, the same for all three pointers */
+  int32_t y_pitch, c_pitch;    /* samples between rows */
+  int32_t c_step;              /* samples between chroma samples of a row: 2 or 1 */
+  int32_t depth, shift, pad_;
+} rrin_yuv420_16;
+/* The conversion is rrin_yuv_coef's with 128 replaced by 2^(depth-1) and clip255 by a clip to
+ * [0, maxval]; the roundings stay.  Coefficients on this path: 0 <= y0 <= maxval, |ay .. bu| < 2^16,
+ * |yr .. vb| < 2^15 (RRIN_E_ARG otherwise); every sum then fits int32 at depth 12, the largest
+ * being a block's chroma, 3 * (2^15 - 1) * 4 * 4095 + 2^15 < 2^31.  rrin_yuv_coef_std16 is
+ * rrin_yuv_coef_std for a depth of 8..16: y0 = 16 << (depth - 8), luma scaled by
+ * 219 * 2^(depth-8) / maxval and chroma by 224 * 2^(depth-8) / maxval (limited range); depth 8
+ * gives rrin_yuv_coef_std's numbers.  Host only. */
+int rrin_yuv_coef_std16(int32_t standard, int32_t full_range, int32_t depth, rrin_yuv_coef* c);
+/* rrin_pack_g16_yuv_h8 from two rrin_yuv420_16 stacks of one depth and shift (RRIN_E_ARG
+ * otherwise): bitwise the records rrin_pack_g16_u16_h8 writes from the frames converted to RGB
+ * samples of that depth.  Checked as there, before any HIP call. */
+int rrin_pack_g16_yuv16_h8(const rrin_yuv420_16* f0, const rrin_yuv420_16* f1, const rrin_yuv_coef* coef, int32_t n,
+                           int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec, void* stream);
 /* NCHW fp32 <-> H8 view (c channels starting at channel ch_off of the view).  rrin_nchw_to_h8
  * stores one element per value: the other channels of a record that [ch_off, ch_off + c) covers
  * only partly keep their contents, as do the padding and every other group. */
@@ -473,6 +511,15 @@ typedef struct rrin_head_h8_desc {
   rrin_yuv420 out_yuv;
   rrin_yuv_coef yuv_coef;
   int32_t pad3_;
+  /* ABI 23, FINAL, optional (NULL: off); at most one of out_u8 / out_yuv / out_u16 / out_yuv16
+     may be set (RRIN_E_ARG otherwise), out may still be.  out_u16: the crop (h0, w0, top as for
+     out_u8) as interleaved 16-bit frames [n][h0][w0][3] of depth u16_depth (9..16), each value v
+     as (uint16)(v * (float)maxval), 0 when poisoned.  out_yuv16 (y NULL: off): those samples at
+     out_yuv16.depth converted with yuv_coef into its 16-bit 4:2:0 planes, each written as
+     sample << shift, under the rules of out_yuv. */
+  uint16_t* out_u16;
+  int32_t u16_depth, pad4_;
+  rrin_yuv420_16 out_yuv16;
 } rrin_head_h8_desc;
 int rrin_head_h8_fwd(const rrin_head_h8_desc* d, void* stream);
 
@@ -639,6 +686,34 @@ typedef struct rrin_net_yuv_desc {
 } rrin_net_yuv_desc;
 int rrin_net_yuv_fwd(const rrin_net_yuv_desc* d, void* stream);
 
+/* ABI 23: rrin_net_u8_fwd on 16-bit RGB frames of depth 9..16 (RRIN_E_ARG otherwise): bit for bit
+ * "edge-pad, min(word, maxval) / maxval -> rrin_net_fwd -> multiply by maxval, truncate, crop"
+ * (rrin_pack_g16_u16_h8 in, rrin_head_h8_desc.out_u16 out).  img_stride in samples
+ * (>= h0*w0*3); everything else as rrin_net_u8_fwd. */
+typedef struct rrin_net_u16_desc {
+  rrin_net_desc net;
+  const uint16_t* f0;   /* [n][h0][w0][3], every frame dense */
+  const uint16_t* f1;
+  int64_t img_stride;
+  uint16_t* out_u16;    /* [n][h0][w0][3] contiguous */
+  int32_t h0, w0, depth, pad_;
+} rrin_net_u16_desc;
+int rrin_net_u16_fwd(const rrin_net_u16_desc* d, void* stream);
+
+/* ABI 23: rrin_net_yuv_fwd on 16-bit 4:2:0 frames of depth 10 or 12: by definition
+ * rgb16_to_yuv420(rrin_net_u16_fwd(yuv420_to_rgb16(f0), yuv420_to_rgb16(f1))) at that depth.  f0,
+ * f1 and out share depth and shift (RRIN_E_ARG otherwise); the checks of rrin_net_yuv_fwd apply,
+ * with the coefficient bounds of rrin_yuv420_16. */
+typedef struct rrin_net_yuv16_desc {
+  rrin_net_desc net;
+  rrin_yuv420_16 f0, f1;   /* n frames each; may be two views of one [n+1] stack */
+  rrin_yuv420_16 out;      /* n frames, written through the const pointers */
+  rrin_yuv_coef coef;
+  int32_t h0, w0;
+  int32_t pad_;
+} rrin_net_yuv16_desc;
+int rrin_net_yuv16_fwd(const rrin_net_yuv16_desc* d, void* stream);
+
 /* ---- Scene-cut / duplicate-frame gate of the 8-bit frame path (ABI 21) ------------------
  * Three small kernels for the stream of a rrin_net_u8_fwd call, so that a caller can replace the
  * interpolated frame of a pair that is a shot change or a repeated frame by one of its input
@@ -662,6 +737,13 @@ int rrin_gate_from_sad_u8(const uint64_t* sad, int32_t n, uint64_t limit, int32_
                           void* stream);
 int rrin_gate_frames_u8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0,
                         int32_t w0, const int32_t* gate, uint8_t* out, void* stream);
+/* ABI 23: rrin_pair_sad_u8 on 16-bit words: sad[p] = sum over the h0*w0*3 samples of pair p of
+ * |a - b| with a, b = min(word >> shift, 2^depth - 1), exact; depth 9..16 and
+ * 0 <= shift <= 16 - depth (RRIN_E_ARG otherwise); img_stride in samples; a frame may start at
+ * any even address.  The code and copy kernels serve 16-bit frames as they are:
+ * rrin_gate_frames_u8 with w0 and img_stride doubled copies whole words. */
+int rrin_pair_sad_u16(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int32_t h0,
+                      int32_t w0, int32_t depth, int32_t shift, uint64_t* sad, void* stream);
 
 /* ---- Training path (autograd): NCHW fp32 kernels ------------------------- */
 /* With autograd on (the reference trains through Net.forward, train.py:98, and

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librrin_hip.so")
 # A/B sessions only (tools/sessions/): another build of the same library, e.g. ab/librrin_hip_X.so
 if os.environ.get("RRIN_LIB_AB"):
@@ -106,13 +106,22 @@ class YuvCoef(C.Structure):
 YUV_BT709, YUV_BT601 = 0, 1
 
 
+class Yuv420x16(C.Structure):
+    """rrin_yuv420_16: one stack of 4:2:0 frames of 16-bit words (pitches and strides in samples; depth 10 or
+    12; shift 0: the sample in the low bits, 16 - depth: in the high bits)."""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("img_stride", C.c_int64),
+                ("y_pitch", C.c_int32), ("c_pitch", C.c_int32), ("c_step", C.c_int32), ("depth", C.c_int32),
+                ("shift", C.c_int32), ("pad_", C.c_int32)]
+
+
 class HeadH8Desc(C.Structure):
     _fields_ = [("n", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("mode", C.c_int32),
                 ("prec", C.c_int32), ("pad_", C.c_int32), ("src", H8), ("g16", H8), ("w", C.c_void_p),
                 ("bias", C.c_void_p), ("coef", C.c_void_p), ("out", C.c_void_p), ("flow_raw", H8),
                 ("raw_out", C.c_void_p), ("status", C.c_void_p), ("out_u8", C.c_void_p), ("h0", C.c_int32),
                 ("w0", C.c_int32), ("top", C.c_int32), ("pad2_", C.c_int32), ("out_yuv", Yuv420),
-                ("yuv_coef", YuvCoef), ("pad3_", C.c_int32)]
+                ("yuv_coef", YuvCoef), ("pad3_", C.c_int32), ("out_u16", C.c_void_p), ("u16_depth", C.c_int32),
+                ("pad4_", C.c_int32), ("out_yuv16", Yuv420x16)]
 
 
 class HeadWeights(C.Structure):
@@ -135,6 +144,17 @@ class NetU8Desc(C.Structure):
 
 class NetYuvDesc(C.Structure):
     _fields_ = [("net", NetDesc), ("f0", Yuv420), ("f1", Yuv420), ("out", Yuv420), ("coef", YuvCoef),
+                ("h0", C.c_int32), ("w0", C.c_int32), ("pad_", C.c_int32)]
+
+
+class NetU16Desc(C.Structure):
+    _fields_ = [("net", NetDesc), ("f0", C.c_void_p), ("f1", C.c_void_p), ("img_stride", C.c_int64),
+                ("out_u16", C.c_void_p), ("h0", C.c_int32), ("w0", C.c_int32), ("depth", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+class NetYuv16Desc(C.Structure):
+    _fields_ = [("net", NetDesc), ("f0", Yuv420x16), ("f1", Yuv420x16), ("out", Yuv420x16), ("coef", YuvCoef),
                 ("h0", C.c_int32), ("w0", C.c_int32), ("pad_", C.c_int32)]
 
 
@@ -225,6 +245,11 @@ SIGNATURES = {
     "rrin_yuv_coef_std": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(YuvCoef)]),
     "rrin_pack_g16_yuv_h8": (C.c_int, [C.POINTER(Yuv420), C.POINTER(Yuv420), C.POINTER(YuvCoef), C.c_int32,
                                        C.c_int32, C.c_int32, C.POINTER(H8), C.c_int32, C.c_void_p]),
+    "rrin_pack_g16_u16_h8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.POINTER(H8), C.c_int32, C.c_void_p]),
+    "rrin_yuv_coef_std16": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(YuvCoef)]),
+    "rrin_pack_g16_yuv16_h8": (C.c_int, [C.POINTER(Yuv420x16), C.POINTER(Yuv420x16), C.POINTER(YuvCoef), C.c_int32,
+                                         C.c_int32, C.c_int32, C.POINTER(H8), C.c_int32, C.c_void_p]),
     "rrin_nchw_to_h8": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(H8), C.c_int32,
                                   C.c_void_p]),
     "rrin_h8_to_nchw": (C.c_int, [C.POINTER(H8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
@@ -236,6 +261,10 @@ SIGNATURES = {
     "rrin_net_fwd": (C.c_int, [C.POINTER(NetDesc), C.c_void_p]),
     "rrin_net_u8_fwd": (C.c_int, [C.POINTER(NetU8Desc), C.c_void_p]),
     "rrin_net_yuv_fwd": (C.c_int, [C.POINTER(NetYuvDesc), C.c_void_p]),
+    "rrin_net_u16_fwd": (C.c_int, [C.POINTER(NetU16Desc), C.c_void_p]),
+    "rrin_net_yuv16_fwd": (C.c_int, [C.POINTER(NetYuv16Desc), C.c_void_p]),
+    "rrin_pair_sad_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_void_p, C.c_void_p]),
     "rrin_pair_sad_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                    C.c_void_p]),
     "rrin_gate_from_sad_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),

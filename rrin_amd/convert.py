@@ -108,12 +108,46 @@ def frames_float_to_u8(t: torch.Tensor, height: int, width: int) -> torch.Tensor
     return a.movedim(-3, -1).contiguous()
 
 
-def scene_limit(threshold, h0: int, w0: int) -> int:
+def _depth_maxval(depth) -> int:
+    if isinstance(depth, bool) or not isinstance(depth, int) or not 9 <= depth <= 16:
+        raise ValueError(f"16-bit RGB frames are 9 to 16 bits deep, got {depth!r}")
+    return (1 << depth) - 1
+
+
+def frames_u16_to_float(frames: torch.Tensor, depth: int) -> torch.Tensor:
+    """:func:`frames_u8_to_float` for uint16 [...,H0,W0,3] frames of ``depth`` 9..16: the sample is
+    ``min(word, maxval)`` with ``maxval = 2**depth - 1``, the value ``sample.float() / float(maxval)``;
+    the same padding.  ``Net.forward_u16`` does this inside its input pack."""
+    maxval = _depth_maxval(depth)
+    if frames.dtype != torch.uint16:
+        raise TypeError("16-bit frames are uint16")
+    h0, w0 = frames.shape[-3], frames.shape[-2]
+    top, right = pad_amounts(w0, h0)
+    rows = (torch.arange(h0 + top, device=frames.device) - top).clamp_(min=0)
+    cols = torch.arange(w0 + right, device=frames.device).clamp_(max=w0 - 1)
+    x = (frames.view(torch.int16).to(torch.int32) & 0xFFFF).clamp_(max=maxval)
+    x = x.index_select(-3, rows).index_select(-2, cols)
+    return x.movedim(-1, -3).float().div_(float(maxval))
+
+
+def frames_float_to_u16(t: torch.Tensor, height: int, width: int, depth: int) -> torch.Tensor:
+    """:func:`frames_float_to_u8` at ``depth`` 9..16: the crop, then ``t * float(maxval)`` (one fp32
+    multiply) truncated toward zero, as uint16 [...,height,width,3].  ``Net.forward_u16`` does this
+    inside its last head's store."""
+    maxval = _depth_maxval(depth)
+    top = t.shape[-2] - height
+    a = t[..., top:top + height, :width].mul(float(maxval)).to(torch.int32)
+    return a.to(torch.int16).view(torch.uint16).movedim(-3, -1).contiguous()
+
+
+def scene_limit(threshold, h0: int, w0: int, maxval: int = 255) -> int:
     """The largest sum of absolute byte differences of an H0 x W0 RGB pair that is not a cut:
-    ``floor(threshold * H0*W0*3)`` for a mean absolute byte difference ``threshold`` in [0, 255]."""
+    ``floor(threshold * H0*W0*3)`` for a mean absolute byte difference ``threshold`` in [0, 255]
+    (16-bit frames: a mean absolute sample difference in [0, ``maxval``])."""
     th = float(threshold)
-    if not 0.0 <= th <= 255.0:
-        raise ValueError(f"scene_threshold is a mean absolute byte difference in [0, 255], got {threshold!r}")
+    if not 0.0 <= th <= float(maxval):
+        what = "byte" if maxval == 255 else "sample"
+        raise ValueError(f"scene_threshold is a mean absolute {what} difference in [0, {maxval}], got {threshold!r}")
     return math.floor(th * (h0 * w0 * 3))
 
 
@@ -422,7 +456,12 @@ def interpolate_y4m(model, src, dst, sf, batch=4, scene_threshold=None, coef=Non
     frames pass through as their own bytes.  ``coef`` (``rrin_amd.yuv.coefficients``; None: BT.709
     limited range) and ``scene_threshold`` go to ``interpolate_yuv`` -- the threshold is a mean over
     luma and chroma bytes there, not the RGB path's number, and no value has been validated on
-    footage.  Single process: ``WORLD_SIZE`` > 1 raises.  Returns the frames written."""
+    footage.  Single process: ``WORLD_SIZE`` > 1 raises.  Returns the frames written.
+
+    A 10- or 12-bit stream (``C420p10`` / ``C420p12``: little-endian 16-bit words, the sample in the
+    low bits) runs the same way on uint16 stacks through ``model.interpolate_yuv16`` at the
+    stream's depth; ``coef`` None is then BT.709 limited range at that depth, ``scene_threshold``
+    a mean absolute sample difference in [0, maxval], and the output keeps the input's tag."""
     from . import y4m
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise RuntimeError("interpolate_y4m runs in a single process (a stream has one reader and one writer)")
@@ -436,9 +475,11 @@ def interpolate_y4m(model, src, dst, sf, batch=4, scene_threshold=None, coef=Non
         dst = open(dst, "wb")
         opened.append(dst)
     try:
-        rd = y4m.Reader(src)
+        rd = y4m.Reader(src, depths=(8, 10, 12))
         w0, h0 = rd.width, rd.height
-        wr = y4m.Writer(dst, w0, h0, rd.fps_num * (sf + 1), rd.fps_den, rd.colorspace)
+        wr = y4m.Writer(dst, w0, h0, rd.fps_num * (sf + 1), rd.fps_den, rd.colorspace, depths=(8, 10, 12))
+        deep = rd.bit_depth > 8
+        dtype = torch.uint16 if deep else torch.uint8
         device = next(model.parameters()).device
         ts = [i / (sf + 1) for i in range(1, sf + 1)]
         gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
@@ -476,12 +517,16 @@ def interpolate_y4m(model, src, dst, sf, batch=4, scene_threshold=None, coef=Non
             if nloc == 0:
                 break
             prev = group[-1]
-            stack = torch.empty((nloc + 1, 3 * h0 // 2, w0), dtype=torch.uint8, pin_memory=True)
+            stack = torch.empty((nloc + 1, 3 * h0 // 2, w0), dtype=dtype, pin_memory=True)
             for j, fr in enumerate(group):
                 stack[j].view(-1).copy_(torch.from_numpy(fr))
             stack = stack.to(device, non_blocking=True)
             with torch.no_grad():
-                outs = model.interpolate_yuv(stack[:-1], stack[1:], ts, layout="i420", coef=coef, **gate_kw)
+                if deep:
+                    outs = model.interpolate_yuv16(stack[:-1], stack[1:], ts, layout="i420", depth=rd.bit_depth,
+                                                   msb=False, coef=coef, **gate_kw)
+                else:
+                    outs = model.interpolate_yuv(stack[:-1], stack[1:], ts, layout="i420", coef=coef, **gate_kw)
             host = []
             for o in outs:
                 hbuf = torch.empty(o.shape, dtype=o.dtype, pin_memory=True)

@@ -1,9 +1,9 @@
 // Every non-conv kernel of the record path (layouts in h8.hpp), each with its entry point:
 // NCHW <-> records (rrin_nchw_to_h8 / rrin_h8_to_nchw), the frame pair into the Net buffer g16
-// from fp32 or uint8 frames (rrin_pack_g16_h8 / rrin_pack_g16_u8_h8), nn.Upsample(bilinear, x2)
+// from fp32, uint8 or uint16 frames (rrin_pack_g16_h8 / rrin_pack_g16_u8_h8 / rrin_pack_g16_u16_h8), nn.Upsample(bilinear, x2)
 // (unet.py:77) as its own pass (rrin_upsample2x_h8), the head convs (Cout <= 4) fused with the
 // model.py glue they feed (rrin_head_h8_fwd; the arithmetic itself in net_glue.hpp; the FINAL
-// head also stores 8-bit frames, interleaved RGB or 4:2:0 planes through yuv.hpp), and the
+// head also stores 8-bit and 16-bit frames, interleaved RGB or 4:2:0 planes through yuv.hpp), and the
 // t-blend of a kept raw flow (rrin_flow_tblend_h8).  Each kernel is written once over a record
 // format F (rec_fmt.hpp) and instantiated for RecH8<1> (F16), RecH8<2> (F16X3) and RecR32.
 #include <string.h>
@@ -163,6 +163,44 @@ __global__ void __launch_bounds__(256) pack_g16_u8_kernel(const uint8_t* __restr
   store_frame_pair<F>(g, g.rec(img, 0, y, x), a, b);
 }
 
+// ---- 16-bit frames straight into g16 (rrin_pack_g16_u16_h8) ------------------------
+// pack_g16_u8_kernel for uint16 [n][h0][w0][3] frames of maxval = 2^depth - 1: the run's 768
+// words of each frame are loaded one per lane and step (2-byte loads: a frame of a stack starts
+// at any even address; a wave's load is 128 consecutive bytes) into LDS; a pixel's samples are
+// min(word, maxval) and its values sample / maxval by the IEEE division (sample_to_float): no
+// table, which at 16 bits would not fit the LDS.  f_img counts words.
+template <class F>
+__global__ void __launch_bounds__(256) pack_g16_u16_kernel(const uint16_t* __restrict__ f0,
+                                                           const uint16_t* __restrict__ f1, int64_t f_img, int w0,
+                                                           int top, RecView g, int w, int maxval) {
+  __shared__ uint16_t s_px[2][768];
+  const int tid = threadIdx.x;
+  const int xs = blockIdx.x * 256, y = blockIdx.y, img = blockIdx.z;
+  const int sy = y > top ? y - top : 0;
+  const int64_t row = (int64_t)img * f_img + ((int64_t)sy * w0 + xs) * 3;
+  const int nb = min(256, w0 - xs) * 3;  // xs < w0: the right pad is < 16 columns, xs a multiple of 256
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int b = tid + 256 * k;
+    if (b < nb) {
+      s_px[0][b] = f0[row + b];
+      s_px[1][b] = f1[row + b];
+    }
+  }
+  __syncthreads();
+  const int x = xs + tid;
+  if (x >= w) return;
+  const int c = (min(x, w0 - 1) - xs) * 3;
+  const float mv = (float)maxval;
+  float a[3], b[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    a[k] = sample_to_float(min((int)s_px[0][c + k], maxval), mv);
+    b[k] = sample_to_float(min((int)s_px[1][c + k], maxval), mv);
+  }
+  store_frame_pair<F>(g, g.rec(img, 0, y, x), a, b);
+}
+
 // ---- head conv (Cout <= 4) + Net glue on the record Net buffer ------------------
 struct HeadH8Args {
   RecView src;      // 32 channels
@@ -184,6 +222,9 @@ struct HeadH8Args {
   int64_t o_img;
   int oy_pitch, oc_pitch, oc_step;
   rrin_yuv_coef yc;
+  // FINAL, the WIDE kernels only (rrin_head_h8_desc.out_u16 / out_yuv16): out8 or oy / ou / ov hold
+  // uint16 pointers, o_img and the pitches count words; samples of [0, maxval], stored << shift
+  int maxval, shift;
 };
 
 // The byte of a clamped FINAL value: (uint8)(q * 255.0f) -- one fp32 multiply, truncation toward
@@ -199,6 +240,19 @@ __device__ inline void final_store_u8(const HeadH8Args& a, int img, int y, int x
   uint8_t* o = a.out8 + (((int64_t)img * a.h0 + yo) * a.w0 + x) * 3;
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) o[ch] = final_byte(q[ch], poison);
+}
+
+// FINAL with a 16-bit output: final_store_u8 with three interleaved words, each
+// (uint16)(q * (float)maxval) -- one fp32 multiply, truncation, as frames_float_to_u16; 0 when poisoned
+__device__ inline int final_word(float q, bool poison, float maxval) { return poison ? 0 : (int)(q * maxval); }
+
+__device__ inline void final_store_u16(const HeadH8Args& a, int img, int y, int x, const float* q, bool poison) {
+  const int yo = y - a.top;
+  if (yo < 0 || yo >= a.h0 || x >= a.w0) return;
+  uint16_t* o = reinterpret_cast<uint16_t*>(a.out8) + (((int64_t)img * a.h0 + yo) * a.w0 + x) * 3;
+  const float mv = (float)a.maxval;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) o[ch] = (uint16_t)final_word(q[ch], poison, mv);
 }
 
 // FINAL with a 4:2:0 output: a thread's two vertically adjacent pixels (rows y, y + 1, y even;
@@ -226,11 +280,38 @@ __device__ inline void final_store_yuv(const HeadH8Args& a, int img, int y, int 
     a.ou[c] = (uint8_t)rgb_sum_to_chroma(a.yc.ur, a.yc.ug, a.yc.ub, sum);
 }
 
+// final_store_yuv for 16-bit planes (rgb: the two pixels' samples of [0, maxval]): the same lane
+// exchange and store pattern, the conversion at the planes' depth, every sample stored << shift
+__device__ inline void final_store_yuv16(const HeadH8Args& a, int img, int y, int x, const int (*rgb)[3]) {
+  int sum[3];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    sum[ch] = rgb[0][ch] + rgb[1][ch];
+    sum[ch] += __shfl_xor(sum[ch], 1);
+  }
+  const int yo = y - a.top;
+  if (yo < 0 || yo >= a.h0 || x >= a.w0) return;
+  const int mid = (a.maxval + 1) >> 1;
+  const int64_t base = (int64_t)img * a.o_img;
+  uint16_t* py = reinterpret_cast<uint16_t*>(a.oy) + base + (int64_t)yo * a.oy_pitch + x;
+  py[0] = (uint16_t)(rgb_to_luma16(a.yc, a.maxval, rgb[0]) << a.shift);
+  py[a.oy_pitch] = (uint16_t)(rgb_to_luma16(a.yc, a.maxval, rgb[1]) << a.shift);
+  const int64_t c = base + (int64_t)(yo >> 1) * a.oc_pitch + (x >> 1) * a.oc_step;
+  if (x & 1)
+    reinterpret_cast<uint16_t*>(a.ov)[c] =
+        (uint16_t)(rgb_sum_to_chroma16(a.yc.vr, a.yc.vg, a.yc.vb, mid, a.maxval, sum) << a.shift);
+  else
+    reinterpret_cast<uint16_t*>(a.ou)[c] =
+        (uint16_t)(rgb_sum_to_chroma16(a.yc.ur, a.yc.ug, a.yc.ub, mid, a.maxval, sum) << a.shift);
+}
+
 // The glue stores whole or partial records as the format does (F::Px): RecR32 updates g16 only in
 // whole 16-B records and reads first those it changes in part (FLOW records 1-2, REFINE 1-3,
 // MASK 1-2); RecH8 stores 2 / 4 / 16 B per plane and sets the range flag.
 // YUV (FINAL only): the 8-bit output as 4:2:0 planes (final_store_yuv) instead of interleaved RGB
-template <class F, int COUT, int MODE, bool YUV = false>
+// WIDE (FINAL only): the frame output in 16-bit words (final_store_u16; with YUV final_store_yuv16).
+// Both are compile-time forms: the fp32 / 8-bit instantiations carry none of the 16-bit code.
+template <class F, int COUT, int MODE, bool YUV = false, bool WIDE = false>
 __global__ void __launch_bounds__(256) head_kernel(HeadH8Args a) {
   // tile 16 rows x 32 cols; thread = 2 vertically adjacent pixels (one float2v per output channel;
   // the library is built without packed fp32 ops, so the FMA is two v_fma_f32)
@@ -300,7 +381,7 @@ __global__ void __launch_bounds__(256) head_kernel(HeadH8Args a) {
     __syncthreads();
   }
 
-  int rgb[2][3] = {};  // YUV: the two pixels' RGB bytes
+  int rgb[2][3] = {};  // YUV: the two pixels' RGB bytes (WIDE: samples)
   for (int p = 0; p < 2; ++p) {
     float acc[COUT];
 #pragma unroll
@@ -363,7 +444,13 @@ __global__ void __launch_bounds__(256) head_kernel(HeadH8Args a) {
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) o[(int64_t)ch * a.h * a.w_] = poison ? __builtin_nanf("") : q[ch];
       }
-      if constexpr (YUV) {
+      if constexpr (YUV && WIDE) {
+        const float mv = (float)a.maxval;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) rgb[p][ch] = final_word(q[ch], poison, mv);
+      } else if constexpr (WIDE) {
+        final_store_u16(a, img, y, x, q, poison);
+      } else if constexpr (YUV) {
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) rgb[p][ch] = final_byte(q[ch], poison);
       } else if (a.out8) {
@@ -371,7 +458,10 @@ __global__ void __launch_bounds__(256) head_kernel(HeadH8Args a) {
       }
     }
   }
-  if constexpr (YUV) final_store_yuv(a, img, y0 + r2, x0 + xl, rgb);
+  if constexpr (YUV && WIDE)
+    final_store_yuv16(a, img, y0 + r2, x0 + xl, rgb);
+  else if constexpr (YUV)
+    final_store_yuv(a, img, y0 + r2, x0 + xl, rgb);
 }
 
 // Ft0 / Ft1 (model.py:38-39) from a kept raw Flow record -> g16 channels 6-9
@@ -469,10 +559,10 @@ extern "C" int rrin_h8_to_nchw(const rrin_h8* src, int32_t n, int32_t c, int32_t
   });
 }
 
-template <int COUT, int MODE, bool YUV = false>
+template <int COUT, int MODE, bool YUV = false, bool WIDE = false>
 static int head_launch(const HeadH8Args& a, int prec, int grid, hipStream_t st) {
   return with_format(prec, [&](auto f) {
-    hipLaunchKernelGGL((head_kernel<decltype(f), COUT, MODE, YUV>), dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((head_kernel<decltype(f), COUT, MODE, YUV, WIDE>), dim3(grid), dim3(256), 0, st, a);
     return hip_code(hipGetLastError());
   });
 }
@@ -490,15 +580,23 @@ static int head_prepare(const rrin_head_h8_desc* d, HeadH8Args& a, int& grid) {
   } else if (cpr * d->g16.groups < d->cout) {
     return RRIN_E_ARG;
   }
-  const bool yuv = d->mode == RRIN_HEAD_FINAL && d->out_yuv.y;
-  if (d->mode == RRIN_HEAD_FINAL && !d->out && !d->out_u8 && !yuv) return RRIN_E_ARG;
-  if (yuv && d->out_u8) return RRIN_E_ARG;
-  if (d->mode == RRIN_HEAD_FINAL && (d->out_u8 || yuv) &&
+  const bool fin = d->mode == RRIN_HEAD_FINAL;
+  const bool yuv = fin && d->out_yuv.y;
+  const bool u16 = fin && d->out_u16, yuv16 = fin && d->out_yuv16.y;
+  if (fin && !d->out && !d->out_u8 && !yuv && !u16 && !yuv16) return RRIN_E_ARG;
+  if ((d->out_u8 != nullptr) + yuv + u16 + yuv16 > 1) return RRIN_E_ARG;
+  if (u16 && (d->u16_depth < 9 || d->u16_depth > 16)) return RRIN_E_ARG;
+  if (fin && (d->out_u8 || yuv || u16 || yuv16) &&
       (d->h0 < 1 || d->w0 < 1 || d->top < 0 || d->top + d->h0 > h || d->w0 > w))
     return RRIN_E_SHAPE;
   if (yuv) {
     if (int rc = yuv_coef_check(&d->yuv_coef)) return rc;
     if (int rc = yuv420_check(d->out_yuv, d->n, d->h0, d->w0)) return rc;
+    if (d->top & 1) return RRIN_E_SHAPE;
+  }
+  if (yuv16) {
+    if (int rc = yuv420_16_check(d->out_yuv16, d->n, d->h0, d->w0)) return rc;
+    if (int rc = yuv_coef_check16(&d->yuv_coef, d->out_yuv16.depth)) return rc;
     if (d->top & 1) return RRIN_E_SHAPE;
   }
   memset(&a, 0, sizeof(a));
@@ -525,6 +623,29 @@ static int head_prepare(const rrin_head_h8_desc* d, HeadH8Args& a, int& grid) {
     a.oc_pitch = d->out_yuv.c_pitch;
     a.oc_step = d->out_yuv.c_step;
     a.yc = d->yuv_coef;
+    a.h0 = d->h0;
+    a.w0 = d->w0;
+    a.top = d->top;
+  }
+  if (u16) {
+    a.out8 = reinterpret_cast<uint8_t*>(d->out_u16);
+    a.maxval = (1 << d->u16_depth) - 1;
+    a.h0 = d->h0;
+    a.w0 = d->w0;
+    a.top = d->top;
+  }
+  if (yuv16) {
+    const rrin_yuv420_16& o = d->out_yuv16;
+    a.oy = reinterpret_cast<uint8_t*>(const_cast<uint16_t*>(o.y));
+    a.ou = reinterpret_cast<uint8_t*>(const_cast<uint16_t*>(o.u));
+    a.ov = reinterpret_cast<uint8_t*>(const_cast<uint16_t*>(o.v));
+    a.o_img = o.img_stride;
+    a.oy_pitch = o.y_pitch;
+    a.oc_pitch = o.c_pitch;
+    a.oc_step = o.c_step;
+    a.yc = d->yuv_coef;
+    a.maxval = (1 << o.depth) - 1;
+    a.shift = o.shift;
     a.h0 = d->h0;
     a.w0 = d->w0;
     a.top = d->top;
@@ -561,6 +682,9 @@ extern "C" int rrin_head_h8_fwd(const rrin_head_h8_desc* d, void* stream) {
       return d->cout == 2 ? head_launch<2, RRIN_HEAD_MASK>(a, d->prec, grid, st) : RRIN_E_ARG;
     case RRIN_HEAD_FINAL:
       if (d->cout != 3) return RRIN_E_ARG;
+      if (a.maxval)  // the 16-bit forms (head_prepare set maxval for them alone)
+        return a.oy ? head_launch<3, RRIN_HEAD_FINAL, true, true>(a, d->prec, grid, st)
+                    : head_launch<3, RRIN_HEAD_FINAL, false, true>(a, d->prec, grid, st);
       return a.oy ? head_launch<3, RRIN_HEAD_FINAL, true>(a, d->prec, grid, st)
                   : head_launch<3, RRIN_HEAD_FINAL>(a, d->prec, grid, st);
   }
@@ -608,6 +732,22 @@ extern "C" int rrin_pack_g16_u8_h8(const uint8_t* f0, const uint8_t* f1, int64_t
   return with_format(prec, [&](auto f) {
     hipLaunchKernelGGL(pack_g16_u8_kernel<decltype(f)>, grid, dim3(256), 0, (hipStream_t)stream, f0, f1, img_stride,
                        w0, h - h0, rec_view(*g16), w);
+    return hip_code(hipGetLastError());
+  });
+}
+
+extern "C" int rrin_pack_g16_u16_h8(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int32_t h0,
+                                    int32_t w0, int32_t depth, const rrin_h8* g16, int32_t prec, void* stream) {
+  if (!f0 || !f1 || !g16 || n < 1 || !rec_prec(prec) || depth < 9 || depth > 16) return RRIN_E_ARG;
+  if (!h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16) return RRIN_E_SHAPE;
+  const int h = g16->g.h, w = g16->g.w;
+  if (h0 < 1 || w0 < 1 || h != (h0 + 15) / 16 * 16 || w != (w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  if (img_stride < (int64_t)h0 * w0 * 3 && n > 1) return RRIN_E_ARG;
+  if (n > 65535 || h > 65535) return RRIN_E_SHAPE;  // grid y / z
+  const dim3 grid((w + 255) / 256, h, n);
+  return with_format(prec, [&](auto f) {
+    hipLaunchKernelGGL(pack_g16_u16_kernel<decltype(f)>, grid, dim3(256), 0, (hipStream_t)stream, f0, f1, img_stride,
+                       w0, h - h0, rec_view(*g16), w, (1 << depth) - 1);
     return hip_code(hipGetLastError());
   });
 }

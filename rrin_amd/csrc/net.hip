@@ -292,6 +292,10 @@ struct HeadIO {
   // or the crop as 4:2:0 planes (rrin_head_h8_desc.out_yuv / yuv_coef); NULL: off
   const rrin_yuv420* out_yuv = nullptr;
   const rrin_yuv_coef* yuv_coef = nullptr;
+  // or in 16-bit words (rrin_head_h8_desc.out_u16 / u16_depth, out_yuv16 with yuv_coef); NULL: off
+  uint16_t* out_u16 = nullptr;
+  int u16_depth = 0;
+  const rrin_yuv420_16* out_yuv16 = nullptr;
 };
 
 // Debug taps (rrin_net_desc.taps): where U-Net u's raw output goes, or NULL.
@@ -600,10 +604,16 @@ int run_unet_h8(const Plan& p, const UNetSpec& u, const rrin_conv_weights* cw, c
   hd.out = io.out;
   hd.raw_out = io.raw;
   hd.status = p.status;
-  if (u.head_mode == RRIN_HEAD_FINAL && (io.out_u8 || io.out_yuv)) {
+  if (u.head_mode == RRIN_HEAD_FINAL && (io.out_u8 || io.out_yuv || io.out_u16 || io.out_yuv16)) {
     hd.out_u8 = io.out_u8;
+    hd.out_u16 = io.out_u16;
+    hd.u16_depth = io.u16_depth;
     if (io.out_yuv) {
       hd.out_yuv = *io.out_yuv;
+      hd.yuv_coef = *io.yuv_coef;
+    }
+    if (io.out_yuv16) {
+      hd.out_yuv16 = *io.out_yuv16;
       hd.yuv_coef = *io.yuv_coef;
     }
     hd.h0 = io.h0;
@@ -681,12 +691,24 @@ extern "C" int64_t rrin_net_scratch_bytes(const rrin_net_desc* d) {
   return scratch_bytes_of(d->n, d->h, d->w, d->prec, d->convs, kUNets, 4);
 }
 
-// The schedule of the three forwards: rrin_net_fwd (u8 and yuv NULL: fp32 NCHW frames d->i0 / i1
-// in, d->out out), rrin_net_u8_fwd (8-bit RGB frames in and out) and rrin_net_yuv_fwd (8-bit
-// 4:2:0 frames in and out); the 8-bit ones leave d->i0 / i1 / out unused and run on the record
-// layouts only.  The callers have validated d (and u8 / yuv).
-static int net_fwd_impl(const rrin_net_desc* d, const rrin_net_u8_desc* u8, const rrin_net_yuv_desc* yuv,
-                        void* stream) {
+// The frames of a forward that is not rrin_net_fwd: at most one member is set
+struct FrameIO {
+  const rrin_net_u8_desc* u8 = nullptr;
+  const rrin_net_yuv_desc* yuv = nullptr;
+  const rrin_net_u16_desc* u16 = nullptr;
+  const rrin_net_yuv16_desc* yuv16 = nullptr;
+};
+
+// The schedule of the forwards: rrin_net_fwd (no member of f set: fp32 NCHW frames d->i0 / i1
+// in, d->out out), rrin_net_u8_fwd (8-bit RGB frames in and out), rrin_net_yuv_fwd (8-bit
+// 4:2:0 frames in and out) and their 16-bit siblings rrin_net_u16_fwd / rrin_net_yuv16_fwd; the
+// frame forwards leave d->i0 / i1 / out unused and run on the record layouts only.  The callers
+// have validated d (and the member of f).
+static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, void* stream) {
+  const rrin_net_u8_desc* u8 = f.u8;
+  const rrin_net_yuv_desc* yuv = f.yuv;
+  const rrin_net_u16_desc* u16 = f.u16;
+  const rrin_net_yuv16_desc* y16 = f.yuv16;
   Plan p;
   make_plan(d->n, d->h, d->w, d->prec, reinterpret_cast<char*>(d->workspace), p);
   if (d->workspace_bytes < p.bytes) return RRIN_E_WORKSPACE;
@@ -708,6 +730,9 @@ static int net_fwd_impl(const rrin_net_desc* d, const rrin_net_u8_desc* u8, cons
       // can stage whole records (their tail channels are finite and meet zero weights)
       rc = u8    ? rrin_pack_g16_u8_h8(u8->f0, u8->f1, u8->img_stride, d->n, u8->h0, u8->w0, &gall, d->prec, st)
            : yuv ? rrin_pack_g16_yuv_h8(&yuv->f0, &yuv->f1, &yuv->coef, d->n, yuv->h0, yuv->w0, &gall, d->prec, st)
+           : u16 ? rrin_pack_g16_u16_h8(u16->f0, u16->f1, u16->img_stride, d->n, u16->h0, u16->w0, u16->depth, &gall,
+                                        d->prec, st)
+           : y16 ? rrin_pack_g16_yuv16_h8(&y16->f0, &y16->f1, &y16->coef, d->n, y16->h0, y16->w0, &gall, d->prec, st)
                  : rrin_pack_g16_h8(d->i0, d->i1, d->n, &gall, d->prec, st);
       if (!rc && d->skip_flow) {
         const rrin_h8 fr = hview(p.FLOWRAW, 0, 4);
@@ -717,7 +742,7 @@ static int net_fwd_impl(const rrin_net_desc* d, const rrin_net_u8_desc* u8, cons
     int k = 0;
     for (int u = 0; u < 4 && !rc; ++u) {
       if (!(u == 0 && d->skip_flow)) {
-        HeadIO io{d->coef, u8 || yuv ? nullptr : d->out, tap_of(d, kUNets[u])};
+        HeadIO io{d->coef, u8 || yuv || u16 || y16 ? nullptr : d->out, tap_of(d, kUNets[u])};
         if (u8) {
           io.out_u8 = u8->out_u8;
           io.h0 = u8->h0;
@@ -729,6 +754,18 @@ static int net_fwd_impl(const rrin_net_desc* d, const rrin_net_u8_desc* u8, cons
           io.h0 = yuv->h0;
           io.w0 = yuv->w0;
           io.top = d->h - yuv->h0;
+        } else if (u16) {
+          io.out_u16 = u16->out_u16;
+          io.u16_depth = u16->depth;
+          io.h0 = u16->h0;
+          io.w0 = u16->w0;
+          io.top = d->h - u16->h0;
+        } else if (y16) {
+          io.out_yuv16 = &y16->out;
+          io.yuv_coef = &y16->coef;
+          io.h0 = y16->h0;
+          io.w0 = y16->w0;
+          io.top = d->h - y16->h0;
         }
         rc = run_unet_h8(p, kUNets[u], d->convs + k, d->heads[u], io, st);
       }
@@ -765,7 +802,7 @@ extern "C" int rrin_net_fwd(const rrin_net_desc* d, void* stream) {
     return RRIN_E_ARG;
   if (d->n < 1 || d->h < 16 || d->w < 16 || (d->h % 16) || (d->w % 16)) return RRIN_E_SHAPE;
   if (d->prec < RRIN_PREC_F32 || d->prec > RRIN_PREC_F32R) return RRIN_E_ARG;
-  return net_fwd_impl(d, nullptr, nullptr, stream);
+  return net_fwd_impl(d, FrameIO{}, stream);
 }
 
 extern "C" int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream) {
@@ -777,7 +814,9 @@ extern "C" int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream) {
   if (nd->n < 1 || d->h0 < 1 || d->w0 < 1) return RRIN_E_SHAPE;
   if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
   if (nd->n > 1 && d->img_stride < (int64_t)d->h0 * d->w0 * 3) return RRIN_E_ARG;
-  return net_fwd_impl(nd, d, nullptr, stream);
+  FrameIO f;
+  f.u8 = d;
+  return net_fwd_impl(nd, f, stream);
 }
 
 extern "C" int rrin_net_yuv_fwd(const rrin_net_yuv_desc* d, void* stream) {
@@ -790,7 +829,39 @@ extern "C" int rrin_net_yuv_fwd(const rrin_net_yuv_desc* d, void* stream) {
   for (const rrin_yuv420* s : {&d->f0, &d->f1, &d->out})
     if (int rc = yuv420_check(*s, nd->n, d->h0, d->w0)) return rc;
   if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
-  return net_fwd_impl(nd, nullptr, d, stream);
+  FrameIO f;
+  f.yuv = d;
+  return net_fwd_impl(nd, f, stream);
+}
+
+extern "C" int rrin_net_u16_fwd(const rrin_net_u16_desc* d, void* stream) {
+  if (!d || !d->f0 || !d->f1 || !d->out_u16 || d->depth < 9 || d->depth > 16) return RRIN_E_ARG;
+  const rrin_net_desc* nd = &d->net;
+  if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
+  // the record precisions only, as rrin_net_u8_fwd
+  if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
+  if (nd->n < 1 || d->h0 < 1 || d->w0 < 1) return RRIN_E_SHAPE;
+  if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  if (nd->n > 1 && d->img_stride < (int64_t)d->h0 * d->w0 * 3) return RRIN_E_ARG;
+  FrameIO f;
+  f.u16 = d;
+  return net_fwd_impl(nd, f, stream);
+}
+
+extern "C" int rrin_net_yuv16_fwd(const rrin_net_yuv16_desc* d, void* stream) {
+  if (!d) return RRIN_E_ARG;
+  const rrin_net_desc* nd = &d->net;
+  if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
+  if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
+  for (const rrin_yuv420_16* s : {&d->f0, &d->f1, &d->out}) {
+    if (int rc = yuv420_16_check(*s, nd->n, d->h0, d->w0)) return rc;
+    if (s->depth != d->f0.depth || s->shift != d->f0.shift) return RRIN_E_ARG;
+  }
+  if (int rc = yuv_coef_check16(&d->coef, d->f0.depth)) return rc;
+  if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  FrameIO f;
+  f.yuv16 = d;
+  return net_fwd_impl(nd, f, stream);
 }
 
 // One U-Net alone (reference UNet.forward, unet.py:40-51): NCHW in -> NCHW out,

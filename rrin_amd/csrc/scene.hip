@@ -2,6 +2,7 @@
 // the frames live, on the forward's own stream, without a host round trip.
 //
 //   rrin_pair_sad_u8       sad[p] = sum |f0[p] - f1[p]| over a pair's h0*w0*3 bytes, exact, 64 bit
+//   rrin_pair_sad_u16      the same over 16-bit words read as min(word >> shift, maxval) (ABI 23)
 //   rrin_gate_from_sad_u8  sad -> code per pair: 1 duplicate (sad == 0), cut_code above the limit
 //   rrin_gate_frames_u8    code 1 / 2: the output frame is overwritten with f0's / f1's bytes
 //
@@ -95,6 +96,71 @@ __global__ void __launch_bounds__(kThreads) pair_sad_u8_kernel(const uint8_t* __
       q = __builtin_amdgcn_sad_u8(x[k].z, y[k].z, q);
       q = __builtin_amdgcn_sad_u8(x[k].w, y[k].w, q);
       part += c * kChunkVecs + (int64_t)k * kThreads + tid < sp.vecs ? q : 0u;
+    }
+    sum += part;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  if ((tid & 63) == 0) s_part[tid >> 6] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    uint64_t t = 0;
+#pragma unroll
+    for (int k = 0; k < kThreads / 64; ++k) t += s_part[k];
+    if (t) atomicAdd((unsigned long long*)&sad[p], (unsigned long long)t);
+  }
+}
+
+// pair_sad_u8_kernel for frames of `len` 16-bit words, each read as min(word >> shift, maxv).
+// Frames start at even addresses, so the body is aligned on f0's dwords (a head of 0 or 1 word, a
+// tail of 0 or 1) and f1 is read as whole dwords from its address rounded down to 4, shifted by
+// 0 or 16 bits into place: a dword of either always holds a word of the frame.  A lane takes
+// kWords dwords per step; its 32-bit partial covers one step (16 words of at most 65535) and is
+// added to the 64-bit lane sum.  The reduction and the atomic add are pair_sad_u8_kernel's.
+constexpr int kWords = 8;  // dwords per lane and step
+
+__device__ inline uint32_t absdiff16(uint32_t a, uint32_t b, int shift, int maxv) {
+  const int x = min((int)(a >> shift), maxv), y = min((int)(b >> shift), maxv);
+  return (uint32_t)(x > y ? x - y : y - x);
+}
+
+__global__ void __launch_bounds__(kThreads) pair_sad_u16_kernel(const uint16_t* __restrict__ f0,
+                                                                const uint16_t* __restrict__ f1, int64_t img_stride,
+                                                                int64_t len, int shift, int maxv, uint64_t* sad) {
+  __shared__ uint64_t s_part[kThreads / 64];
+  const int tid = threadIdx.x;
+  const int p = blockIdx.y;
+  const uint16_t* a = f0 + (int64_t)p * img_stride;
+  const uint16_t* b = f1 + (int64_t)p * img_stride;
+  const int64_t head = (int64_t)(((uintptr_t)a >> 1) & 1);  // len >= 3: the head word exists
+  const int64_t nd = (len - head) / 2;                        // dwords of the body
+  const int64_t tail = len - head - 2 * nd;
+  uint64_t sum = 0;
+  if (blockIdx.x == 0 && tid < head + tail) {
+    const int64_t i = tid < head ? 0 : len - 1;
+    sum = absdiff16(a[i], b[i], shift, maxv);
+  }
+  const uint32_t* aw = (const uint32_t*)(a + head);
+  const uint32_t sh = (uint32_t)(((uintptr_t)(b + head) >> 1) & 1);  // b's body starts in a dword's high half
+  const uint32_t* bw = (const uint32_t*)(b + head - sh);
+  const int64_t step = (int64_t)kThreads * kWords;
+  for (int64_t c = (int64_t)blockIdx.x * step; c < nd; c += (int64_t)gridDim.x * step) {
+    uint32_t x[kWords], y[kWords];
+#pragma unroll
+    for (int k = 0; k < kWords; ++k) {
+      // a dword past the body re-reads the last one (nd > 0 here) and counts nothing
+      const int64_t v = c + (int64_t)k * kThreads + tid;
+      const int64_t vc = v < nd ? v : nd - 1;
+      x[k] = aw[vc];
+      const uint32_t lo = bw[vc], hi = bw[vc + sh];  // sh == 0 reads the same dword twice
+      y[k] = sh ? (lo >> 16) | (hi << 16) : lo;
+    }
+    uint32_t part = 0;
+#pragma unroll
+    for (int k = 0; k < kWords; ++k) {
+      const uint32_t q = absdiff16(x[k] & 0xffffu, y[k] & 0xffffu, shift, maxv) +
+                         absdiff16(x[k] >> 16, y[k] >> 16, shift, maxv);
+      part += c + (int64_t)k * kThreads + tid < nd ? q : 0u;
     }
     sum += part;
   }
@@ -207,5 +273,23 @@ extern "C" int rrin_gate_frames_u8(const uint8_t* f0, const uint8_t* f1, int64_t
   if (n > 65535) return RRIN_E_SHAPE;  // one pair per blockIdx.y
   hipLaunchKernelGGL(gate_frames_u8_kernel, dim3(grid_x(len), n), dim3(kThreads), 0, (hipStream_t)stream, f0, f1,
                      img_stride, len, gate, out);
+  return hip_code(hipGetLastError());
+}
+
+extern "C" int rrin_pair_sad_u16(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int32_t h0,
+                                 int32_t w0, int32_t depth, int32_t shift, uint64_t* sad, void* stream) {
+  if (!sad || ((uintptr_t)sad & 7)) return RRIN_E_ARG;
+  if (depth < 9 || depth > 16 || shift < 0 || shift > 16 - depth) return RRIN_E_ARG;
+  if (((uintptr_t)f0 & 1) || ((uintptr_t)f1 & 1)) return RRIN_E_ARG;
+  int64_t len = 0;
+  const int rc = frames_ok(f0, f1, img_stride, n, h0, w0, &len);
+  if (rc) return rc;
+  if (n > 65535) return RRIN_E_SHAPE;  // one pair per blockIdx.y
+  const int64_t steps = (len / 2 + kThreads * kWords - 1) / (kThreads * kWords);
+  const int gx = (int)(steps < 1 ? 1 : (steps > kMaxGridX ? kMaxGridX : steps));
+  hipLaunchKernelGGL(zero_u64_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream,
+                     sad, n);
+  hipLaunchKernelGGL(pair_sad_u16_kernel, dim3(gx, n), dim3(kThreads), 0, (hipStream_t)stream, f0, f1, img_stride,
+                     len, shift, (1 << depth) - 1, sad);
   return hip_code(hipGetLastError());
 }

@@ -831,20 +831,22 @@ class RRINEngine:
                 off += n * c * h * w
         return out
 
-    def _frames(self, f0, f1, what: str, rgb: bool):
-        """Checks two uint8 frame stacks of ``what`` -- ``[N,H0,W0,3]`` (``rgb``) or 4:2:0
-        ``[N, 3*H0//2, W0]`` -- and returns them with (H0, W0) and the bytes between their frames:
-        every frame dense, a uniform stride over dim 0 taken as it is (``frames[:-1]`` /
-        ``frames[1:]`` of one stack need no copy), anything else copied."""
+    def _frames(self, f0, f1, what: str, rgb: bool, dtype=torch.uint8):
+        """Checks two frame stacks of ``what`` (uint8, or uint16 for the 16-bit paths) --
+        ``[N,H0,W0,3]`` (``rgb``) or 4:2:0 ``[N, 3*H0//2, W0]`` -- and returns them with (H0, W0) and
+        the elements (bytes or 16-bit words) between their frames: every frame dense, a uniform
+        stride over dim 0 taken as it is (``frames[:-1]`` / ``frames[1:]`` of one stack need no
+        copy), anything else copied."""
+        name = str(dtype).split(".")[-1]
         if not isinstance(f0, torch.Tensor) or not isinstance(f1, torch.Tensor):
-            raise TypeError(f"{what} takes two uint8 tensors")
+            raise TypeError(f"{what} takes two {name} tensors")
         if f0.device != self.device or f1.device != self.device:
             raise RuntimeError(f"inputs on {f0.device}/{f1.device}, model on {self.device}")
-        if f0.dtype != torch.uint8 or f1.dtype != torch.uint8:
-            raise TypeError(f"{what} takes uint8 frames (forward takes float32)")
+        if f0.dtype != dtype or f1.dtype != dtype:
+            raise TypeError(f"{what} takes {name} frames (forward takes float32)")
         if rgb:
             if f0.dim() != 4 or f0.shape != f1.shape or f0.shape[3] != 3:
-                raise ValueError(f"expected two [N,H0,W0,3] uint8 tensors, got {tuple(f0.shape)} / {tuple(f1.shape)}")
+                raise ValueError(f"expected two [N,H0,W0,3] {name} tensors, got {tuple(f0.shape)} / {tuple(f1.shape)}")
             h0, w0 = f0.shape[1:3]
         else:
             from . import yuv
@@ -857,7 +859,7 @@ class RRINEngine:
             raise ValueError(f"empty frames: {tuple(f0.shape)}")
         frame = math.prod(f0.shape[1:])
 
-        def stride_of(f):  # bytes between frames, or None if f needs a copy
+        def stride_of(f):  # elements between frames, or None if f needs a copy
             dense = 1
             for d in range(f.dim() - 1, 0, -1):  # the trailing dims: dense (a dim of 1 has no stride to check)
                 if f.shape[d] > 1 and f.stride(d) != dense:
@@ -871,7 +873,8 @@ class RRINEngine:
             s0 = frame
         return f0, f1, h0, w0, s0
 
-    def _scene_gate(self, path: str, n: int, rows: int, cols: int, t, bounds, reuse_flow, scene_threshold, gate):
+    def _scene_gate(self, path: str, n: int, rows: int, cols: int, t, bounds, reuse_flow, scene_threshold, gate,
+                    maxval: int = 255):
         """The scene gate of a byte-frame forward whose frames are ``rows x cols x 3`` bytes each
         (RGB: H0 x W0; 4:2:0: H0/2 x W0).  Checks ``scene_threshold`` against ``gate`` and the gate
         tensor, keeps :attr:`last_gate` and the key of the cached sums, and returns None (gate
@@ -881,7 +884,7 @@ class RRINEngine:
             raise ValueError("scene_threshold and gate exclude each other")
         sad, have_sad, limit, cut_code = None, False, None, None
         if scene_threshold is not None:
-            limit, cut_code = scene_limit(scene_threshold, rows, cols), scene_cut_code(t)
+            limit, cut_code = scene_limit(scene_threshold, rows, cols, maxval), scene_cut_code(t)
             # the sums belong to the batch and its split: kept for the next t of the same pairs
             skey = (path, n, rows, cols, tuple(bounds))
             have_sad = bool(reuse_flow) and self._sad_key == skey
@@ -900,29 +903,40 @@ class RRINEngine:
         return sad, have_sad, limit, cut_code, gate
 
     def _enqueue_gate(self, g, p0: int, p1: int, img_stride: int, lo: int, hi: int, rows: int, cols: int, out: int,
-                      stream):
+                      stream, wide=None):
         """The gate kernels of pairs [lo, hi) on ``stream``, behind the part's forward: the sums
         (unless kept), the codes from the sums (unless given), the copy of the gated frames from
-        the frames at p0 / p1 (``rows x cols x 3`` bytes each) over those at ``out``."""
+        the frames at p0 / p1 (``rows x cols x 3`` bytes each) over those at ``out``.  ``wide``
+        (depth, shift): the frames are 16-bit words and ``img_stride`` counts them; the sums are
+        rrin_pair_sad_u16's, and the byte-wise copy kernel runs on twice the width."""
         sad, have_sad, limit, cut_code, codes = g
         sp, m = C.c_void_p(stream.cuda_stream), hi - lo
         cp = codes[lo:hi].data_ptr()
         if sad is not None:
             sums = sad[lo:hi].data_ptr()
-            if not have_sad:
+            if not have_sad and wide is None:
                 _lib.check(self.lib.rrin_pair_sad_u8(p0, p1, img_stride, m, rows, cols, sums, sp), "rrin_pair_sad_u8")
+            elif not have_sad:
+                _lib.check(self.lib.rrin_pair_sad_u16(p0, p1, img_stride, m, rows, cols, wide[0], wide[1], sums, sp),
+                           "rrin_pair_sad_u16")
             _lib.check(self.lib.rrin_gate_from_sad_u8(sums, m, limit, cut_code, cp, sp), "rrin_gate_from_sad_u8")
-        _lib.check(self.lib.rrin_gate_frames_u8(p0, p1, img_stride, m, rows, cols, cp, out, sp),
+        k = 1 if wide is None else 2
+        _lib.check(self.lib.rrin_gate_frames_u8(p0, p1, img_stride * k, m, rows, cols * k, cp, out, sp),
                    "rrin_gate_frames_u8")
 
-    def _pair_sad(self, f0, f1, img_stride: int, rows: int, cols: int) -> torch.Tensor:
-        """rrin_pair_sad_u8 of two checked stacks on the current stream: a fresh int64 ``[N]``."""
+    def _pair_sad(self, f0, f1, img_stride: int, rows: int, cols: int, wide=None) -> torch.Tensor:
+        """rrin_pair_sad_u8 (``wide`` = (depth, shift): rrin_pair_sad_u16) of two checked stacks on
+        the current stream: a fresh int64 ``[N]``."""
         n = f0.shape[0]
         sad = torch.empty(n, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
-            st = torch.cuda.current_stream(self.device)
-            _lib.check(self.lib.rrin_pair_sad_u8(f0.data_ptr(), f1.data_ptr(), img_stride, n, rows, cols,
-                                                 sad.data_ptr(), C.c_void_p(st.cuda_stream)), "rrin_pair_sad_u8")
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            if wide is None:
+                _lib.check(self.lib.rrin_pair_sad_u8(f0.data_ptr(), f1.data_ptr(), img_stride, n, rows, cols,
+                                                     sad.data_ptr(), st), "rrin_pair_sad_u8")
+            else:
+                _lib.check(self.lib.rrin_pair_sad_u16(f0.data_ptr(), f1.data_ptr(), img_stride, n, rows, cols,
+                                                      wide[0], wide[1], sad.data_ptr(), st), "rrin_pair_sad_u16")
         return sad
 
     def forward_u8(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, reuse_flow: bool = False,
@@ -1083,6 +1097,125 @@ class RRINEngine:
         ``floor(threshold * H0*W0*3/2)``."""
         f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_yuv", rgb=False)
         return self._pair_sad(f0, f1, s0, h0 // 2, w0)
+
+    # ---- 10- to 16-bit frames in 16-bit words ----------------------------------------------
+    @staticmethod
+    def _depth16(depth, lo: int, what: str) -> int:
+        if isinstance(depth, bool) or not isinstance(depth, int) or not lo <= depth <= 16:
+            raise ValueError(f"{what}: depth must be an int in {lo}..16, got {depth!r}")
+        return depth
+
+    def forward_u16(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, depth: int = 10, reuse_flow: bool = False,
+                    streams: int | None = None, split=None, scene_threshold=None, gate=None) -> torch.Tensor:
+        """:meth:`forward_u8` on 16-bit frames: ``f0`` / ``f1`` uint16 ``[N,H0,W0,3]`` holding RGB
+        samples of ``depth`` 9..16 in the words' low bits -> uint16 ``[N,H0,W0,3]`` of that depth.
+        Bit for bit ``convert.frames_u16_to_float`` -> :meth:`forward` ->
+        ``convert.frames_float_to_u16``: a sample is ``min(word, maxval)``, its value
+        ``sample / maxval`` by the fp32 division (rrin_pack_g16_u16_h8), the output
+        ``(uint16)(v * maxval)`` (rrin_net_u16_fwd).  Everything else is :meth:`forward_u8`'s:
+        views of one stack without a copy, the stream split, ``reuse_flow``, the range guard and
+        the scene gate -- with ``scene_threshold`` a mean absolute sample difference in
+        [0, maxval] over ``min(word, maxval)`` (rrin_pair_sad_u16), and a gated frame its input
+        frame's words as they are.  A kept raw Flow is only reused by this path at this depth."""
+        self._need_records("forward_u16")
+        depth = self._depth16(depth, 9, "forward_u16")
+        f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_u16", rgb=True, dtype=torch.uint16)
+        n = f0.shape[0]
+        h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
+        self._poll_range()
+        coef = t_coefficients(t, n).to(self.device, non_blocking=True)
+        bounds = self._bounds(n, streams, split)
+        tag = f"u16:{depth}"
+        g = self._scene_gate(tag, n, h0, w0, t, bounds, reuse_flow, scene_threshold, gate, (1 << depth) - 1)
+        out = torch.empty((n, h0, w0, 3), dtype=torch.uint16, device=self.device)
+
+        def part(j, lo, hi, stream, p):
+            d = _lib.NetU16Desc()
+            self._fill_net(d.net, p, coef[lo:hi])
+            p0, p1, po = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), out[lo:hi].data_ptr()
+            d.f0, d.f1, d.img_stride, d.out_u16 = p0, p1, s0, po
+            d.h0, d.w0, d.depth = h0, w0, depth
+            self._launch(self.lib.rrin_net_u16_fwd, "rrin_net_u16_fwd", d, d.net, p, tag, reuse_flow, stream)
+            if g is not None:
+                self._enqueue_gate(g, p0, p1, s0, lo, hi, h0, w0, po, stream, wide=(depth, 0))
+
+        self._run_parts(h, w, bounds, part)
+        return out
+
+    def pair_stats_u16(self, f0: torch.Tensor, f1: torch.Tensor, depth: int = 10) -> torch.Tensor:
+        """:meth:`pair_stats_u8` for two uint16 ``[N,H0,W0,3]`` stacks of ``depth`` 9..16: the exact
+        sum of ``|min(a, maxval) - min(b, maxval)|`` per pair (rrin_pair_sad_u16), int64 ``[N]``."""
+        depth = self._depth16(depth, 9, "pair_stats_u16")
+        f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_u16", rgb=True, dtype=torch.uint16)
+        return self._pair_sad(f0, f1, s0, h0, w0, wide=(depth, 0))
+
+    @staticmethod
+    def _yuv16_stack(ptr: int, img_stride: int, h0: int, w0: int, layout: str, depth: int, shift: int):
+        """The rrin_yuv420_16 of a dense-frame uint16 stack at device address ``ptr`` (strides in words)."""
+        s = _lib.Yuv420x16()
+        s.y, s.u = ptr, ptr + 2 * h0 * w0
+        s.img_stride, s.y_pitch, s.depth, s.shift = img_stride, w0, depth, shift
+        if layout == "nv12":
+            s.v, s.c_pitch, s.c_step = s.u + 2, w0, 2
+        else:
+            s.v, s.c_pitch, s.c_step = s.u + 2 * (h0 // 2) * (w0 // 2), w0 // 2, 1
+        return s
+
+    def forward_yuv16(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, layout: str = "nv12", depth: int = 10,
+                      msb: bool = False, coef=None, reuse_flow: bool = False, streams: int | None = None, split=None,
+                      scene_threshold=None, gate=None) -> torch.Tensor:
+        """:meth:`forward_yuv` on 10- or 12-bit 4:2:0 frames in 16-bit words: ``f0`` / ``f1`` uint16
+        ``[N, 3*H0//2, W0]`` -> uint16 of the same shape, layout, depth and alignment (``msb=False``:
+        the sample in the low bits, as yuv420p10le and Y4M C420p10; ``True``: in the high bits, as
+        P010 / P012).  By definition, and bit for bit, ``yuv.rgb16_to_yuv420(forward_u16(
+        yuv.yuv420_to_rgb16(f0), yuv.yuv420_to_rgb16(f1), t, depth))`` with ``coef`` (None: BT.709
+        limited range at this depth; bounds in ``yuv.as_coef``): rrin_pack_g16_yuv16_h8 in, the
+        FINAL head's 16-bit 4:2:0 store out (rrin_net_yuv16_fwd).  Other depths raise: the Q14
+        sums leave int32.  The rest is :meth:`forward_yuv`'s, the scene gate on the frames' samples
+        ``min(word >> shift, maxval)``, luma and chroma, with ``scene_threshold`` in [0, maxval]; a
+        kept raw Flow is only reused by a call of the same layout, depth, alignment and matrix."""
+        from . import yuv
+        self._need_records("forward_yuv16")
+        if layout not in yuv.LAYOUTS:
+            raise ValueError(f"layout must be one of {yuv.LAYOUTS}, got {layout!r}")
+        depth = yuv.check_depth16(depth)
+        shift = 16 - depth if msb else 0
+        k = yuv.as_coef(coef, depth)
+        f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_yuv16", rgb=False, dtype=torch.uint16)
+        n = f0.shape[0]
+        h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
+        self._poll_range()
+        tcoef = t_coefficients(t, n).to(self.device, non_blocking=True)
+        bounds = self._bounds(n, streams, split)
+        g = self._scene_gate(f"yuv16:{depth}:{shift}", n, h0 // 2, w0, t, bounds, reuse_flow, scene_threshold, gate,
+                             (1 << depth) - 1)
+        out = torch.empty((n, 3 * h0 // 2, w0), dtype=torch.uint16, device=self.device)
+        tag = f"yuv16:{depth}:{shift}:{layout}:" + ",".join(str(v) for v in k)
+        kc = _lib.YuvCoef(*k)
+        frame = out.stride(0)
+
+        def part(j, lo, hi, stream, p):
+            d = _lib.NetYuv16Desc()
+            self._fill_net(d.net, p, tcoef[lo:hi])
+            p0, p1, po = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), out[lo:hi].data_ptr()
+            d.f0 = self._yuv16_stack(p0, s0, h0, w0, layout, depth, shift)
+            d.f1 = self._yuv16_stack(p1, s0, h0, w0, layout, depth, shift)
+            d.out = self._yuv16_stack(po, frame, h0, w0, layout, depth, shift)
+            d.coef, d.h0, d.w0 = kc, h0, w0
+            self._launch(self.lib.rrin_net_yuv16_fwd, "rrin_net_yuv16_fwd", d, d.net, p, tag, reuse_flow, stream)
+            if g is not None:
+                self._enqueue_gate(g, p0, p1, s0, lo, hi, h0 // 2, w0, po, stream, wide=(depth, shift))
+
+        self._run_parts(h, w, bounds, part)
+        return out
+
+    def pair_stats_yuv16(self, f0: torch.Tensor, f1: torch.Tensor, depth: int = 10, msb: bool = False) -> torch.Tensor:
+        """:meth:`pair_stats_yuv` for two uint16 4:2:0 stacks: the exact sum of absolute differences
+        of the samples ``min(word >> shift, maxval)``, luma and chroma (rrin_pair_sad_u16)."""
+        from . import yuv
+        depth = yuv.check_depth16(depth)
+        f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_yuv16", rgb=False, dtype=torch.uint16)
+        return self._pair_sad(f0, f1, s0, h0 // 2, w0, wide=(depth, 16 - depth if msb else 0))
 
     def unet_forward(self, x: torch.Tensor) -> torch.Tensor:
         """The single packed U-Net (engine built with one unit) on x [N,C,H,W]:

@@ -178,6 +178,62 @@ class Net(nn.Module):
         ``floor(threshold * H0*W0*3/2)``."""
         return self.engine().pair_stats_yuv(f0, f1)
 
+    def forward_u16(self, f0, f1, t=0.5, depth=10, scene_threshold=None, gate=None):
+        """``forward_u8`` on 16-bit frames: uint16 ``[N,H0,W0,3]`` RGB samples of ``depth`` 9..16 (in
+        the words' low bits; a word above ``maxval = 2**depth - 1`` is read as maxval) in and out on
+        the device; bit for bit ``convert.frames_u16_to_float`` -> ``forward`` ->
+        ``convert.frames_float_to_u16`` (``RRINEngine.forward_u16``).  Inference-only; not for
+        ``precision='fp32_planar'``.  The scene gate is ``forward_u8``'s with ``scene_threshold`` a
+        mean absolute sample difference in [0, maxval]."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("rrin_amd.Net.forward_u16 is inference-only: use torch.no_grad()")
+        return self.engine().forward_u16(f0, f1, t, depth=depth, streams=self.streams,
+                                         scene_threshold=scene_threshold, gate=gate)
+
+    def interpolate_u16(self, f0, f1, ts, depth=10, scene_threshold=None, gate=None):
+        """``[forward_u16(f0, f1, t, depth) for t in ts]`` with the Flow U-Net (and the pairs' sums
+        of absolute differences) computed once, as :meth:`interpolate_u8`."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("rrin_amd.Net.interpolate_u16 is inference-only: use torch.no_grad()")
+        eng = self.engine()
+        return [eng.forward_u16(f0, f1, t, depth=depth, reuse_flow=(k > 0), streams=self.streams,
+                                scene_threshold=scene_threshold, gate=gate)
+                for k, t in enumerate(ts)]
+
+    def pair_stats_u16(self, f0, f1, depth=10):
+        """int64 device tensor ``[N]``: the exact sum of absolute sample differences (samples
+        ``min(word, maxval)``) of every pair of two uint16 ``[N,H0,W0,3]`` stacks."""
+        return self.engine().pair_stats_u16(f0, f1, depth=depth)
+
+    def forward_yuv16(self, f0, f1, t=0.5, layout="nv12", depth=10, msb=False, coef=None, scene_threshold=None,
+                      gate=None):
+        """``forward_yuv`` on 10- or 12-bit 4:2:0 frames in 16-bit words: uint16 ``[N, 3*H0//2, W0]`` in
+        and out on the device, ``msb=False`` for samples in the low bits (yuv420p10le, Y4M C420p10),
+        ``True`` for the high bits (P010 / P012).  By definition, and bit for bit,
+        ``yuv.rgb16_to_yuv420(forward_u16(yuv.yuv420_to_rgb16(f0), yuv.yuv420_to_rgb16(f1), t,
+        depth))`` (``RRINEngine.forward_yuv16``); ``coef`` None is BT.709 limited range at this
+        depth.  Other depths raise.  Inference-only; not for ``precision='fp32_planar'``."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("rrin_amd.Net.forward_yuv16 is inference-only: use torch.no_grad()")
+        return self.engine().forward_yuv16(f0, f1, t, layout=layout, depth=depth, msb=msb, coef=coef,
+                                           streams=self.streams, scene_threshold=scene_threshold, gate=gate)
+
+    def interpolate_yuv16(self, f0, f1, ts, layout="nv12", depth=10, msb=False, coef=None, scene_threshold=None,
+                          gate=None):
+        """``[forward_yuv16(f0, f1, t, ...) for t in ts]`` with the Flow U-Net (and the pairs' sums of
+        absolute differences) computed once, as :meth:`interpolate_yuv`."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("rrin_amd.Net.interpolate_yuv16 is inference-only: use torch.no_grad()")
+        eng = self.engine()
+        return [eng.forward_yuv16(f0, f1, t, layout=layout, depth=depth, msb=msb, coef=coef, reuse_flow=(k > 0),
+                                  streams=self.streams, scene_threshold=scene_threshold, gate=gate)
+                for k, t in enumerate(ts)]
+
+    def pair_stats_yuv16(self, f0, f1, depth=10, msb=False):
+        """int64 device tensor ``[N]``: the exact sum of absolute differences of the samples
+        ``min(word >> shift, maxval)``, luma and chroma, of every pair of two uint16 4:2:0 stacks."""
+        return self.engine().pair_stats_yuv16(f0, f1, depth=depth, msb=msb)
+
     @property
     def last_gate(self):
         """The int32 device codes ``[N]`` of the last gated ``forward_u8`` (0: interpolated, 1:

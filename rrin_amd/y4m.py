@@ -1,4 +1,6 @@
-"""YUV4MPEG2 (Y4M) streams of 8-bit 4:2:0 frames: what ``ffmpeg -f yuv4mpegpipe`` writes and reads.
+"""YUV4MPEG2 (Y4M) streams of 8-bit 4:2:0 frames: what ``ffmpeg -f yuv4mpegpipe`` writes and reads
+(and, for callers that ask with ``depths=``, the 10- and 12-bit ``C420p10`` / ``C420p12`` streams of
+``-pix_fmt yuv420p10le`` / ``yuv420p12le``).
 
 A stream is one header line ``YUV4MPEG2 W<w> H<h> F<num>:<den> [I..] [A..] [C..] [X..]`` and, per
 frame, a line ``FRAME[ params]`` followed by the planes Y, U, V (``w*h*3/2`` bytes for 4:2:0:
@@ -12,6 +14,8 @@ import numpy as np
 MAGIC = b"YUV4MPEG2"
 # colour-space tags that are all the 8-bit I420 byte layout (they differ in chroma siting only)
 C420 = ("420", "420jpeg", "420mpeg2", "420paldv")
+# tags of 4:2:0 in 16-bit little-endian words, the sample in the low bits: tag -> bit depth
+C420_DEEP = {"420p10": 10, "420p12": 12}
 _MAX_LINE = 4096
 
 
@@ -50,10 +54,16 @@ class Reader:
     ``height*width*3/2`` bytes (Y, then U, then V).  ``width``, ``height``, ``fps_num``,
     ``fps_den`` and ``colorspace`` come from the header.  Anything but progressive 8-bit 4:2:0
     (``C420``, ``C420jpeg``, ``C420mpeg2``, ``C420paldv`` or no ``C`` tag) raises ValueError
-    naming the tag; a frame cut short raises ValueError."""
+    naming the tag; a frame cut short raises ValueError.
 
-    def __init__(self, fileobj):
+    ``depths`` lists the bit depths the caller takes.  With the default ``(8,)`` nothing else is
+    read.  With 10 and / or 12 in it ``C420p10`` / ``C420p12`` streams are read too: a frame is then
+    a uint16 array of ``height*width*3/2`` little-endian samples (``frame_bytes`` is twice that
+    count) and ``bit_depth`` says which; an 8-bit stream still yields uint8."""
+
+    def __init__(self, fileobj, depths=(8,)):
         self.f = fileobj
+        self.bit_depth = 8
         line = _read_line(fileobj)
         tags = line.split(b" ")
         if tags[0] != MAGIC:
@@ -77,15 +87,18 @@ class Reader:
                 if val not in ("p", "?"):
                     raise ValueError(f"Y4M: interlaced streams are not supported (tag {tag!r})")
             elif key == "C":
-                if val not in C420:
-                    raise ValueError(f"Y4M: only 8-bit 4:2:0 is supported (tag {tag!r})")
+                if val in C420_DEEP and C420_DEEP[val] in depths:
+                    self.bit_depth = C420_DEEP[val]
+                elif val not in C420 or 8 not in depths:
+                    raise ValueError(f"Y4M: only 8-bit 4:2:0 is supported (tag {tag!r})" if tuple(depths) == (8,)
+                                     else f"Y4M: only 4:2:0 of {tuple(depths)} bits is supported (tag {tag!r})")
                 self.colorspace = val
             # A (pixel aspect) and X (comments) do not change the bytes
         if not self.width or not self.height or self.width < 1 or self.height < 1:
             raise ValueError("Y4M: the header lacks W or H")
         if self.width % 2 or self.height % 2:
             raise ValueError(f"Y4M: 4:2:0 frames need even W and H, got {self.width}x{self.height}")
-        self.frame_bytes = self.width * self.height * 3 // 2
+        self.frame_bytes = self.width * self.height * 3 // 2 * (2 if self.bit_depth > 8 else 1)
 
     def __iter__(self):
         return self
@@ -99,24 +112,34 @@ class Reader:
         data = _read_exact(self.f, self.frame_bytes)
         if data.size != self.frame_bytes:
             raise ValueError(f"Y4M: truncated frame ({data.size} of {self.frame_bytes} bytes)")
-        return data
+        return data.view("<u2").astype(np.uint16, copy=False) if self.bit_depth > 8 else data
 
 
 class Writer:
     """Writes a progressive 8-bit 4:2:0 Y4M stream to a file object open for binary writing: the
-    header on construction, then :meth:`write` per frame (``height*width*3/2`` bytes: Y, U, V)."""
+    header on construction, then :meth:`write` per frame (``height*width*3/2`` bytes: Y, U, V).
+    With 10 and / or 12 in ``depths`` the colour spaces ``420p10`` / ``420p12`` are written too:
+    a frame is then ``height*width*3/2`` uint16 samples, stored little-endian."""
 
-    def __init__(self, fileobj, w: int, h: int, fps_num: int, fps_den: int = 1, colorspace: str = "420"):
+    def __init__(self, fileobj, w: int, h: int, fps_num: int, fps_den: int = 1, colorspace: str = "420",
+                 depths=(8,)):
         if w < 2 or h < 2 or w % 2 or h % 2:
             raise ValueError(f"Y4M: 4:2:0 frames need even W and H, got {w}x{h}")
-        if colorspace not in C420:
-            raise ValueError(f"Y4M: only 8-bit 4:2:0 is supported (C{colorspace})")
+        self.bit_depth = 8
+        if colorspace in C420_DEEP and C420_DEEP[colorspace] in depths:
+            self.bit_depth = C420_DEEP[colorspace]
+        elif colorspace not in C420 or 8 not in depths:
+            raise ValueError(f"Y4M: only 8-bit 4:2:0 is supported (C{colorspace})" if tuple(depths) == (8,)
+                             else f"Y4M: only 4:2:0 of {tuple(depths)} bits is supported (C{colorspace})")
         self.f, self.width, self.height = fileobj, int(w), int(h)
-        self.frame_bytes = w * h * 3 // 2
+        self.frame_bytes = w * h * 3 // 2 * (2 if self.bit_depth > 8 else 1)
         fileobj.write(b"%s W%d H%d F%d:%d Ip C%s\n" % (MAGIC, w, h, fps_num, fps_den, colorspace.encode()))
 
     def write(self, frame) -> None:
-        data = np.ascontiguousarray(frame, dtype=np.uint8).reshape(-1)
+        if self.bit_depth > 8:
+            data = np.ascontiguousarray(frame, dtype="<u2").reshape(-1).view(np.uint8)
+        else:
+            data = np.ascontiguousarray(frame, dtype=np.uint8).reshape(-1)
         if data.size != self.frame_bytes:
             raise ValueError(f"Y4M: a frame is {self.frame_bytes} bytes, got {data.size}")
         self.f.write(b"FRAME\n")

@@ -34,16 +34,24 @@ gu, gv, bu take YUV to RGB; yr .. vb take RGB to YUV."""
 _KR_KB = {"bt709": (0.2126, 0.0722), "bt601": (0.299, 0.114)}
 
 
-def coefficients(standard: str = "bt709", full_range: bool = False) -> Coef:
+def coefficients(standard: str = "bt709", full_range: bool = False, depth: int = 8) -> Coef:
     """The coefficients of a standard, ``round(x * 2**14)`` of the matrix its Kr / Kb give, for
     limited range (Y 16..235, chroma 16..240: the default) or full range.  ``yg``, ``ug`` and
     ``vg`` are remainders, so that grey maps to U = V = 128 exactly.  ``rrin_yuv_coef_std`` holds
-    the same numbers."""
+    the same numbers.
+
+    ``depth`` d (8..16; the 16-bit YUV path itself takes 10 and 12) scales the limited range to
+    d-bit code values: ``y0 = 16 << (d-8)``, luma by ``219 * 2**(d-8) / maxval`` and chroma by
+    ``224 * 2**(d-8) / maxval`` with ``maxval = 2**d - 1``; grey then maps to U = V = ``1 << (d-1)``.
+    Full range has no scale at any depth.  ``rrin_yuv_coef_std16`` holds the same numbers."""
     if standard not in _KR_KB:
         raise ValueError(f"standard must be one of {sorted(_KR_KB)}, got {standard!r}")
+    if not 8 <= int(depth) <= 16:
+        raise ValueError(f"depth must be 8..16, got {depth!r}")
     kr, kb = _KR_KB[standard]
     kg = 1.0 - kr - kb
-    ys, cs = (1.0, 1.0) if full_range else (219.0 / 255.0, 224.0 / 255.0)
+    up, maxval = float(1 << (depth - 8)), float((1 << depth) - 1)
+    ys, cs = (1.0, 1.0) if full_range else (219.0 * up / maxval, 224.0 * up / maxval)
 
     def q(x):
         return int(round(x * 16384.0))
@@ -51,20 +59,56 @@ def coefficients(standard: str = "bt709", full_range: bool = False) -> Coef:
     yr, yb = q(kr * ys), q(kb * ys)
     ur, ub = q(-kr / (2 * (1 - kb)) * cs), q(0.5 * cs)
     vr, vb = q(0.5 * cs), q(-kb / (2 * (1 - kr)) * cs)
-    return Coef(y0=0 if full_range else 16, ay=q(1.0 / ys),
+    return Coef(y0=0 if full_range else 16 << (depth - 8), ay=q(1.0 / ys),
                 rv=q(2 * (1 - kr) / cs), gu=q(-2 * (1 - kb) * kb / kg / cs), gv=q(-2 * (1 - kr) * kr / kg / cs),
                 bu=q(2 * (1 - kb) / cs),
                 yr=yr, yg=q(ys) - yr - yb, yb=yb, ur=ur, ug=-(ur + ub), ub=ub, vr=vr, vg=-(vr + vb), vb=vb)
 
 
-def as_coef(coef) -> Coef:
-    """``None`` (bt709 limited), a :class:`Coef` or any 15 ints -> a validated :class:`Coef`."""
+def as_coef(coef, depth: int = 8) -> Coef:
+    """``None`` (bt709 limited), a :class:`Coef` or any 15 ints -> a validated :class:`Coef`.
+
+    With ``depth`` above 8 (the 16-bit path) ``None`` is bt709 limited at that depth, ``y0`` may
+    reach ``maxval`` and the nine RGB -> YUV coefficients are bounded by 2**15 instead of 2**16:
+    the chroma sum of a 2x2 block of 12-bit samples, ``3 * (2**15 - 1) * 4 * 4095 + 2**15``, then
+    stays below 2**31 (with 2**16 it would not)."""
+    if depth == 8:
+        if coef is None:
+            return coefficients()
+        c = Coef(*(int(v) for v in coef))
+        if not 0 <= c.y0 <= 255 or any(abs(v) >= 65536 for v in c[1:]):
+            raise ValueError("yuv coefficients: 0 <= y0 <= 255 and |coefficient| < 2**16")
+        return c
     if coef is None:
-        return coefficients()
+        return coefficients(depth=depth)
     c = Coef(*(int(v) for v in coef))
-    if not 0 <= c.y0 <= 255 or any(abs(v) >= 65536 for v in c[1:]):
-        raise ValueError("yuv coefficients: 0 <= y0 <= 255 and |coefficient| < 2**16")
+    if (not 0 <= c.y0 <= (1 << depth) - 1 or any(abs(v) >= IN_BOUND for v in c[1:6])
+            or any(abs(v) >= OUT_BOUND16 for v in c[6:])):
+        raise ValueError(f"yuv coefficients at depth {depth}: 0 <= y0 <= {(1 << depth) - 1}, |ay .. bu| < 2**16 "
+                         "and |yr .. vb| < 2**15")
     return c
+
+
+# bounds of the coefficients (exclusive): YUV -> RGB at any depth; RGB -> YUV on the 16-bit path
+IN_BOUND, OUT_BOUND16 = 1 << 16, 1 << 15
+DEPTHS16 = (10, 12)
+
+
+def check_depth16(depth) -> int:
+    """The depth of a 16-bit 4:2:0 call: 10 or 12, ValueError otherwise."""
+    if isinstance(depth, bool) or not isinstance(depth, int) or depth not in DEPTHS16:
+        raise ValueError(f"16-bit 4:2:0 frames are 10 or 12 bits deep, got {depth!r}")
+    return int(depth)
+
+
+def words_to_int(x: torch.Tensor) -> torch.Tensor:
+    """uint16 -> int32 values 0..65535."""
+    return x.view(torch.int16).to(torch.int32) & 0xFFFF
+
+
+def int_to_words(x: torch.Tensor) -> torch.Tensor:
+    """Integers 0..65535 -> uint16."""
+    return x.to(torch.int16).view(torch.uint16)
 
 
 def frame_size(frames: torch.Tensor):
@@ -146,3 +190,75 @@ def rgb_to_yuv420(rgb: torch.Tensor, layout: str = "nv12", coef=None) -> torch.T
     u = (128 + ((k.ur * rs + k.ug * gs + k.ub * bs + 32768) >> 16)).clamp_(0, 255)
     v = (128 + ((k.vr * rs + k.vg * gs + k.vb * bs + 32768) >> 16)).clamp_(0, 255)
     return join_planes(y.to(torch.uint8), u.to(torch.uint8), v.to(torch.uint8), layout)
+
+
+# ---- 10- and 12-bit frames in 16-bit words ------------------------------------------------
+# The 16-bit YUV path is defined as
+#
+#     forward_yuv16(f0, f1, t) == rgb16_to_yuv420(forward_u16(yuv420_to_rgb16(f0), yuv420_to_rgb16(f1), t, depth))
+#
+# with the conversions below: the 8-bit formulas with 128 replaced by 1 << (depth-1) and clip255 by
+# a clip to maxval = 2**depth - 1.  Depths 10 and 12 only: with |coefficient| < 2**16 the sums of the
+# way in reach 3 * 2**16 * 2**depth, inside int32 up to 14 bits and not at 16, and the chroma sum
+# of the way out (four samples, see as_coef) is the tighter bound.  Frames are uint16
+# [N, 3*H0//2, W0] in the 8-bit layouts; ``msb=False`` takes the sample from the word's low bits
+# (yuv420p10le, Y4M C420p10), ``msb=True`` from its high bits (``word >> (16 - depth)`` in,
+# ``sample << (16 - depth)`` out: P010 / P012).  A sample above maxval is read as maxval.
+def samples16(words: torch.Tensor, depth: int, msb: bool) -> torch.Tensor:
+    """The int32 samples of uint16 words: ``min(word >> shift, maxval)``."""
+    v = words_to_int(words)
+    if msb:
+        v = v >> (16 - depth)
+    return v.clamp_(max=(1 << depth) - 1)
+
+
+def yuv420_to_rgb16(frames: torch.Tensor, layout: str = "nv12", coef=None, depth: int = 10,
+                    msb: bool = False) -> torch.Tensor:
+    """uint16 ``[N, 3*H0//2, W0]`` of ``depth`` 10 or 12 -> uint16 RGB ``[N,H0,W0,3]`` samples of that
+    depth (low bits), by :func:`yuv420_to_rgb`'s formulas with d = U - half, e = V - half and a
+    clip to maxval.  ``coef`` None: BT.709 limited range at this depth."""
+    return _to_rgb_words(frames, layout, coef, check_depth16(depth), msb)
+
+
+def _to_rgb_words(frames, layout, coef, depth, msb):
+    """yuv420_to_rgb16 at any depth 8..14 (depth 8 is yuv420_to_rgb on the same values)."""
+    if frames.dtype != torch.uint16:
+        raise TypeError("16-bit 4:2:0 frames are uint16")
+    k = as_coef(coef, depth)
+    half, maxval = 1 << (depth - 1), (1 << depth) - 1
+    y, u, v = split_planes(frames, layout)
+    c = (samples16(y, depth, msb) - k.y0) * k.ay + 8192
+    d = (samples16(u, depth, msb) - half).repeat_interleave(2, 1).repeat_interleave(2, 2)
+    e = (samples16(v, depth, msb) - half).repeat_interleave(2, 1).repeat_interleave(2, 2)
+    rgb = torch.stack((c + k.rv * e, c + k.gu * d + k.gv * e, c + k.bu * d), dim=3)
+    return int_to_words((rgb >> 14).clamp_(0, maxval))
+
+
+def rgb16_to_yuv420(rgb: torch.Tensor, layout: str = "nv12", coef=None, depth: int = 10,
+                    msb: bool = False) -> torch.Tensor:
+    """uint16 RGB ``[N,H0,W0,3]`` samples of ``depth`` 10 or 12 (above maxval: read as maxval) ->
+    uint16 ``[N, 3*H0//2, W0]``, by :func:`rgb_to_yuv420`'s formulas with ``half`` for 128 and a clip
+    to maxval; ``msb`` shifts the samples into the words' high bits."""
+    return _to_yuv_words(rgb, layout, coef, check_depth16(depth), msb)
+
+
+def _to_yuv_words(rgb, layout, coef, depth, msb):
+    """rgb16_to_yuv420 at any depth 8..12 (depth 8 is rgb_to_yuv420 on the same values)."""
+    if rgb.dtype != torch.uint16:
+        raise TypeError("16-bit RGB frames are uint16")
+    if rgb.dim() != 4 or rgb.shape[3] != 3:
+        raise ValueError(f"expected [N,H0,W0,3] RGB frames, got {tuple(rgb.shape)}")
+    n, h0, w0, _ = rgb.shape
+    if h0 < 2 or w0 < 2 or h0 % 2 or w0 % 2:
+        raise ValueError(f"4:2:0 needs even H0 and W0, got {h0}x{w0}")
+    k = as_coef(coef, depth)
+    half, maxval = 1 << (depth - 1), (1 << depth) - 1
+    p = samples16(rgb, depth, False)
+    r, g, b = p[..., 0], p[..., 1], p[..., 2]
+    y = (k.y0 + ((k.yr * r + k.yg * g + k.yb * b + 8192) >> 14)).clamp_(0, maxval)
+    s = p.reshape(n, h0 // 2, 2, w0 // 2, 2, 3).sum(dim=(2, 4), dtype=torch.int32)
+    rs, gs, bs = s[..., 0], s[..., 1], s[..., 2]
+    u = (half + ((k.ur * rs + k.ug * gs + k.ub * bs + 32768) >> 16)).clamp_(0, maxval)
+    v = (half + ((k.vr * rs + k.vg * gs + k.vb * bs + 32768) >> 16)).clamp_(0, maxval)
+    sh = 16 - depth if msb else 0
+    return join_planes(int_to_words(y << sh), int_to_words(u << sh), int_to_words(v << sh), layout)
