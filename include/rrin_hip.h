@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define RRIN_ABI_VERSION 23
+#define RRIN_ABI_VERSION 24
 
 #define RRIN_OK 0
 #define RRIN_E_SHAPE (-1)     /* H or W not a multiple of 16, or N < 1          */
@@ -398,12 +398,20 @@ int rrin_pack_g16_u8_h8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride
 /* ---- 8-bit YUV 4:2:0 frames (ABI 22) -------------------------------------------------------
  * One stack of 4:2:0 frames: a luma plane of h0 x w0 bytes and two chroma planes of h0/2 x w0/2
  * samples, one sample per 2x2 block of pixels.  NV12 (one interleaved UV plane): v == u + 1,
- * c_step 2; I420 (planar): c_step 1.  h0 and w0 are even. */
+ * c_step 2; I420 (planar): c_step 1.  h0 and w0 are even.
+ *
+ * ABI 24: chroma (the former pad_ word, which every caller zero-filled: 4:2:0) picks the chroma
+ * block.  RRIN_CHROMA_422: one U and one V sample per 2x1 block (two pixels wide, one row tall),
+ * chroma planes of h0 x w0/2 samples, w0 even and >= 2, any h0 >= 1 (NV16: c_step 2; I422: 1).
+ * RRIN_CHROMA_444: one per pixel, planes of h0 x w0, any h0, w0 >= 1 (c_step 1; a semi-planar
+ * 4:4:4 with c_step 2 is legal here).  Another value: RRIN_E_ARG.  c_pitch >= (chroma columns) *
+ * c_step.  The stacks of one call share chroma (RRIN_E_ARG otherwise). */
+enum rrin_chroma { RRIN_CHROMA_420 = 0, RRIN_CHROMA_422 = 1, RRIN_CHROMA_444 = 2 };
 typedef struct rrin_yuv420 {
   const uint8_t *y, *u, *v;    /* frame 0; NV12: v == u + 1 */
   int64_t img_stride;          /* bytes between frames, the same for all three pointers */
   int32_t y_pitch, c_pitch;    /* bytes between rows (>= w0, >= (w0/2)*c_step) */
-  int32_t c_step, pad_;        /* bytes between chroma samples of a row: 2 NV12, 1 I420 */
+  int32_t c_step, chroma;      /* bytes between chroma samples of a row: 2 NV12, 1 I420; rrin_chroma */
 } rrin_yuv420;
 
 /* The colour conversion around the 8-bit frame path, pure int32 arithmetic on Q14 coefficients
@@ -417,6 +425,8 @@ typedef struct rrin_yuv420 {
  *        per block, Rs / Gs / Bs the sums of its four pixels' bytes:
  *     U = clip255(128 + ((ur*Rs + ug*Gs + ub*Bs + 32768) >> 16))
  *     V = clip255(128 + ((vr*Rs + vg*Gs + vb*Bs + 32768) >> 16))
+ *        ABI 24, a block of P pixels (4:2:0: 4, 4:2:2: 2, 4:4:4: 1) with sums Rs / Gs / Bs:
+ *     U = clip255(128 + ((ur*Rs + ug*Gs + ub*Bs + 8192*P) >> (14 + log2 P))), V likewise
  * Any 15 values with |coefficient| < 2^16 and 0 <= y0 <= 255 may be passed (RRIN_E_ARG
  * otherwise: the sums then fit int32). */
 typedef struct rrin_yuv_coef {
@@ -433,7 +443,8 @@ int rrin_yuv_coef_std(int32_t standard, int32_t full_range, rrin_yuv_coef* c);
 /* rrin_pack_g16_u8_h8 from two stacks of 4:2:0 frames: the records are bitwise those it writes
  * from the frames converted to RGB bytes as above.  Padding is its rule applied to source
  * coordinates: padded pixel (y, x) reads source pixel (sy, sx) = (max(y - (h - h0), 0),
- * min(x, w0 - 1)), its luma and the chroma of block (sy/2, sx/2).  A frame may start at any
+ * min(x, w0 - 1)), its luma and the chroma of block (sy/2, sx/2) -- (sy, sx/2) at 4:2:2, (sy, sx)
+ * at 4:4:4; f0 and f1 share chroma (RRIN_E_ARG otherwise).  A frame may start at any
  * byte.  Null planes or coef, c_step not 1 or 2, a coefficient out of range: RRIN_E_ARG; odd or
  * < 2 h0 / w0, a pitch smaller than its row, frames of a stack that overlap (n > 1), a g16 that
  * is not round_up(h0,16) x round_up(w0,16): RRIN_E_SHAPE.  Validated before any HIP call. */
@@ -462,12 +473,13 @@ typedef struct rrin_yuv420_16 {
   int64_t img_stride;          /* samples between frames, the same for all three pointers */
   int32_t y_pitch, c_pitch;    /* samples between rows */
   int32_t c_step;              /* samples between chroma samples of a row: 2 or 1 */
-  int32_t depth, shift, pad_;
+  int32_t depth, shift, chroma; /* chroma: rrin_chroma (ABI 24), as in rrin_yuv420 */
 } rrin_yuv420_16;
 /* The conversion is rrin_yuv_coef's with 128 replaced by 2^(depth-1) and clip255 by a clip to
  * [0, maxval]; the roundings stay.  Coefficients on this path: 0 <= y0 <= maxval, |ay .. bu| < 2^16,
  * |yr .. vb| < 2^15 (RRIN_E_ARG otherwise); every sum then fits int32 at depth 12, the largest
- * being a block's chroma, 3 * (2^15 - 1) * 4 * 4095 + 2^15 < 2^31.  rrin_yuv_coef_std16 is
+ * being a 2x2 block's chroma, 3 * (2^15 - 1) * 4 * 4095 + 2^15 < 2^31 (the blocks of 4:2:2 and
+ * 4:4:4 sum fewer samples: further inside).  rrin_yuv_coef_std16 is
  * rrin_yuv_coef_std for a depth of 8..16: y0 = 16 << (depth - 8), luma scaled by
  * 219 * 2^(depth-8) / maxval and chroma by 224 * 2^(depth-8) / maxval (limited range); depth 8
  * gives rrin_yuv_coef_std's numbers.  Host only. */
@@ -507,7 +519,9 @@ typedef struct rrin_head_h8_desc {
      yuv_coef (see rrin_yuv_coef) into the planes of out_yuv, which are written through in spite
      of the const of the struct's pointers.  h0, w0 and top must be even (RRIN_E_SHAPE).  Y is
      written for the crop's pixels and U / V once per 2x2 block; pitch bytes beyond w0 and
-     anything outside the crop are never written. */
+     anything outside the crop are never written.  ABI 24, by out_yuv.chroma: at 4:2:2 only w0
+     must be even (h0 and top may be odd) and U / V are written once per 2x1 block; at 4:4:4 no
+     size need be even and U / V are written per pixel. */
   rrin_yuv420 out_yuv;
   rrin_yuv_coef yuv_coef;
   int32_t pad3_;
@@ -675,7 +689,10 @@ int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream);
  * rrin_net_u8_fwd (same schedule, skip_flow, range guard -- a poisoned pixel is RGB (0,0,0)
  * before the conversion -- and record precisions only).  h0 and w0 even.  Null planes, a c_step
  * not 1 or 2: RRIN_E_ARG; odd sizes, pitches smaller than a row, overlapping frames:
- * RRIN_E_SHAPE.  Arguments are validated before any HIP call. */
+ * RRIN_E_SHAPE.  Arguments are validated before any HIP call.  ABI 24: f0, f1 and out share
+ * chroma (RRIN_E_ARG otherwise); at RRIN_CHROMA_422 / 444 the sizes follow rrin_yuv420's rules
+ * and the definition reads rgb_to_yuv(rrin_net_u8_fwd(yuv_to_rgb(f0), yuv_to_rgb(f1))) with the
+ * block of that format. */
 typedef struct rrin_net_yuv_desc {
   rrin_net_desc net;
   rrin_yuv420 f0, f1;   /* n frames each; may be two views of one [n+1] stack */
@@ -702,7 +719,7 @@ int rrin_net_u16_fwd(const rrin_net_u16_desc* d, void* stream);
 
 /* ABI 23: rrin_net_yuv_fwd on 16-bit 4:2:0 frames of depth 10 or 12: by definition
  * rgb16_to_yuv420(rrin_net_u16_fwd(yuv420_to_rgb16(f0), yuv420_to_rgb16(f1))) at that depth.  f0,
- * f1 and out share depth and shift (RRIN_E_ARG otherwise); the checks of rrin_net_yuv_fwd apply,
+ * f1 and out share depth, shift and chroma (RRIN_E_ARG otherwise); the checks of rrin_net_yuv_fwd apply,
  * with the coefficient bounds of rrin_yuv420_16. */
 typedef struct rrin_net_yuv16_desc {
   rrin_net_desc net;
@@ -744,6 +761,17 @@ int rrin_gate_frames_u8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride
  * rrin_gate_frames_u8 with w0 and img_stride doubled copies whole words. */
 int rrin_pair_sad_u16(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int32_t h0,
                       int32_t w0, int32_t depth, int32_t shift, uint64_t* sad, void* stream);
+/* ABI 24: the same three on frames that are blobs of any length (a dense 4:2:2 frame is
+ * 2*h0*w0 bytes, no multiple of 3 in general): len bytes (rrin_pair_sad_u16_len: samples) per
+ * frame in place of h0 and w0, img_stride >= len; len < 1: RRIN_E_SHAPE.  The same kernels, the
+ * same exactness and error rules: rrin_pair_sad_u8 / _u16 / rrin_gate_frames_u8 are these with
+ * len = h0*w0*3. */
+int rrin_pair_sad_u8_len(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int64_t len,
+                         uint64_t* sad, void* stream);
+int rrin_pair_sad_u16_len(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int64_t len,
+                          int32_t depth, int32_t shift, uint64_t* sad, void* stream);
+int rrin_gate_frames_u8_len(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int64_t len,
+                            const int32_t* gate, uint8_t* out, void* stream);
 
 /* ---- Training path (autograd): NCHW fp32 kernels ------------------------- */
 /* With autograd on (the reference trains through Net.forward, train.py:98, and

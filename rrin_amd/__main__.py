@@ -37,7 +37,8 @@ def build_parser():
                          "is a shot change and yields the nearer input frame instead of a blend; repeated "
                          "frames are passed through.  No value has been validated on real footage")
     cv.add_argument("--y4m_in", type=str, default=None, metavar="PATH|-",
-                    help="read an 8-bit 4:2:0 Y4M stream (\"-\": stdin, e.g. from ffmpeg -f yuv4mpegpipe) instead "
+                    help="read a Y4M stream (4:2:0, 4:2:2 or 4:4:4 of 8, 10 or 12 bits; \"-\": stdin, e.g. from "
+                         "ffmpeg -f yuv4mpegpipe) instead "
                          "of a video or folder; needs --y4m_out.  No PNG folder, no RGB frame: the frames go "
                          "through the network as YUV.  --fps is ignored (the rate comes from the stream)")
     cv.add_argument("--y4m_out", type=str, default=None, metavar="PATH|-",

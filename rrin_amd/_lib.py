@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librrin_hip.so")
 # A/B sessions only (tools/sessions/): another build of the same library, e.g. ab/librrin_hip_X.so
 if os.environ.get("RRIN_LIB_AB"):
@@ -92,9 +92,13 @@ class EdgeFixDesc(C.Structure):
 
 
 class Yuv420(C.Structure):
-    """rrin_yuv420: one stack of 8-bit 4:2:0 frames (NV12: v == u + 1, c_step 2; I420: c_step 1)."""
+    """rrin_yuv420: one stack of 8-bit YUV frames (NV12: v == u + 1, c_step 2; I420: c_step 1); ``chroma`` is
+    CHROMA_420 (zero, the default), CHROMA_422 or CHROMA_444."""
     _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("img_stride", C.c_int64),
-                ("y_pitch", C.c_int32), ("c_pitch", C.c_int32), ("c_step", C.c_int32), ("pad_", C.c_int32)]
+                ("y_pitch", C.c_int32), ("c_pitch", C.c_int32), ("c_step", C.c_int32), ("chroma", C.c_int32)]
+
+
+CHROMA_420, CHROMA_422, CHROMA_444 = 0, 1, 2   # enum rrin_chroma
 
 
 class YuvCoef(C.Structure):
@@ -111,7 +115,7 @@ class Yuv420x16(C.Structure):
     12; shift 0: the sample in the low bits, 16 - depth: in the high bits)."""
     _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("img_stride", C.c_int64),
                 ("y_pitch", C.c_int32), ("c_pitch", C.c_int32), ("c_step", C.c_int32), ("depth", C.c_int32),
-                ("shift", C.c_int32), ("pad_", C.c_int32)]
+                ("shift", C.c_int32), ("chroma", C.c_int32)]
 
 
 class HeadH8Desc(C.Structure):
@@ -270,6 +274,12 @@ SIGNATURES = {
     "rrin_gate_from_sad_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
     "rrin_gate_frames_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rrin_pair_sad_u8_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
+                                       C.c_void_p]),
+    "rrin_pair_sad_u16_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32,
+                                        C.c_int32, C.c_void_p, C.c_void_p]),
+    "rrin_gate_frames_u8_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
     "rrin_unet_conv_count": (C.c_int64, [C.c_int32]),
     "rrin_unet_fwd": (C.c_int, [C.POINTER(UNetDesc), C.c_void_p]),
     "rrin_prof_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),

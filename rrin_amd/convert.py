@@ -151,6 +151,16 @@ def scene_limit(threshold, h0: int, w0: int, maxval: int = 255) -> int:
     return math.floor(th * (h0 * w0 * 3))
 
 
+def scene_limit_len(threshold, samples: int, maxval: int = 255) -> int:
+    """:func:`scene_limit` for frames that are blobs of ``samples`` bytes (or 16-bit samples), as the
+    4:2:2 and 4:4:4 YUV paths gate them: ``floor(threshold * samples)``."""
+    th = float(threshold)
+    if not 0.0 <= th <= float(maxval):
+        what = "byte" if maxval == 255 else "sample"
+        raise ValueError(f"scene_threshold is a mean absolute {what} difference in [0, {maxval}], got {threshold!r}")
+    return math.floor(th * int(samples))
+
+
 def scene_cut_code(t) -> int:
     """Gate code of a cut pair at time t: 1 (the first frame) for t < 0.5, else 2 (the second)."""
     if isinstance(t, torch.Tensor):
@@ -445,7 +455,7 @@ def _retire(item, sf, dest, put, model=None):
 
 
 def interpolate_y4m(model, src, dst, sf, batch=4, scene_threshold=None, coef=None, log=print):
-    """Interpolate a Y4M stream (8-bit 4:2:0) into another: no image folder, no RGB frame anywhere.
+    """Interpolate a Y4M stream (8-bit 4:2:0; also 10 / 12 bits and 4:2:2 / 4:4:4, below) into another: no image folder, no RGB frame anywhere.
 
     ``src`` / ``dst`` are binary file objects (files or pipes: they are read and written
     sequentially, never sought) or paths.  Every step takes the next ``batch`` pairs: their
@@ -461,8 +471,13 @@ def interpolate_y4m(model, src, dst, sf, batch=4, scene_threshold=None, coef=Non
     A 10- or 12-bit stream (``C420p10`` / ``C420p12``: little-endian 16-bit words, the sample in the
     low bits) runs the same way on uint16 stacks through ``model.interpolate_yuv16`` at the
     stream's depth; ``coef`` None is then BT.709 limited range at that depth, ``scene_threshold``
-    a mean absolute sample difference in [0, maxval], and the output keeps the input's tag."""
-    from . import y4m
+    a mean absolute sample difference in [0, maxval], and the output keeps the input's tag.
+
+    A 4:2:2 or 4:4:4 stream (``C422``, ``C444`` and their ``p10`` / ``p12`` forms) runs through the same
+    two calls with ``layout="i422"`` / ``"i444"`` on ``[N, 2*H0, W0]`` / ``[N, 3*H0, W0]`` stacks; the
+    output keeps the tag, and ``scene_threshold`` is a mean over the frame's ``2*H0*W0`` / ``3*H0*W0``
+    samples."""
+    from . import y4m, yuv
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise RuntimeError("interpolate_y4m runs in a single process (a stream has one reader and one writer)")
     if sf < 1 or batch < 1:
@@ -475,12 +490,15 @@ def interpolate_y4m(model, src, dst, sf, batch=4, scene_threshold=None, coef=Non
         dst = open(dst, "wb")
         opened.append(dst)
     try:
-        rd = y4m.Reader(src, depths=(8, 10, 12))
+        rd = y4m.Reader(src, depths=(8, 10, 12), chroma=yuv.CHROMAS)
         w0, h0 = rd.width, rd.height
-        wr = y4m.Writer(dst, w0, h0, rd.fps_num * (sf + 1), rd.fps_den, rd.colorspace, depths=(8, 10, 12))
+        wr = y4m.Writer(dst, w0, h0, rd.fps_num * (sf + 1), rd.fps_den, rd.colorspace, depths=(8, 10, 12),
+                        chroma=yuv.CHROMAS)
+        layout = "i" + rd.chroma
         deep = rd.bit_depth > 8
         dtype = torch.uint16 if deep else torch.uint8
         device = next(model.parameters()).device
+        on_gpu = device.type == "cuda"   # a host model (tests) has nothing to pin for and no events
         ts = [i / (sf + 1) for i in range(1, sf + 1)]
         gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
         frames = iter(rd)
@@ -495,7 +513,8 @@ def interpolate_y4m(model, src, dst, sf, batch=4, scene_threshold=None, coef=Non
         def retire(item):
             nonlocal written, cuts, dups
             ev, host, inputs, codes = item
-            ev.synchronize()
+            if ev is not None:
+                ev.synchronize()
             if hasattr(model, "check_range"):
                 model.check_range(wait=False)  # fp16-stored precisions: raise instead of writing poisoned frames
             for p, nxt in enumerate(inputs):
@@ -517,27 +536,29 @@ def interpolate_y4m(model, src, dst, sf, batch=4, scene_threshold=None, coef=Non
             if nloc == 0:
                 break
             prev = group[-1]
-            stack = torch.empty((nloc + 1, 3 * h0 // 2, w0), dtype=dtype, pin_memory=True)
+            stack = torch.empty((nloc + 1, yuv.stack_rows(h0, layout), w0), dtype=dtype, pin_memory=on_gpu)
             for j, fr in enumerate(group):
                 stack[j].view(-1).copy_(torch.from_numpy(fr))
             stack = stack.to(device, non_blocking=True)
             with torch.no_grad():
                 if deep:
-                    outs = model.interpolate_yuv16(stack[:-1], stack[1:], ts, layout="i420", depth=rd.bit_depth,
+                    outs = model.interpolate_yuv16(stack[:-1], stack[1:], ts, layout=layout, depth=rd.bit_depth,
                                                    msb=False, coef=coef, **gate_kw)
                 else:
-                    outs = model.interpolate_yuv(stack[:-1], stack[1:], ts, layout="i420", coef=coef, **gate_kw)
+                    outs = model.interpolate_yuv(stack[:-1], stack[1:], ts, layout=layout, coef=coef, **gate_kw)
             host = []
             for o in outs:
-                hbuf = torch.empty(o.shape, dtype=o.dtype, pin_memory=True)
+                hbuf = torch.empty(o.shape, dtype=o.dtype, pin_memory=on_gpu)
                 hbuf.copy_(o, non_blocking=True)
                 host.append(hbuf)
             codes = None
             if gate_kw:
-                codes = torch.empty(nloc, dtype=torch.int32, pin_memory=True)
+                codes = torch.empty(nloc, dtype=torch.int32, pin_memory=on_gpu)
                 codes.copy_(model.last_gate, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
+            ev = None
+            if on_gpu:
+                ev = torch.cuda.Event()
+                ev.record()
             pending.append((ev, host, group[1:], codes))
             pairs += nloc
             while len(pending) > 1:  # retire the previous step while this one computes

@@ -305,13 +305,58 @@ __device__ inline void final_store_yuv16(const HeadH8Args& a, int img, int y, in
         (uint16_t)(rgb_sum_to_chroma16(a.yc.ur, a.yc.ug, a.yc.ub, mid, a.maxval, sum) << a.shift);
 }
 
+// FINAL with a 4:2:2 (CH = RRIN_CHROMA_422) or 4:4:4 output, 8-bit planes (WIDE false) or 16-bit
+// words (rules of final_store_yuv16).  4:2:2: a thread's pixel of row y + p and that of its xl ^ 1
+// lane are one 2x1 block (w0 is even), so each row has its own sums; the even lane writes U of
+// both its rows and the odd lane V.  4:4:4: a block is a pixel, no lane exchange.  As in
+// final_store_yuv every lane of the wave reaches the exchange before any return.  h0 and top may
+// be odd, so each of the two rows is guarded on its own: yo may be -1 with row yo + 1 in the crop.
+template <int CH, bool WIDE>
+__device__ inline void final_store_yuv4xx(const HeadH8Args& a, int img, int y, int x, const int (*rgb)[3]) {
+  constexpr int LOG2P = CH == RRIN_CHROMA_422 ? 1 : 0;
+  int sum[2][3];
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      sum[p][ch] = rgb[p][ch];
+      if constexpr (CH == RRIN_CHROMA_422) sum[p][ch] += __shfl_xor(sum[p][ch], 1);
+    }
+  if (x >= a.w0) return;
+  const int mid = (a.maxval + 1) >> 1;
+  const int64_t base = (int64_t)img * a.o_img;
+  const int cx = CH == RRIN_CHROMA_422 ? x >> 1 : x;
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int yo = y + p - a.top;
+    if (yo < 0 || yo >= a.h0) continue;
+    const int64_t l = base + (int64_t)yo * a.oy_pitch + x;
+    const int64_t c = base + (int64_t)yo * a.oc_pitch + (int64_t)cx * a.oc_step;
+    const bool put_u = CH == RRIN_CHROMA_444 || !(x & 1), put_v = CH == RRIN_CHROMA_444 || (x & 1);
+    if constexpr (WIDE) {
+      reinterpret_cast<uint16_t*>(a.oy)[l] = (uint16_t)(rgb_to_luma16(a.yc, a.maxval, rgb[p]) << a.shift);
+      if (put_u)
+        reinterpret_cast<uint16_t*>(a.ou)[c] =
+            (uint16_t)(rgb_block_to_chroma16<LOG2P>(a.yc.ur, a.yc.ug, a.yc.ub, mid, a.maxval, sum[p]) << a.shift);
+      if (put_v)
+        reinterpret_cast<uint16_t*>(a.ov)[c] =
+            (uint16_t)(rgb_block_to_chroma16<LOG2P>(a.yc.vr, a.yc.vg, a.yc.vb, mid, a.maxval, sum[p]) << a.shift);
+    } else {
+      a.oy[l] = (uint8_t)rgb_to_luma(a.yc, rgb[p]);
+      if (put_u) a.ou[c] = (uint8_t)rgb_block_to_chroma<LOG2P>(a.yc.ur, a.yc.ug, a.yc.ub, sum[p]);
+      if (put_v) a.ov[c] = (uint8_t)rgb_block_to_chroma<LOG2P>(a.yc.vr, a.yc.vg, a.yc.vb, sum[p]);
+    }
+  }
+}
+
 // The glue stores whole or partial records as the format does (F::Px): RecR32 updates g16 only in
 // whole 16-B records and reads first those it changes in part (FLOW records 1-2, REFINE 1-3,
 // MASK 1-2); RecH8 stores 2 / 4 / 16 B per plane and sets the range flag.
 // YUV (FINAL only): the 8-bit output as 4:2:0 planes (final_store_yuv) instead of interleaved RGB
 // WIDE (FINAL only): the frame output in 16-bit words (final_store_u16; with YUV final_store_yuv16).
-// Both are compile-time forms: the fp32 / 8-bit instantiations carry none of the 16-bit code.
-template <class F, int COUT, int MODE, bool YUV = false, bool WIDE = false>
+// CH (with YUV): the chroma block of the planes, rrin_chroma (4:2:2 / 4:4:4: final_store_yuv4xx).
+// All are compile-time forms: the fp32 / 8-bit / 4:2:0 instantiations carry none of the other code.
+template <class F, int COUT, int MODE, bool YUV = false, bool WIDE = false, int CH = RRIN_CHROMA_420>
 __global__ void __launch_bounds__(256) head_kernel(HeadH8Args a) {
   // tile 16 rows x 32 cols; thread = 2 vertically adjacent pixels (one float2v per output channel;
   // the library is built without packed fp32 ops, so the FMA is two v_fma_f32)
@@ -458,7 +503,9 @@ __global__ void __launch_bounds__(256) head_kernel(HeadH8Args a) {
       }
     }
   }
-  if constexpr (YUV && WIDE)
+  if constexpr (YUV && CH != RRIN_CHROMA_420)
+    final_store_yuv4xx<CH, WIDE>(a, img, y0 + r2, x0 + xl, rgb);
+  else if constexpr (YUV && WIDE)
     final_store_yuv16(a, img, y0 + r2, x0 + xl, rgb);
   else if constexpr (YUV)
     final_store_yuv(a, img, y0 + r2, x0 + xl, rgb);
@@ -559,10 +606,10 @@ extern "C" int rrin_h8_to_nchw(const rrin_h8* src, int32_t n, int32_t c, int32_t
   });
 }
 
-template <int COUT, int MODE, bool YUV = false, bool WIDE = false>
+template <int COUT, int MODE, bool YUV = false, bool WIDE = false, int CH = RRIN_CHROMA_420>
 static int head_launch(const HeadH8Args& a, int prec, int grid, hipStream_t st) {
   return with_format(prec, [&](auto f) {
-    hipLaunchKernelGGL((head_kernel<decltype(f), COUT, MODE, YUV, WIDE>), dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((head_kernel<decltype(f), COUT, MODE, YUV, WIDE, CH>), dim3(grid), dim3(256), 0, st, a);
     return hip_code(hipGetLastError());
   });
 }
@@ -592,12 +639,12 @@ static int head_prepare(const rrin_head_h8_desc* d, HeadH8Args& a, int& grid) {
   if (yuv) {
     if (int rc = yuv_coef_check(&d->yuv_coef)) return rc;
     if (int rc = yuv420_check(d->out_yuv, d->n, d->h0, d->w0)) return rc;
-    if (d->top & 1) return RRIN_E_SHAPE;
+    if (d->out_yuv.chroma == RRIN_CHROMA_420 && (d->top & 1)) return RRIN_E_SHAPE;
   }
   if (yuv16) {
     if (int rc = yuv420_16_check(d->out_yuv16, d->n, d->h0, d->w0)) return rc;
     if (int rc = yuv_coef_check16(&d->yuv_coef, d->out_yuv16.depth)) return rc;
-    if (d->top & 1) return RRIN_E_SHAPE;
+    if (d->out_yuv16.chroma == RRIN_CHROMA_420 && (d->top & 1)) return RRIN_E_SHAPE;
   }
   memset(&a, 0, sizeof(a));
   a.src = rec_view(d->src);
@@ -682,11 +729,20 @@ extern "C" int rrin_head_h8_fwd(const rrin_head_h8_desc* d, void* stream) {
       return d->cout == 2 ? head_launch<2, RRIN_HEAD_MASK>(a, d->prec, grid, st) : RRIN_E_ARG;
     case RRIN_HEAD_FINAL:
       if (d->cout != 3) return RRIN_E_ARG;
-      if (a.maxval)  // the 16-bit forms (head_prepare set maxval for them alone)
-        return a.oy ? head_launch<3, RRIN_HEAD_FINAL, true, true>(a, d->prec, grid, st)
-                    : head_launch<3, RRIN_HEAD_FINAL, false, true>(a, d->prec, grid, st);
-      return a.oy ? head_launch<3, RRIN_HEAD_FINAL, true>(a, d->prec, grid, st)
-                  : head_launch<3, RRIN_HEAD_FINAL>(a, d->prec, grid, st);
+      if (a.maxval) {  // the 16-bit forms (head_prepare set maxval for them alone)
+        if (!a.oy) return head_launch<3, RRIN_HEAD_FINAL, false, true>(a, d->prec, grid, st);
+        if (d->out_yuv16.chroma == RRIN_CHROMA_422)
+          return head_launch<3, RRIN_HEAD_FINAL, true, true, RRIN_CHROMA_422>(a, d->prec, grid, st);
+        if (d->out_yuv16.chroma == RRIN_CHROMA_444)
+          return head_launch<3, RRIN_HEAD_FINAL, true, true, RRIN_CHROMA_444>(a, d->prec, grid, st);
+        return head_launch<3, RRIN_HEAD_FINAL, true, true>(a, d->prec, grid, st);
+      }
+      if (!a.oy) return head_launch<3, RRIN_HEAD_FINAL>(a, d->prec, grid, st);
+      if (d->out_yuv.chroma == RRIN_CHROMA_422)
+        return head_launch<3, RRIN_HEAD_FINAL, true, false, RRIN_CHROMA_422>(a, d->prec, grid, st);
+      if (d->out_yuv.chroma == RRIN_CHROMA_444)
+        return head_launch<3, RRIN_HEAD_FINAL, true, false, RRIN_CHROMA_444>(a, d->prec, grid, st);
+      return head_launch<3, RRIN_HEAD_FINAL, true>(a, d->prec, grid, st);
   }
   return RRIN_E_ARG;
 }

@@ -826,8 +826,10 @@ extern "C" int rrin_net_yuv_fwd(const rrin_net_yuv_desc* d, void* stream) {
   // the record precisions only, as rrin_net_u8_fwd
   if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
   if (int rc = yuv_coef_check(&d->coef)) return rc;
-  for (const rrin_yuv420* s : {&d->f0, &d->f1, &d->out})
+  for (const rrin_yuv420* s : {&d->f0, &d->f1, &d->out}) {
     if (int rc = yuv420_check(*s, nd->n, d->h0, d->w0)) return rc;
+    if (s->chroma != d->f0.chroma) return RRIN_E_ARG;
+  }
   if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
   FrameIO f;
   f.yuv = d;
@@ -855,7 +857,7 @@ extern "C" int rrin_net_yuv16_fwd(const rrin_net_yuv16_desc* d, void* stream) {
   if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
   for (const rrin_yuv420_16* s : {&d->f0, &d->f1, &d->out}) {
     if (int rc = yuv420_16_check(*s, nd->n, d->h0, d->w0)) return rc;
-    if (s->depth != d->f0.depth || s->shift != d->f0.shift) return RRIN_E_ARG;
+    if (s->depth != d->f0.depth || s->shift != d->f0.shift || s->chroma != d->f0.chroma) return RRIN_E_ARG;
   }
   if (int rc = yuv_coef_check16(&d->coef, d->f0.depth)) return rc;
   if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;

@@ -5,6 +5,8 @@
 //   rrin_pair_sad_u16      the same over 16-bit words read as min(word >> shift, maxval) (ABI 23)
 //   rrin_gate_from_sad_u8  sad -> code per pair: 1 duplicate (sad == 0), cut_code above the limit
 //   rrin_gate_frames_u8    code 1 / 2: the output frame is overwritten with f0's / f1's bytes
+//   rrin_*_len             the three frame entry points on blobs of any length (ABI 24): the YUV
+//                          4:2:2 / 4:4:4 frames, whose size is no multiple of 3
 //
 // Frames are dense uint8 [h0][w0][3] at any byte address (f1 is usually f0 + one frame of one
 // stack: 17 x 33 x 3 = 1683 bytes), so the two operands of a pair have no common alignment.  Both
@@ -132,7 +134,7 @@ __global__ void __launch_bounds__(kThreads) pair_sad_u16_kernel(const uint16_t* 
   const int p = blockIdx.y;
   const uint16_t* a = f0 + (int64_t)p * img_stride;
   const uint16_t* b = f1 + (int64_t)p * img_stride;
-  const int64_t head = (int64_t)(((uintptr_t)a >> 1) & 1);  // len >= 3: the head word exists
+  const int64_t head = (int64_t)(((uintptr_t)a >> 1) & 1);  // len >= 1: the head word exists
   const int64_t nd = (len - head) / 2;                        // dwords of the body
   const int64_t tail = len - head - 2 * nd;
   uint64_t sum = 0;
@@ -220,15 +222,16 @@ __global__ void __launch_bounds__(kThreads) gate_frames_u8_kernel(const uint8_t*
   }
 }
 
-// shared argument rules of the two frame entry points; len = h0*w0*3
-inline int frames_ok(const void* f0, const void* f1, int64_t img_stride, int32_t n, int32_t h0, int32_t w0,
-                     int64_t* len) {
+// shared argument rules of the frame entry points, on the frame's length
+inline int frames_ok(const void* f0, const void* f1, int64_t img_stride, int32_t n, int64_t len) {
   if (!f0 || !f1) return RRIN_E_ARG;
-  if (n < 1 || h0 < 1 || w0 < 1) return RRIN_E_SHAPE;
-  *len = (int64_t)h0 * w0 * 3;
-  if (img_stride < *len) return RRIN_E_ARG;
+  if (n < 1 || len < 1) return RRIN_E_SHAPE;
+  if (img_stride < len) return RRIN_E_ARG;
   return RRIN_OK;
 }
+
+// the length of h0 x w0 x 3 frames; 0 (refused as a shape) unless both sizes are >= 1
+inline int64_t rgb_len(int32_t h0, int32_t w0) { return h0 < 1 || w0 < 1 ? 0 : (int64_t)h0 * w0 * 3; }
 
 // workgroups per frame: one per 32 KiB chunk of the body, at least 1 (head and tail), capped
 inline int grid_x(int64_t len) {
@@ -243,9 +246,13 @@ using namespace rrin;
 
 extern "C" int rrin_pair_sad_u8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0,
                                 int32_t w0, uint64_t* sad, void* stream) {
+  return rrin_pair_sad_u8_len(f0, f1, img_stride, n, rgb_len(h0, w0), sad, stream);
+}
+
+extern "C" int rrin_pair_sad_u8_len(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int64_t len,
+                                    uint64_t* sad, void* stream) {
   if (!sad || ((uintptr_t)sad & 7)) return RRIN_E_ARG;
-  int64_t len = 0;
-  const int rc = frames_ok(f0, f1, img_stride, n, h0, w0, &len);
+  const int rc = frames_ok(f0, f1, img_stride, n, len);
   if (rc) return rc;
   if (n > 65535) return RRIN_E_SHAPE;  // one pair per blockIdx.y
   hipLaunchKernelGGL(zero_u64_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream,
@@ -266,9 +273,13 @@ extern "C" int rrin_gate_from_sad_u8(const uint64_t* sad, int32_t n, uint64_t li
 
 extern "C" int rrin_gate_frames_u8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n,
                                    int32_t h0, int32_t w0, const int32_t* gate, uint8_t* out, void* stream) {
+  return rrin_gate_frames_u8_len(f0, f1, img_stride, n, rgb_len(h0, w0), gate, out, stream);
+}
+
+extern "C" int rrin_gate_frames_u8_len(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n,
+                                       int64_t len, const int32_t* gate, uint8_t* out, void* stream) {
   if (!gate || !out) return RRIN_E_ARG;
-  int64_t len = 0;
-  const int rc = frames_ok(f0, f1, img_stride, n, h0, w0, &len);
+  const int rc = frames_ok(f0, f1, img_stride, n, len);
   if (rc) return rc;
   if (n > 65535) return RRIN_E_SHAPE;  // one pair per blockIdx.y
   hipLaunchKernelGGL(gate_frames_u8_kernel, dim3(grid_x(len), n), dim3(kThreads), 0, (hipStream_t)stream, f0, f1,
@@ -278,11 +289,15 @@ extern "C" int rrin_gate_frames_u8(const uint8_t* f0, const uint8_t* f1, int64_t
 
 extern "C" int rrin_pair_sad_u16(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int32_t h0,
                                  int32_t w0, int32_t depth, int32_t shift, uint64_t* sad, void* stream) {
+  return rrin_pair_sad_u16_len(f0, f1, img_stride, n, rgb_len(h0, w0), depth, shift, sad, stream);
+}
+
+extern "C" int rrin_pair_sad_u16_len(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n,
+                                     int64_t len, int32_t depth, int32_t shift, uint64_t* sad, void* stream) {
   if (!sad || ((uintptr_t)sad & 7)) return RRIN_E_ARG;
   if (depth < 9 || depth > 16 || shift < 0 || shift > 16 - depth) return RRIN_E_ARG;
   if (((uintptr_t)f0 & 1) || ((uintptr_t)f1 & 1)) return RRIN_E_ARG;
-  int64_t len = 0;
-  const int rc = frames_ok(f0, f1, img_stride, n, h0, w0, &len);
+  const int rc = frames_ok(f0, f1, img_stride, n, len);
   if (rc) return rc;
   if (n > 65535) return RRIN_E_SHAPE;  // one pair per blockIdx.y
   const int64_t steps = (len / 2 + kThreads * kWords - 1) / (kThreads * kWords);

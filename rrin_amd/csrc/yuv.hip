@@ -1,7 +1,9 @@
-// 8-bit YUV 4:2:0 frames (NV12 / I420) straight into the Net buffer g16 (rrin_pack_g16_yuv_h8) and
+// 8-bit YUV frames (4:2:0 NV12 / I420; by rrin_chroma also 4:2:2 and 4:4:4) straight into the Net buffer g16 (rrin_pack_g16_yuv_h8) and
 // the standard coefficient sets (rrin_yuv_coef_std), and their siblings for 10- and 12-bit samples in
 // 16-bit words (rrin_pack_g16_yuv16_h8, rrin_yuv_coef_std16).  The conversion itself is yuv.hpp; the
 // way out is the FINAL head's store (glue_h8.hip).
+#include <type_traits>
+
 #include "h8.hpp"
 #include "yuv.hpp"
 
@@ -16,34 +18,48 @@ __constant__ const U8ScaleTab kU8Scale{};
 // pixel (max(y - top, 0), min(x, w0 - 1)), the chroma of its 2x2 block -- to RGB bytes in
 // integers, through the LDS copy of the scale table, and writes the whole records
 // pack_g16_u8_kernel writes.  MODE 0: fp32 records, 1: fp16, 2: split16 (hi and lo planes).
-template <int MODE>
+// CH (rrin_chroma) is the chroma block: 4:2:0 as above; 4:2:2 the same 128 + 128 samples from
+// chroma row sy instead of sy >> 1; 4:4:4 one U and one V per pixel, 256 + 256 samples, each lane
+// loading those of its own pixel (the run may then be odd: nothing here assumes an even np).
+template <int MODE, int CH>
 __global__ void __launch_bounds__(256) pack_g16_yuv_kernel(rrin_yuv420 f0, rrin_yuv420 f1, rrin_yuv_coef k, int w0,
                                                            int top, uint4* ghi, uint4* glo, int64_t img_stride,
                                                            int64_t gp, int wp, int w) {
   __shared__ float s_tab[256];
   __shared__ uint8_t s_y[2][256];
-  __shared__ uint8_t s_c[2][2][128];  // [frame][U, V][block of the run]
+  constexpr int kCW = CH == RRIN_CHROMA_444 ? 256 : 128;  // chroma samples of a run, per plane
+  __shared__ uint8_t s_c[2][2][kCW];  // [frame][U, V][block of the run]
   const int tid = threadIdx.x;
   const int xs = blockIdx.x * 256, y = blockIdx.y, img = blockIdx.z;
   s_tab[tid] = kU8Scale.v[tid];
   const int sy = y > top ? y - top : 0;
-  const int np = min(256, w0 - xs);  // xs < w0: the right pad is < 16 columns, xs a multiple of 256; np is even
+  // xs < w0: the right pad is < 16 columns, xs a multiple of 256; np is even unless 4:4:4 (w0 odd)
+  const int np = min(256, w0 - xs);
+  const int cy = CH == RRIN_CHROMA_420 ? sy >> 1 : sy;
   const int which = tid >> 7, blk = tid & 127;
 #pragma unroll
   for (int f = 0; f < 2; ++f) {
     const rrin_yuv420& s = f ? f1 : f0;
     const int64_t base = (int64_t)img * s.img_stride;
     if (tid < np) s_y[f][tid] = s.y[base + (int64_t)sy * s.y_pitch + xs + tid];
-    if (2 * blk < np)
-      s_c[f][which][blk] = (which ? s.v : s.u)[base + (int64_t)(sy >> 1) * s.c_pitch + (xs / 2 + blk) * s.c_step];
+    if constexpr (CH == RRIN_CHROMA_444) {
+      if (tid < np) {
+        const int64_t c = base + (int64_t)cy * s.c_pitch + (int64_t)(xs + tid) * s.c_step;
+        s_c[f][0][tid] = s.u[c];
+        s_c[f][1][tid] = s.v[c];
+      }
+    } else if (2 * blk < np) {
+      s_c[f][which][blk] = (which ? s.v : s.u)[base + (int64_t)cy * s.c_pitch + (xs / 2 + blk) * s.c_step];
+    }
   }
   __syncthreads();
   const int x = xs + tid;
   if (x >= w) return;
   const int sx = min(x, w0 - 1) - xs;
+  const int cx = CH == RRIN_CHROMA_444 ? sx : sx >> 1;
   int rgb0[3], rgb1[3];
-  yuv_to_rgb(k, s_y[0][sx], s_c[0][0][sx >> 1], s_c[0][1][sx >> 1], rgb0);
-  yuv_to_rgb(k, s_y[1][sx], s_c[1][0][sx >> 1], s_c[1][1][sx >> 1], rgb1);
+  yuv_to_rgb(k, s_y[0][sx], s_c[0][0][cx], s_c[0][1][cx], rgb0);
+  yuv_to_rgb(k, s_y[1][sx], s_c[1][0][cx], s_c[1][1][cx], rgb1);
   float a[3], b[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -78,36 +94,47 @@ __global__ void __launch_bounds__(256) pack_g16_yuv_kernel(rrin_yuv420 f0, rrin_
 // the same run of 256 pixels and the same staging with 2-byte loads (pitches and strides count
 // words, so a frame starts at any even address), the samples min(word >> shift, maxv), the
 // conversion at that depth (yuv_to_rgb16) and every RGB sample divided by maxv
-// (sample_to_float: the IEEE division, as rrin_pack_g16_u16_h8) -- no table.
-template <int MODE>
+// (sample_to_float: the IEEE division, as rrin_pack_g16_u16_h8) -- no table.  CH as there.
+template <int MODE, int CH>
 __global__ void __launch_bounds__(256) pack_g16_yuv16_kernel(rrin_yuv420_16 f0, rrin_yuv420_16 f1, rrin_yuv_coef k,
                                                              int w0, int top, uint4* ghi, uint4* glo,
                                                              int64_t img_stride, int64_t gp, int wp, int w) {
   __shared__ uint16_t s_y[2][256];
-  __shared__ uint16_t s_c[2][2][128];  // [frame][U, V][block of the run]
+  constexpr int kCW = CH == RRIN_CHROMA_444 ? 256 : 128;  // chroma samples of a run, per plane
+  __shared__ uint16_t s_c[2][2][kCW];  // [frame][U, V][block of the run]
   const int tid = threadIdx.x;
   const int xs = blockIdx.x * 256, y = blockIdx.y, img = blockIdx.z;
   const int sy = y > top ? y - top : 0;
-  const int np = min(256, w0 - xs);  // xs < w0: the right pad is < 16 columns, xs a multiple of 256; np is even
+  // xs < w0: the right pad is < 16 columns, xs a multiple of 256; np is even unless 4:4:4 (w0 odd)
+  const int np = min(256, w0 - xs);
+  const int cy = CH == RRIN_CHROMA_420 ? sy >> 1 : sy;
   const int which = tid >> 7, blk = tid & 127;
 #pragma unroll
   for (int f = 0; f < 2; ++f) {
     const rrin_yuv420_16& s = f ? f1 : f0;
     const int64_t base = (int64_t)img * s.img_stride;
     if (tid < np) s_y[f][tid] = s.y[base + (int64_t)sy * s.y_pitch + xs + tid];
-    if (2 * blk < np)
-      s_c[f][which][blk] = (which ? s.v : s.u)[base + (int64_t)(sy >> 1) * s.c_pitch + (xs / 2 + blk) * s.c_step];
+    if constexpr (CH == RRIN_CHROMA_444) {
+      if (tid < np) {
+        const int64_t c = base + (int64_t)cy * s.c_pitch + (int64_t)(xs + tid) * s.c_step;
+        s_c[f][0][tid] = s.u[c];
+        s_c[f][1][tid] = s.v[c];
+      }
+    } else if (2 * blk < np) {
+      s_c[f][which][blk] = (which ? s.v : s.u)[base + (int64_t)cy * s.c_pitch + (xs / 2 + blk) * s.c_step];
+    }
   }
   __syncthreads();
   const int x = xs + tid;
   if (x >= w) return;
   const int sx = min(x, w0 - 1) - xs;
+  const int cx = CH == RRIN_CHROMA_444 ? sx : sx >> 1;
   const int shift = f0.shift, maxv = (1 << f0.depth) - 1, mid = 1 << (f0.depth - 1);
   int rgb0[3], rgb1[3];
-  yuv_to_rgb16(k, mid, maxv, sample16(s_y[0][sx], shift, maxv), sample16(s_c[0][0][sx >> 1], shift, maxv),
-               sample16(s_c[0][1][sx >> 1], shift, maxv), rgb0);
-  yuv_to_rgb16(k, mid, maxv, sample16(s_y[1][sx], shift, maxv), sample16(s_c[1][0][sx >> 1], shift, maxv),
-               sample16(s_c[1][1][sx >> 1], shift, maxv), rgb1);
+  yuv_to_rgb16(k, mid, maxv, sample16(s_y[0][sx], shift, maxv), sample16(s_c[0][0][cx], shift, maxv),
+               sample16(s_c[0][1][cx], shift, maxv), rgb0);
+  yuv_to_rgb16(k, mid, maxv, sample16(s_y[1][sx], shift, maxv), sample16(s_c[1][0][cx], shift, maxv),
+               sample16(s_c[1][1][cx], shift, maxv), rgb1);
   const float mv = (float)maxv;
   float a[3], b[3];
 #pragma unroll
@@ -139,6 +166,37 @@ __global__ void __launch_bounds__(256) pack_g16_yuv16_kernel(rrin_yuv420_16 f0, 
   }
 }
 
+// the launch of a pack kernel K<MODE, CH> (K8 / K16 below) for a record precision and a chroma format
+template <template <int, int> class K, class Stack>
+static int launch_yuv_pack(int prec, int chroma, dim3 grid, hipStream_t st, const Stack& f0, const Stack& f1,
+                           const rrin_yuv_coef& k, int w0, int top, const rrin_h8& g16, int w) {
+  uint4* hi = static_cast<uint4*>(g16.hi);
+  uint4* lo = planes_of(prec) == 2 ? static_cast<uint4*>(g16.lo) : nullptr;
+  const int mode = prec == RRIN_PREC_F32R ? 0 : (planes_of(prec) == 2 ? 2 : 1);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, f0, f1, k, w0, top, hi, lo, g16.img_stride, g16.g.plane,
+                       g16.g.wp, w);
+    return hip_code(hipGetLastError());
+  };
+  auto by_chroma = [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    if (chroma == RRIN_CHROMA_422) return go(K<M, RRIN_CHROMA_422>::fn);
+    if (chroma == RRIN_CHROMA_444) return go(K<M, RRIN_CHROMA_444>::fn);
+    return go(K<M, RRIN_CHROMA_420>::fn);
+  };
+  if (mode == 0) return by_chroma(std::integral_constant<int, 0>{});
+  if (mode == 2) return by_chroma(std::integral_constant<int, 2>{});
+  return by_chroma(std::integral_constant<int, 1>{});
+}
+template <int MODE, int CH>
+struct K8 {
+  static constexpr auto fn = pack_g16_yuv_kernel<MODE, CH>;
+};
+template <int MODE, int CH>
+struct K16 {
+  static constexpr auto fn = pack_g16_yuv16_kernel<MODE, CH>;
+};
+
 }  // namespace rrin
 
 using namespace rrin;
@@ -164,24 +222,14 @@ extern "C" int rrin_pack_g16_yuv_h8(const rrin_yuv420* f0, const rrin_yuv420* f1
   if (int rc = yuv_coef_check(coef)) return rc;
   if (int rc = yuv420_check(*f0, n, h0, w0)) return rc;
   if (int rc = yuv420_check(*f1, n, h0, w0)) return rc;
+  if (f0->chroma != f1->chroma) return RRIN_E_ARG;
   if (!h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16) return RRIN_E_SHAPE;
   const int h = g16->g.h, w = g16->g.w;
   if (h != (h0 + 15) / 16 * 16 || w != (w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
   if (n > 65535 || h > 65535) return RRIN_E_SHAPE;  // grid y / z
   const dim3 grid((w + 255) / 256, h, n);
   const int top = h - h0;
-  hipStream_t st = (hipStream_t)stream;
-  if (prec == RRIN_PREC_F32R)
-    hipLaunchKernelGGL(pack_g16_yuv_kernel<0>, grid, dim3(256), 0, st, *f0, *f1, *coef, w0, top,
-                       static_cast<uint4*>(g16->hi), (uint4*)nullptr, g16->img_stride, g16->g.plane, g16->g.wp, w);
-  else if (planes_of(prec) == 2)
-    hipLaunchKernelGGL(pack_g16_yuv_kernel<2>, grid, dim3(256), 0, st, *f0, *f1, *coef, w0, top,
-                       static_cast<uint4*>(g16->hi), static_cast<uint4*>(g16->lo), g16->img_stride, g16->g.plane,
-                       g16->g.wp, w);
-  else
-    hipLaunchKernelGGL(pack_g16_yuv_kernel<1>, grid, dim3(256), 0, st, *f0, *f1, *coef, w0, top,
-                       static_cast<uint4*>(g16->hi), (uint4*)nullptr, g16->img_stride, g16->g.plane, g16->g.wp, w);
-  return hip_code(hipGetLastError());
+  return launch_yuv_pack<K8>(prec, f0->chroma, grid, (hipStream_t)stream, *f0, *f1, *coef, w0, top, *g16, w);
 }
 
 extern "C" int rrin_yuv_coef_std16(int32_t standard, int32_t full_range, int32_t depth, rrin_yuv_coef* c) {
@@ -216,7 +264,7 @@ extern "C" int rrin_pack_g16_yuv16_h8(const rrin_yuv420_16* f0, const rrin_yuv42
   if (!f0 || !f1 || !g16 || n < 1 || !rec_prec(prec)) return RRIN_E_ARG;
   if (int rc = yuv420_16_check(*f0, n, h0, w0)) return rc;
   if (int rc = yuv420_16_check(*f1, n, h0, w0)) return rc;
-  if (f0->depth != f1->depth || f0->shift != f1->shift) return RRIN_E_ARG;
+  if (f0->depth != f1->depth || f0->shift != f1->shift || f0->chroma != f1->chroma) return RRIN_E_ARG;
   if (int rc = yuv_coef_check16(coef, f0->depth)) return rc;
   if (!h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16) return RRIN_E_SHAPE;
   const int h = g16->g.h, w = g16->g.w;
@@ -224,16 +272,5 @@ extern "C" int rrin_pack_g16_yuv16_h8(const rrin_yuv420_16* f0, const rrin_yuv42
   if (n > 65535 || h > 65535) return RRIN_E_SHAPE;  // grid y / z
   const dim3 grid((w + 255) / 256, h, n);
   const int top = h - h0;
-  hipStream_t st = (hipStream_t)stream;
-  if (prec == RRIN_PREC_F32R)
-    hipLaunchKernelGGL(pack_g16_yuv16_kernel<0>, grid, dim3(256), 0, st, *f0, *f1, *coef, w0, top,
-                       static_cast<uint4*>(g16->hi), (uint4*)nullptr, g16->img_stride, g16->g.plane, g16->g.wp, w);
-  else if (planes_of(prec) == 2)
-    hipLaunchKernelGGL(pack_g16_yuv16_kernel<2>, grid, dim3(256), 0, st, *f0, *f1, *coef, w0, top,
-                       static_cast<uint4*>(g16->hi), static_cast<uint4*>(g16->lo), g16->img_stride, g16->g.plane,
-                       g16->g.wp, w);
-  else
-    hipLaunchKernelGGL(pack_g16_yuv16_kernel<1>, grid, dim3(256), 0, st, *f0, *f1, *coef, w0, top,
-                       static_cast<uint4*>(g16->hi), (uint4*)nullptr, g16->img_stride, g16->g.plane, g16->g.wp, w);
-  return hip_code(hipGetLastError());
+  return launch_yuv_pack<K16>(prec, f0->chroma, grid, (hipStream_t)stream, *f0, *f1, *coef, w0, top, *g16, w);
 }

@@ -1,4 +1,4 @@
-// The integer colour conversion of the YUV 4:2:0 frame path (rrin_yuv_coef in rrin_hip.h), shared
+// The integer colour conversion of the YUV frame path (4:2:0, and by rrin_chroma 4:2:2 / 4:4:4) (rrin_yuv_coef in rrin_hip.h), shared
 // by the input pack (yuv.hip) and the FINAL head's store (glue_h8.hip), and the host-side checks
 // of a rrin_yuv420 stack; below them the same for 10- and 12-bit samples in 16-bit words
 // (rrin_yuv420_16).  int32 only: no float colour math, so no FMA contraction can change a bit.
@@ -26,6 +26,13 @@ __device__ inline int rgb_sum_to_chroma(int kr, int kg, int kb, const int* sum) 
   return clip255(128 + ((kr * sum[0] + kg * sum[1] + kb * sum[2] + 32768) >> 16));
 }
 
+// the same for a block of P = 2^LOG2P pixels (4:2:2: 2, 4:4:4: 1): + 8192 P, >> (14 + log2 P);
+// LOG2P 2 is rgb_sum_to_chroma
+template <int LOG2P>
+__device__ inline int rgb_block_to_chroma(int kr, int kg, int kb, const int* sum) {
+  return clip255(128 + ((kr * sum[0] + kg * sum[1] + kb * sum[2] + (8192 << LOG2P)) >> (14 + LOG2P)));
+}
+
 // ---- 10- and 12-bit samples in 16-bit words (rrin_yuv420_16) -----------------------------
 // the same formulas with mid = 2^(depth-1) for 128 and a clip to maxv = 2^depth - 1
 __device__ inline int clip_to(int v, int maxv) { return min(max(v, 0), maxv); }
@@ -48,6 +55,11 @@ __device__ inline int rgb_sum_to_chroma16(int kr, int kg, int kb, int mid, int m
   return clip_to(mid + ((kr * sum[0] + kg * sum[1] + kb * sum[2] + 32768) >> 16), maxv);
 }
 
+template <int LOG2P>
+__device__ inline int rgb_block_to_chroma16(int kr, int kg, int kb, int mid, int maxv, const int* sum) {
+  return clip_to(mid + ((kr * sum[0] + kg * sum[1] + kb * sum[2] + (8192 << LOG2P)) >> (14 + LOG2P)), maxv);
+}
+
 // float(v) / float(maxv) as torch computes it: the IEEE fp32 division (v_div_scale / v_div_fmas /
 // v_div_fixup: correctly rounded; the library is built without fast-math), never a reciprocal
 // multiply, which differs from it in the last bit for some v
@@ -62,15 +74,33 @@ inline int yuv_coef_check(const rrin_yuv_coef* k) {
   return 0;
 }
 
+inline bool chroma_ok(int chroma) { return chroma >= RRIN_CHROMA_420 && chroma <= RRIN_CHROMA_444; }
+
+// sizes, pitches and frame stride of n frames of h0 x w0 at a valid chroma format: 4:2:0 takes
+// even sizes >= 2 and has h0/2 x w0/2 chroma samples, 4:2:2 an even w0 >= 2 and any h0 >= 1
+// (h0 x w0/2), 4:4:4 any sizes >= 1 (h0 x w0); the frames of a stack must not overlap
+inline int yuv_sizes_check(int chroma, int c_step, int64_t img_stride, int y_pitch, int c_pitch, int n, int h0,
+                           int w0) {
+  if (n < 1) return RRIN_E_SHAPE;
+  if (chroma == RRIN_CHROMA_420) {
+    if (h0 < 2 || w0 < 2 || (h0 & 1) || (w0 & 1)) return RRIN_E_SHAPE;
+  } else if (chroma == RRIN_CHROMA_422) {
+    if (h0 < 1 || w0 < 2 || (w0 & 1)) return RRIN_E_SHAPE;
+  } else if (h0 < 1 || w0 < 1) {
+    return RRIN_E_SHAPE;
+  }
+  const int ch = chroma == RRIN_CHROMA_420 ? h0 / 2 : h0, cw = chroma == RRIN_CHROMA_444 ? w0 : w0 / 2;
+  if (y_pitch < w0 || c_pitch < (int64_t)cw * c_step) return RRIN_E_SHAPE;
+  const int64_t y_span = (int64_t)(h0 - 1) * y_pitch + w0;
+  const int64_t c_span = (int64_t)(ch - 1) * c_pitch + (int64_t)(cw - 1) * c_step + 1;
+  if (n > 1 && (img_stride < y_span || img_stride < c_span)) return RRIN_E_SHAPE;
+  return 0;
+}
+
 // n frames of h0 x w0 in s: planes, layout, sizes and pitches (nothing is dereferenced)
 __attribute__((visibility("hidden"))) inline int yuv420_check(const rrin_yuv420& s, int n, int h0, int w0) {
-  if (!s.y || !s.u || !s.v || (s.c_step != 1 && s.c_step != 2)) return RRIN_E_ARG;
-  if (n < 1 || h0 < 2 || w0 < 2 || (h0 & 1) || (w0 & 1)) return RRIN_E_SHAPE;
-  if (s.y_pitch < w0 || s.c_pitch < (w0 / 2) * s.c_step) return RRIN_E_SHAPE;
-  const int64_t y_span = (int64_t)(h0 - 1) * s.y_pitch + w0;
-  const int64_t c_span = (int64_t)(h0 / 2 - 1) * s.c_pitch + (int64_t)(w0 / 2 - 1) * s.c_step + 1;
-  if (n > 1 && (s.img_stride < y_span || s.img_stride < c_span)) return RRIN_E_SHAPE;
-  return 0;
+  if (!s.y || !s.u || !s.v || (s.c_step != 1 && s.c_step != 2) || !chroma_ok(s.chroma)) return RRIN_E_ARG;
+  return yuv_sizes_check(s.chroma, s.c_step, s.img_stride, s.y_pitch, s.c_pitch, n, h0, w0);
 }
 
 // the coefficient bounds of the 16-bit path (rrin_yuv420_16): with them every sum fits int32 at depth 12
@@ -87,13 +117,8 @@ inline int yuv_coef_check16(const rrin_yuv_coef* k, int depth) {
 // yuv420_check for 16-bit words: depth, shift, then planes, sizes and pitches in samples
 __attribute__((visibility("hidden"))) inline int yuv420_16_check(const rrin_yuv420_16& s, int n, int h0, int w0) {
   if ((s.depth != 10 && s.depth != 12) || (s.shift != 0 && s.shift != 16 - s.depth)) return RRIN_E_ARG;
-  if (!s.y || !s.u || !s.v || (s.c_step != 1 && s.c_step != 2)) return RRIN_E_ARG;
-  if (n < 1 || h0 < 2 || w0 < 2 || (h0 & 1) || (w0 & 1)) return RRIN_E_SHAPE;
-  if (s.y_pitch < w0 || s.c_pitch < (w0 / 2) * s.c_step) return RRIN_E_SHAPE;
-  const int64_t y_span = (int64_t)(h0 - 1) * s.y_pitch + w0;
-  const int64_t c_span = (int64_t)(h0 / 2 - 1) * s.c_pitch + (int64_t)(w0 / 2 - 1) * s.c_step + 1;
-  if (n > 1 && (s.img_stride < y_span || s.img_stride < c_span)) return RRIN_E_SHAPE;
-  return 0;
+  if (!s.y || !s.u || !s.v || (s.c_step != 1 && s.c_step != 2) || !chroma_ok(s.chroma)) return RRIN_E_ARG;
+  return yuv_sizes_check(s.chroma, s.c_step, s.img_stride, s.y_pitch, s.c_pitch, n, h0, w0);
 }
 
 }  // namespace rrin

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .convert import scene_cut_code, scene_limit
+from .convert import scene_cut_code, scene_limit, scene_limit_len
 from .unet import _level_of
 
 UNET_ORDER = ("Flow", "refine_flow", "Mask", "final")
@@ -831,9 +831,10 @@ class RRINEngine:
                 off += n * c * h * w
         return out
 
-    def _frames(self, f0, f1, what: str, rgb: bool, dtype=torch.uint8):
+    def _frames(self, f0, f1, what: str, rgb: bool, dtype=torch.uint8, layout: str = "nv12"):
         """Checks two frame stacks of ``what`` (uint8, or uint16 for the 16-bit paths) --
-        ``[N,H0,W0,3]`` (``rgb``) or 4:2:0 ``[N, 3*H0//2, W0]`` -- and returns them with (H0, W0) and
+        ``[N,H0,W0,3]`` (``rgb``) or YUV planes of ``layout`` (4:2:0: ``[N, 3*H0//2, W0]``; 4:2:2:
+        ``[N, 2*H0, W0]``; 4:4:4: ``[N, 3*H0, W0]``) -- and returns them with (H0, W0) and
         the elements (bytes or 16-bit words) between their frames: every frame dense, a uniform
         stride over dim 0 taken as it is (``frames[:-1]`` / ``frames[1:]`` of one stack need no
         copy), anything else copied."""
@@ -853,7 +854,7 @@ class RRINEngine:
             if f0.shape != f1.shape:
                 raise ValueError(f"expected two equal [N, 3*H0//2, W0] stacks, got {tuple(f0.shape)} / "
                                  f"{tuple(f1.shape)}")
-            h0, w0 = yuv.frame_size(f0)
+            h0, w0 = yuv.stack_size(f0, layout)
         n = f0.shape[0]
         if n < 1 or h0 < 1 or w0 < 1:
             raise ValueError(f"empty frames: {tuple(f0.shape)}")
@@ -874,9 +875,10 @@ class RRINEngine:
         return f0, f1, h0, w0, s0
 
     def _scene_gate(self, path: str, n: int, rows: int, cols: int, t, bounds, reuse_flow, scene_threshold, gate,
-                    maxval: int = 255):
+                    maxval: int = 255, samples: int | None = None):
         """The scene gate of a byte-frame forward whose frames are ``rows x cols x 3`` bytes each
-        (RGB: H0 x W0; 4:2:0: H0/2 x W0).  Checks ``scene_threshold`` against ``gate`` and the gate
+        (RGB: H0 x W0; 4:2:0: H0/2 x W0) or, with ``samples``, blobs of that many bytes or 16-bit
+        samples (4:2:2, 4:4:4: no multiple of 3 in general).  Checks ``scene_threshold`` against ``gate`` and the gate
         tensor, keeps :attr:`last_gate` and the key of the cached sums, and returns None (gate
         off) or (sums or None, sums already there, limit, cut code, codes) for _enqueue_gate.
         Changes state, so it runs after everything else that may refuse the call."""
@@ -884,9 +886,11 @@ class RRINEngine:
             raise ValueError("scene_threshold and gate exclude each other")
         sad, have_sad, limit, cut_code = None, False, None, None
         if scene_threshold is not None:
-            limit, cut_code = scene_limit(scene_threshold, rows, cols, maxval), scene_cut_code(t)
+            limit = (scene_limit(scene_threshold, rows, cols, maxval) if samples is None
+                     else scene_limit_len(scene_threshold, samples, maxval))
+            cut_code = scene_cut_code(t)
             # the sums belong to the batch and its split: kept for the next t of the same pairs
-            skey = (path, n, rows, cols, tuple(bounds))
+            skey = (path, n, rows, cols, tuple(bounds)) if samples is None else (path, n, samples, tuple(bounds))
             have_sad = bool(reuse_flow) and self._sad_key == skey
             sad, gate = self._gate_buffers(n)
             self._sad_key = skey
@@ -903,15 +907,30 @@ class RRINEngine:
         return sad, have_sad, limit, cut_code, gate
 
     def _enqueue_gate(self, g, p0: int, p1: int, img_stride: int, lo: int, hi: int, rows: int, cols: int, out: int,
-                      stream, wide=None):
+                      stream, wide=None, samples: int | None = None):
         """The gate kernels of pairs [lo, hi) on ``stream``, behind the part's forward: the sums
         (unless kept), the codes from the sums (unless given), the copy of the gated frames from
         the frames at p0 / p1 (``rows x cols x 3`` bytes each) over those at ``out``.  ``wide``
         (depth, shift): the frames are 16-bit words and ``img_stride`` counts them; the sums are
-        rrin_pair_sad_u16's, and the byte-wise copy kernel runs on twice the width."""
+        rrin_pair_sad_u16's, and the byte-wise copy kernel runs on twice the width.  ``samples``:
+        the frames are blobs of that many elements (``rows`` / ``cols`` unused): the _len entry points."""
         sad, have_sad, limit, cut_code, codes = g
         sp, m = C.c_void_p(stream.cuda_stream), hi - lo
         cp = codes[lo:hi].data_ptr()
+        if samples is not None:
+            k = 1 if wide is None else 2
+            if sad is not None:
+                sums = sad[lo:hi].data_ptr()
+                if not have_sad and wide is None:
+                    _lib.check(self.lib.rrin_pair_sad_u8_len(p0, p1, img_stride, m, samples, sums, sp),
+                               "rrin_pair_sad_u8_len")
+                elif not have_sad:
+                    _lib.check(self.lib.rrin_pair_sad_u16_len(p0, p1, img_stride, m, samples, wide[0], wide[1], sums,
+                                                              sp), "rrin_pair_sad_u16_len")
+                _lib.check(self.lib.rrin_gate_from_sad_u8(sums, m, limit, cut_code, cp, sp), "rrin_gate_from_sad_u8")
+            _lib.check(self.lib.rrin_gate_frames_u8_len(p0, p1, img_stride * k, m, samples * k, cp, out, sp),
+                       "rrin_gate_frames_u8_len")
+            return
         if sad is not None:
             sums = sad[lo:hi].data_ptr()
             if not have_sad and wide is None:
@@ -924,14 +943,23 @@ class RRINEngine:
         _lib.check(self.lib.rrin_gate_frames_u8(p0, p1, img_stride * k, m, rows, cols * k, cp, out, sp),
                    "rrin_gate_frames_u8")
 
-    def _pair_sad(self, f0, f1, img_stride: int, rows: int, cols: int, wide=None) -> torch.Tensor:
+    def _pair_sad(self, f0, f1, img_stride: int, rows: int, cols: int, wide=None,
+                  samples: int | None = None) -> torch.Tensor:
         """rrin_pair_sad_u8 (``wide`` = (depth, shift): rrin_pair_sad_u16) of two checked stacks on
-        the current stream: a fresh int64 ``[N]``."""
+        the current stream: a fresh int64 ``[N]``.  ``samples``: frames of that many elements, through
+        the _len entry points."""
         n = f0.shape[0]
         sad = torch.empty(n, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            if wide is None:
+            if samples is not None and wide is None:
+                _lib.check(self.lib.rrin_pair_sad_u8_len(f0.data_ptr(), f1.data_ptr(), img_stride, n, samples,
+                                                         sad.data_ptr(), st), "rrin_pair_sad_u8_len")
+            elif samples is not None:
+                _lib.check(self.lib.rrin_pair_sad_u16_len(f0.data_ptr(), f1.data_ptr(), img_stride, n, samples,
+                                                          wide[0], wide[1], sad.data_ptr(), st),
+                           "rrin_pair_sad_u16_len")
+            elif wide is None:
                 _lib.check(self.lib.rrin_pair_sad_u8(f0.data_ptr(), f1.data_ptr(), img_stride, n, rows, cols,
                                                      sad.data_ptr(), st), "rrin_pair_sad_u8")
             else:
@@ -1028,9 +1056,23 @@ class RRINEngine:
         s.img_stride, s.y_pitch = img_stride, w0
         if layout == "nv12":
             s.v, s.c_pitch, s.c_step = s.u + 1, w0, 2
-        else:
+        elif layout == "i420":
             s.v, s.c_pitch, s.c_step = s.u + (h0 // 2) * (w0 // 2), w0 // 2, 1
+        elif layout == "nv16":
+            s.v, s.c_pitch, s.c_step, s.chroma = s.u + 1, w0, 2, _lib.CHROMA_422
+        elif layout == "i422":
+            s.v, s.c_pitch, s.c_step, s.chroma = s.u + h0 * (w0 // 2), w0 // 2, 1, _lib.CHROMA_422
+        else:  # i444
+            s.v, s.c_pitch, s.c_step, s.chroma = s.u + h0 * w0, w0, 1, _lib.CHROMA_444
         return s
+
+    @staticmethod
+    def _yuv_gate_samples(h0: int, w0: int, layout: str):
+        """None for a 4:2:0 layout (its gate keeps running on (H0/2) x W0 x 3 bytes), else the
+        samples of a 4:2:2 / 4:4:4 frame: 2*H0*W0 / 3*H0*W0."""
+        from . import yuv
+        chroma = yuv.chroma_of(layout)
+        return None if chroma == "420" else (2 if chroma == "422" else 3) * h0 * w0
 
     def forward_yuv(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, layout: str = "nv12", coef=None,
                     reuse_flow: bool = False, streams: int | None = None, split=None, scene_threshold=None,
@@ -1055,21 +1097,28 @@ class RRINEngine:
         unchanged, with no round trip through RGB.  ``scene_threshold`` is therefore a mean
         absolute difference over luma *and* chroma bytes: a pair is a cut when its sum exceeds
         ``floor(scene_threshold * H0*W0*3/2)``.  That is not the same number as the RGB path's
-        threshold for the same footage, and like it no value has been validated on footage."""
+        threshold for the same footage, and like it no value has been validated on footage.
+
+        4:2:2 (``layout`` "nv16" / "i422": ``[N, 2*H0, W0]``, W0 even, any H0) and 4:4:4 ("i444":
+        ``[N, 3*H0, W0]``, any size) run the same way: by definition ``yuv.rgb_to_yuv(forward_u8(
+        yuv.yuv_to_rgb(f0, layout), yuv.yuv_to_rgb(f1, layout), t), layout)``, the output a stack of
+        the input's layout and shape.  Their gate sums the frame's ``2*H0*W0`` / ``3*H0*W0`` bytes
+        (rrin_pair_sad_u8_len): a cut exceeds ``floor(scene_threshold * that count)``."""
         from . import yuv
         self._need_records("forward_yuv")
-        if layout not in yuv.LAYOUTS:
-            raise ValueError(f"layout must be one of {yuv.LAYOUTS}, got {layout!r}")
+        if layout not in yuv.ALL_LAYOUTS:
+            raise ValueError(f"layout must be one of {yuv.ALL_LAYOUTS}, got {layout!r}")
         k = yuv.as_coef(coef)
-        f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_yuv", rgb=False)
+        f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_yuv", rgb=False, layout=layout)
+        samples = self._yuv_gate_samples(h0, w0, layout)
         n = f0.shape[0]
         h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
         self._poll_range()
         tcoef = t_coefficients(t, n).to(self.device, non_blocking=True)
         bounds = self._bounds(n, streams, split)
         # the gate of forward_u8 on the frames' bytes: (H0/2) * W0 * 3 of them per frame
-        g = self._scene_gate("yuv", n, h0 // 2, w0, t, bounds, reuse_flow, scene_threshold, gate)
-        out = torch.empty((n, 3 * h0 // 2, w0), dtype=torch.uint8, device=self.device)
+        g = self._scene_gate("yuv", n, h0 // 2, w0, t, bounds, reuse_flow, scene_threshold, gate, samples=samples)
+        out = torch.empty((n, yuv.stack_rows(h0, layout), w0), dtype=torch.uint8, device=self.device)
         # the raw Flow kept in a workspace is that of these frames under this layout and matrix:
         # no other path, layout or matrix may take it for its previous pair
         tag = "yuv:" + layout + ":" + ",".join(str(v) for v in k)
@@ -1085,18 +1134,19 @@ class RRINEngine:
             d.coef, d.h0, d.w0 = kc, h0, w0
             self._launch(self.lib.rrin_net_yuv_fwd, "rrin_net_yuv_fwd", d, d.net, p, tag, reuse_flow, stream)
             if g is not None:
-                self._enqueue_gate(g, p0, p1, s0, lo, hi, h0 // 2, w0, po, stream)
+                self._enqueue_gate(g, p0, p1, s0, lo, hi, h0 // 2, w0, po, stream, samples=samples)
 
         self._run_parts(h, w, bounds, part)
         return out
 
-    def pair_stats_yuv(self, f0: torch.Tensor, f1: torch.Tensor) -> torch.Tensor:
+    def pair_stats_yuv(self, f0: torch.Tensor, f1: torch.Tensor, layout: str = "nv12") -> torch.Tensor:
         """The sum of absolute byte differences (luma and chroma) of every pair of two 4:2:0
         stacks as :meth:`forward_yuv` takes them: a fresh int64 device tensor ``[N]``, exact
         (rrin_pair_sad_u8 on the frames' bytes) -- what its ``scene_threshold`` compares with
-        ``floor(threshold * H0*W0*3/2)``."""
-        f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_yuv", rgb=False)
-        return self._pair_sad(f0, f1, s0, h0 // 2, w0)
+        ``floor(threshold * H0*W0*3/2)``.  ``layout`` matters for the stack's shape only: a 4:2:2 or
+        4:4:4 layout sums the frame's ``2*H0*W0`` / ``3*H0*W0`` bytes (rrin_pair_sad_u8_len)."""
+        f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_yuv", rgb=False, layout=layout)
+        return self._pair_sad(f0, f1, s0, h0 // 2, w0, samples=self._yuv_gate_samples(h0, w0, layout))
 
     # ---- 10- to 16-bit frames in 16-bit words ----------------------------------------------
     @staticmethod
@@ -1157,8 +1207,14 @@ class RRINEngine:
         s.img_stride, s.y_pitch, s.depth, s.shift = img_stride, w0, depth, shift
         if layout == "nv12":
             s.v, s.c_pitch, s.c_step = s.u + 2, w0, 2
-        else:
+        elif layout == "i420":
             s.v, s.c_pitch, s.c_step = s.u + 2 * (h0 // 2) * (w0 // 2), w0 // 2, 1
+        elif layout == "nv16":
+            s.v, s.c_pitch, s.c_step, s.chroma = s.u + 2, w0, 2, _lib.CHROMA_422
+        elif layout == "i422":
+            s.v, s.c_pitch, s.c_step, s.chroma = s.u + 2 * h0 * (w0 // 2), w0 // 2, 1, _lib.CHROMA_422
+        else:  # i444
+            s.v, s.c_pitch, s.c_step, s.chroma = s.u + 2 * h0 * w0, w0, 1, _lib.CHROMA_444
         return s
 
     def forward_yuv16(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, layout: str = "nv12", depth: int = 10,
@@ -1173,23 +1229,26 @@ class RRINEngine:
         FINAL head's 16-bit 4:2:0 store out (rrin_net_yuv16_fwd).  Other depths raise: the Q14
         sums leave int32.  The rest is :meth:`forward_yuv`'s, the scene gate on the frames' samples
         ``min(word >> shift, maxval)``, luma and chroma, with ``scene_threshold`` in [0, maxval]; a
-        kept raw Flow is only reused by a call of the same layout, depth, alignment and matrix."""
+        kept raw Flow is only reused by a call of the same layout, depth, alignment and matrix.
+        The 4:2:2 and 4:4:4 layouts ("nv16", "i422", "i444") run as in :meth:`forward_yuv`, defined by
+        ``yuv.rgb16_to_yuv`` / ``yuv.yuv_to_rgb16``, the gate on the frame's samples (rrin_pair_sad_u16_len)."""
         from . import yuv
         self._need_records("forward_yuv16")
-        if layout not in yuv.LAYOUTS:
-            raise ValueError(f"layout must be one of {yuv.LAYOUTS}, got {layout!r}")
+        if layout not in yuv.ALL_LAYOUTS:
+            raise ValueError(f"layout must be one of {yuv.ALL_LAYOUTS}, got {layout!r}")
         depth = yuv.check_depth16(depth)
         shift = 16 - depth if msb else 0
         k = yuv.as_coef(coef, depth)
-        f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_yuv16", rgb=False, dtype=torch.uint16)
+        f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_yuv16", rgb=False, dtype=torch.uint16, layout=layout)
+        samples = self._yuv_gate_samples(h0, w0, layout)
         n = f0.shape[0]
         h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
         self._poll_range()
         tcoef = t_coefficients(t, n).to(self.device, non_blocking=True)
         bounds = self._bounds(n, streams, split)
         g = self._scene_gate(f"yuv16:{depth}:{shift}", n, h0 // 2, w0, t, bounds, reuse_flow, scene_threshold, gate,
-                             (1 << depth) - 1)
-        out = torch.empty((n, 3 * h0 // 2, w0), dtype=torch.uint16, device=self.device)
+                             (1 << depth) - 1, samples=samples)
+        out = torch.empty((n, yuv.stack_rows(h0, layout), w0), dtype=torch.uint16, device=self.device)
         tag = f"yuv16:{depth}:{shift}:{layout}:" + ",".join(str(v) for v in k)
         kc = _lib.YuvCoef(*k)
         frame = out.stride(0)
@@ -1204,18 +1263,21 @@ class RRINEngine:
             d.coef, d.h0, d.w0 = kc, h0, w0
             self._launch(self.lib.rrin_net_yuv16_fwd, "rrin_net_yuv16_fwd", d, d.net, p, tag, reuse_flow, stream)
             if g is not None:
-                self._enqueue_gate(g, p0, p1, s0, lo, hi, h0 // 2, w0, po, stream, wide=(depth, shift))
+                self._enqueue_gate(g, p0, p1, s0, lo, hi, h0 // 2, w0, po, stream, wide=(depth, shift),
+                                   samples=samples)
 
         self._run_parts(h, w, bounds, part)
         return out
 
-    def pair_stats_yuv16(self, f0: torch.Tensor, f1: torch.Tensor, depth: int = 10, msb: bool = False) -> torch.Tensor:
+    def pair_stats_yuv16(self, f0: torch.Tensor, f1: torch.Tensor, depth: int = 10, msb: bool = False,
+                         layout: str = "nv12") -> torch.Tensor:
         """:meth:`pair_stats_yuv` for two uint16 4:2:0 stacks: the exact sum of absolute differences
         of the samples ``min(word >> shift, maxval)``, luma and chroma (rrin_pair_sad_u16)."""
         from . import yuv
         depth = yuv.check_depth16(depth)
-        f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_yuv16", rgb=False, dtype=torch.uint16)
-        return self._pair_sad(f0, f1, s0, h0 // 2, w0, wide=(depth, 16 - depth if msb else 0))
+        f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_yuv16", rgb=False, dtype=torch.uint16, layout=layout)
+        return self._pair_sad(f0, f1, s0, h0 // 2, w0, wide=(depth, 16 - depth if msb else 0),
+                              samples=self._yuv_gate_samples(h0, w0, layout))
 
     def unet_forward(self, x: torch.Tensor) -> torch.Tensor:
         """The single packed U-Net (engine built with one unit) on x [N,C,H,W]:

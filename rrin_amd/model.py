@@ -145,7 +145,9 @@ class Net(nn.Module):
 
     def forward_yuv(self, f0, f1, t=0.5, layout="nv12", coef=None, scene_threshold=None, gate=None):
         """``forward`` on 8-bit YUV 4:2:0 frames, as decoders and video pipes deliver them: uint8
-        ``[N, 3*H0//2, W0]`` in and out on the device (H0, W0 even; ``layout`` "nv12" or "i420").
+        ``[N, 3*H0//2, W0]`` in and out on the device (H0, W0 even; ``layout`` "nv12" or "i420") -- or
+        4:2:2 (``layout`` "nv16" / "i422": ``[N, 2*H0, W0]``, W0 even) and 4:4:4 ("i444": ``[N, 3*H0,
+        W0]``, any size), defined by ``yuv.rgb_to_yuv`` / ``yuv.yuv_to_rgb`` with that layout.
         By definition, and bit for bit, ``yuv.rgb_to_yuv420(forward_u8(yuv.yuv420_to_rgb(f0),
         yuv.yuv420_to_rgb(f1), t))`` with the integer conversions of :mod:`rrin_amd.yuv` (``coef``:
         ``yuv.coefficients(...)`` or any 15 ints; None is BT.709 limited range), computed inside
@@ -172,11 +174,11 @@ class Net(nn.Module):
                                 scene_threshold=scene_threshold, gate=gate)
                 for k, t in enumerate(ts)]
 
-    def pair_stats_yuv(self, f0, f1):
+    def pair_stats_yuv(self, f0, f1, layout="nv12"):
         """int64 device tensor ``[N]``: the sum of absolute byte differences, luma and chroma, of
         every pair of two 4:2:0 stacks -- what ``forward_yuv``'s ``scene_threshold`` compares with
-        ``floor(threshold * H0*W0*3/2)``."""
-        return self.engine().pair_stats_yuv(f0, f1)
+        ``floor(threshold * H0*W0*3/2)`` (a 4:2:2 / 4:4:4 ``layout``: ``2*H0*W0`` / ``3*H0*W0`` bytes)."""
+        return self.engine().pair_stats_yuv(f0, f1, layout=layout)
 
     def forward_u16(self, f0, f1, t=0.5, depth=10, scene_threshold=None, gate=None):
         """``forward_u8`` on 16-bit frames: uint16 ``[N,H0,W0,3]`` RGB samples of ``depth`` 9..16 (in
@@ -229,10 +231,10 @@ class Net(nn.Module):
                                   streams=self.streams, scene_threshold=scene_threshold, gate=gate)
                 for k, t in enumerate(ts)]
 
-    def pair_stats_yuv16(self, f0, f1, depth=10, msb=False):
+    def pair_stats_yuv16(self, f0, f1, depth=10, msb=False, layout="nv12"):
         """int64 device tensor ``[N]``: the exact sum of absolute differences of the samples
         ``min(word >> shift, maxval)``, luma and chroma, of every pair of two uint16 4:2:0 stacks."""
-        return self.engine().pair_stats_yuv16(f0, f1, depth=depth, msb=msb)
+        return self.engine().pair_stats_yuv16(f0, f1, depth=depth, msb=msb, layout=layout)
 
     @property
     def last_gate(self):

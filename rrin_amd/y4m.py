@@ -1,6 +1,7 @@
 """YUV4MPEG2 (Y4M) streams of 8-bit 4:2:0 frames: what ``ffmpeg -f yuv4mpegpipe`` writes and reads
 (and, for callers that ask with ``depths=``, the 10- and 12-bit ``C420p10`` / ``C420p12`` streams of
-``-pix_fmt yuv420p10le`` / ``yuv420p12le``).
+``-pix_fmt yuv420p10le`` / ``yuv420p12le``; with ``chroma=``, planar 4:2:2 and 4:4:4 of 8, 10 and 12
+bits: ``-pix_fmt yuv422p10le`` and its kin).
 
 A stream is one header line ``YUV4MPEG2 W<w> H<h> F<num>:<den> [I..] [A..] [C..] [X..]`` and, per
 frame, a line ``FRAME[ params]`` followed by the planes Y, U, V (``w*h*3/2`` bytes for 4:2:0:
@@ -16,7 +17,23 @@ MAGIC = b"YUV4MPEG2"
 C420 = ("420", "420jpeg", "420mpeg2", "420paldv")
 # tags of 4:2:0 in 16-bit little-endian words, the sample in the low bits: tag -> bit depth
 C420_DEEP = {"420p10": 10, "420p12": 12}
+# opt-in (``chroma=``): tags of planar 4:2:2 / 4:4:4 -> (chroma format, bit depth); the deep ones in
+# 16-bit little-endian words like C420_DEEP
+C4XX = {"422": ("422", 8), "444": ("444", 8), "422p10": ("422", 10), "422p12": ("422", 12),
+        "444p10": ("444", 10), "444p12": ("444", 12)}
 _MAX_LINE = 4096
+
+
+def _samples(w: int, h: int, chroma: str) -> int:
+    """Samples of a w x h frame: Y, U and V planes of the chroma format."""
+    return w * h * 3 // 2 if chroma == "420" else w * h * (2 if chroma == "422" else 3)
+
+
+def _check_size(w: int, h: int, chroma: str) -> None:
+    if chroma == "420" and (w % 2 or h % 2):
+        raise ValueError(f"Y4M: 4:2:0 frames need even W and H, got {w}x{h}")
+    if chroma == "422" and w % 2:
+        raise ValueError(f"Y4M: 4:2:2 frames need an even W, got {w}x{h}")
 
 
 def _read_exact(f, n: int) -> np.ndarray:
@@ -59,11 +76,19 @@ class Reader:
     ``depths`` lists the bit depths the caller takes.  With the default ``(8,)`` nothing else is
     read.  With 10 and / or 12 in it ``C420p10`` / ``C420p12`` streams are read too: a frame is then
     a uint16 array of ``height*width*3/2`` little-endian samples (``frame_bytes`` is twice that
-    count) and ``bit_depth`` says which; an 8-bit stream still yields uint8."""
+    count) and ``bit_depth`` says which; an 8-bit stream still yields uint8.
 
-    def __init__(self, fileobj, depths=(8,)):
+    ``chroma`` lists the chroma formats the caller takes; the default ``("420",)`` reads what is
+    described above and nothing else.  With "422" / "444" in it the tags ``C422`` / ``C444`` are read
+    too (planar: the "i422" / "i444" layouts of :mod:`rrin_amd.yuv`; ``height*width*2`` resp. ``*3``
+    samples a frame), and ``C422p10``, ``C422p12``, ``C444p10``, ``C444p12`` if ``depths`` has the
+    depth; ``chroma`` then says which format the stream has.  4:2:2 needs an even W only, 4:4:4 takes
+    any size.  ``Cmono``, ``C411``, ``C444alpha`` and interlaced streams are always refused."""
+
+    def __init__(self, fileobj, depths=(8,), chroma=("420",)):
         self.f = fileobj
         self.bit_depth = 8
+        self.chroma = "420"
         line = _read_line(fileobj)
         tags = line.split(b" ")
         if tags[0] != MAGIC:
@@ -87,7 +112,12 @@ class Reader:
                 if val not in ("p", "?"):
                     raise ValueError(f"Y4M: interlaced streams are not supported (tag {tag!r})")
             elif key == "C":
-                if val in C420_DEEP and C420_DEEP[val] in depths:
+                if val in C4XX and C4XX[val][0] in chroma and C4XX[val][1] in depths:
+                    self.chroma, self.bit_depth = C4XX[val]
+                elif tuple(chroma) != ("420",) and (val not in C420 and val not in C420_DEEP or "420" not in chroma):
+                    raise ValueError(f"Y4M: tag {tag!r} is not among the formats asked for (chroma {tuple(chroma)}, "
+                                     f"depths {tuple(depths)})")
+                elif val in C420_DEEP and C420_DEEP[val] in depths:
                     self.bit_depth = C420_DEEP[val]
                 elif val not in C420 or 8 not in depths:
                     raise ValueError(f"Y4M: only 8-bit 4:2:0 is supported (tag {tag!r})" if tuple(depths) == (8,)
@@ -96,9 +126,8 @@ class Reader:
             # A (pixel aspect) and X (comments) do not change the bytes
         if not self.width or not self.height or self.width < 1 or self.height < 1:
             raise ValueError("Y4M: the header lacks W or H")
-        if self.width % 2 or self.height % 2:
-            raise ValueError(f"Y4M: 4:2:0 frames need even W and H, got {self.width}x{self.height}")
-        self.frame_bytes = self.width * self.height * 3 // 2 * (2 if self.bit_depth > 8 else 1)
+        _check_size(self.width, self.height, self.chroma)
+        self.frame_bytes = _samples(self.width, self.height, self.chroma) * (2 if self.bit_depth > 8 else 1)
 
     def __iter__(self):
         return self
@@ -119,20 +148,31 @@ class Writer:
     """Writes a progressive 8-bit 4:2:0 Y4M stream to a file object open for binary writing: the
     header on construction, then :meth:`write` per frame (``height*width*3/2`` bytes: Y, U, V).
     With 10 and / or 12 in ``depths`` the colour spaces ``420p10`` / ``420p12`` are written too:
-    a frame is then ``height*width*3/2`` uint16 samples, stored little-endian."""
+    a frame is then ``height*width*3/2`` uint16 samples, stored little-endian.  With "422" / "444" in
+    ``chroma`` the colour spaces of ``C4XX`` are written as :class:`Reader` reads them."""
 
     def __init__(self, fileobj, w: int, h: int, fps_num: int, fps_den: int = 1, colorspace: str = "420",
-                 depths=(8,)):
-        if w < 2 or h < 2 or w % 2 or h % 2:
-            raise ValueError(f"Y4M: 4:2:0 frames need even W and H, got {w}x{h}")
+                 depths=(8,), chroma=("420",)):
         self.bit_depth = 8
-        if colorspace in C420_DEEP and C420_DEEP[colorspace] in depths:
+        self.chroma = "420"
+        if colorspace in C4XX and C4XX[colorspace][0] in chroma and C4XX[colorspace][1] in depths:
+            self.chroma, self.bit_depth = C4XX[colorspace]
+            if w < 1 or h < 1:
+                raise ValueError(f"Y4M: W and H must be >= 1, got {w}x{h}")
+            _check_size(w, h, self.chroma)
+        elif w < 2 or h < 2 or w % 2 or h % 2:
+            raise ValueError(f"Y4M: 4:2:0 frames need even W and H, got {w}x{h}")
+        elif tuple(chroma) != ("420",) and (colorspace not in C420 and colorspace not in C420_DEEP
+                                            or "420" not in chroma):
+            raise ValueError(f"Y4M: colour space C{colorspace} is not among the formats asked for "
+                             f"(chroma {tuple(chroma)}, depths {tuple(depths)})")
+        elif colorspace in C420_DEEP and C420_DEEP[colorspace] in depths:
             self.bit_depth = C420_DEEP[colorspace]
         elif colorspace not in C420 or 8 not in depths:
             raise ValueError(f"Y4M: only 8-bit 4:2:0 is supported (C{colorspace})" if tuple(depths) == (8,)
                              else f"Y4M: only 4:2:0 of {tuple(depths)} bits is supported (C{colorspace})")
         self.f, self.width, self.height = fileobj, int(w), int(h)
-        self.frame_bytes = w * h * 3 // 2 * (2 if self.bit_depth > 8 else 1)
+        self.frame_bytes = _samples(w, h, self.chroma) * (2 if self.bit_depth > 8 else 1)
         fileobj.write(b"%s W%d H%d F%d:%d Ip C%s\n" % (MAGIC, w, h, fps_num, fps_den, colorspace.encode()))
 
     def write(self, frame) -> None:

@@ -18,6 +18,13 @@ bytes: H0 rows of luma, then
 
 Chroma is one sample per 2x2 block of pixels, replicated on the way in and the block's mean on
 the way out (no interpolated siting).
+
+4:2:2 and 4:4:4 (``yuv_to_rgb`` / ``rgb_to_yuv`` and their 16-bit twins, below the 4:2:0 functions)
+are the same path with another chroma block -- 2x1 pixels (two wide, one row tall) and one pixel:
+
+* ``"nv16"`` / ``"i422"``: uint8 ``[N, 2*H0, W0]``, H0 luma rows then ``H0*W0`` chroma bytes: H0 rows
+  of interleaved U, V, or the U plane then the V plane, each H0 x W0/2.  W0 even, any H0 >= 1.
+* ``"i444"``: ``[N, 3*H0, W0]``, the Y, U and V planes; any H0, W0 >= 1.
 """
 from __future__ import annotations
 
@@ -26,6 +33,10 @@ from collections import namedtuple
 import torch
 
 LAYOUTS = ("nv12", "i420")
+LAYOUTS_422 = ("nv16", "i422")
+LAYOUTS_444 = ("i444",)
+ALL_LAYOUTS = LAYOUTS + LAYOUTS_422 + LAYOUTS_444
+CHROMAS = ("420", "422", "444")
 
 Coef = namedtuple("Coef", "y0 ay rv gu gv bu yr yg yb ur ug ub vr vg vb")
 Coef.__doc__ = """The 15 Q14 integers of rrin_yuv_coef (include/rrin_hip.h), in its order: y0, ay, rv,
@@ -111,6 +122,11 @@ def int_to_words(x: torch.Tensor) -> torch.Tensor:
     return x.to(torch.int16).view(torch.uint16)
 
 
+def _need_420(layout) -> None:
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout must be one of {LAYOUTS}, got {layout!r}")
+
+
 def frame_size(frames: torch.Tensor):
     """(H0, W0) of a uint8 ``[N, 3*H0//2, W0]`` stack; ValueError unless both are even."""
     if frames.dim() != 3:
@@ -122,7 +138,10 @@ def frame_size(frames: torch.Tensor):
 
 
 def split_planes(frames: torch.Tensor, layout: str = "nv12"):
-    """Y ``[N,H0,W0]``, U and V ``[N,H0/2,W0/2]`` of a stack (copies, same dtype)."""
+    """Y ``[N,H0,W0]``, U and V ``[N,H0/2,W0/2]`` of a stack (copies, same dtype); for a 4:2:2 or
+    4:4:4 layout U and V are ``[N,H0,W0/2]`` / ``[N,H0,W0]``."""
+    if layout in LAYOUTS_422 or layout in LAYOUTS_444:
+        return _split_planes_4xx(frames, layout)
     if layout not in LAYOUTS:
         raise ValueError(f"layout must be one of {LAYOUTS}, got {layout!r}")
     h0, w0 = frame_size(frames)
@@ -137,7 +156,12 @@ def split_planes(frames: torch.Tensor, layout: str = "nv12"):
 
 
 def join_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, layout: str = "nv12") -> torch.Tensor:
-    """The inverse of :func:`split_planes`: a dense ``[N, 3*H0//2, W0]`` stack."""
+    """The inverse of :func:`split_planes`: a dense ``[N, 3*H0//2, W0]`` stack (4:2:2: ``[N, 2*H0, W0]``,
+    4:4:4: ``[N, 3*H0, W0]``)."""
+    if layout in LAYOUTS_422 or layout in LAYOUTS_444:
+        n, _, w0 = y.shape
+        c = torch.stack((u, v), dim=3 if layout == "nv16" else 1)
+        return torch.cat((y, c.reshape(n, -1, w0)), dim=1)
     if layout not in LAYOUTS:
         raise ValueError(f"layout must be one of {LAYOUTS}, got {layout!r}")
     n, h0, w0 = y.shape
@@ -155,6 +179,7 @@ def yuv420_to_rgb(frames: torch.Tensor, layout: str = "nv12", coef=None) -> torc
     """
     if frames.dtype != torch.uint8:
         raise TypeError("4:2:0 frames are uint8")
+    _need_420(layout)
     k = as_coef(coef)
     y, u, v = split_planes(frames, layout)
     c = (y.to(torch.int32) - k.y0) * k.ay + 8192
@@ -181,6 +206,7 @@ def rgb_to_yuv420(rgb: torch.Tensor, layout: str = "nv12", coef=None) -> torch.T
     n, h0, w0, _ = rgb.shape
     if h0 < 2 or w0 < 2 or h0 % 2 or w0 % 2:
         raise ValueError(f"4:2:0 needs even H0 and W0, got {h0}x{w0}")
+    _need_420(layout)
     k = as_coef(coef)
     p = rgb.to(torch.int32)
     r, g, b = p[..., 0], p[..., 1], p[..., 2]
@@ -224,6 +250,7 @@ def _to_rgb_words(frames, layout, coef, depth, msb):
     """yuv420_to_rgb16 at any depth 8..14 (depth 8 is yuv420_to_rgb on the same values)."""
     if frames.dtype != torch.uint16:
         raise TypeError("16-bit 4:2:0 frames are uint16")
+    _need_420(layout)
     k = as_coef(coef, depth)
     half, maxval = 1 << (depth - 1), (1 << depth) - 1
     y, u, v = split_planes(frames, layout)
@@ -251,6 +278,7 @@ def _to_yuv_words(rgb, layout, coef, depth, msb):
     n, h0, w0, _ = rgb.shape
     if h0 < 2 or w0 < 2 or h0 % 2 or w0 % 2:
         raise ValueError(f"4:2:0 needs even H0 and W0, got {h0}x{w0}")
+    _need_420(layout)
     k = as_coef(coef, depth)
     half, maxval = 1 << (depth - 1), (1 << depth) - 1
     p = samples16(rgb, depth, False)
@@ -260,5 +288,182 @@ def _to_yuv_words(rgb, layout, coef, depth, msb):
     rs, gs, bs = s[..., 0], s[..., 1], s[..., 2]
     u = (half + ((k.ur * rs + k.ug * gs + k.ub * bs + 32768) >> 16)).clamp_(0, maxval)
     v = (half + ((k.vr * rs + k.vg * gs + k.vb * bs + 32768) >> 16)).clamp_(0, maxval)
+    sh = 16 - depth if msb else 0
+    return join_planes(int_to_words(y << sh), int_to_words(u << sh), int_to_words(v << sh), layout)
+
+
+# ---- any chroma format: 4:2:0, 4:2:2, 4:4:4 ---------------------------------------------------
+# The path of a layout is defined as
+#
+#     forward_yuv(f0, f1, t, layout) == rgb_to_yuv(forward_u8(yuv_to_rgb(f0, layout), yuv_to_rgb(f1, layout), t), layout)
+#
+# The way in is the per-pixel formula of yuv420_to_rgb with the U, V of the pixel's block.  The way
+# out keeps the luma formula; a chroma block of P pixels (4:2:0: 4, 4:2:2: 2, 4:4:4: 1) with
+# component sums Rs, Gs, Bs gives
+#
+#     U = clip(mid + ((ur*Rs + ug*Gs + ub*Bs + 8192*P) >> (14 + log2 P)))        (V likewise)
+#
+# which for P = 4 is the "+ 32768 >> 16" above: the mean of the block's Q14 values, rounded half
+# up.  Since ur + ug + ub == 0, grey still maps to U = V = mid exactly at every P.
+def chroma_of(layout: str) -> str:
+    """The chroma format of a layout: "420", "422" or "444"; ValueError for an unknown layout."""
+    if layout in LAYOUTS:
+        return "420"
+    if layout in LAYOUTS_422:
+        return "422"
+    if layout in LAYOUTS_444:
+        return "444"
+    raise ValueError(f"layout must be one of {ALL_LAYOUTS}, got {layout!r}")
+
+
+def block_of(chroma: str):
+    """(rows, columns) of pixels per chroma sample."""
+    return {"420": (2, 2), "422": (1, 2), "444": (1, 1)}[chroma]
+
+
+def stack_size(frames: torch.Tensor, layout: str = "nv12"):
+    """(H0, W0) of a dense stack of ``layout``: :func:`frame_size` for the 4:2:0 layouts,
+    ``[N, 2*H0, W0]`` with W0 even for 4:2:2 and ``[N, 3*H0, W0]`` for 4:4:4."""
+    chroma = chroma_of(layout)
+    if chroma == "420":
+        return frame_size(frames)
+    if frames.dim() != 3:
+        raise ValueError(f"expected a [N, rows, W0] 4:{chroma[1:2]}:{chroma[2:]} stack, got {tuple(frames.shape)}")
+    rows, w0 = frames.shape[1], frames.shape[2]
+    if chroma == "422":
+        if rows < 2 or rows % 2 or w0 < 2 or w0 % 2:
+            raise ValueError(f"4:2:2 needs an even W0: a [N, 2*H0, W0] stack, got {tuple(frames.shape)}")
+        return rows // 2, w0
+    if rows < 3 or rows % 3 or w0 < 1:
+        raise ValueError(f"4:4:4 needs a [N, 3*H0, W0] stack, got {tuple(frames.shape)}")
+    return rows // 3, w0
+
+
+def stack_rows(h0: int, layout: str) -> int:
+    """Rows of a dense ``[N, rows, W0]`` stack of H0-row frames."""
+    return {"420": 3 * h0 // 2, "422": 2 * h0, "444": 3 * h0}[chroma_of(layout)]
+
+
+def check_size(h0: int, w0: int, layout: str) -> None:
+    """ValueError unless H0 x W0 frames exist in ``layout``'s chroma format."""
+    chroma = chroma_of(layout)
+    by, bx = block_of(chroma)
+    if h0 < by or w0 < bx or h0 % by or w0 % bx:
+        need = {"420": "even H0 and W0", "422": "an even W0", "444": "H0, W0 >= 1"}[chroma]
+        raise ValueError(f"4:{chroma[1]}:{chroma[2]} needs {need}, got {h0}x{w0}")
+
+
+def _split_planes_4xx(frames: torch.Tensor, layout: str):
+    """split_planes for the 4:2:2 and 4:4:4 layouts."""
+    chroma = chroma_of(layout)
+    h0, w0 = stack_size(frames, layout)
+    n = frames.shape[0]
+    y = frames[:, :h0]
+    c = frames[:, h0:].reshape(n, -1)
+    cw = w0 // 2 if chroma == "422" else w0
+    if layout == "nv16":
+        uv = c.reshape(n, h0, cw, 2)
+        return y, uv[..., 0], uv[..., 1]
+    uv = c.reshape(n, 2, h0, cw)
+    return y, uv[:, 0], uv[:, 1]
+
+
+def _spread(c: torch.Tensor, chroma: str) -> torch.Tensor:
+    """A chroma plane replicated over its blocks: ``[N,H0,W0]``."""
+    by, bx = block_of(chroma)
+    if by > 1:
+        c = c.repeat_interleave(by, 1)
+    return c.repeat_interleave(bx, 2) if bx > 1 else c
+
+
+def _block_chroma(p, kr, kg, kb, mid, maxval, chroma):
+    """The chroma plane of int32 RGB samples ``p`` [N,H0,W0,3]: the block rule written above."""
+    n, h0, w0, _ = p.shape
+    by, bx = block_of(chroma)
+    s = p.reshape(n, h0 // by, by, w0 // bx, bx, 3).sum(dim=(2, 4), dtype=torch.int32)
+    log2p = {4: 2, 2: 1, 1: 0}[by * bx]
+    q = kr * s[..., 0] + kg * s[..., 1] + kb * s[..., 2] + (8192 << log2p)
+    return (mid + (q >> (14 + log2p))).clamp_(0, maxval)
+
+
+def yuv_to_rgb(frames: torch.Tensor, layout: str = "nv12", coef=None) -> torch.Tensor:
+    """A uint8 stack of any layout -> uint8 RGB ``[N,H0,W0,3]``: :func:`yuv420_to_rgb`'s formulas with
+    the U, V of the pixel's block (2x2, 2x1 or the pixel itself), replicated."""
+    chroma = chroma_of(layout)
+    if chroma == "420":
+        return yuv420_to_rgb(frames, layout, coef)
+    if frames.dtype != torch.uint8:
+        raise TypeError(f"4:{chroma[1]}:{chroma[2]} frames are uint8")
+    k = as_coef(coef)
+    y, u, v = split_planes(frames, layout)
+    c = (y.to(torch.int32) - k.y0) * k.ay + 8192
+    d = _spread(u.to(torch.int32) - 128, chroma)
+    e = _spread(v.to(torch.int32) - 128, chroma)
+    rgb = torch.stack((c + k.rv * e, c + k.gu * d + k.gv * e, c + k.bu * d), dim=3)
+    return (rgb >> 14).clamp_(0, 255).to(torch.uint8)
+
+
+def rgb_to_yuv(rgb: torch.Tensor, layout: str = "nv12", coef=None) -> torch.Tensor:
+    """uint8 RGB ``[N,H0,W0,3]`` -> a uint8 stack of ``layout``: the luma of :func:`rgb_to_yuv420` per
+    pixel, and per chroma block of P pixels ``clip255(128 + ((ur*Rs + ug*Gs + ub*Bs + 8192*P) >>
+    (14 + log2 P)))`` (V likewise)."""
+    chroma = chroma_of(layout)
+    if chroma == "420":
+        return rgb_to_yuv420(rgb, layout, coef)
+    if rgb.dtype != torch.uint8:
+        raise TypeError("RGB frames are uint8")
+    if rgb.dim() != 4 or rgb.shape[3] != 3:
+        raise ValueError(f"expected [N,H0,W0,3] RGB frames, got {tuple(rgb.shape)}")
+    check_size(rgb.shape[1], rgb.shape[2], layout)
+    k = as_coef(coef)
+    p = rgb.to(torch.int32)
+    y = (k.y0 + ((k.yr * p[..., 0] + k.yg * p[..., 1] + k.yb * p[..., 2] + 8192) >> 14)).clamp_(0, 255)
+    u = _block_chroma(p, k.ur, k.ug, k.ub, 128, 255, chroma)
+    v = _block_chroma(p, k.vr, k.vg, k.vb, 128, 255, chroma)
+    return join_planes(y.to(torch.uint8), u.to(torch.uint8), v.to(torch.uint8), layout)
+
+
+def yuv_to_rgb16(frames: torch.Tensor, layout: str = "nv12", coef=None, depth: int = 10,
+                 msb: bool = False) -> torch.Tensor:
+    """:func:`yuv420_to_rgb16` for any layout: a uint16 stack of ``depth`` 10 or 12 -> uint16 RGB
+    ``[N,H0,W0,3]`` samples of that depth.  The int32 bound of the way in does not depend on the
+    block; that of the way out (:func:`as_coef`: a 2x2 block of 12-bit samples) is only looser
+    for the 2- and 1-pixel blocks, so the coefficient bounds are those of 4:2:0."""
+    depth = check_depth16(depth)
+    chroma = chroma_of(layout)
+    if chroma == "420":
+        return _to_rgb_words(frames, layout, coef, depth, msb)
+    if frames.dtype != torch.uint16:
+        raise TypeError(f"16-bit 4:{chroma[1]}:{chroma[2]} frames are uint16")
+    k = as_coef(coef, depth)
+    half, maxval = 1 << (depth - 1), (1 << depth) - 1
+    y, u, v = split_planes(frames, layout)
+    c = (samples16(y, depth, msb) - k.y0) * k.ay + 8192
+    d = _spread(samples16(u, depth, msb) - half, chroma)
+    e = _spread(samples16(v, depth, msb) - half, chroma)
+    rgb = torch.stack((c + k.rv * e, c + k.gu * d + k.gv * e, c + k.bu * d), dim=3)
+    return int_to_words((rgb >> 14).clamp_(0, maxval))
+
+
+def rgb16_to_yuv(rgb: torch.Tensor, layout: str = "nv12", coef=None, depth: int = 10,
+                 msb: bool = False) -> torch.Tensor:
+    """:func:`rgb16_to_yuv420` for any layout, with :func:`rgb_to_yuv`'s block rule, ``half`` for 128
+    and a clip to maxval.  The chroma sum of a block of P <= 4 samples, ``3 * (2**15 - 1) * P * 4095 +
+    8192 * P``, is largest at P = 4 (:func:`as_coef`): the smaller blocks only loosen the int32 bound."""
+    depth = check_depth16(depth)
+    chroma = chroma_of(layout)
+    if chroma == "420":
+        return _to_yuv_words(rgb, layout, coef, depth, msb)
+    if rgb.dtype != torch.uint16:
+        raise TypeError("16-bit RGB frames are uint16")
+    if rgb.dim() != 4 or rgb.shape[3] != 3:
+        raise ValueError(f"expected [N,H0,W0,3] RGB frames, got {tuple(rgb.shape)}")
+    check_size(rgb.shape[1], rgb.shape[2], layout)
+    k = as_coef(coef, depth)
+    half, maxval = 1 << (depth - 1), (1 << depth) - 1
+    p = samples16(rgb, depth, False)
+    y = (k.y0 + ((k.yr * p[..., 0] + k.yg * p[..., 1] + k.yb * p[..., 2] + 8192) >> 14)).clamp_(0, maxval)
+    u = _block_chroma(p, k.ur, k.ug, k.ub, half, maxval, chroma)
+    v = _block_chroma(p, k.vr, k.vg, k.vb, half, maxval, chroma)
     sh = 16 - depth if msb else 0
     return join_planes(int_to_words(y << sh), int_to_words(u << sh), int_to_words(v << sh), layout)

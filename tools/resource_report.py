@@ -22,4 +22,5 @@ for k, v in rows.items():
     name = re.sub(r"_ZN4rrin\d+", "", k)
     print(f"{name[:60]:60s} vgpr {v.get('VGPRs','?'):>4} agpr {v.get('AGPRs','?'):>4} "
           f"occ {v.get('Occupancy [waves/SIMD]','?')} sgpr_spill {v.get('SGPRs Spill','?')} "
-          f"vgpr_spill {v.get('VGPRs Spill','?')} lds {v.get('LDS Size [bytes/block]','?')}")
+          f"vgpr_spill {v.get('VGPRs Spill','?')} scratch {v.get('ScratchSize [bytes/lane]','?')} "
+          f"lds {v.get('LDS Size [bytes/block]','?')}")
