@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define RRIN_ABI_VERSION 24
+#define RRIN_ABI_VERSION 25
 
 #define RRIN_OK 0
 #define RRIN_E_SHAPE (-1)     /* H or W not a multiple of 16, or N < 1          */
@@ -544,6 +544,12 @@ int rrin_flow_tblend_fwd(const rrin_pp* flow_raw, const rrin_pp* g16, const floa
                          void* stream);
 int rrin_flow_tblend_h8(const rrin_h8* flow_raw, const rrin_h8* g16, const float* coef, int32_t n,
                         int32_t prec, void* stream);
+/* ABI 25: the same blend for n items over the kept raw Flow of n_pairs pairs: image k of g16 gets
+ * Ft0 / Ft1 from image clamp(pair_map[k], 0, n_pairs - 1) of flow_raw with coef row k.  pair_map:
+ * device int32 [n].  A null map, n_pairs < 1 or n_pairs > n: RRIN_E_ARG; the other checks are
+ * rrin_flow_tblend_h8's.  With pair_map[k] == k it writes what rrin_flow_tblend_h8 writes. */
+int rrin_flow_tblend_items_h8(const rrin_h8* flow_raw, const rrin_h8* g16, const float* coef, int32_t n,
+                              const int32_t* pair_map, int32_t n_pairs, int32_t prec, void* stream);
 
 /* ---- Whole forward (native schedule) ------------------------------------- */
 /* Per-conv weight table entry, in Net conv order (rrin_net_conv_count). */
@@ -731,6 +737,31 @@ typedef struct rrin_net_yuv16_desc {
 } rrin_net_yuv16_desc;
 int rrin_net_yuv16_fwd(const rrin_net_yuv16_desc* d, void* stream);
 
+/* ABI 25: item forwards.  A frame forward whose batch is a list of net.n ITEMS (pair index, t)
+ * over n_pairs <= net.n distinct pairs: f0 / f1 hold n_pairs frames each (two views of one
+ * [n_pairs + 1] stack), out holds net.n frames, net.coef has one row per item, and item k is, bit
+ * for bit, the frame that the plain forward of pair pair_map[k] alone returns for coef row k.  The
+ * Flow U-Net runs once over the n_pairs pairs, the other three U-Nets over the net.n items; both
+ * phases share the one workspace and scratch of a plain forward of net.n (rrin_net_workspace_bytes
+ * / rrin_net_scratch_bytes with n = net.n): no buffer's image stride depends on the batch, so the
+ * Flow phase uses images [0, n_pairs) of the same plan.  net.skip_flow = 1 skips the Flow phase:
+ * the workspace then keeps the raw Flow of the same n_pairs pairs from the previous item call.
+ * pair_map: device int32 [net.n]; its values are clamped to [0, n_pairs) where they are read, so
+ * no map reads outside the stacks (callers check them on the host).  Validated before any HIP
+ * call: a null rrin_items, n_pairs < 1, n_pairs > net.n, a null map with n_pairs != net.n, or
+ * net.taps set: RRIN_E_ARG; then the frame forward's own checks, with the stride / span rules of
+ * f0 and f1 applied to n_pairs frames and those of out to net.n.  A null map with
+ * n_pairs == net.n is the plain forward. */
+typedef struct rrin_items {
+  int32_t n_pairs;
+  int32_t pad_;
+  const int32_t* pair_map;
+} rrin_items;
+int rrin_net_u8_items_fwd(const rrin_net_u8_desc* d, const rrin_items* items, void* stream);
+int rrin_net_yuv_items_fwd(const rrin_net_yuv_desc* d, const rrin_items* items, void* stream);
+int rrin_net_u16_items_fwd(const rrin_net_u16_desc* d, const rrin_items* items, void* stream);
+int rrin_net_yuv16_items_fwd(const rrin_net_yuv16_desc* d, const rrin_items* items, void* stream);
+
 /* ---- Scene-cut / duplicate-frame gate of the 8-bit frame path (ABI 21) ------------------
  * Three small kernels for the stream of a rrin_net_u8_fwd call, so that a caller can replace the
  * interpolated frame of a pair that is a shot change or a repeated frame by one of its input
@@ -772,6 +803,19 @@ int rrin_pair_sad_u16_len(const uint16_t* f0, const uint16_t* f1, int64_t img_st
                           int32_t depth, int32_t shift, uint64_t* sad, void* stream);
 int rrin_gate_frames_u8_len(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int64_t len,
                             const int32_t* gate, uint8_t* out, void* stream);
+/* ABI 25: the gate of an item forward.  The sums and rrin_gate_from_sad_u8 (with cut_code 2) run
+ * once per pair; an item inherits its pair's decision.
+ * rrin_gate_items_u8: gate[k] = 1 if pair_gate[p] == 1 (a duplicate: the first frame), cut_codes[k]
+ * if pair_gate[p] == 2 (a cut: the item's own nearer frame, 1 or 2; anything else gives 0), else
+ * 0, with p = clamp(pair_map[k], 0, n_pairs - 1); all arrays on the device, pair_gate [n_pairs],
+ * the others [n].
+ * rrin_gate_frames_items_u8_len: rrin_gate_frames_u8_len for n output frames whose sources are
+ * frame p (as above) of f0 / f1.  Null pointers, n_pairs < 1 or n_pairs > n: RRIN_E_ARG. */
+int rrin_gate_items_u8(const int32_t* pair_gate, int32_t n_pairs, const int32_t* pair_map, const int32_t* cut_codes,
+                       int32_t n, int32_t* gate, void* stream);
+int rrin_gate_frames_items_u8_len(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int64_t len,
+                                  const int32_t* gate, uint8_t* out, const int32_t* pair_map, int32_t n_pairs,
+                                  void* stream);
 
 /* ---- Training path (autograd): NCHW fp32 kernels ------------------------- */
 /* With autograd on (the reference trains through Net.forward, train.py:98, and

@@ -43,6 +43,10 @@ def build_parser():
                          "through the network as YUV.  --fps is ignored (the rate comes from the stream)")
     cv.add_argument("--y4m_out", type=str, default=None, metavar="PATH|-",
                     help="write the interpolated Y4M stream here (\"-\": stdout)")
+    cv.add_argument("--fps_out", type=str, default=None, metavar="NUM[/DEN]",
+                    help="with --y4m_in / --y4m_out: convert the stream's frame rate to this higher rate, e.g. "
+                         "60000/1001 or 60 (24 -> 60, 25 -> 30, ...), instead of --sf intermediates per pair; "
+                         "needs --sf 0.  Quality at uneven t has not been validated on footage")
     return p
 
 

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librrin_hip.so")
 # A/B sessions only (tools/sessions/): another build of the same library, e.g. ab/librrin_hip_X.so
 if os.environ.get("RRIN_LIB_AB"):
@@ -162,6 +162,11 @@ class NetYuv16Desc(C.Structure):
                 ("h0", C.c_int32), ("w0", C.c_int32), ("pad_", C.c_int32)]
 
 
+class Items(C.Structure):
+    """rrin_items: the pairs of an item forward and the device int32 map item -> pair."""
+    _fields_ = [("n_pairs", C.c_int32), ("pad_", C.c_int32), ("pair_map", C.c_void_p)]
+
+
 class TConvDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
                 ("mode", C.c_int32), ("leaky", C.c_int32), ("slope", C.c_float), ("x", C.c_void_p),
@@ -262,6 +267,16 @@ SIGNATURES = {
     "rrin_flow_tblend_fwd": (C.c_int, [C.POINTER(PP), C.POINTER(PP), C.c_void_p, C.c_int32, C.c_void_p]),
     "rrin_flow_tblend_h8": (C.c_int, [C.POINTER(H8), C.POINTER(H8), C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_void_p]),
+    "rrin_flow_tblend_items_h8": (C.c_int, [C.POINTER(H8), C.POINTER(H8), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                            C.c_int32, C.c_void_p]),
+    "rrin_net_u8_items_fwd": (C.c_int, [C.POINTER(NetU8Desc), C.POINTER(Items), C.c_void_p]),
+    "rrin_net_yuv_items_fwd": (C.c_int, [C.POINTER(NetYuvDesc), C.POINTER(Items), C.c_void_p]),
+    "rrin_net_u16_items_fwd": (C.c_int, [C.POINTER(NetU16Desc), C.POINTER(Items), C.c_void_p]),
+    "rrin_net_yuv16_items_fwd": (C.c_int, [C.POINTER(NetYuv16Desc), C.POINTER(Items), C.c_void_p]),
+    "rrin_gate_items_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                     C.c_void_p]),
+    "rrin_gate_frames_items_u8_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "rrin_net_fwd": (C.c_int, [C.POINTER(NetDesc), C.c_void_p]),
     "rrin_net_u8_fwd": (C.c_int, [C.POINTER(NetU8Desc), C.c_void_p]),
     "rrin_net_yuv_fwd": (C.c_int, [C.POINTER(NetYuvDesc), C.c_void_p]),

@@ -454,7 +454,7 @@ def _retire(item, sf, dest, put, model=None):
         put(shutil.copy, m1["path"], os.path.join(dest, f"{base + sf + 1:09d}{m1['filetype']}"))
 
 
-def interpolate_y4m(model, src, dst, sf, batch=4, scene_threshold=None, coef=None, log=print):
+def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coef=None, log=print, fps_out=None):
     """Interpolate a Y4M stream (8-bit 4:2:0; also 10 / 12 bits and 4:2:2 / 4:4:4, below) into another: no image folder, no RGB frame anywhere.
 
     ``src`` / ``dst`` are binary file objects (files or pipes: they are read and written
@@ -476,8 +476,16 @@ def interpolate_y4m(model, src, dst, sf, batch=4, scene_threshold=None, coef=Non
     A 4:2:2 or 4:4:4 stream (``C422``, ``C444`` and their ``p10`` / ``p12`` forms) runs through the same
     two calls with ``layout="i422"`` / ``"i444"`` on ``[N, 2*H0, W0]`` / ``[N, 3*H0, W0]`` stacks; the
     output keeps the tag, and ``scene_threshold`` is a mean over the frame's ``2*H0*W0`` / ``3*H0*W0``
-    samples."""
+    samples.
+
+    Exactly one of ``sf`` and ``fps_out`` is given.  ``fps_out`` (a ``fractions.Fraction``, an int or
+    a string ``"60000/1001"`` / ``"60"``, above the stream's rate) converts the frame rate instead:
+    :func:`retime_y4m`."""
     from . import y4m, yuv
+    if (sf is None) == (fps_out is None):
+        raise ValueError("interpolate_y4m takes exactly one of sf and fps_out")
+    if fps_out is not None:
+        return retime_y4m(model, src, dst, fps_out, batch=batch, scene_threshold=scene_threshold, coef=coef, log=log)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise RuntimeError("interpolate_y4m runs in a single process (a stream has one reader and one writer)")
     if sf < 1 or batch < 1:
@@ -581,6 +589,151 @@ def interpolate_y4m(model, src, dst, sf, batch=4, scene_threshold=None, coef=Non
             f.close()
 
 
+def retime_y4m(model, src, dst, fps_out, batch=4, scene_threshold=None, coef=None, log=print):
+    """Convert the frame rate of a Y4M stream to any higher rate ``fps_out`` (24 -> 60, 24000/1001 ->
+    60000/1001, 25 -> 30, ...): ``interpolate_y4m(fps_out=)``.  Output j is the frame at source time
+    ``j * fps_in / fps_out`` (:mod:`rrin_amd.retime`): an input frame's own bytes where that time is
+    a whole number (a pass-through, never sent to the network), else one item of
+    ``model.interpolate_items_yuv`` / ``interpolate_items_yuv16``.  A step takes the next ``batch``
+    ITEMS of the schedule, however unevenly they fall on the pairs (at 24 -> 60 a pair gets 3, 2,
+    3, 2, ... of them), and uploads the frames they span as one stack, so the device sees full
+    batches until the stream ends; the Flow U-Net runs once per pair of a step.  The header
+    carries ``fps_out`` reduced; tag, depth, chroma, ``coef`` and ``scene_threshold`` follow the
+    stream as in :func:`interpolate_y4m` (a cut pair's items take the nearer frame by their own t).
+    Output quality at uneven t has not been validated on footage.  Returns the frames written."""
+    from collections import deque
+
+    from . import retime, y4m, yuv
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("interpolate_y4m runs in a single process (a stream has one reader and one writer)")
+    if batch < 1:
+        raise ValueError(f"batch must be >= 1, got {batch}")
+    rate_out = retime.as_rate(fps_out)
+    opened = []
+    if isinstance(src, (str, os.PathLike)):
+        src = open(src, "rb")
+        opened.append(src)
+    if isinstance(dst, (str, os.PathLike)):
+        dst = open(dst, "wb")
+        opened.append(dst)
+    try:
+        rd = y4m.Reader(src, depths=(8, 10, 12), chroma=yuv.CHROMAS)
+        w0, h0 = rd.width, rd.height
+        if rd.fps_num < 1 or rd.fps_den < 1:
+            raise ValueError(f"Y4M: the stream has no frame rate to convert (F{rd.fps_num}:{rd.fps_den})")
+        rate_in = retime.as_rate(f"{rd.fps_num}/{rd.fps_den}")
+        sched = retime.Stream(rate_in, rate_out)  # raises unless fps_out > fps_in
+        wr = y4m.Writer(dst, w0, h0, rate_out.numerator, rate_out.denominator, rd.colorspace, depths=(8, 10, 12),
+                        chroma=yuv.CHROMAS)
+        layout = "i" + rd.chroma
+        deep = rd.bit_depth > 8
+        dtype = torch.uint16 if deep else torch.uint8
+        device = next(model.parameters()).device
+        on_gpu = device.type == "cuda"   # a host model (tests) has nothing to pin for and no events
+        gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
+        rows = yuv.stack_rows(h0, layout)
+        t0 = time.time()
+        held = {}        # input frames still needed by an item, by index
+        order = deque()  # the outputs not written yet: a frame's array, or (step, index in it)
+        items = []       # network items (pair, float t) not sent yet
+        steps = deque()  # steps on the device, oldest first
+        n_in = written = passed = gated = 0
+
+        def drain():
+            nonlocal written
+            while order and order[0] is not None and (not isinstance(order[0], tuple) or order[0][0]["done"]):
+                e = order.popleft()
+                wr.write(e[0]["host"][e[1]].numpy() if isinstance(e, tuple) else e)
+                written += 1
+
+        def retire(step):
+            nonlocal gated
+            if step["ev"] is not None:
+                step["ev"].synchronize()
+            if hasattr(model, "check_range"):
+                model.check_range(wait=False)  # fp16-stored precisions: raise instead of writing poisoned frames
+            if step["codes"] is not None:
+                gated += int((step["codes"] != 0).sum())
+            step["done"] = True
+            drain()
+
+        def launch(part):
+            lo, hi = part[0][0], part[-1][0] + 1
+            stack = torch.empty((hi - lo + 1, rows, w0), dtype=dtype, pin_memory=on_gpu)
+            for j in range(lo, hi + 1):
+                stack[j - lo].view(-1).copy_(torch.from_numpy(held[j]))
+            stack = stack.to(device, non_blocking=True)
+            pair, ts = [p - lo for p, _ in part], [t for _, t in part]
+            with torch.no_grad():
+                if deep:
+                    out = model.interpolate_items_yuv16(stack, pair, ts, layout=layout, depth=rd.bit_depth, msb=False,
+                                                        coef=coef, **gate_kw)
+                else:
+                    out = model.interpolate_items_yuv(stack, pair, ts, layout=layout, coef=coef, **gate_kw)
+            host = torch.empty(out.shape, dtype=out.dtype, pin_memory=on_gpu)
+            host.copy_(out, non_blocking=True)
+            codes = None
+            if gate_kw:
+                codes = torch.empty(len(part), dtype=torch.int32, pin_memory=on_gpu)
+                codes.copy_(model.last_gate, non_blocking=True)
+            ev = None
+            if on_gpu:
+                ev = torch.cuda.Event()
+                ev.record()
+            step = {"ev": ev, "host": host, "codes": codes, "done": False}
+            steps.append(step)
+            return step
+
+        def send(part):
+            step = launch(part)
+            k = 0
+            for i, e in enumerate(order):  # the step's items are the oldest unsent ones, in order
+                if e is None:
+                    order[i] = (step, k)
+                    k += 1
+                    if k == len(part):
+                        break
+            for j in [j for j in held if j < part[-1][0]]:  # later items start at the last pair
+                del held[j]
+            while len(steps) > 1:  # retire the previous step while this one computes
+                retire(steps.popleft())
+
+        for fr in rd:
+            held[n_in] = fr
+            n_in += 1
+            for pair, t in sched.feed():
+                if t == 0:  # time == pair: the frame that has just arrived
+                    order.append(fr)
+                    passed += 1
+                else:
+                    order.append(None)  # filled when its step is sent
+                    items.append((pair, float(t)))
+            while len(items) >= batch:
+                send(items[:batch])
+                del items[:batch]
+            drain()
+        if n_in < 2:
+            raise ValueError("need at least two frames in the Y4M stream")
+        if items:
+            send(items)
+        while steps:
+            retire(steps.popleft())
+        drain()
+        if hasattr(model, "check_range"):
+            model.check_range()
+        wr.flush()
+        msg = (f"y4m: {n_in} frames of {w0}x{h0} at {rate_in.numerator}:{rate_in.denominator} fps -> {written} "
+               f"frames at {rate_out.numerator}:{rate_out.denominator} fps in {time.time() - t0:.2f} s, "
+               f"{passed} of them input frames passed through")
+        if gate_kw:
+            msg += f"; scene gate (threshold {scene_threshold:g}): {gated} items replaced by an input frame"
+        log(msg)
+        return written
+    finally:
+        for f in opened:
+            f.close()
+
+
 def find_checkpoint(model_name, models_dir="models"):
     """Last checkpoint whose name starts with model_name (convert.py:100-108);
     sorted order, so Model0150.pth wins over Model0001.pth."""
@@ -621,6 +774,9 @@ def _convert_y4m(args):
         raise Exception("Missing arguments! --y4m_in and --y4m_out go together")
     if args.input_video is not None or args.image_folder is not None:
         raise Exception("--y4m_in / --y4m_out replace --input_video / --image_folder")
+    fps_out = getattr(args, "fps_out", None)
+    if fps_out is not None and args.sf:
+        raise Exception("--fps_out replaces --sf on the Y4M path: pass --sf 0 with it")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise RuntimeError("the Y4M pipe runs in a single process (WORLD_SIZE > 1)")
     if args.no_cuda or not torch.cuda.is_available():
@@ -628,11 +784,12 @@ def _convert_y4m(args):
     src = sys.stdin.buffer if args.y4m_in == "-" else args.y4m_in
     dst = sys.stdout.buffer if args.y4m_out == "-" else args.y4m_out
     with contextlib.redirect_stdout(sys.stderr):
-        print("--fps is ignored with --y4m_in: the output rate is the stream's times (sf + 1)")
+        print("--fps is ignored with --y4m_in: the output rate is " +
+              ("--fps_out" if fps_out is not None else "the stream's times (sf + 1)"))
         dev = torch.device("cuda", torch.cuda.current_device())
         net = load_net(args.model_name, dev, getattr(args, "precision", "fp32"))
-        interpolate_y4m(net, src, dst, args.sf, batch=getattr(args, "batch", 4),
-                        scene_threshold=getattr(args, "scene_threshold", None))
+        interpolate_y4m(net, src, dst, None if fps_out is not None else args.sf, batch=getattr(args, "batch", 4),
+                        scene_threshold=getattr(args, "scene_threshold", None), fps_out=fps_out)
         print("Finished conversion")
 
 

@@ -318,6 +318,26 @@ constexpr size_t kWinoLds = (size_t)(2 * 704 + 2 * 16 * 2 * 32) * 16;
 int launch_wino(const ConvH8Args& a, int epi, hipStream_t st);
 // zero channels [c0, c1) of a record-layout view (glue_h8.hip)
 int clear_channels_h8(const rrin_h8* v, int32_t n, int32_t c0, int32_t c1, int32_t prec, hipStream_t st);
+// Item forwards (ABI 25): image k of the Net buffer reads the frames and the kept raw Flow of pair
+// map[k] of n_pairs.  The map lives on the device, so its values are clamped where they are read: a
+// bad map picks a wrong pair, never memory outside the stacks.
+__device__ inline int pair_of(const int32_t* __restrict__ map, int k, int n_pairs) {
+  return min(max(map[k], 0), n_pairs - 1);
+}
+// The four frame packs (rrin_pack_g16_u8_h8 / _u16 in glue_h8.hip, _yuv / _yuv16 in yuv.hip) for n
+// images that read n_pairs frames of f0 / f1 through the device map (NULL: image k reads frame k
+// and n_pairs == n: the entry points' own launch); the stacks are checked for n_pairs frames.
+int pack_g16_u8_items(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0, int32_t w0,
+                      const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs, hipStream_t st);
+int pack_g16_u16_items(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int32_t h0, int32_t w0,
+                       int32_t depth, const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs,
+                       hipStream_t st);
+int pack_g16_yuv_items(const rrin_yuv420* f0, const rrin_yuv420* f1, const rrin_yuv_coef* coef, int32_t n, int32_t h0,
+                       int32_t w0, const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs,
+                       hipStream_t st);
+int pack_g16_yuv16_items(const rrin_yuv420_16* f0, const rrin_yuv420_16* f1, const rrin_yuv_coef* coef, int32_t n,
+                         int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs,
+                         hipStream_t st);
 // cfg 18's tile on 8 waves of 4 accumulators (<= 128 VGPRs: 4 waves per SIMD),
 // two stages of [raw 680 | U 1024] records (three in A/B builds: two blocks per
 // CU would fill 163,584 B)

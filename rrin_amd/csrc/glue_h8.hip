@@ -130,17 +130,22 @@ __constant__ const U8ScaleTab kU8Scale{};
 // 768 source bytes of each frame are loaded one byte per lane (a wave's load is 64 consecutive
 // bytes, whatever the alignment of the row) into LDS, then every lane converts its pixel through
 // the LDS copy of the scale table and writes the whole records pack_g16_kernel writes.
-template <class F>
+// ITEMS (ABI 25): image img of g16 reads frame pair_of(map, img, n_pairs) of both stacks -- f1 is f0
+// one frame on, so that is pair map[img] of one [n_pairs + 1] stack.  Without it map / n_pairs are
+// unused and the kernel is, instruction for instruction, the one it was before they existed.
+template <class F, bool ITEMS = false>
 __global__ void __launch_bounds__(256) pack_g16_u8_kernel(const uint8_t* __restrict__ f0,
                                                           const uint8_t* __restrict__ f1, int64_t f_img, int w0,
-                                                          int top, RecView g, int w) {
+                                                          int top, RecView g, int w,
+                                                          const int32_t* __restrict__ map, int n_pairs) {
   __shared__ float s_tab[256];
   __shared__ uint8_t s_px[2][768];
   const int tid = threadIdx.x;
   const int xs = blockIdx.x * 256, y = blockIdx.y, img = blockIdx.z;
   s_tab[tid] = kU8Scale.v[tid];
   const int sy = y > top ? y - top : 0;
-  const int64_t row = (int64_t)img * f_img + ((int64_t)sy * w0 + xs) * 3;
+  const int src = ITEMS ? pair_of(map, img, n_pairs) : img;
+  const int64_t row = (int64_t)src * f_img + ((int64_t)sy * w0 + xs) * 3;
   const int nb = min(256, w0 - xs) * 3;  // xs < w0: the right pad is < 16 columns, xs a multiple of 256
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -169,15 +174,18 @@ __global__ void __launch_bounds__(256) pack_g16_u8_kernel(const uint8_t* __restr
 // at any even address; a wave's load is 128 consecutive bytes) into LDS; a pixel's samples are
 // min(word, maxval) and its values sample / maxval by the IEEE division (sample_to_float): no
 // table, which at 16 bits would not fit the LDS.  f_img counts words.
-template <class F>
+// ITEMS: as pack_g16_u8_kernel
+template <class F, bool ITEMS = false>
 __global__ void __launch_bounds__(256) pack_g16_u16_kernel(const uint16_t* __restrict__ f0,
                                                            const uint16_t* __restrict__ f1, int64_t f_img, int w0,
-                                                           int top, RecView g, int w, int maxval) {
+                                                           int top, RecView g, int w, int maxval,
+                                                           const int32_t* __restrict__ map, int n_pairs) {
   __shared__ uint16_t s_px[2][768];
   const int tid = threadIdx.x;
   const int xs = blockIdx.x * 256, y = blockIdx.y, img = blockIdx.z;
   const int sy = y > top ? y - top : 0;
-  const int64_t row = (int64_t)img * f_img + ((int64_t)sy * w0 + xs) * 3;
+  const int src = ITEMS ? pair_of(map, img, n_pairs) : img;
+  const int64_t row = (int64_t)src * f_img + ((int64_t)sy * w0 + xs) * 3;
   const int nb = min(256, w0 - xs) * 3;  // xs < w0: the right pad is < 16 columns, xs a multiple of 256
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -511,9 +519,11 @@ __global__ void __launch_bounds__(256) head_kernel(HeadH8Args a) {
     final_store_yuv(a, img, y0 + r2, x0 + xl, rgb);
 }
 
-// Ft0 / Ft1 (model.py:38-39) from a kept raw Flow record -> g16 channels 6-9
-template <class F>
-__global__ void flow_tblend_kernel(RecView fr, RecView g, const float* coef, int h, int w, int64_t total) {
+// Ft0 / Ft1 (model.py:38-39) from a kept raw Flow record -> g16 channels 6-9.  ITEMS (ABI 25): item
+// img blends the kept raw Flow of pair pair_of(map, img, n_pairs) with its own coefficients
+template <class F, bool ITEMS = false>
+__global__ void flow_tblend_kernel(RecView fr, RecView g, const float* coef, int h, int w, int64_t total,
+                                   const int32_t* __restrict__ map, int n_pairs) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const int x = (int)(i % w);
@@ -522,7 +532,8 @@ __global__ void flow_tblend_kernel(RecView fr, RecView g, const float* coef, int
   const int img = (int)(t / h);
   const float* cf = coef + img * 8;
   float f[F::kChans];
-  F::load_rec(fr, fr.rec(img, 0, y, x), f);
+  const int src = ITEMS ? pair_of(map, img, n_pairs) : img;
+  F::load_rec(fr, fr.rec(src, 0, y, x), f);
   float o[4];
   flow_blend(cf, f, o, o + 2);
   typename F::Px px{g, g.rec(img, 0, y, x), nullptr};
@@ -747,8 +758,9 @@ extern "C" int rrin_head_h8_fwd(const rrin_head_h8_desc* d, void* stream) {
   return RRIN_E_ARG;
 }
 
-extern "C" int rrin_flow_tblend_h8(const rrin_h8* fr, const rrin_h8* g16, const float* coef, int32_t n, int32_t prec,
-                                   void* stream) {
+// rrin_flow_tblend_h8 (map NULL) and rrin_flow_tblend_items_h8
+static int flow_tblend_launch(const rrin_h8* fr, const rrin_h8* g16, const float* coef, int32_t n, const int32_t* map,
+                              int32_t n_pairs, int32_t prec, void* stream) {
   if (!fr || !g16 || !coef || n < 1 || !rec_prec(prec)) return RRIN_E_ARG;
   if (!h8_ok(*fr, prec) || !h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16)
     return RRIN_E_SHAPE;
@@ -757,10 +769,25 @@ extern "C" int rrin_flow_tblend_h8(const rrin_h8* fr, const rrin_h8* g16, const 
   const int64_t total = (int64_t)n * h * w;
   const int grid = (int)((total + 255) / 256);
   return with_format(prec, [&](auto f) {
-    hipLaunchKernelGGL(flow_tblend_kernel<decltype(f)>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                       rec_view(*fr), rec_view(*g16), coef, h, w, total);
+    if (map)
+      hipLaunchKernelGGL((flow_tblend_kernel<decltype(f), true>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                         rec_view(*fr), rec_view(*g16), coef, h, w, total, map, n_pairs);
+    else
+      hipLaunchKernelGGL((flow_tblend_kernel<decltype(f), false>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                         rec_view(*fr), rec_view(*g16), coef, h, w, total, map, n_pairs);
     return hip_code(hipGetLastError());
   });
+}
+
+extern "C" int rrin_flow_tblend_h8(const rrin_h8* fr, const rrin_h8* g16, const float* coef, int32_t n, int32_t prec,
+                                   void* stream) {
+  return flow_tblend_launch(fr, g16, coef, n, nullptr, n, prec, stream);
+}
+
+extern "C" int rrin_flow_tblend_items_h8(const rrin_h8* fr, const rrin_h8* g16, const float* coef, int32_t n,
+                                         const int32_t* pair_map, int32_t n_pairs, int32_t prec, void* stream) {
+  if (!pair_map || n_pairs < 1 || n_pairs > n) return RRIN_E_ARG;
+  return flow_tblend_launch(fr, g16, coef, n, pair_map, n_pairs, prec, stream);
 }
 
 extern "C" int rrin_pack_g16_h8(const float* i0, const float* i1, int32_t n, const rrin_h8* g16, int32_t prec,
@@ -776,34 +803,59 @@ extern "C" int rrin_pack_g16_h8(const float* i0, const float* i1, int32_t n, con
   });
 }
 
-extern "C" int rrin_pack_g16_u8_h8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0,
-                                   int32_t w0, const rrin_h8* g16, int32_t prec, void* stream) {
+namespace rrin {
+// rrin_pack_g16_u8_h8 for n images that read the frames of n_pairs pairs through the device map
+// (NULL: image k reads frame k, n_pairs == n); the stride rule is on the n_pairs frames of a stack
+int pack_g16_u8_items(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0, int32_t w0,
+                      const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs, hipStream_t st) {
   if (!f0 || !f1 || !g16 || n < 1 || !rec_prec(prec)) return RRIN_E_ARG;
+  if (n_pairs < 1 || n_pairs > n || (!map && n_pairs != n)) return RRIN_E_ARG;
   if (!h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16) return RRIN_E_SHAPE;
   const int h = g16->g.h, w = g16->g.w;
   if (h0 < 1 || w0 < 1 || h != (h0 + 15) / 16 * 16 || w != (w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
-  if (img_stride < (int64_t)h0 * w0 * 3 && n > 1) return RRIN_E_ARG;
+  if (img_stride < (int64_t)h0 * w0 * 3 && n_pairs > 1) return RRIN_E_ARG;
   if (n > 65535 || h > 65535) return RRIN_E_SHAPE;  // grid y / z
   const dim3 grid((w + 255) / 256, h, n);
   return with_format(prec, [&](auto f) {
-    hipLaunchKernelGGL(pack_g16_u8_kernel<decltype(f)>, grid, dim3(256), 0, (hipStream_t)stream, f0, f1, img_stride,
-                       w0, h - h0, rec_view(*g16), w);
+    if (map)
+      hipLaunchKernelGGL((pack_g16_u8_kernel<decltype(f), true>), grid, dim3(256), 0, st, f0, f1, img_stride, w0,
+                         h - h0, rec_view(*g16), w, map, n_pairs);
+    else
+      hipLaunchKernelGGL((pack_g16_u8_kernel<decltype(f), false>), grid, dim3(256), 0, st, f0, f1, img_stride, w0,
+                         h - h0, rec_view(*g16), w, map, n_pairs);
     return hip_code(hipGetLastError());
   });
 }
 
-extern "C" int rrin_pack_g16_u16_h8(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int32_t h0,
-                                    int32_t w0, int32_t depth, const rrin_h8* g16, int32_t prec, void* stream) {
+int pack_g16_u16_items(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int32_t h0, int32_t w0,
+                       int32_t depth, const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs,
+                       hipStream_t st) {
   if (!f0 || !f1 || !g16 || n < 1 || !rec_prec(prec) || depth < 9 || depth > 16) return RRIN_E_ARG;
+  if (n_pairs < 1 || n_pairs > n || (!map && n_pairs != n)) return RRIN_E_ARG;
   if (!h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16) return RRIN_E_SHAPE;
   const int h = g16->g.h, w = g16->g.w;
   if (h0 < 1 || w0 < 1 || h != (h0 + 15) / 16 * 16 || w != (w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
-  if (img_stride < (int64_t)h0 * w0 * 3 && n > 1) return RRIN_E_ARG;
+  if (img_stride < (int64_t)h0 * w0 * 3 && n_pairs > 1) return RRIN_E_ARG;
   if (n > 65535 || h > 65535) return RRIN_E_SHAPE;  // grid y / z
   const dim3 grid((w + 255) / 256, h, n);
   return with_format(prec, [&](auto f) {
-    hipLaunchKernelGGL(pack_g16_u16_kernel<decltype(f)>, grid, dim3(256), 0, (hipStream_t)stream, f0, f1, img_stride,
-                       w0, h - h0, rec_view(*g16), w, (1 << depth) - 1);
+    if (map)
+      hipLaunchKernelGGL((pack_g16_u16_kernel<decltype(f), true>), grid, dim3(256), 0, st, f0, f1, img_stride, w0,
+                         h - h0, rec_view(*g16), w, (1 << depth) - 1, map, n_pairs);
+    else
+      hipLaunchKernelGGL((pack_g16_u16_kernel<decltype(f), false>), grid, dim3(256), 0, st, f0, f1, img_stride, w0,
+                         h - h0, rec_view(*g16), w, (1 << depth) - 1, map, n_pairs);
     return hip_code(hipGetLastError());
   });
+}
+}  // namespace rrin
+
+extern "C" int rrin_pack_g16_u8_h8(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0,
+                                   int32_t w0, const rrin_h8* g16, int32_t prec, void* stream) {
+  return pack_g16_u8_items(f0, f1, img_stride, n, h0, w0, g16, prec, nullptr, n, (hipStream_t)stream);
+}
+
+extern "C" int rrin_pack_g16_u16_h8(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int32_t h0,
+                                    int32_t w0, int32_t depth, const rrin_h8* g16, int32_t prec, void* stream) {
+  return pack_g16_u16_items(f0, f1, img_stride, n, h0, w0, depth, g16, prec, nullptr, n, (hipStream_t)stream);
 }

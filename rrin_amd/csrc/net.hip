@@ -699,12 +699,36 @@ struct FrameIO {
   const rrin_net_yuv16_desc* yuv16 = nullptr;
 };
 
+// An item forward (ABI 25): d->n items over n_pairs pairs through the device map; map NULL: a
+// plain forward (every rrin_net_*_fwd)
+struct Items {
+  int n_pairs = 0;
+  const int32_t* map = nullptr;
+};
+
+// rrin_items of a forward of n items, checked: RRIN_E_ARG for a null descriptor, n_pairs outside
+// [1, n], or no map with n_pairs != n
+static int items_of(const rrin_items* it, int n, Items& out) {
+  if (!it || it->n_pairs < 1 || it->n_pairs > n) return RRIN_E_ARG;
+  if (!it->pair_map && it->n_pairs != n) return RRIN_E_ARG;
+  out.n_pairs = it->n_pairs;
+  out.map = it->pair_map;
+  return 0;
+}
+
 // The schedule of the forwards: rrin_net_fwd (no member of f set: fp32 NCHW frames d->i0 / i1
 // in, d->out out), rrin_net_u8_fwd (8-bit RGB frames in and out), rrin_net_yuv_fwd (8-bit
 // 4:2:0 frames in and out) and their 16-bit siblings rrin_net_u16_fwd / rrin_net_yuv16_fwd; the
 // frame forwards leave d->i0 / i1 / out unused and run on the record layouts only.  The callers
 // have validated d (and the member of f).
-static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, void* stream) {
+//
+// With a map (items.map, frame forwards only) the call is an item forward.  One plan, sized for
+// the d->n items, serves both of its phases, since no buffer's image stride depends on the batch:
+// the Flow phase packs the n_pairs pairs into images [0, n_pairs) of the Net buffer and runs the
+// Flow U-Net on them alone, which leaves the pairs' raw Flow in FLOWRAW; the item phase packs
+// item k from the frames of pair map[k] into image k, blends that pair's raw Flow with item k's
+// coefficients -- the skip_flow path, indexed -- and runs the other three U-Nets on the d->n items.
+static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, const Items& items, void* stream) {
   const rrin_net_u8_desc* u8 = f.u8;
   const rrin_net_yuv_desc* yuv = f.yuv;
   const rrin_net_u16_desc* u16 = f.u16;
@@ -723,25 +747,43 @@ static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, void* stream) 
   }
   if (d->prec != RRIN_PREC_F32) {
     const rrin_h8 gall = hview(p.G, 0, 16);
+    // the frame pack of m images: image k from frame k, or with a map from frame map[k] of np
+    auto pack = [&](int m, const int32_t* map, int np) {
+      return u8    ? pack_g16_u8_items(u8->f0, u8->f1, u8->img_stride, m, u8->h0, u8->w0, &gall, d->prec, map, np, st)
+             : yuv ? pack_g16_yuv_items(&yuv->f0, &yuv->f1, &yuv->coef, m, yuv->h0, yuv->w0, &gall, d->prec, map, np, st)
+             : u16 ? pack_g16_u16_items(u16->f0, u16->f1, u16->img_stride, m, u16->h0, u16->w0, u16->depth, &gall,
+                                        d->prec, map, np, st)
+                   : pack_g16_yuv16_items(&y16->f0, &y16->f1, &y16->coef, m, y16->h0, y16->w0, &gall, d->prec, map, np,
+                                          st);
+    };
     int rc = 0;
-    {
+    if (items.map && !d->skip_flow) {  // Flow phase: the Flow U-Net once per pair
+      Plan pf = p;
+      pf.n = items.n_pairs;
+      {
+        ProfScope ps(p.prof, st, RRIN_KIND_LAYOUT, 0.0);
+        rc = pack(items.n_pairs, nullptr, items.n_pairs);
+      }
+      // its head also blends into the pairs' images with the first items' coefficients: the item
+      // pack below overwrites those channels
+      if (!rc) rc = run_unet_h8(pf, kUNets[0], d->convs, d->heads[0], HeadIO{d->coef, nullptr, nullptr}, st);
+    }
+    const bool blend = d->skip_flow || items.map;  // Ft0 / Ft1 from the kept raw Flow
+    if (!rc) {
       ProfScope ps(p.prof, st, RRIN_KIND_LAYOUT, 0.0);
       // x0, x1 into channels 0-5; channels 6-15 zeroed, so the first convs (cin 6/9/10)
       // can stage whole records (their tail channels are finite and meet zero weights)
-      rc = u8    ? rrin_pack_g16_u8_h8(u8->f0, u8->f1, u8->img_stride, d->n, u8->h0, u8->w0, &gall, d->prec, st)
-           : yuv ? rrin_pack_g16_yuv_h8(&yuv->f0, &yuv->f1, &yuv->coef, d->n, yuv->h0, yuv->w0, &gall, d->prec, st)
-           : u16 ? rrin_pack_g16_u16_h8(u16->f0, u16->f1, u16->img_stride, d->n, u16->h0, u16->w0, u16->depth, &gall,
-                                        d->prec, st)
-           : y16 ? rrin_pack_g16_yuv16_h8(&y16->f0, &y16->f1, &y16->coef, d->n, y16->h0, y16->w0, &gall, d->prec, st)
-                 : rrin_pack_g16_h8(d->i0, d->i1, d->n, &gall, d->prec, st);
-      if (!rc && d->skip_flow) {
+      rc = u8 || yuv || u16 || y16 ? pack(d->n, items.map, items.map ? items.n_pairs : d->n)
+                                   : rrin_pack_g16_h8(d->i0, d->i1, d->n, &gall, d->prec, st);
+      if (!rc && blend) {
         const rrin_h8 fr = hview(p.FLOWRAW, 0, 4);
-        rc = rrin_flow_tblend_h8(&fr, &gall, d->coef, d->n, d->prec, st);
+        rc = items.map ? rrin_flow_tblend_items_h8(&fr, &gall, d->coef, d->n, items.map, items.n_pairs, d->prec, st)
+                       : rrin_flow_tblend_h8(&fr, &gall, d->coef, d->n, d->prec, st);
       }
     }
     int k = 0;
     for (int u = 0; u < 4 && !rc; ++u) {
-      if (!(u == 0 && d->skip_flow)) {
+      if (!(u == 0 && blend)) {
         HeadIO io{d->coef, u8 || yuv || u16 || y16 ? nullptr : d->out, tap_of(d, kUNets[u])};
         if (u8) {
           io.out_u8 = u8->out_u8;
@@ -802,10 +844,13 @@ extern "C" int rrin_net_fwd(const rrin_net_desc* d, void* stream) {
     return RRIN_E_ARG;
   if (d->n < 1 || d->h < 16 || d->w < 16 || (d->h % 16) || (d->w % 16)) return RRIN_E_SHAPE;
   if (d->prec < RRIN_PREC_F32 || d->prec > RRIN_PREC_F32R) return RRIN_E_ARG;
-  return net_fwd_impl(d, FrameIO{}, stream);
+  return net_fwd_impl(d, FrameIO{}, Items{}, stream);
 }
 
-extern "C" int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream) {
+// The argument checks of the frame forwards, shared with their item forms: `frames` is the number
+// of frames of f0 and of f1 -- net.n for a plain forward, the pairs of an item forward -- and the
+// output always holds net.n frames.
+static int net_u8_check(const rrin_net_u8_desc* d, int frames) {
   if (!d || !d->f0 || !d->f1 || !d->out_u8) return RRIN_E_ARG;
   const rrin_net_desc* nd = &d->net;
   if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
@@ -813,13 +858,11 @@ extern "C" int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream) {
   if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
   if (nd->n < 1 || d->h0 < 1 || d->w0 < 1) return RRIN_E_SHAPE;
   if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
-  if (nd->n > 1 && d->img_stride < (int64_t)d->h0 * d->w0 * 3) return RRIN_E_ARG;
-  FrameIO f;
-  f.u8 = d;
-  return net_fwd_impl(nd, f, stream);
+  if (frames > 1 && d->img_stride < (int64_t)d->h0 * d->w0 * 3) return RRIN_E_ARG;
+  return 0;
 }
 
-extern "C" int rrin_net_yuv_fwd(const rrin_net_yuv_desc* d, void* stream) {
+static int net_yuv_check(const rrin_net_yuv_desc* d, int frames) {
   if (!d) return RRIN_E_ARG;
   const rrin_net_desc* nd = &d->net;
   if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
@@ -827,16 +870,14 @@ extern "C" int rrin_net_yuv_fwd(const rrin_net_yuv_desc* d, void* stream) {
   if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
   if (int rc = yuv_coef_check(&d->coef)) return rc;
   for (const rrin_yuv420* s : {&d->f0, &d->f1, &d->out}) {
-    if (int rc = yuv420_check(*s, nd->n, d->h0, d->w0)) return rc;
+    if (int rc = yuv420_check(*s, s == &d->out ? nd->n : frames, d->h0, d->w0)) return rc;
     if (s->chroma != d->f0.chroma) return RRIN_E_ARG;
   }
   if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
-  FrameIO f;
-  f.yuv = d;
-  return net_fwd_impl(nd, f, stream);
+  return 0;
 }
 
-extern "C" int rrin_net_u16_fwd(const rrin_net_u16_desc* d, void* stream) {
+static int net_u16_check(const rrin_net_u16_desc* d, int frames) {
   if (!d || !d->f0 || !d->f1 || !d->out_u16 || d->depth < 9 || d->depth > 16) return RRIN_E_ARG;
   const rrin_net_desc* nd = &d->net;
   if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
@@ -844,26 +885,93 @@ extern "C" int rrin_net_u16_fwd(const rrin_net_u16_desc* d, void* stream) {
   if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
   if (nd->n < 1 || d->h0 < 1 || d->w0 < 1) return RRIN_E_SHAPE;
   if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
-  if (nd->n > 1 && d->img_stride < (int64_t)d->h0 * d->w0 * 3) return RRIN_E_ARG;
-  FrameIO f;
-  f.u16 = d;
-  return net_fwd_impl(nd, f, stream);
+  if (frames > 1 && d->img_stride < (int64_t)d->h0 * d->w0 * 3) return RRIN_E_ARG;
+  return 0;
 }
 
-extern "C" int rrin_net_yuv16_fwd(const rrin_net_yuv16_desc* d, void* stream) {
+static int net_yuv16_check(const rrin_net_yuv16_desc* d, int frames) {
   if (!d) return RRIN_E_ARG;
   const rrin_net_desc* nd = &d->net;
   if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
   if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
   for (const rrin_yuv420_16* s : {&d->f0, &d->f1, &d->out}) {
-    if (int rc = yuv420_16_check(*s, nd->n, d->h0, d->w0)) return rc;
+    if (int rc = yuv420_16_check(*s, s == &d->out ? nd->n : frames, d->h0, d->w0)) return rc;
     if (s->depth != d->f0.depth || s->shift != d->f0.shift || s->chroma != d->f0.chroma) return RRIN_E_ARG;
   }
   if (int rc = yuv_coef_check16(&d->coef, d->f0.depth)) return rc;
   if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  return 0;
+}
+
+extern "C" int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream) {
+  if (int rc = net_u8_check(d, d ? d->net.n : 0)) return rc;
+  FrameIO f;
+  f.u8 = d;
+  return net_fwd_impl(&d->net, f, Items{}, stream);
+}
+
+extern "C" int rrin_net_yuv_fwd(const rrin_net_yuv_desc* d, void* stream) {
+  if (int rc = net_yuv_check(d, d ? d->net.n : 0)) return rc;
+  FrameIO f;
+  f.yuv = d;
+  return net_fwd_impl(&d->net, f, Items{}, stream);
+}
+
+extern "C" int rrin_net_u16_fwd(const rrin_net_u16_desc* d, void* stream) {
+  if (int rc = net_u16_check(d, d ? d->net.n : 0)) return rc;
+  FrameIO f;
+  f.u16 = d;
+  return net_fwd_impl(&d->net, f, Items{}, stream);
+}
+
+extern "C" int rrin_net_yuv16_fwd(const rrin_net_yuv16_desc* d, void* stream) {
+  if (int rc = net_yuv16_check(d, d ? d->net.n : 0)) return rc;
   FrameIO f;
   f.yuv16 = d;
-  return net_fwd_impl(nd, f, stream);
+  return net_fwd_impl(&d->net, f, Items{}, stream);
+}
+
+// ---- item forwards (ABI 25): rrin_items beside the frame descriptors ----------------------
+// The items first (RRIN_E_ARG), then the frame forward's own checks with the stacks' n_pairs frames.
+// taps are a plain forward's: an item forward refuses them.
+extern "C" int rrin_net_u8_items_fwd(const rrin_net_u8_desc* d, const rrin_items* it, void* stream) {
+  Items items;
+  if (!d || d->net.taps) return RRIN_E_ARG;
+  if (int rc = items_of(it, d->net.n, items)) return rc;
+  if (int rc = net_u8_check(d, items.n_pairs)) return rc;
+  FrameIO f;
+  f.u8 = d;
+  return net_fwd_impl(&d->net, f, items, stream);
+}
+
+extern "C" int rrin_net_yuv_items_fwd(const rrin_net_yuv_desc* d, const rrin_items* it, void* stream) {
+  Items items;
+  if (!d || d->net.taps) return RRIN_E_ARG;
+  if (int rc = items_of(it, d->net.n, items)) return rc;
+  if (int rc = net_yuv_check(d, items.n_pairs)) return rc;
+  FrameIO f;
+  f.yuv = d;
+  return net_fwd_impl(&d->net, f, items, stream);
+}
+
+extern "C" int rrin_net_u16_items_fwd(const rrin_net_u16_desc* d, const rrin_items* it, void* stream) {
+  Items items;
+  if (!d || d->net.taps) return RRIN_E_ARG;
+  if (int rc = items_of(it, d->net.n, items)) return rc;
+  if (int rc = net_u16_check(d, items.n_pairs)) return rc;
+  FrameIO f;
+  f.u16 = d;
+  return net_fwd_impl(&d->net, f, items, stream);
+}
+
+extern "C" int rrin_net_yuv16_items_fwd(const rrin_net_yuv16_desc* d, const rrin_items* it, void* stream) {
+  Items items;
+  if (!d || d->net.taps) return RRIN_E_ARG;
+  if (int rc = items_of(it, d->net.n, items)) return rc;
+  if (int rc = net_yuv16_check(d, items.n_pairs)) return rc;
+  FrameIO f;
+  f.yuv16 = d;
+  return net_fwd_impl(&d->net, f, items, stream);
 }
 
 // One U-Net alone (reference UNet.forward, unet.py:40-51): NCHW in -> NCHW out,

@@ -186,17 +186,34 @@ __global__ void __launch_bounds__(kThreads) gate_from_sad_kernel(const uint64_t*
   gate[i] = s == 0 ? 1 : (s > limit ? cut_code : 0);
 }
 
+// An item's code from its pair's (ABI 25): a duplicate pair (1) gives every item the first frame,
+// a cut pair (2) gives item k its own cut[k] -- the nearer frame by the item's t --, else 0.
+__global__ void __launch_bounds__(kThreads) gate_items_kernel(const int32_t* __restrict__ pair_gate, int n_pairs,
+                                                              const int32_t* __restrict__ map,
+                                                              const int32_t* __restrict__ cut, int n, int32_t* gate) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const int32_t c = pair_gate[pair_of(map, i, n_pairs)];
+  const int32_t k = cut[i];
+  gate[i] = c == 1 ? 1 : (c == 2 ? (k == 1 || k == 2 ? k : 0) : 0);
+}
+
 // One pair per blockIdx.y.  A workgroup of an ungated pair leaves after reading the code; the
-// others copy the chosen input frame over the output frame, aligned on the output.
+// others copy the chosen input frame over the output frame, aligned on the output.  ITEMS (ABI 25):
+// output frame p is an item, gated from the frames of pair pair_of(map, p, n_pairs); without it map
+// and n_pairs are unused.
+template <bool ITEMS>
 __global__ void __launch_bounds__(kThreads) gate_frames_u8_kernel(const uint8_t* __restrict__ f0,
                                                                   const uint8_t* __restrict__ f1,
                                                                   int64_t img_stride, int64_t len,
-                                                                  const int32_t* __restrict__ gate, uint8_t* out) {
+                                                                  const int32_t* __restrict__ gate, uint8_t* out,
+                                                                  const int32_t* __restrict__ map, int n_pairs) {
   const int p = blockIdx.y;
   const int32_t code = gate[p];
   if (code != 1 && code != 2) return;
   const int tid = threadIdx.x;
-  const uint8_t* s = (code == 1 ? f0 : f1) + (int64_t)p * img_stride;
+  const int src = ITEMS ? pair_of(map, p, n_pairs) : p;
+  const uint8_t* s = (code == 1 ? f0 : f1) + (int64_t)src * img_stride;
   uint8_t* d = out + (int64_t)p * len;
   const Span sp = span_of((uintptr_t)d, len);
   if (blockIdx.x == 0 && tid < sp.head + sp.tail) {
@@ -282,8 +299,8 @@ extern "C" int rrin_gate_frames_u8_len(const uint8_t* f0, const uint8_t* f1, int
   const int rc = frames_ok(f0, f1, img_stride, n, len);
   if (rc) return rc;
   if (n > 65535) return RRIN_E_SHAPE;  // one pair per blockIdx.y
-  hipLaunchKernelGGL(gate_frames_u8_kernel, dim3(grid_x(len), n), dim3(kThreads), 0, (hipStream_t)stream, f0, f1,
-                     img_stride, len, gate, out);
+  hipLaunchKernelGGL(gate_frames_u8_kernel<false>, dim3(grid_x(len), n), dim3(kThreads), 0, (hipStream_t)stream, f0,
+                     f1, img_stride, len, gate, out, (const int32_t*)nullptr, n);
   return hip_code(hipGetLastError());
 }
 
@@ -306,5 +323,27 @@ extern "C" int rrin_pair_sad_u16_len(const uint16_t* f0, const uint16_t* f1, int
                      sad, n);
   hipLaunchKernelGGL(pair_sad_u16_kernel, dim3(gx, n), dim3(kThreads), 0, (hipStream_t)stream, f0, f1, img_stride,
                      len, shift, (1 << depth) - 1, sad);
+  return hip_code(hipGetLastError());
+}
+
+extern "C" int rrin_gate_items_u8(const int32_t* pair_gate, int32_t n_pairs, const int32_t* pair_map,
+                                  const int32_t* cut_codes, int32_t n, int32_t* gate, void* stream) {
+  if (!pair_gate || !pair_map || !cut_codes || !gate) return RRIN_E_ARG;
+  if (n_pairs < 1 || n_pairs > n) return RRIN_E_ARG;
+  hipLaunchKernelGGL(gate_items_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream,
+                     pair_gate, n_pairs, pair_map, cut_codes, n, gate);
+  return hip_code(hipGetLastError());
+}
+
+extern "C" int rrin_gate_frames_items_u8_len(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n,
+                                             int64_t len, const int32_t* gate, uint8_t* out, const int32_t* pair_map,
+                                             int32_t n_pairs, void* stream) {
+  if (!gate || !out || !pair_map) return RRIN_E_ARG;
+  if (n_pairs < 1 || n_pairs > n) return RRIN_E_ARG;
+  const int rc = frames_ok(f0, f1, img_stride, n, len);
+  if (rc) return rc;
+  if (n > 65535) return RRIN_E_SHAPE;  // one item per blockIdx.y
+  hipLaunchKernelGGL(gate_frames_u8_kernel<true>, dim3(grid_x(len), n), dim3(kThreads), 0, (hipStream_t)stream, f0,
+                     f1, img_stride, len, gate, out, pair_map, n_pairs);
   return hip_code(hipGetLastError());
 }

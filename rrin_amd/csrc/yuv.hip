@@ -21,16 +21,17 @@ __constant__ const U8ScaleTab kU8Scale{};
 // CH (rrin_chroma) is the chroma block: 4:2:0 as above; 4:2:2 the same 128 + 128 samples from
 // chroma row sy instead of sy >> 1; 4:4:4 one U and one V per pixel, 256 + 256 samples, each lane
 // loading those of its own pixel (the run may then be odd: nothing here assumes an even np).
+// src: the frame of both stacks that image img of g16 reads (img itself, or its pair through a map).
 template <int MODE, int CH>
-__global__ void __launch_bounds__(256) pack_g16_yuv_kernel(rrin_yuv420 f0, rrin_yuv420 f1, rrin_yuv_coef k, int w0,
-                                                           int top, uint4* ghi, uint4* glo, int64_t img_stride,
-                                                           int64_t gp, int wp, int w) {
+__device__ inline void pack_g16_yuv_body(const rrin_yuv420& f0, const rrin_yuv420& f1, const rrin_yuv_coef& k, int w0,
+                                         int top, uint4* ghi, uint4* glo, int64_t img_stride, int64_t gp, int wp,
+                                         int w, int src, int img) {
   __shared__ float s_tab[256];
   __shared__ uint8_t s_y[2][256];
   constexpr int kCW = CH == RRIN_CHROMA_444 ? 256 : 128;  // chroma samples of a run, per plane
   __shared__ uint8_t s_c[2][2][kCW];  // [frame][U, V][block of the run]
   const int tid = threadIdx.x;
-  const int xs = blockIdx.x * 256, y = blockIdx.y, img = blockIdx.z;
+  const int xs = blockIdx.x * 256, y = blockIdx.y;
   s_tab[tid] = kU8Scale.v[tid];
   const int sy = y > top ? y - top : 0;
   // xs < w0: the right pad is < 16 columns, xs a multiple of 256; np is even unless 4:4:4 (w0 odd)
@@ -40,7 +41,7 @@ __global__ void __launch_bounds__(256) pack_g16_yuv_kernel(rrin_yuv420 f0, rrin_
 #pragma unroll
   for (int f = 0; f < 2; ++f) {
     const rrin_yuv420& s = f ? f1 : f0;
-    const int64_t base = (int64_t)img * s.img_stride;
+    const int64_t base = (int64_t)src * s.img_stride;
     if (tid < np) s_y[f][tid] = s.y[base + (int64_t)sy * s.y_pitch + xs + tid];
     if constexpr (CH == RRIN_CHROMA_444) {
       if (tid < np) {
@@ -90,20 +91,38 @@ __global__ void __launch_bounds__(256) pack_g16_yuv_kernel(rrin_yuv420 f0, rrin_
   }
 }
 
+template <int MODE, int CH>
+__global__ void __launch_bounds__(256) pack_g16_yuv_kernel(rrin_yuv420 f0, rrin_yuv420 f1, rrin_yuv_coef k, int w0,
+                                                           int top, uint4* ghi, uint4* glo, int64_t img_stride,
+                                                           int64_t gp, int wp, int w) {
+  pack_g16_yuv_body<MODE, CH>(f0, f1, k, w0, top, ghi, glo, img_stride, gp, wp, w, blockIdx.z, blockIdx.z);
+}
+
+// The item form (ABI 25): image k of g16 reads frame pair_of(map, k, n_pairs) of both stacks (f1
+// is f0 one frame on: pair map[k] of one [n_pairs + 1] stack).
+template <int MODE, int CH>
+__global__ void __launch_bounds__(256) pack_g16_yuv_items_kernel(rrin_yuv420 f0, rrin_yuv420 f1, rrin_yuv_coef k,
+                                                                 int w0, int top, uint4* ghi, uint4* glo,
+                                                                 int64_t img_stride, int64_t gp, int wp, int w,
+                                                                 const int32_t* __restrict__ map, int n_pairs) {
+  pack_g16_yuv_body<MODE, CH>(f0, f1, k, w0, top, ghi, glo, img_stride, gp, wp, w, pair_of(map, blockIdx.z, n_pairs),
+                              blockIdx.z);
+}
+
 // pack_g16_yuv_kernel for planes of 16-bit words (rrin_yuv420_16; depth 10 or 12, maxv = 2^depth - 1):
 // the same run of 256 pixels and the same staging with 2-byte loads (pitches and strides count
 // words, so a frame starts at any even address), the samples min(word >> shift, maxv), the
 // conversion at that depth (yuv_to_rgb16) and every RGB sample divided by maxv
 // (sample_to_float: the IEEE division, as rrin_pack_g16_u16_h8) -- no table.  CH as there.
 template <int MODE, int CH>
-__global__ void __launch_bounds__(256) pack_g16_yuv16_kernel(rrin_yuv420_16 f0, rrin_yuv420_16 f1, rrin_yuv_coef k,
-                                                             int w0, int top, uint4* ghi, uint4* glo,
-                                                             int64_t img_stride, int64_t gp, int wp, int w) {
+__device__ inline void pack_g16_yuv16_body(const rrin_yuv420_16& f0, const rrin_yuv420_16& f1, const rrin_yuv_coef& k,
+                                           int w0, int top, uint4* ghi, uint4* glo, int64_t img_stride, int64_t gp,
+                                           int wp, int w, int src, int img) {
   __shared__ uint16_t s_y[2][256];
   constexpr int kCW = CH == RRIN_CHROMA_444 ? 256 : 128;  // chroma samples of a run, per plane
   __shared__ uint16_t s_c[2][2][kCW];  // [frame][U, V][block of the run]
   const int tid = threadIdx.x;
-  const int xs = blockIdx.x * 256, y = blockIdx.y, img = blockIdx.z;
+  const int xs = blockIdx.x * 256, y = blockIdx.y;
   const int sy = y > top ? y - top : 0;
   // xs < w0: the right pad is < 16 columns, xs a multiple of 256; np is even unless 4:4:4 (w0 odd)
   const int np = min(256, w0 - xs);
@@ -112,7 +131,7 @@ __global__ void __launch_bounds__(256) pack_g16_yuv16_kernel(rrin_yuv420_16 f0, 
 #pragma unroll
   for (int f = 0; f < 2; ++f) {
     const rrin_yuv420_16& s = f ? f1 : f0;
-    const int64_t base = (int64_t)img * s.img_stride;
+    const int64_t base = (int64_t)src * s.img_stride;
     if (tid < np) s_y[f][tid] = s.y[base + (int64_t)sy * s.y_pitch + xs + tid];
     if constexpr (CH == RRIN_CHROMA_444) {
       if (tid < np) {
@@ -166,23 +185,46 @@ __global__ void __launch_bounds__(256) pack_g16_yuv16_kernel(rrin_yuv420_16 f0, 
   }
 }
 
-// the launch of a pack kernel K<MODE, CH> (K8 / K16 below) for a record precision and a chroma format
+template <int MODE, int CH>
+__global__ void __launch_bounds__(256) pack_g16_yuv16_kernel(rrin_yuv420_16 f0, rrin_yuv420_16 f1, rrin_yuv_coef k,
+                                                             int w0, int top, uint4* ghi, uint4* glo,
+                                                             int64_t img_stride, int64_t gp, int wp, int w) {
+  pack_g16_yuv16_body<MODE, CH>(f0, f1, k, w0, top, ghi, glo, img_stride, gp, wp, w, blockIdx.z, blockIdx.z);
+}
+
+template <int MODE, int CH>
+__global__ void __launch_bounds__(256) pack_g16_yuv16_items_kernel(rrin_yuv420_16 f0, rrin_yuv420_16 f1,
+                                                                   rrin_yuv_coef k, int w0, int top, uint4* ghi,
+                                                                   uint4* glo, int64_t img_stride, int64_t gp, int wp,
+                                                                   int w, const int32_t* __restrict__ map,
+                                                                   int n_pairs) {
+  pack_g16_yuv16_body<MODE, CH>(f0, f1, k, w0, top, ghi, glo, img_stride, gp, wp, w,
+                                pair_of(map, blockIdx.z, n_pairs), blockIdx.z);
+}
+
+// the launch of a pack kernel K<MODE, CH> (K8 / K16 below; with a map its item form K::items) for a
+// record precision and a chroma format
 template <template <int, int> class K, class Stack>
 static int launch_yuv_pack(int prec, int chroma, dim3 grid, hipStream_t st, const Stack& f0, const Stack& f1,
-                           const rrin_yuv_coef& k, int w0, int top, const rrin_h8& g16, int w) {
+                           const rrin_yuv_coef& k, int w0, int top, const rrin_h8& g16, int w, const int32_t* map,
+                           int n_pairs) {
   uint4* hi = static_cast<uint4*>(g16.hi);
   uint4* lo = planes_of(prec) == 2 ? static_cast<uint4*>(g16.lo) : nullptr;
   const int mode = prec == RRIN_PREC_F32R ? 0 : (planes_of(prec) == 2 ? 2 : 1);
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, f0, f1, k, w0, top, hi, lo, g16.img_stride, g16.g.plane,
-                       g16.g.wp, w);
+  auto go = [&](auto kern, auto items) {
+    if (map)
+      hipLaunchKernelGGL(items, grid, dim3(256), 0, st, f0, f1, k, w0, top, hi, lo, g16.img_stride, g16.g.plane,
+                         g16.g.wp, w, map, n_pairs);
+    else
+      hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, f0, f1, k, w0, top, hi, lo, g16.img_stride, g16.g.plane,
+                         g16.g.wp, w);
     return hip_code(hipGetLastError());
   };
   auto by_chroma = [&](auto m) {
     constexpr int M = decltype(m)::value;
-    if (chroma == RRIN_CHROMA_422) return go(K<M, RRIN_CHROMA_422>::fn);
-    if (chroma == RRIN_CHROMA_444) return go(K<M, RRIN_CHROMA_444>::fn);
-    return go(K<M, RRIN_CHROMA_420>::fn);
+    if (chroma == RRIN_CHROMA_422) return go(K<M, RRIN_CHROMA_422>::fn, K<M, RRIN_CHROMA_422>::items);
+    if (chroma == RRIN_CHROMA_444) return go(K<M, RRIN_CHROMA_444>::fn, K<M, RRIN_CHROMA_444>::items);
+    return go(K<M, RRIN_CHROMA_420>::fn, K<M, RRIN_CHROMA_420>::items);
   };
   if (mode == 0) return by_chroma(std::integral_constant<int, 0>{});
   if (mode == 2) return by_chroma(std::integral_constant<int, 2>{});
@@ -191,10 +233,12 @@ static int launch_yuv_pack(int prec, int chroma, dim3 grid, hipStream_t st, cons
 template <int MODE, int CH>
 struct K8 {
   static constexpr auto fn = pack_g16_yuv_kernel<MODE, CH>;
+  static constexpr auto items = pack_g16_yuv_items_kernel<MODE, CH>;
 };
 template <int MODE, int CH>
 struct K16 {
   static constexpr auto fn = pack_g16_yuv16_kernel<MODE, CH>;
+  static constexpr auto items = pack_g16_yuv16_items_kernel<MODE, CH>;
 };
 
 }  // namespace rrin
@@ -215,13 +259,16 @@ extern "C" int rrin_yuv_coef_std(int32_t standard, int32_t full_range, rrin_yuv_
   return 0;
 }
 
-extern "C" int rrin_pack_g16_yuv_h8(const rrin_yuv420* f0, const rrin_yuv420* f1, const rrin_yuv_coef* coef,
-                                    int32_t n, int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec,
-                                    void* stream) {
+// rrin_pack_g16_yuv_h8 for n images that read the frames of n_pairs pairs through the device map
+// (NULL: image k reads frame k, n_pairs == n); the stacks are checked for their n_pairs frames
+int rrin::pack_g16_yuv_items(const rrin_yuv420* f0, const rrin_yuv420* f1, const rrin_yuv_coef* coef, int32_t n,
+                             int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec, const int32_t* map,
+                             int32_t n_pairs, hipStream_t stream) {
   if (!f0 || !f1 || !g16 || n < 1 || !rec_prec(prec)) return RRIN_E_ARG;
+  if (n_pairs < 1 || n_pairs > n || (!map && n_pairs != n)) return RRIN_E_ARG;
   if (int rc = yuv_coef_check(coef)) return rc;
-  if (int rc = yuv420_check(*f0, n, h0, w0)) return rc;
-  if (int rc = yuv420_check(*f1, n, h0, w0)) return rc;
+  if (int rc = yuv420_check(*f0, n_pairs, h0, w0)) return rc;
+  if (int rc = yuv420_check(*f1, n_pairs, h0, w0)) return rc;
   if (f0->chroma != f1->chroma) return RRIN_E_ARG;
   if (!h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16) return RRIN_E_SHAPE;
   const int h = g16->g.h, w = g16->g.w;
@@ -229,7 +276,13 @@ extern "C" int rrin_pack_g16_yuv_h8(const rrin_yuv420* f0, const rrin_yuv420* f1
   if (n > 65535 || h > 65535) return RRIN_E_SHAPE;  // grid y / z
   const dim3 grid((w + 255) / 256, h, n);
   const int top = h - h0;
-  return launch_yuv_pack<K8>(prec, f0->chroma, grid, (hipStream_t)stream, *f0, *f1, *coef, w0, top, *g16, w);
+  return launch_yuv_pack<K8>(prec, f0->chroma, grid, stream, *f0, *f1, *coef, w0, top, *g16, w, map, n_pairs);
+}
+
+extern "C" int rrin_pack_g16_yuv_h8(const rrin_yuv420* f0, const rrin_yuv420* f1, const rrin_yuv_coef* coef,
+                                    int32_t n, int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec,
+                                    void* stream) {
+  return pack_g16_yuv_items(f0, f1, coef, n, h0, w0, g16, prec, nullptr, n, (hipStream_t)stream);
 }
 
 extern "C" int rrin_yuv_coef_std16(int32_t standard, int32_t full_range, int32_t depth, rrin_yuv_coef* c) {
@@ -258,12 +311,13 @@ extern "C" int rrin_yuv_coef_std16(int32_t standard, int32_t full_range, int32_t
   return 0;
 }
 
-extern "C" int rrin_pack_g16_yuv16_h8(const rrin_yuv420_16* f0, const rrin_yuv420_16* f1, const rrin_yuv_coef* coef,
-                                      int32_t n, int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec,
-                                      void* stream) {
+int rrin::pack_g16_yuv16_items(const rrin_yuv420_16* f0, const rrin_yuv420_16* f1, const rrin_yuv_coef* coef,
+                               int32_t n, int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec,
+                               const int32_t* map, int32_t n_pairs, hipStream_t stream) {
   if (!f0 || !f1 || !g16 || n < 1 || !rec_prec(prec)) return RRIN_E_ARG;
-  if (int rc = yuv420_16_check(*f0, n, h0, w0)) return rc;
-  if (int rc = yuv420_16_check(*f1, n, h0, w0)) return rc;
+  if (n_pairs < 1 || n_pairs > n || (!map && n_pairs != n)) return RRIN_E_ARG;
+  if (int rc = yuv420_16_check(*f0, n_pairs, h0, w0)) return rc;
+  if (int rc = yuv420_16_check(*f1, n_pairs, h0, w0)) return rc;
   if (f0->depth != f1->depth || f0->shift != f1->shift || f0->chroma != f1->chroma) return RRIN_E_ARG;
   if (int rc = yuv_coef_check16(coef, f0->depth)) return rc;
   if (!h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16) return RRIN_E_SHAPE;
@@ -272,5 +326,11 @@ extern "C" int rrin_pack_g16_yuv16_h8(const rrin_yuv420_16* f0, const rrin_yuv42
   if (n > 65535 || h > 65535) return RRIN_E_SHAPE;  // grid y / z
   const dim3 grid((w + 255) / 256, h, n);
   const int top = h - h0;
-  return launch_yuv_pack<K16>(prec, f0->chroma, grid, (hipStream_t)stream, *f0, *f1, *coef, w0, top, *g16, w);
+  return launch_yuv_pack<K16>(prec, f0->chroma, grid, stream, *f0, *f1, *coef, w0, top, *g16, w, map, n_pairs);
+}
+
+extern "C" int rrin_pack_g16_yuv16_h8(const rrin_yuv420_16* f0, const rrin_yuv420_16* f1, const rrin_yuv_coef* coef,
+                                      int32_t n, int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec,
+                                      void* stream) {
+  return pack_g16_yuv16_items(f0, f1, coef, n, h0, w0, g16, prec, nullptr, n, (hipStream_t)stream);
 }

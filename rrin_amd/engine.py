@@ -403,6 +403,52 @@ def t_coefficients(t, n: int) -> torch.Tensor:
     return c
 
 
+def check_items(pair, t, n_pairs: int):
+    """The host check of an item batch over ``n_pairs`` pairs, before anything is uploaded:
+    ``pair`` M >= 1 non-decreasing ints in [0, n_pairs) (a list or a 1-D int32 tensor), ``t`` M
+    floats in [0, 1) (a list or a 1-D fp32 tensor).  Returns (the pairs as a list of ints, t as
+    a list of Python floats or as the fp32 CPU tensor); raises ValueError otherwise."""
+    if isinstance(pair, torch.Tensor):
+        if pair.dtype != torch.int32 or pair.dim() != 1:
+            raise ValueError("pair must be a list of ints or a 1-D int32 tensor")
+        pl = pair.detach().cpu().tolist()
+    else:
+        pl = list(pair)
+        if any(isinstance(p, bool) or not isinstance(p, (int, np.integer)) for p in pl):
+            raise ValueError(f"pair must hold ints, got {pl!r}")
+        pl = [int(p) for p in pl]
+    if isinstance(t, torch.Tensor):
+        if t.dtype != torch.float32 or t.dim() != 1:
+            raise ValueError("t must be a list of floats or a 1-D fp32 tensor")
+        ts = t.detach().to("cpu")
+        tl = ts.tolist()
+    else:
+        ts = tl = [float(v) for v in t]
+    if len(pl) < 1 or len(tl) != len(pl):
+        raise ValueError(f"an item batch needs M >= 1 pairs and M times, got {len(pl)} / {len(tl)}")
+    if n_pairs < 1:
+        raise ValueError("an item batch needs a stack of at least two frames")
+    prev = 0
+    for k, (p, v) in enumerate(zip(pl, tl)):
+        if not 0 <= p < n_pairs:
+            raise ValueError(f"pair[{k}] = {p} is outside [0, {n_pairs})")
+        if p < prev:
+            raise ValueError(f"pair must be non-decreasing, got {p} after {prev} at item {k}")
+        if not 0.0 <= v < 1.0:
+            raise ValueError(f"t[{k}] = {v!r} is outside [0, 1)")
+        prev = p
+    return pl, ts
+
+
+def item_coefficients(ts, m: int) -> torch.Tensor:
+    """[m, 8] fp32 coefficient rows of an item batch (check_items' t): row k is
+    ``t_coefficients(t[k], 1)`` -- a list's values as Python floats (double arithmetic, rounded
+    once), a tensor's in fp32 tensor arithmetic, as a forward with that t computes them."""
+    if isinstance(ts, torch.Tensor):
+        return t_coefficients(ts if m > 1 else ts.reshape(()), m)
+    return torch.cat([t_coefficients(v, 1) for v in ts], dim=0)
+
+
 # ---- host-only construction: the walk over the U-Nets, the per-conv schedule, the packing ----
 # No torch device and no engine: tests/test_engine_host.py checks these without a GPU.
 
@@ -1278,6 +1324,232 @@ class RRINEngine:
         f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_yuv16", rgb=False, dtype=torch.uint16, layout=layout)
         return self._pair_sad(f0, f1, s0, h0 // 2, w0, wide=(depth, 16 - depth if msb else 0),
                               samples=self._yuv_gate_samples(h0, w0, layout))
+
+    # ---- item forwards: a batch of (pair index, t) over one frame stack -------------------
+    # rrin_net_*_items_fwd (ABI 25): the Flow U-Net once per distinct pair, the other three U-Nets
+    # once per item.  Item k is bit for bit forward_*(frames[pair[k]:pair[k]+1],
+    # frames[pair[k]+1:pair[k]+2], t=t[k])[0]: batch-size independence and the t-blend of a kept
+    # raw Flow (reuse_flow) are the two bitwise guarantees it rests on.
+
+    def _run_items(self, f0, f1, s0: int, h0: int, w0: int, pairs, ts, out, make, fwd, streams, split, prof,
+                   gate_cfg):
+        """The item forward of every frame path.  f0 / f1: the checked views ``frames[:-1]`` /
+        ``frames[1:]`` (stride s0 elements); pairs / ts: :func:`check_items`' result; out: the ``[M,
+        ...]`` output stack; ``make(p0, p1, po)`` returns the path's descriptor with its frames set
+        to the device addresses of a part's first pair (two of them) and output frame, and its
+        rrin_net_desc; ``fwd``: the name of the library's item entry.  The items are split over
+        ``streams`` as a forward's pairs are; each part runs the Flow U-Net on the distinct pairs
+        of its own items (a pair whose items straddle two parts is computed in both).  A part's
+        pairs are a run of the stack, so its frames are views; pairs that skip some (an arbitrary
+        caller) are gathered into a copy.  ``gate_cfg``: None or (scene_threshold, gate, maxval,
+        frame length in elements, (depth, shift) or None)."""
+        m = len(pairs)
+        n_stack = f0.shape[0]
+        h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
+        self._poll_range()
+        tl = ts.tolist() if isinstance(ts, torch.Tensor) else ts
+        bounds = self._bounds(m, streams, split)
+        if prof is not None and len(bounds) != 1:
+            raise ValueError("prof needs a single forward part (streams=1)")
+        glimit = pair_gate = None
+        if gate_cfg is not None:
+            scene_threshold, gate, maxval, flen, wide = gate_cfg
+            if scene_threshold is not None and gate is not None:
+                raise ValueError("scene_threshold and gate exclude each other")
+            if scene_threshold is not None:
+                glimit = scene_limit_len(scene_threshold, flen, maxval)
+            elif gate is not None:
+                if (not isinstance(gate, torch.Tensor) or gate.dtype != torch.int32 or gate.device != self.device
+                        or tuple(gate.shape) != (n_stack,)):
+                    raise ValueError(f"gate must be an int32 tensor [{n_stack}] (one code per pair) on {self.device}")
+                pair_gate = gate.contiguous()
+            else:
+                gate_cfg = None
+        # per part: its distinct pairs; per item: its pair's index among them and its cut code
+        distinct, local = [], []
+        for lo, hi in bounds:
+            d = sorted(set(pairs[lo:hi]))
+            pos = {p: i for i, p in enumerate(d)}
+            distinct.append(d)
+            local += [pos[p] for p in pairs[lo:hi]]
+        host = torch.tensor(local + [scene_cut_code(v) for v in tl], dtype=torch.int32)
+        dev = host.to(self.device, non_blocking=True)
+        maps, cuts = dev[:m], dev[m:]
+        coef = item_coefficients(ts, m).to(self.device, non_blocking=True)
+        codes = None
+        if gate_cfg is not None:
+            # sums and codes of the pairs (per part: at most its items), the items' codes
+            sad, pcodes = self._gate_buffers(m) if glimit is not None else (None, None)
+            codes = torch.empty(m, dtype=torch.int32, device=self.device)
+            self._sad_key = None  # the cached sums of a forward_* call are gone
+            self.last_gate = codes
+        esize = f0.element_size()
+
+        def part(j, lo, hi, stream, p):
+            d = distinct[j]
+            npairs = len(d)
+            if d[-1] - d[0] + 1 == npairs:  # a run of the stack: views
+                a, b = f0[d[0]:d[-1] + 1], f1[d[0]:d[-1] + 1]
+                stride = s0
+            else:
+                idx = torch.tensor(d, dtype=torch.int64, device=self.device)
+                with torch.cuda.stream(stream):
+                    a, b = f0.index_select(0, idx), f1.index_select(0, idx)
+                    a.record_stream(stream)
+                    b.record_stream(stream)
+                stride = a.stride(0)
+            p0, p1, po = a.data_ptr(), b.data_ptr(), out[lo:hi].data_ptr()
+            desc, nd = make(p0, p1, po, stride)
+            self._fill_net(nd, p, coef[lo:hi])
+            nd.prof = prof
+            it = _lib.Items()
+            it.n_pairs, it.pair_map = npairs, maps[lo:hi].data_ptr()
+            nd.skip_flow = 0
+            _lib.check(getattr(self.lib, fwd)(C.byref(desc), C.byref(it), C.c_void_p(stream.cuda_stream)), fwd)
+            # the workspace now keeps the raw Flow of this call's pairs: no forward_* may reuse it
+            self._flow_valid[p.key] = False
+            if p.status is not None:
+                self._queue_status(p.key[3], stream)
+            if gate_cfg is None:
+                return
+            sp, k = C.c_void_p(stream.cuda_stream), esize
+            if glimit is not None:
+                sums, pc = sad[lo:lo + npairs].data_ptr(), pcodes[lo:lo + npairs].data_ptr()
+                if wide is None:
+                    _lib.check(self.lib.rrin_pair_sad_u8_len(p0, p1, stride, npairs, flen, sums, sp),
+                               "rrin_pair_sad_u8_len")
+                else:
+                    _lib.check(self.lib.rrin_pair_sad_u16_len(p0, p1, stride, npairs, flen, wide[0], wide[1], sums, sp),
+                               "rrin_pair_sad_u16_len")
+                _lib.check(self.lib.rrin_gate_from_sad_u8(sums, npairs, glimit, 2, pc, sp), "rrin_gate_from_sad_u8")
+            else:
+                if d[-1] - d[0] + 1 == npairs:
+                    pg = pair_gate[d[0]:d[-1] + 1]
+                else:
+                    with torch.cuda.stream(stream):
+                        pg = pair_gate.index_select(0, idx)
+                        pg.record_stream(stream)
+                pc = pg.data_ptr()
+            cp = codes[lo:hi].data_ptr()
+            _lib.check(self.lib.rrin_gate_items_u8(pc, npairs, maps[lo:hi].data_ptr(), cuts[lo:hi].data_ptr(), hi - lo,
+                                                   cp, sp), "rrin_gate_items_u8")
+            _lib.check(self.lib.rrin_gate_frames_items_u8_len(p0, p1, stride * k, hi - lo, flen * k, cp, po,
+                                                              maps[lo:hi].data_ptr(), npairs, sp),
+                       "rrin_gate_frames_items_u8_len")
+
+        self._run_parts(h, w, bounds, part)
+        return out
+
+    def _item_frames(self, frames, what: str, rgb: bool, dtype=torch.uint8, layout: str = "nv12"):
+        """The two checked views of a ``[P+1, ...]`` frame stack (:meth:`_frames`)."""
+        if not isinstance(frames, torch.Tensor) or frames.dim() < 1 or frames.shape[0] < 2:
+            raise ValueError(f"{what} takes one stack of at least two frames")
+        return self._frames(frames[:-1], frames[1:], what, rgb=rgb, dtype=dtype, layout=layout)
+
+    def interpolate_items_u8(self, frames: torch.Tensor, pair, t, streams: int | None = None, split=None,
+                             scene_threshold=None, gate=None, prof=None) -> torch.Tensor:
+        """A batch of M items ``(pair[k], t[k])`` over one stack of 8-bit frames: ``frames`` uint8
+        ``[P+1,H0,W0,3]`` on the device (pair p is frames p and p + 1), ``pair`` M non-decreasing
+        ints in [0, P) (list or int32 tensor), ``t`` M floats in [0, 1) (list or fp32 tensor) ->
+        uint8 ``[M,H0,W0,3]``.  Item k is bit for bit ``forward_u8(frames[pair[k]:pair[k]+1],
+        frames[pair[k]+1:pair[k]+2], t=t[k])[0]`` (a list's t as Python floats, a tensor's as fp32
+        tensors), with the Flow U-Net run once per distinct pair and the other three once per item
+        (rrin_net_u8_items_fwd).  This is what a frame-rate conversion needs: its output instants
+        fall unevenly on the input pairs (:mod:`rrin_amd.retime`).
+
+        The scene gate: an item inherits its pair's decision -- a duplicate pair returns the first
+        frame, a cut pair the nearer frame by the item's own t (``scene_cut_code(t[k])``).  The sums
+        run once per distinct pair.  ``gate``: an int32 device tensor ``[P]`` of pair codes (1: a
+        duplicate, 2: a cut, else interpolate).  :attr:`last_gate` is then the ``[M]`` item codes
+        (1: the first frame, 2: the second, 0: interpolated)."""
+        self._need_records("interpolate_items_u8")
+        f0, f1, h0, w0, s0 = self._item_frames(frames, "interpolate_items_u8", rgb=True)
+        pairs, ts = check_items(pair, t, f0.shape[0])
+        out = torch.empty((len(pairs), h0, w0, 3), dtype=torch.uint8, device=self.device)
+
+        def make(p0, p1, po, stride):
+            d = _lib.NetU8Desc()
+            d.f0, d.f1, d.img_stride, d.out_u8 = p0, p1, stride, po
+            d.h0, d.w0 = h0, w0
+            return d, d.net
+
+        return self._run_items(f0, f1, s0, h0, w0, pairs, ts, out, make, "rrin_net_u8_items_fwd", streams, split,
+                               prof, (scene_threshold, gate, 255, h0 * w0 * 3, None))
+
+    def interpolate_items_u16(self, frames: torch.Tensor, pair, t, depth: int = 10, streams: int | None = None,
+                              split=None, scene_threshold=None, gate=None, prof=None) -> torch.Tensor:
+        """:meth:`interpolate_items_u8` on uint16 ``[P+1,H0,W0,3]`` frames of ``depth`` 9..16, defined
+        by :meth:`forward_u16` (rrin_net_u16_items_fwd)."""
+        self._need_records("interpolate_items_u16")
+        depth = self._depth16(depth, 9, "interpolate_items_u16")
+        f0, f1, h0, w0, s0 = self._item_frames(frames, "interpolate_items_u16", rgb=True, dtype=torch.uint16)
+        pairs, ts = check_items(pair, t, f0.shape[0])
+        out = torch.empty((len(pairs), h0, w0, 3), dtype=torch.uint16, device=self.device)
+
+        def make(p0, p1, po, stride):
+            d = _lib.NetU16Desc()
+            d.f0, d.f1, d.img_stride, d.out_u16 = p0, p1, stride, po
+            d.h0, d.w0, d.depth = h0, w0, depth
+            return d, d.net
+
+        return self._run_items(f0, f1, s0, h0, w0, pairs, ts, out, make, "rrin_net_u16_items_fwd", streams,
+                               split, prof, (scene_threshold, gate, (1 << depth) - 1, h0 * w0 * 3, (depth, 0)))
+
+    def interpolate_items_yuv(self, frames: torch.Tensor, pair, t, layout: str = "nv12", coef=None,
+                              streams: int | None = None, split=None, scene_threshold=None, gate=None,
+                              prof=None) -> torch.Tensor:
+        """:meth:`interpolate_items_u8` on one stack of 8-bit YUV frames (``[P+1, rows, W0]`` of
+        ``layout``, as :meth:`forward_yuv` takes them), defined by :meth:`forward_yuv` with the same
+        ``layout`` and ``coef`` (rrin_net_yuv_items_fwd); the gate on the frames' bytes as there."""
+        from . import yuv
+        self._need_records("interpolate_items_yuv")
+        if layout not in yuv.ALL_LAYOUTS:
+            raise ValueError(f"layout must be one of {yuv.ALL_LAYOUTS}, got {layout!r}")
+        kc = _lib.YuvCoef(*yuv.as_coef(coef))
+        f0, f1, h0, w0, s0 = self._item_frames(frames, "interpolate_items_yuv", rgb=False, layout=layout)
+        pairs, ts = check_items(pair, t, f0.shape[0])
+        out = torch.empty((len(pairs), yuv.stack_rows(h0, layout), w0), dtype=torch.uint8, device=self.device)
+        frame = out.stride(0)
+
+        def make(p0, p1, po, stride):
+            d = _lib.NetYuvDesc()
+            d.f0, d.f1 = self._yuv_stack(p0, stride, h0, w0, layout), self._yuv_stack(p1, stride, h0, w0, layout)
+            d.out = self._yuv_stack(po, frame, h0, w0, layout)
+            d.coef, d.h0, d.w0 = kc, h0, w0
+            return d, d.net
+
+        return self._run_items(f0, f1, s0, h0, w0, pairs, ts, out, make, "rrin_net_yuv_items_fwd", streams,
+                               split, prof, (scene_threshold, gate, 255, frame, None))
+
+    def interpolate_items_yuv16(self, frames: torch.Tensor, pair, t, layout: str = "nv12", depth: int = 10,
+                                msb: bool = False, coef=None, streams: int | None = None, split=None,
+                                scene_threshold=None, gate=None, prof=None) -> torch.Tensor:
+        """:meth:`interpolate_items_yuv` on 10- or 12-bit frames in 16-bit words, defined by
+        :meth:`forward_yuv16` with the same ``layout``, ``depth``, ``msb`` and ``coef``
+        (rrin_net_yuv16_items_fwd)."""
+        from . import yuv
+        self._need_records("interpolate_items_yuv16")
+        if layout not in yuv.ALL_LAYOUTS:
+            raise ValueError(f"layout must be one of {yuv.ALL_LAYOUTS}, got {layout!r}")
+        depth = yuv.check_depth16(depth)
+        shift = 16 - depth if msb else 0
+        kc = _lib.YuvCoef(*yuv.as_coef(coef, depth))
+        f0, f1, h0, w0, s0 = self._item_frames(frames, "interpolate_items_yuv16", rgb=False, dtype=torch.uint16,
+                                               layout=layout)
+        pairs, ts = check_items(pair, t, f0.shape[0])
+        out = torch.empty((len(pairs), yuv.stack_rows(h0, layout), w0), dtype=torch.uint16, device=self.device)
+        frame = out.stride(0)
+
+        def make(p0, p1, po, stride):
+            d = _lib.NetYuv16Desc()
+            d.f0 = self._yuv16_stack(p0, stride, h0, w0, layout, depth, shift)
+            d.f1 = self._yuv16_stack(p1, stride, h0, w0, layout, depth, shift)
+            d.out = self._yuv16_stack(po, frame, h0, w0, layout, depth, shift)
+            d.coef, d.h0, d.w0 = kc, h0, w0
+            return d, d.net
+
+        return self._run_items(f0, f1, s0, h0, w0, pairs, ts, out, make, "rrin_net_yuv16_items_fwd", streams,
+                               split, prof, (scene_threshold, gate, (1 << depth) - 1, frame, (depth, shift)))
 
     def unet_forward(self, x: torch.Tensor) -> torch.Tensor:
         """The single packed U-Net (engine built with one unit) on x [N,C,H,W]:

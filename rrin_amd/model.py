@@ -236,6 +236,51 @@ class Net(nn.Module):
         ``min(word >> shift, maxval)``, luma and chroma, of every pair of two uint16 4:2:0 stacks."""
         return self.engine().pair_stats_yuv16(f0, f1, depth=depth, msb=msb, layout=layout)
 
+    # ---- item forwards: a batch of (pair index, t) over one frame stack ----------------------
+    def _items(self, name, frames, pair, t, **kw):
+        """The item forward ``name`` of the engine, after the host checks of ``pair`` and ``t``
+        (ValueError before any device work)."""
+        from .engine import check_items
+        if not isinstance(frames, torch.Tensor) or frames.dim() < 1:
+            raise TypeError(f"{name} takes one stack of frames")
+        check_items(pair, t, frames.shape[0] - 1)
+        if torch.is_grad_enabled():
+            raise RuntimeError(f"rrin_amd.Net.{name} is inference-only: use torch.no_grad()")
+        return getattr(self.engine(), name)(frames, pair, t, streams=self.streams, **kw)
+
+    def interpolate_items_u8(self, frames, pair, t, scene_threshold=None, gate=None):
+        """A batch of M items over one stack of 8-bit frames, for frame-rate conversion
+        (:mod:`rrin_amd.retime`): ``frames`` uint8 ``[P+1,H0,W0,3]`` on the device (pair p is
+        ``frames[p]``, ``frames[p+1]``), ``pair`` M non-decreasing ints in [0, P) (list or int32
+        tensor), ``t`` M floats in [0, 1) (list or fp32 tensor) -> uint8 ``[M,H0,W0,3]``.  By
+        definition, and bit for bit, ``out[k] == forward_u8(frames[pair[k]:pair[k]+1],
+        frames[pair[k]+1:pair[k]+2], t=t[k])[0]``; the Flow U-Net runs once per distinct pair, the
+        other three U-Nets once per item (``RRINEngine.interpolate_items_u8``).
+
+        With ``scene_threshold`` or ``gate`` (int32 ``[P]`` pair codes: 1 duplicate, 2 cut) an item
+        inherits its pair's decision: a duplicate returns the first frame, a cut the nearer frame
+        by the item's own t; :attr:`last_gate` is then ``[M]``.  Output quality at uneven t has not
+        been validated on footage."""
+        return self._items("interpolate_items_u8", frames, pair, t, scene_threshold=scene_threshold, gate=gate)
+
+    def interpolate_items_yuv(self, frames, pair, t, layout="nv12", coef=None, scene_threshold=None, gate=None):
+        """:meth:`interpolate_items_u8` on one stack of 8-bit YUV frames, defined by
+        :meth:`forward_yuv` with the same ``layout`` and ``coef``."""
+        return self._items("interpolate_items_yuv", frames, pair, t, layout=layout, coef=coef,
+                           scene_threshold=scene_threshold, gate=gate)
+
+    def interpolate_items_u16(self, frames, pair, t, depth=10, scene_threshold=None, gate=None):
+        """:meth:`interpolate_items_u8` on uint16 RGB frames of ``depth``, defined by :meth:`forward_u16`."""
+        return self._items("interpolate_items_u16", frames, pair, t, depth=depth, scene_threshold=scene_threshold,
+                           gate=gate)
+
+    def interpolate_items_yuv16(self, frames, pair, t, layout="nv12", depth=10, msb=False, coef=None,
+                                scene_threshold=None, gate=None):
+        """:meth:`interpolate_items_yuv` on 10- or 12-bit frames in 16-bit words, defined by
+        :meth:`forward_yuv16` with the same ``layout``, ``depth``, ``msb`` and ``coef``."""
+        return self._items("interpolate_items_yuv16", frames, pair, t, layout=layout, depth=depth, msb=msb, coef=coef,
+                           scene_threshold=scene_threshold, gate=gate)
+
     @property
     def last_gate(self):
         """The int32 device codes ``[N]`` of the last gated ``forward_u8`` (0: interpolated, 1:
