@@ -817,6 +817,52 @@ int rrin_gate_frames_items_u8_len(const uint8_t* f0, const uint8_t* f1, int64_t 
                                   const int32_t* gate, uint8_t* out, const int32_t* pair_map, int32_t n_pairs,
                                   void* stream);
 
+/* ---- Frame metrics: squared error and SSIM per plane, on the device --------------------------
+ * History: added after ABI 25 without a new version number -- entry points only, no struct or
+ * existing entry point changes, so RRIN_ABI_VERSION stays 25; a caller finds out whether a build
+ * has them by looking the symbols up.
+ *
+ * A plane of a frame: sample (r, c), 0 <= r < h, 0 <= c < w, is element off + r*pitch + c*step of
+ * the frame (an element is a byte for rrin_frame_metrics_u8, a 16-bit word for _u16).  RGB
+ * [h][w][3] is three planes of step 3 and pitch 3*w at off 0, 1, 2; interleaved chroma two of step
+ * 2; a planar plane has step 1.
+ *
+ * rrin_frame_metrics_u8 / _u16: for frame k < n of the stacks a and b (a_stride / b_stride elements
+ * between frames, each at least the planes' reach; any byte address, for _u16 any even one) and
+ * plane p < n_planes (1..4; a host array, copied by the call):
+ *   sse[k*n_planes + p]  = sum over the plane's h*w samples of (a - b)^2, exact;
+ *   ssim[k*n_planes + p] (flags & 1) = the mean over the windows of the 8x8-window, 4-sample-step
+ *     SSIM as rrin_amd/metrics.py defines it: with bh = h/4, bw = w/4 and per 4x4 block the integer
+ *     sums s1 = sum a, s2 = sum b, ss = sum a^2 + b^2, s12 = sum ab, window (i, j), i < bh-1,
+ *     j < bw-1, adds blocks (i..i+1, j..j+1) to S1, S2, SS, S12 and is worth
+ *     ((2*S1*S2 + C1) * (2*covar + C2)) / ((S1^2 + S2^2 + C1) * (vars + C2)), vars = 64*SS - S1^2 -
+ *     S2^2, covar = 64*S12 - S1*S2, C1 = floor(1e-4 * M^2 * 64 + 0.5), C2 = floor(9e-4 * M^2 * 64 * 63
+ *     + 0.5), M = 2^depth - 1 (255 for _u8): the four factors exact integers, two float64
+ *     products, one division; samples beyond 4*bh, 4*bw take no part.
+ * _u16 reads a sample as min(word >> shift, M), depth 9..16, 0 <= shift <= 16 - depth (RRIN_E_ARG
+ * otherwise).  No byte outside a plane's rows is read.  The result is the same bits on every run
+ * (no floating-point atomics: per-workgroup partials in the workspace, added in index order).
+ * sse, ssim and workspace are 8-byte aligned device memory; ssim may be NULL without the flag;
+ * workspace_bytes >= rrin_frame_metrics_workspace_bytes(...) (RRIN_E_WORKSPACE otherwise; the query
+ * returns a negative error code for arguments the call would refuse).
+ * Null pointers, n_planes outside 1..4, step outside 1..3, off < 0, pitch < (w-1)*step + 1, a stride
+ * below the planes' reach, flags other than 0 / 1, an odd _u16 address: RRIN_E_ARG; n, h or w < 1,
+ * n > 65535, or the flag with h or w < 8 (no window): RRIN_E_SHAPE.  Validated before any launch.
+ * rrin_frame_metrics_tile: the kernel's tile, for tests that want sizes around it: a wave covers
+ * tile_cols window columns and band_rows window rows per step. */
+typedef struct rrin_plane {
+  int64_t off, pitch;
+  int32_t step, h, w, pad;
+} rrin_plane;
+int64_t rrin_frame_metrics_workspace_bytes(int32_t n, const rrin_plane* planes, int32_t n_planes, int32_t flags);
+int rrin_frame_metrics_u8(const uint8_t* a, int64_t a_stride, const uint8_t* b, int64_t b_stride, int32_t n,
+                          const rrin_plane* planes, int32_t n_planes, int32_t flags, uint64_t* sse, double* ssim,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+int rrin_frame_metrics_u16(const uint16_t* a, int64_t a_stride, const uint16_t* b, int64_t b_stride, int32_t n,
+                           const rrin_plane* planes, int32_t n_planes, int32_t flags, int32_t depth, int32_t shift,
+                           uint64_t* sse, double* ssim, void* workspace, int64_t workspace_bytes, void* stream);
+int rrin_frame_metrics_tile(int32_t* tile_cols, int32_t* band_rows);
+
 /* ---- Training path (autograd): NCHW fp32 kernels ------------------------- */
 /* With autograd on (the reference trains through Net.forward, train.py:98, and
  * loss.backward(), train.py:144) rrin_amd.train wraps these in autograd

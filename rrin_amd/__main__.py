@@ -5,7 +5,10 @@ Same command line as the reference (`/root/reference/__main__.py:33-72`).
 losses (reference ``train.py`` / ``losses.py``: AdamW, the VGG19 perceptual loss
 whose weights come from the network) are out of scope.  The
 model's own forward and backward do run on the HIP training kernels
-(``rrin_amd.autograd``): call ``Net`` under autograd from your loop."""
+(``rrin_amd.autograd``): call ``Net`` under autograd from your loop.
+
+``python -m rrin_amd --model_name M evaluate --y4m_in clip.y4m|-`` is rrin_amd's own: hold-out PSNR /
+SSIM of the model on a clip (``convert.evaluate_y4m``)."""
 import argparse
 import warnings
 
@@ -47,11 +50,29 @@ def build_parser():
                     help="with --y4m_in / --y4m_out: convert the stream's frame rate to this higher rate, e.g. "
                          "60000/1001 or 60 (24 -> 60, 25 -> 30, ...), instead of --sf intermediates per pair; "
                          "needs --sf 0.  Quality at uneven t has not been validated on footage")
+    ev = sub.add_parser("evaluate", help="Hold-out PSNR / SSIM of the model on a Y4M clip.")
+    ev.add_argument("--y4m_in", type=str, required=True, metavar="PATH|-",
+                    help="the clip: a Y4M stream of any format convert --y4m_in takes (\"-\": stdin)")
+    ev.add_argument("--hold", type=int, default=2,
+                    help="every hold-th frame is an input; the hold-1 frames between two inputs are dropped, "
+                         "interpolated back and compared with the originals (default 2)")
+    ev.add_argument("--batch", type=int, default=4, help="held-out frames per GPU call")
+    ev.add_argument("--precision", default="fp32", choices=["fp32", "fp32_split16", "fp16"])
+    ev.add_argument("--scene_threshold", type=float, default=None,
+                    help="scene gate as in convert (off by default); the report counts cut and duplicate pairs")
+    ev.add_argument("--report", type=str, default=None, metavar="PATH",
+                    help="write every row and the summary here as JSON (the summary is printed either way)")
     return p
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.mode == "evaluate":
+        from .convert import evaluate
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", category=UserWarning)
+            evaluate(args)
+        return
     if args.mode == "train":
         raise SystemExit("rrin_amd does not ship the training loop (AdamW, VGG19 perceptual loss: out of "
                          "scope, SURVEY §2 rows 11-12); Net.forward / backward run on the HIP training "

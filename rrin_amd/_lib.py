@@ -167,6 +167,12 @@ class Items(C.Structure):
     _fields_ = [("n_pairs", C.c_int32), ("pad_", C.c_int32), ("pair_map", C.c_void_p)]
 
 
+class Plane(C.Structure):
+    """rrin_plane: sample (r, c) of a frame's plane is element ``off + r*pitch + c*step`` (rrin_amd.metrics.planes_of)."""
+    _fields_ = [("off", C.c_int64), ("pitch", C.c_int64), ("step", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("pad", C.c_int32)]
+
+
 class TConvDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
                 ("mode", C.c_int32), ("leaky", C.c_int32), ("slope", C.c_float), ("x", C.c_void_p),
@@ -295,6 +301,14 @@ SIGNATURES = {
                                         C.c_int32, C.c_void_p, C.c_void_p]),
     "rrin_gate_frames_u8_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "rrin_frame_metrics_workspace_bytes": (C.c_int64, [C.c_int32, C.POINTER(Plane), C.c_int32, C.c_int32]),
+    "rrin_frame_metrics_u8": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Plane),
+                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_void_p]),
+    "rrin_frame_metrics_u16": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Plane),
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int64, C.c_void_p]),
+    "rrin_frame_metrics_tile": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rrin_unet_conv_count": (C.c_int64, [C.c_int32]),
     "rrin_unet_fwd": (C.c_int, [C.POINTER(UNetDesc), C.c_void_p]),
     "rrin_prof_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),

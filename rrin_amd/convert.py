@@ -734,6 +734,193 @@ def retime_y4m(model, src, dst, fps_out, batch=4, scene_threshold=None, coef=Non
             f.close()
 
 
+def _finite(values):
+    """Floats for a report: an infinite PSNR (no sample differs) is None, JSON's null."""
+    return [float(v) if math.isfinite(v) else None for v in values]
+
+
+def _summarise(sse, ssim, counts, maxval):
+    """The summary of one side (interpolated or baseline): ``sse`` / ``ssim`` lists of per-row lists."""
+    from .metrics import psnr
+    names = range(len(counts))
+    per_row = [[psnr(r[p], counts[p], maxval) for p in names] for r in sse]
+    finite = [[r[p] for r in per_row if math.isfinite(r[p])] for p in names]
+    total = [sum(r[p] for r in sse) for p in names]
+    return {
+        # mean over the rows whose PSNR is finite (a frame equal to the truth has none)
+        "psnr_mean": [sum(f) / len(f) if f else None for f in finite],
+        # from the summed squared error: per plane, and over all samples of all planes
+        "psnr_global": _finite([psnr(total[p], counts[p] * len(sse), maxval) for p in names]),
+        "psnr_global_all": _finite([psnr(sum(total), sum(counts) * len(sse), maxval)])[0],
+        "ssim_mean": [sum(r[p] for r in ssim) / len(ssim) for p in names],
+    }
+
+
+def evaluate_y4m(model, src, hold=2, batch=4, scene_threshold=None, coef=None, log=print, report=None):
+    """Hold-out evaluation on a Y4M clip (any tag :func:`interpolate_y4m` takes): what PSNR and SSIM
+    does this model reach on this footage, at the model's precision, with this gate -- and what does
+    it gain over repeating a frame?
+
+    Frames ``k*hold`` are the inputs.  The ``hold - 1`` frames between two inputs are held out and
+    interpolated back at ``t = j/hold`` (``rrin_amd.metrics.holdout_schedule``), ``batch`` items per
+    ``model.interpolate_items_yuv`` / ``_yuv16`` call, so the Flow U-Net runs once per pair of a step;
+    frames after the last input are ignored (the log line counts them); fewer than ``hold + 1``
+    frames raise ValueError.  Each interpolated frame is compared with the frame that was dropped,
+    per Y, U and V plane, by ``model.frame_metrics_yuv`` / ``_yuv16`` (:mod:`rrin_amd.metrics`; on the
+    device, on the forward's stream), and so is the *baseline*: the nearer input frame by t (a tie
+    takes the first), which is what a player shows without interpolation.  A step's numbers come to
+    the host once, behind the next step's launch.
+
+    Hold-out measures at ``hold`` times the clip's frame spacing, so it understates the quality at
+    the clip's own spacing; it compares models, precisions and gates on the same footage.
+
+    Returns ``{"summary": ..., "rows": [...]}`` and writes it as JSON to ``report`` (a path or a text
+    file object) when given.  A row: ``frame``, ``pair``, ``t``, ``gate`` (the item's code: 0
+    interpolated, 1 / 2 replaced by the first / second input), ``sse`` / ``psnr`` / ``ssim`` per plane,
+    and the same under ``baseline``.  The summary: per plane the mean PSNR (over rows where it is
+    finite), the PSNR of the summed squared error (also over all planes together) and the mean
+    SSIM, the same for the baseline, ``cut_pairs`` / ``duplicate_pairs`` (with ``scene_threshold``),
+    ``precision``, ``hold``, the stream's ``tag`` and the frame counts.  An infinite PSNR is None."""
+    import json
+    from collections import deque
+
+    from . import metrics, y4m, yuv
+    hold = metrics._hold(hold)
+    if batch < 1:
+        raise ValueError(f"batch must be >= 1, got {batch}")
+    opened = []
+    if isinstance(src, (str, os.PathLike)):
+        src = open(src, "rb")
+        opened.append(src)
+    try:
+        rd = y4m.Reader(src, depths=(8, 10, 12), chroma=yuv.CHROMAS)
+        w0, h0 = rd.width, rd.height
+        layout = "i" + rd.chroma
+        deep = rd.bit_depth > 8
+        dtype = torch.uint16 if deep else torch.uint8
+        maxval = (1 << rd.bit_depth) - 1
+        device = next(model.parameters()).device
+        on_gpu = device.type == "cuda"   # a host model (tests) has nothing to pin for and no events
+        gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
+        depth_kw = {"depth": rd.bit_depth, "msb": False} if deep else {}
+        name = "frame_metrics_yuv16" if deep else "frame_metrics_yuv"
+        measure = getattr(model, name, None) or getattr(metrics, name)  # a host model: the definitions
+        forward = model.interpolate_items_yuv16 if deep else model.interpolate_items_yuv
+        planes = metrics.planes_of("yuv", h0, w0, layout)
+        counts = [p[3] * p[4] for p in planes]
+        rows_per = yuv.stack_rows(h0, layout)
+        t0 = time.time()
+        held = {}        # frames still needed, by index
+        items = []       # (frame, pair, Fraction t) not sent yet
+        steps = deque()  # steps on the device, oldest first
+        rows = []
+        pair_dup, pair_gated = {}, set()
+
+        def retire(step):
+            if step["ev"] is not None:
+                step["ev"].synchronize()
+            if hasattr(model, "check_range"):
+                model.check_range(wait=False)  # fp16-stored precisions: raise instead of reporting poisoned frames
+            sse, val = step["sse"].tolist(), step["ssim"].tolist()
+            codes = step["codes"].tolist() if step["codes"] is not None else [0] * len(step["part"])
+            for k, (frame, pair, t) in enumerate(step["part"]):
+                if codes[k]:
+                    pair_gated.add(pair)
+                row = {"frame": frame, "pair": pair, "t": float(t), "gate": int(codes[k])}
+                for key, side in ((None, 0), ("baseline", 1)):
+                    d = {"sse": [int(v) for v in sse[side][k]],
+                         "psnr": _finite([metrics.psnr(v, c, maxval) for v, c in zip(sse[side][k], counts)]),
+                         "ssim": [float(v) for v in val[side][k]]}
+                    if key is None:
+                        row.update(d)
+                    else:
+                        row[key] = d
+                rows.append(row)
+
+        def send(part):
+            lo, hi = part[0][1], part[-1][1] + 1  # the inputs lo .. hi, then the truth frames, as one stack
+            n_in_ = hi - lo + 1
+            stack = torch.empty((n_in_ + len(part), rows_per, w0), dtype=dtype, pin_memory=on_gpu)
+            for j in range(lo, hi + 1):
+                stack[j - lo].view(-1).copy_(torch.from_numpy(held[j * hold]))
+            for k, (frame, _, _) in enumerate(part):
+                stack[n_in_ + k].view(-1).copy_(torch.from_numpy(held[frame]))
+            near = torch.tensor([p - lo + metrics.nearer_input(t) for _, p, t in part], dtype=torch.int64)
+            if on_gpu:
+                near = near.pin_memory()
+            stack, near = stack.to(device, non_blocking=True), near.to(device, non_blocking=True)
+            inputs, truth = stack[:n_in_], stack[n_in_:]
+            with torch.no_grad():
+                out = forward(inputs, [p - lo for _, p, _ in part], [float(t) for _, _, t in part], layout=layout,
+                              coef=coef, **depth_kw, **gate_kw)
+                got = measure(out, truth, layout=layout, **depth_kw)
+                # 16-bit frames are gathered as the same bits: index_select has no uint16 kernel everywhere
+                nearer = (inputs.view(torch.int16).index_select(0, near).view(torch.uint16) if deep
+                          else inputs.index_select(0, near))
+                base = measure(nearer, truth, layout=layout, **depth_kw)
+                sse = torch.stack((got.sse, base.sse))
+                val = torch.stack((got.ssim, base.ssim))
+            step = {"part": part, "codes": None, "ev": None}
+            for key, dev_t in (("sse", sse), ("ssim", val)):
+                step[key] = torch.empty(dev_t.shape, dtype=dev_t.dtype, pin_memory=on_gpu)
+                step[key].copy_(dev_t, non_blocking=True)
+            if gate_kw:
+                step["codes"] = torch.empty(len(part), dtype=torch.int32, pin_memory=on_gpu)
+                step["codes"].copy_(model.last_gate, non_blocking=True)
+            if on_gpu:
+                step["ev"] = torch.cuda.Event()
+                step["ev"].record()
+            steps.append(step)
+            sent = {frame for frame, _, _ in part}
+            for j in [j for j in held if j in sent or j < part[-1][1] * hold]:  # later items start at the last pair
+                del held[j]
+            while len(steps) > 1:  # retire the previous step while this one computes
+                retire(steps.popleft())
+
+        n_in = 0
+        for fr in rd:
+            held[n_in] = fr
+            n_in += 1
+            if n_in - 1 >= hold and (n_in - 1) % hold == 0:  # the second input of a pair has arrived
+                pair = (n_in - 1) // hold - 1
+                if gate_kw:  # a duplicate pair, as the gate sees it: no sample differs
+                    first = held[pair * hold]
+                    pair_dup[pair] = bool(np.array_equal(np.minimum(first, maxval), np.minimum(fr, maxval)))
+                items.extend(metrics.holdout_pair_items(pair, hold))
+                while len(items) >= batch:
+                    send(items[:batch])
+                    del items[:batch]
+        _, ignored = metrics.holdout_schedule(n_in, hold)  # fewer than hold + 1 frames: ValueError
+        if items:
+            send(items)
+        while steps:
+            retire(steps.popleft())
+        if hasattr(model, "check_range"):
+            model.check_range()
+        dups = sum(1 for v in pair_dup.values() if v)
+        summary = {"tag": "C" + rd.colorspace, "width": w0, "height": h0, "bit_depth": rd.bit_depth,
+                   "planes": list(metrics.YUV_NAMES), "precision": getattr(model, "precision", None), "hold": hold,
+                   "batch": batch, "scene_threshold": scene_threshold, "frames": n_in, "held_out": len(rows),
+                   "ignored": ignored, "cut_pairs": sum(1 for p in pair_gated if not pair_dup.get(p)),
+                   "duplicate_pairs": dups}
+        summary.update(_summarise([r["sse"] for r in rows], [r["ssim"] for r in rows], counts, maxval))
+        summary["baseline"] = _summarise([r["baseline"]["sse"] for r in rows], [r["baseline"]["ssim"] for r in rows],
+                                         counts, maxval)
+        log(f"evaluate: {len(rows)} held-out frames of {n_in} ({w0}x{h0}, hold {hold}) in {time.time() - t0:.2f} s; "
+            f"{ignored} frames after the last input ignored")
+        result = {"summary": summary, "rows": rows}
+        if report is not None:
+            if isinstance(report, (str, os.PathLike)):
+                with open(report, "w") as f:
+                    json.dump(result, f, indent=1, allow_nan=False)
+            else:
+                json.dump(result, report, indent=1, allow_nan=False)
+        return result
+    finally:
+        for f in opened:
+            f.close()
+
+
 def find_checkpoint(model_name, models_dir="models"):
     """Last checkpoint whose name starts with model_name (convert.py:100-108);
     sorted order, so Model0150.pth wins over Model0001.pth."""
@@ -791,6 +978,22 @@ def _convert_y4m(args):
         interpolate_y4m(net, src, dst, None if fps_out is not None else args.sf, batch=getattr(args, "batch", 4),
                         scene_threshold=getattr(args, "scene_threshold", None), fps_out=fps_out)
         print("Finished conversion")
+
+
+def evaluate(args):
+    """``evaluate --y4m_in PATH|- [--hold 2] [--batch 4] [--precision P] [--scene_threshold X] [--report
+    out.json]``: :func:`evaluate_y4m` on the checkpoint, the summary printed as JSON."""
+    import json
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("evaluate runs in a single process (WORLD_SIZE > 1)")
+    if args.no_cuda or not torch.cuda.is_available():
+        raise RuntimeError("rrin_amd runs on ROCm GPUs only")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    net = load_net(args.model_name, dev, args.precision)
+    result = evaluate_y4m(net, sys.stdin.buffer if args.y4m_in == "-" else args.y4m_in, hold=args.hold,
+                          batch=args.batch, scene_threshold=args.scene_threshold, report=args.report)
+    print(json.dumps(result["summary"], indent=1))
+    return result
 
 
 def convert(args):

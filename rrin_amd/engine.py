@@ -687,6 +687,7 @@ class RRINEngine:
         self._gate_bufs = {}        # pairs -> (int64 sums, int32 codes) of the scene gate
         self._sad_key = None        # (path, pairs, byte rows, byte columns, parts) whose sums the buffers hold
         self.last_gate = None       # int32 device codes of the last gated forward_u8 / forward_yuv
+        self._metrics_ws = None     # workspace of the frame metrics (per-workgroup partials)
 
     def _pack_h8(self, size: str, h: int = None, w: int = None):
         """(weight blob, bias blob, ConvWeights table, cfgs) of size class ``size`` at image
@@ -1324,6 +1325,45 @@ class RRINEngine:
         f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_yuv16", rgb=False, dtype=torch.uint16, layout=layout)
         return self._pair_sad(f0, f1, s0, h0 // 2, w0, wide=(depth, 16 - depth if msb else 0),
                               samples=self._yuv_gate_samples(h0, w0, layout))
+
+    # ---- frame metrics: squared error, PSNR and SSIM per plane, on the device -----------------
+    def _metrics_workspace(self, nbytes: int) -> torch.Tensor:
+        """The cached workspace of rrin_frame_metrics_* (a few KiB of per-workgroup partials): calls
+        are stream-ordered on the current stream, so successive calls may share it."""
+        ws = self._metrics_ws
+        if ws is None or ws.numel() * 8 < nbytes:
+            ws = self._metrics_ws = torch.empty(max(nbytes, 4096) // 8 + 1, dtype=torch.int64, device=self.device)
+        return ws
+
+    def _metrics_call(self, fn, a, b, **kw):
+        for f in (a, b):
+            if isinstance(f, torch.Tensor) and f.device != self.device:
+                raise RuntimeError(f"frames on {f.device}, model on {self.device}")
+        return fn(a, b, _workspace=self._metrics_workspace, **kw)
+
+    def frame_metrics_u8(self, a: torch.Tensor, b: torch.Tensor, ssim: bool = True):
+        """``metrics.frame_metrics_u8`` of two uint8 ``[N,H0,W0,3]`` device stacks (``a`` typically a
+        forward's output, ``b`` the truth frames) on the current stream, the forward's, with the
+        engine's cached workspace: a ``metrics.FrameMetrics`` of device tensors, no host sync
+        (rrin_frame_metrics_u8)."""
+        from . import metrics
+        return self._metrics_call(metrics.frame_metrics_u8, a, b, ssim=ssim)
+
+    def frame_metrics_yuv(self, a: torch.Tensor, b: torch.Tensor, layout: str = "nv12", ssim: bool = True):
+        """:meth:`frame_metrics_u8` per Y, U and V plane of two uint8 YUV stacks of ``layout``."""
+        from . import metrics
+        return self._metrics_call(metrics.frame_metrics_yuv, a, b, layout=layout, ssim=ssim)
+
+    def frame_metrics_u16(self, a: torch.Tensor, b: torch.Tensor, depth: int = 10, ssim: bool = True):
+        """:meth:`frame_metrics_u8` for uint16 RGB stacks of ``depth`` 9..16 (rrin_frame_metrics_u16)."""
+        from . import metrics
+        return self._metrics_call(metrics.frame_metrics_u16, a, b, depth=depth, ssim=ssim)
+
+    def frame_metrics_yuv16(self, a: torch.Tensor, b: torch.Tensor, layout: str = "nv12", depth: int = 10,
+                            msb: bool = False, ssim: bool = True):
+        """:meth:`frame_metrics_yuv` for uint16 stacks of ``depth`` 9..16, samples ``min(word >> shift, maxval)``."""
+        from . import metrics
+        return self._metrics_call(metrics.frame_metrics_yuv16, a, b, layout=layout, depth=depth, msb=msb, ssim=ssim)
 
     # ---- item forwards: a batch of (pair index, t) over one frame stack -------------------
     # rrin_net_*_items_fwd (ABI 25): the Flow U-Net once per distinct pair, the other three U-Nets

@@ -236,6 +236,27 @@ class Net(nn.Module):
         ``min(word >> shift, maxval)``, luma and chroma, of every pair of two uint16 4:2:0 stacks."""
         return self.engine().pair_stats_yuv16(f0, f1, depth=depth, msb=msb, layout=layout)
 
+    # ---- frame metrics: how good an output is, measured where the frames live ---------------
+    def frame_metrics_u8(self, a, b, ssim=True):
+        """Squared error, PSNR and SSIM per frame and channel of two uint8 ``[N,H0,W0,3]`` device
+        stacks -- ``a`` typically a forward's output, ``b`` the truth frames (a device
+        ``index_select`` of them is fine) -- as :mod:`rrin_amd.metrics` defines them: a
+        ``metrics.FrameMetrics`` of device tensors (``sse`` exact, ``ssim``, ``psnr()``), computed
+        by one kernel pass on the forward's stream without a host sync (``RRINEngine.frame_metrics_u8``)."""
+        return self.engine().frame_metrics_u8(a, b, ssim=ssim)
+
+    def frame_metrics_yuv(self, a, b, layout="nv12", ssim=True):
+        """:meth:`frame_metrics_u8` per Y, U and V plane of two uint8 YUV stacks of ``layout``."""
+        return self.engine().frame_metrics_yuv(a, b, layout=layout, ssim=ssim)
+
+    def frame_metrics_u16(self, a, b, depth=10, ssim=True):
+        """:meth:`frame_metrics_u8` for uint16 RGB stacks of ``depth`` 9..16 (samples ``min(word, maxval)``)."""
+        return self.engine().frame_metrics_u16(a, b, depth=depth, ssim=ssim)
+
+    def frame_metrics_yuv16(self, a, b, layout="nv12", depth=10, msb=False, ssim=True):
+        """:meth:`frame_metrics_yuv` for uint16 stacks of ``depth`` 9..16; ``msb`` as in :meth:`forward_yuv16`."""
+        return self.engine().frame_metrics_yuv16(a, b, layout=layout, depth=depth, msb=msb, ssim=ssim)
+
     # ---- item forwards: a batch of (pair index, t) over one frame stack ----------------------
     def _items(self, name, frames, pair, t, **kw):
         """The item forward ``name`` of the engine, after the host checks of ``pair`` and ``t``
