@@ -863,6 +863,61 @@ int rrin_frame_metrics_u16(const uint16_t* a, int64_t a_stride, const uint16_t* 
                            uint64_t* sse, double* ssim, void* workspace, int64_t workspace_bytes, void* stream);
 int rrin_frame_metrics_tile(int32_t* tile_cols, int32_t* band_rows);
 
+/* ---- Fine-tuning on a clip: triplet sampler and loss (csrc/finetune.hip) ----------------------
+ * History: added after ABI 25 without a new version number -- entry points only, no struct or
+ * existing entry point changes, so RRIN_ABI_VERSION stays 25; a caller finds out whether a build
+ * has them by looking the symbols up.
+ *
+ * rrin_triplet_crop_u8 / _u16: training triplets from one stack of n_frames frames on the device
+ * (frame_stride elements between frames; an element is a byte, for _u16 a 16-bit word at an even
+ * address).  planes[3] describe a frame as rrin_frame_metrics_* read it: Y, U, V of any layout
+ * (the chroma block -- one sample per pixel, per 2x1 or per 2x2 pixels -- follows from the plane
+ * sizes), with coef the colour conversion; or, with coef NULL, R, G, B of one size (interleaved
+ * RGB: step 3).  items: a host array of n_items x 6 int32 (frame0, frame_t, frame1, y0, x0, flip),
+ * copied by the call, 1 <= n_items <= RRIN_TRIPLET_MAX_ITEMS.  i0, it, i1: contiguous fp32
+ * [n_items][3][ch][cw] on the device, 16-byte aligned.  For item k and its frame f of the three,
+ * in frame coordinates (rrin_amd/finetune.py: sample_triplets is the definition, bit for bit):
+ *   rgb(y, x) = the frame's R, G, B at pixel (y0 + y, x0 + x), 0 <= y < ch, 0 <= x < cw: the
+ *               planes' samples, or rrin_yuv_coef's YUV -> RGB (rrin_yuv420_16's at depth 10 / 12)
+ *               of the pixel's luma and its block's chroma;
+ *   value     = float(rgb) / float(maxval), the IEEE fp32 division (maxval 255, or 2^depth - 1 with
+ *               a sample read as min(word >> shift, maxval));
+ *   flip 0: out[k][c][y][x] = value(y, x); 1 (left-right): value(y, cw-1-x); 2 (top-bottom):
+ *               value(ch-1-y, x).
+ * No element outside the crops' rows is read, no float outside the three outputs written.
+ * RRIN_E_ARG: a null pointer, an odd _u16 address, an output not 16-byte aligned, a plane with
+ * step outside 1..3, off < 0 or pitch < (w-1)*step + 1, a frame_stride below the planes' reach, a
+ * frame index outside [0, n_frames), a flip outside 0..2, an origin that is no multiple of the
+ * chroma block, a coefficient out of range, _u16 with depth outside 9..16 or shift outside
+ * 0..16-depth, or with coef at a depth other than 10 or 12.  RRIN_E_SHAPE: n_frames < 1, n_items
+ * outside 1..RRIN_TRIPLET_MAX_ITEMS, ch or cw no positive multiple of 16, a crop that leaves
+ * the luma plane (or is larger than it), chroma planes that are no 1x1, 2x1 or 2x2 reduction of the
+ * luma plane (coef NULL: planes of different sizes).  Validated before any launch.
+ *
+ * rrin_tloss: the training loss and its gradient in one pass over out and target (contiguous
+ * fp32, count = N*C*H*W >= 1 elements, 4-byte aligned; 16-byte aligned data takes 16-byte loads).
+ * With d = out - target, per element in fp32 (IEEE sqrt and division, no contraction):
+ *   sums[0] = sum sqrt(d*d + eps)   sums[1] = sum |d|   sums[2] = sum d*d          (float64)
+ *   grad    = float(w_charb / n) * d / sqrt(d*d + eps) + float(w_l1 / count) * sign(d), sign(0) = 0
+ * which is the gradient of loss = w_charb * sums[0] / n + w_l1 * sums[1] / count (the reference's
+ * charbonnierLoss / 1e3 + L1Loss / 10 at w_charb 1e-3, w_l1 1e-1, eps 1e-6).  The sums are per-
+ * workgroup float64 partials in the workspace, added in index order by a last step: no floating-
+ * point atomics, the same bits on every run.  grad may be NULL.  sums (3 doubles) and workspace are
+ * 8-byte aligned device memory, workspace_bytes >= rrin_tloss_workspace_bytes(count)
+ * (RRIN_E_WORKSPACE otherwise; the query returns RRIN_E_SHAPE for count < 1).  A null required
+ * pointer, a misaligned one, eps <= 0 or a weight that is not finite: RRIN_E_ARG; count < 1 or
+ * n < 1: RRIN_E_SHAPE.  Validated before any launch. */
+#define RRIN_TRIPLET_MAX_ITEMS 64
+int rrin_triplet_crop_u8(const uint8_t* frames, int64_t frame_stride, int32_t n_frames, const rrin_plane* planes,
+                         const int32_t* items, int32_t n_items, int32_t ch, int32_t cw, const rrin_yuv_coef* coef,
+                         float* i0, float* it, float* i1, void* stream);
+int rrin_triplet_crop_u16(const uint16_t* frames, int64_t frame_stride, int32_t n_frames, const rrin_plane* planes,
+                          const int32_t* items, int32_t n_items, int32_t ch, int32_t cw, const rrin_yuv_coef* coef,
+                          int32_t depth, int32_t shift, float* i0, float* it, float* i1, void* stream);
+int64_t rrin_tloss_workspace_bytes(int64_t count);
+int rrin_tloss(const float* out, const float* target, int64_t count, int32_t n, double w_charb, double w_l1,
+               float eps, double* sums, float* grad, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Training path (autograd): NCHW fp32 kernels ------------------------- */
 /* With autograd on (the reference trains through Net.forward, train.py:98, and
  * loss.backward(), train.py:144) rrin_amd.train wraps these in autograd

@@ -8,7 +8,11 @@ model's own forward and backward do run on the HIP training kernels
 (``rrin_amd.autograd``): call ``Net`` under autograd from your loop.
 
 ``python -m rrin_amd --model_name M evaluate --y4m_in clip.y4m|-`` is rrin_amd's own: hold-out PSNR /
-SSIM of the model on a clip (``convert.evaluate_y4m``)."""
+SSIM of the model on a clip (``convert.evaluate_y4m``).
+
+``python -m rrin_amd --model_name M finetune --y4m_in clip.y4m|- --steps N`` is rrin_amd's own too:
+fine-tuning on the clip's own held-out frames (``finetune.finetune_y4m``); it writes
+``models/M<epoch+1:04d>.pth``."""
 import argparse
 import warnings
 
@@ -20,7 +24,7 @@ def build_parser():
     p.add_argument("--rm", action="store_true", default=False, help="Removed temp folder on proper finish.")
     sub = p.add_subparsers(dest="mode")
     sub.required = True
-    tr = sub.add_parser("train", help="Train the model (the loop is not shipped by rrin_amd)")
+    tr = sub.add_parser("train", help="Train the model (the loop is not shipped by rrin_amd: see finetune)")
     tr.add_argument("--train_folder", type=str, required=True)
     tr.add_argument("--resume", action="store_true", default=False)
     tr.add_argument("--batch_size", type=int, default=2)
@@ -62,7 +66,38 @@ def build_parser():
                     help="scene gate as in convert (off by default); the report counts cut and duplicate pairs")
     ev.add_argument("--report", type=str, default=None, metavar="PATH",
                     help="write every row and the summary here as JSON (the summary is printed either way)")
+    ft = sub.add_parser("finetune", help="Fine-tune the model on a Y4M clip's own held-out frames.")
+    ft.add_argument("--y4m_in", type=str, required=True, metavar="PATH|-",
+                    help="the clip: a Y4M stream of any format convert --y4m_in takes (\"-\": stdin); it is kept "
+                         "on the device as a whole")
+    ft.add_argument("--steps", type=int, required=True, help="optimiser steps")
+    ft.add_argument("--batch", type=int, default=2, help="triplets per step (default 2, the reference's batch)")
+    ft.add_argument("--crop", type=int, default=256, help="side of the square training crop, a multiple of 16")
+    ft.add_argument("--spans", type=_spans, default=(2,), metavar="2,3,4",
+                    help="frame distances between the two inputs of a triplet; the first is also the hold of the "
+                         "validation (default 2)")
+    ft.add_argument("--lr", type=float, default=1e-4, help="AdamW learning rate (default 1e-4, the reference's)")
+    ft.add_argument("--seed", type=int, default=0, help="seed of the triplet schedule")
+    ft.add_argument("--scene_threshold", type=float, default=None,
+                    help="scene gate as in convert (off by default): cut and duplicate pairs give no triplet")
+    ft.add_argument("--val_fraction", type=float, default=0.1,
+                    help="share of the clip's last frames that is never trained on and measured before and after")
+    ft.add_argument("--no_augment", action="store_true", default=False,
+                    help="no random crop origin, flip or time reversal")
+    ft.add_argument("--report", type=str, default=None, metavar="PATH",
+                    help="write the losses, the schedule and both validations here as JSON")
     return p
+
+
+def _spans(text):
+    """``2,3,4`` -> (2, 3, 4)."""
+    try:
+        spans = tuple(int(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"spans are comma-separated ints, got {text!r}")
+    if not spans or any(s < 2 for s in spans):
+        raise argparse.ArgumentTypeError(f"spans are ints >= 2, got {text!r}")
+    return spans
 
 
 def main(argv=None):
@@ -72,6 +107,12 @@ def main(argv=None):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", category=UserWarning)
             evaluate(args)
+        return
+    if args.mode == "finetune":
+        from .finetune import finetune
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", category=UserWarning)
+            finetune(args)
         return
     if args.mode == "train":
         raise SystemExit("rrin_amd does not ship the training loop (AdamW, VGG19 perceptual loss: out of "

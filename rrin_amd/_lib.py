@@ -309,6 +309,15 @@ SIGNATURES = {
                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_int64, C.c_void_p]),
     "rrin_frame_metrics_tile": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rrin_triplet_crop_u8": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Plane), C.POINTER(C.c_int32),
+                                       C.c_int32, C.c_int32, C.c_int32, C.POINTER(YuvCoef), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "rrin_triplet_crop_u16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Plane), C.POINTER(C.c_int32),
+                                        C.c_int32, C.c_int32, C.c_int32, C.POINTER(YuvCoef), C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rrin_tloss_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "rrin_tloss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_float,
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "rrin_unet_conv_count": (C.c_int64, [C.c_int32]),
     "rrin_unet_fwd": (C.c_int, [C.POINTER(UNetDesc), C.c_void_p]),
     "rrin_prof_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),

@@ -342,3 +342,58 @@ def net_forward(net, input0, input1, t=0.5):
     w1, w2 = (1 - t) * m[:, 0:1], t * m[:, 1:2]
     out = (w1 * xt1 + w2 * xt2) / (w1 + w2 + 1e-8)
     return (unet_forward(net.final, torch.cat((input0, input1, out), 1)) + out).clamp(0, 1)
+
+
+def _tloss(out, target, w_charb, w_l1, eps, want_grad=True):
+    """rrin_tloss on two fp32 device tensors of one shape ``[N, ...]``: (sums float64 ``[3]`` on the
+    device, grad fp32 like ``out`` or None)."""
+    out, target = _f32(out), _f32(target)
+    if out.shape != target.shape or out.dim() < 1 or out.numel() < 1:
+        raise ValueError(f"frame_loss takes two tensors of one shape [N, ...], got {tuple(out.shape)} / "
+                         f"{tuple(target.shape)}")
+    if out.device != target.device:
+        raise RuntimeError(f"frame_loss: tensors on {out.device} / {target.device}")
+    L = _lib.lib()
+    count = out.numel()
+    need = int(L.rrin_tloss_workspace_bytes(count))
+    if need < 0:
+        _lib.check(need, "rrin_tloss_workspace_bytes")
+    ws = torch.empty(need // 8, dtype=torch.float64, device=out.device)
+    sums = torch.empty(3, dtype=torch.float64, device=out.device)
+    grad = torch.empty_like(out) if want_grad else None
+    _lib.check(L.rrin_tloss(out.data_ptr(), target.data_ptr(), count, out.shape[0], float(w_charb), float(w_l1),
+                            float(eps), sums.data_ptr(), grad.data_ptr() if want_grad else None, ws.data_ptr(),
+                            need, _stream(out.device)), "rrin_tloss")
+    return sums, grad
+
+
+class _FrameLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out, target, w_charb, w_l1, eps):
+        sums, grad = _tloss(out, target, w_charb, w_l1, eps, want_grad=ctx.needs_input_grad[0])
+        loss = sums[0] * (w_charb / out.shape[0]) + sums[1] * (w_l1 / out.numel())
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(sums)
+        return loss, sums
+
+    @staticmethod
+    def backward(ctx, gloss, _gsums):
+        grad, = ctx.saved_tensors
+        return (grad * gloss.to(grad.dtype) if grad is not None else None), None, None, None, None
+
+
+def frame_loss(out, target, w_charb=1e-3, w_l1=1e-1, eps=1e-6, return_sums=False):
+    """The fine-tuning loss of two fp32 ``[N,C,H,W]`` device tensors, one HIP pass (rrin_tloss) that
+    also writes the gradient: with ``d = out - target``
+
+        loss = w_charb * sum(sqrt(d^2 + eps)) / N + w_l1 * mean(|d|)
+
+    a float64 scalar on the device (``rrin_amd.finetune.frame_loss_ref`` is the definition).  The
+    defaults are the reference's ``comboLoss / 10 + charLoss / 1e3`` (train.py:105) with the VGG19 term
+    of ``CombinedLoss`` (losses.py:29-36) left out -- its weights come from the network --, i.e.
+    ``charbonnierLoss / 1e3 + L1Loss / 10``.  Backward returns the kept gradient times the incoming
+    scalar; ``target`` gets none.  ``return_sums=True``: (loss, sums) with sums float64 ``[3]`` = the
+    Charbonnier sum, sum |d| and sum d^2 (the PSNR the reference logs, train.py:112-113, is
+    ``10 * log10(count / sums[2])``), from the same pass."""
+    loss, sums = _FrameLoss.apply(out, target, float(w_charb), float(w_l1), float(eps))
+    return (loss, sums) if return_sums else loss
