@@ -762,6 +762,72 @@ int rrin_net_yuv_items_fwd(const rrin_net_yuv_desc* d, const rrin_items* items, 
 int rrin_net_u16_items_fwd(const rrin_net_u16_desc* d, const rrin_items* items, void* stream);
 int rrin_net_yuv16_items_fwd(const rrin_net_yuv16_desc* d, const rrin_items* items, void* stream);
 
+/* ---- Low-resolution flow estimation: flow_scale 2 and 4 (csrc/flow_scale.hip, net.hip) --------
+ * History: added after ABI 25 without a new version number -- a new struct passed to new entry
+ * points only, no existing struct or entry point changes, so RRIN_ABI_VERSION stays 25; a caller
+ * finds out whether a build has them by looking the symbols up.
+ *
+ * The forward with model.py:35, `Flow = self.Flow(x)`, replaced by
+ *   Flow = s * F.interpolate(self.Flow(F.avg_pool2d(x, s)), scale_factor=s, mode="bilinear",
+ *                            align_corners=False)
+ * for s = 2 or 4; everything after that line runs at full size (rrin_amd/flowscale.py).  The padded
+ * size is the frame size rounded up to a multiple of 16 * s.
+ *
+ * rrin_g16_downscale_h8: F.avg_pool2d(x, s) of channels 0-5 of n images of the full-size Net buffer
+ * src (16 channels, h x w) into the Net buffer dst of a plan at exactly (h / s, w / s); channels 6-15
+ * of dst are zeroed.  Per value in fp32, in raster order of the s x s block: s = 2
+ * (((p00 + p01) + p10) + p11) * 0.25f; s = 4 the 16 values row by row, then * 0.0625f; stored with
+ * the format's rounding.  Only interior records of dst are written (its conv halo stays zero).
+ *
+ * rrin_flow_upscale_h8: s * F.interpolate(flow, scale_factor=s, bilinear, align_corners=False) of
+ * the 4-channel raw Flow src (a plan at (h / s, w / s)) into the raw Flow dst at h x w.  Source
+ * coordinate (dst + 0.5) / s - 0.5, clamped to the image; the weights are exact dyadic numbers;
+ *   v = (1-wy) * ((1-wx)*p00 + wx*p01) + wy * ((1-wx)*p10 + wx*p11)
+ * with every operation rounded to fp32 (no contraction), then v * s, stored with the format's
+ * rounding as a whole record (its channels past 3 zero).  status: optional fp16 range flag, set
+ * where a stored value leaves the fp16 range (ignored for F32R).
+ *
+ * Both: a null view, s not 2 or 4, n < 1, a prec that is no record precision: RRIN_E_ARG; views
+ * that fail the layout checks, g_off != 0, fewer channels than 16 (downscale) / 4 (upscale), sizes
+ * that are not the exact quotient: RRIN_E_SHAPE.  Validated before any HIP call. */
+int rrin_g16_downscale_h8(const rrin_h8* src, const rrin_h8* dst, int32_t n, int32_t s, int32_t prec, void* stream);
+int rrin_flow_upscale_h8(const rrin_h8* src, const rrin_h8* dst, int32_t n, int32_t s, int32_t prec,
+                         int32_t* status, void* stream);
+
+/* The second plan of a flow_scale forward of net (n, h, w, prec): the Flow U-Net runs at
+ * (h / s, w / s) with its own memory, because its interior writes would land in the zero halos of
+ * the full-size plan.  workspace: rrin_net_workspace_bytes(n, h / s, w / s, prec) bytes, zero-filled
+ * once; convs: the conv table for that size (at least the Flow U-Net's rrin_unet_conv_count(5)
+ * entries, packed as for rrin_net_fwd); scratch: rrin_net_scratch_bytes of (n, h / s, w / s, prec,
+ * convs), nullable when that is 0.  The range flag is net.status. */
+typedef struct rrin_flow_scale {
+  int32_t s;            /* 2 or 4 */
+  int32_t pad_;
+  const rrin_conv_weights* convs;
+  void* workspace;
+  int64_t workspace_bytes;
+  void* scratch;
+  int64_t scratch_bytes;
+} rrin_flow_scale;
+/* The forwards with the second plan: rrin_net_fwd (record precisions only) and the four frame
+ * forwards, plain (items NULL) or as item forwards.  net.h / net.w are the frame size rounded up to
+ * 16 * s (RRIN_E_SHAPE otherwise).  Order: pack into the full-size g16 (once for a plain forward;
+ * an item forward packs its n_pairs pairs, then its items), downscale, the Flow U-Net on the second
+ * plan, upscale into the full-size raw Flow, then the blend of the kept raw Flow and the other three
+ * U-Nets as for skip_flow.  net.skip_flow = 1 skips all of the Flow phase: the workspace keeps the
+ * upscaled raw Flow of the previous call, which must have been one of the same s.  A null or
+ * malformed rrin_flow_scale, net.taps set, RRIN_PREC_F32: RRIN_E_ARG; a second workspace that is too
+ * small: RRIN_E_WORKSPACE; then the checks of the forward itself.  Validated before any HIP call. */
+int rrin_net_scaled_fwd(const rrin_net_desc* d, const rrin_flow_scale* fs, void* stream);
+int rrin_net_u8_scaled_fwd(const rrin_net_u8_desc* d, const rrin_items* items, const rrin_flow_scale* fs,
+                           void* stream);
+int rrin_net_yuv_scaled_fwd(const rrin_net_yuv_desc* d, const rrin_items* items, const rrin_flow_scale* fs,
+                            void* stream);
+int rrin_net_u16_scaled_fwd(const rrin_net_u16_desc* d, const rrin_items* items, const rrin_flow_scale* fs,
+                            void* stream);
+int rrin_net_yuv16_scaled_fwd(const rrin_net_yuv16_desc* d, const rrin_items* items, const rrin_flow_scale* fs,
+                              void* stream);
+
 /* ---- Scene-cut / duplicate-frame gate of the 8-bit frame path (ABI 21) ------------------
  * Three small kernels for the stream of a rrin_net_u8_fwd call, so that a caller can replace the
  * interpolated frame of a pair that is a shot change or a repeated frame by one of its input

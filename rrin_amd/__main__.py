@@ -43,6 +43,10 @@ def build_parser():
                     help="scene gate, off by default: mean absolute byte difference (0-255) above which a pair "
                          "is a shot change and yields the nearer input frame instead of a blend; repeated "
                          "frames are passed through.  No value has been validated on real footage")
+    cv.add_argument("--flow_scale", type=int, default=1, choices=[1, 2, 4],
+                    help="estimate the flow on frames reduced by this factor and scale it up (large frames, large "
+                         "motion); warp, mask and refinement stay at full size.  Quality is not validated: judge "
+                         "it with `evaluate --flow_scale`")
     cv.add_argument("--y4m_in", type=str, default=None, metavar="PATH|-",
                     help="read a Y4M stream (4:2:0, 4:2:2 or 4:4:4 of 8, 10 or 12 bits; \"-\": stdin, e.g. from "
                          "ffmpeg -f yuv4mpegpipe) instead "
@@ -64,6 +68,8 @@ def build_parser():
     ev.add_argument("--precision", default="fp32", choices=["fp32", "fp32_split16", "fp16"])
     ev.add_argument("--scene_threshold", type=float, default=None,
                     help="scene gate as in convert (off by default); the report counts cut and duplicate pairs")
+    ev.add_argument("--flow_scale", type=int, default=1, choices=[1, 2, 4],
+                    help="as in convert: the Flow U-Net at 1/s of the frame size; the report records it")
     ev.add_argument("--report", type=str, default=None, metavar="PATH",
                     help="write every row and the summary here as JSON (the summary is printed either way)")
     ft = sub.add_parser("finetune", help="Fine-tune the model on a Y4M clip's own held-out frames.")

@@ -167,6 +167,13 @@ class Items(C.Structure):
     _fields_ = [("n_pairs", C.c_int32), ("pad_", C.c_int32), ("pair_map", C.c_void_p)]
 
 
+class FlowScale(C.Structure):
+    """rrin_flow_scale: the second plan (Flow U-Net at (h / s, w / s)) of a flow_scale forward."""
+    _fields_ = [("s", C.c_int32), ("pad_", C.c_int32), ("convs", C.POINTER(ConvWeights)),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("scratch", C.c_void_p),
+                ("scratch_bytes", C.c_int64)]
+
+
 class Plane(C.Structure):
     """rrin_plane: sample (r, c) of a frame's plane is element ``off + r*pitch + c*step`` (rrin_amd.metrics.planes_of)."""
     _fields_ = [("off", C.c_int64), ("pitch", C.c_int64), ("step", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
@@ -279,6 +286,17 @@ SIGNATURES = {
     "rrin_net_yuv_items_fwd": (C.c_int, [C.POINTER(NetYuvDesc), C.POINTER(Items), C.c_void_p]),
     "rrin_net_u16_items_fwd": (C.c_int, [C.POINTER(NetU16Desc), C.POINTER(Items), C.c_void_p]),
     "rrin_net_yuv16_items_fwd": (C.c_int, [C.POINTER(NetYuv16Desc), C.POINTER(Items), C.c_void_p]),
+    "rrin_g16_downscale_h8": (C.c_int, [C.POINTER(H8), C.POINTER(H8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "rrin_flow_upscale_h8": (C.c_int, [C.POINTER(H8), C.POINTER(H8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_void_p]),
+    "rrin_net_scaled_fwd": (C.c_int, [C.POINTER(NetDesc), C.POINTER(FlowScale), C.c_void_p]),
+    "rrin_net_u8_scaled_fwd": (C.c_int, [C.POINTER(NetU8Desc), C.POINTER(Items), C.POINTER(FlowScale), C.c_void_p]),
+    "rrin_net_yuv_scaled_fwd": (C.c_int, [C.POINTER(NetYuvDesc), C.POINTER(Items), C.POINTER(FlowScale),
+                                          C.c_void_p]),
+    "rrin_net_u16_scaled_fwd": (C.c_int, [C.POINTER(NetU16Desc), C.POINTER(Items), C.POINTER(FlowScale),
+                                          C.c_void_p]),
+    "rrin_net_yuv16_scaled_fwd": (C.c_int, [C.POINTER(NetYuv16Desc), C.POINTER(Items), C.POINTER(FlowScale),
+                                            C.c_void_p]),
     "rrin_gate_items_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p]),
     "rrin_gate_frames_items_u8_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,

@@ -46,10 +46,13 @@ def list_frames(folder):
     return sorted(f for f in os.listdir(folder) if f.lower().endswith(IMG_EXT))
 
 
-def pad_amounts(width, height):
-    """(top_pad, right_pad) to the next multiple of 16 (dataloader.py:91-101)."""
-    right = (-width) % 16
-    top = (-height) % 16
+def pad_amounts(width, height, flow_scale=1):
+    """(top_pad, right_pad) to the next multiple of 16 (dataloader.py:91-101); of 16 * s for a
+    ``flow_scale`` s forward (:mod:`rrin_amd.flowscale`)."""
+    from .flowscale import pad_multiple
+    m = pad_multiple(flow_scale)
+    right = (-width) % m
+    top = (-height) % m
     return top, right
 
 
@@ -85,13 +88,14 @@ def load_frame_u8(path):
                                           "filetype": os.path.splitext(path)[1], "path": path}
 
 
-def frames_u8_to_float(frames: torch.Tensor) -> torch.Tensor:
+def frames_u8_to_float(frames: torch.Tensor, flow_scale: int = 1) -> torch.Tensor:
     """The input mapping of the byte path in plain torch: uint8 [...,H0,W0,3] -> float32
-    [...,3,H,W] with H, W the next multiples of 16, edge-replicated on top and on the right
-    (padded pixel (y, x) reads source pixel (max(y - top, 0), min(x, W0 - 1))) and divided by
-    255 -- bit for bit load_frame's tensor.  ``Net.forward_u8`` does this inside its input pack."""
+    [...,3,H,W] with H, W the next multiples of 16 (of 16 * ``flow_scale``), edge-replicated on top
+    and on the right (padded pixel (y, x) reads source pixel (max(y - top, 0), min(x, W0 - 1))) and
+    divided by 255 -- bit for bit load_frame's tensor.  ``Net.forward_u8`` does this inside its
+    input pack."""
     h0, w0 = frames.shape[-3], frames.shape[-2]
-    top, right = pad_amounts(w0, h0)
+    top, right = pad_amounts(w0, h0, flow_scale)
     rows = (torch.arange(h0 + top, device=frames.device) - top).clamp_(min=0)
     cols = torch.arange(w0 + right, device=frames.device).clamp_(max=w0 - 1)
     x = frames.index_select(-3, rows).index_select(-2, cols)
@@ -114,7 +118,7 @@ def _depth_maxval(depth) -> int:
     return (1 << depth) - 1
 
 
-def frames_u16_to_float(frames: torch.Tensor, depth: int) -> torch.Tensor:
+def frames_u16_to_float(frames: torch.Tensor, depth: int, flow_scale: int = 1) -> torch.Tensor:
     """:func:`frames_u8_to_float` for uint16 [...,H0,W0,3] frames of ``depth`` 9..16: the sample is
     ``min(word, maxval)`` with ``maxval = 2**depth - 1``, the value ``sample.float() / float(maxval)``;
     the same padding.  ``Net.forward_u16`` does this inside its input pack."""
@@ -122,7 +126,7 @@ def frames_u16_to_float(frames: torch.Tensor, depth: int) -> torch.Tensor:
     if frames.dtype != torch.uint16:
         raise TypeError("16-bit frames are uint16")
     h0, w0 = frames.shape[-3], frames.shape[-2]
-    top, right = pad_amounts(w0, h0)
+    top, right = pad_amounts(w0, h0, flow_scale)
     rows = (torch.arange(h0 + top, device=frames.device) - top).clamp_(min=0)
     cols = torch.arange(w0 + right, device=frames.device).clamp_(max=w0 - 1)
     x = (frames.view(torch.int16).to(torch.int32) & 0xFFFF).clamp_(max=maxval)
@@ -236,8 +240,11 @@ class _Reader:
 
 
 def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None, writers=4, log=print,
-                       rank=0, world=1, group=None, gather=True, u8="auto", scene_threshold=None):
+                       rank=0, world=1, group=None, gather=True, u8="auto", scene_threshold=None, flow_scale=1):
     """Interpolate every consecutive pair of frames in ``src`` into ``dest``.
+
+    ``flow_scale`` 2 or 4 (byte pipeline only; :mod:`rrin_amd.flowscale`) is passed to
+    ``model.interpolate_u8``: the Flow U-Net runs at 1/s of the frame size.
 
     ``model`` is an ``rrin_amd.Net`` (anything with ``interpolate(i0, i1, ts)``
     returning a list of ``[N,3,H,W]`` tensors works).  Returns the frames this
@@ -275,7 +282,12 @@ def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None,
         raise ValueError("u8=True needs a model with interpolate_u8(f0, f1, ts)")
     if scene_threshold is not None and not u8:
         raise ValueError("scene_threshold needs the byte pipeline (u8): the gate works on 8-bit frames")
+    from .flowscale import check_flow_scale
+    if check_flow_scale(flow_scale) > 1 and not u8:
+        raise ValueError("flow_scale needs the byte pipeline (u8): the float pipeline pads to 16 only")
     gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
+    # kept apart from gate_kw, whose truth means "the scene gate is on"; scale 1 passes no keyword
+    scale_kw = {} if flow_scale == 1 else {"flow_scale": flow_scale}
     gate_codes = []  # per step: (event or None, host int32 codes of its pairs)
     frames = list_frames(src)
     if len(frames) < 2:
@@ -332,7 +344,7 @@ def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None,
             if device is not None:
                 stack = stack.to(device, non_blocking=True)
             with torch.no_grad():
-                outs = model.interpolate_u8(stack[:-1], stack[1:], ts, **gate_kw)
+                outs = model.interpolate_u8(stack[:-1], stack[1:], ts, **gate_kw, **scale_kw)
             if gate_kw:
                 gate_codes.append(_codes_to_host(getattr(model, "last_gate", None), nloc, device))
         elif nloc:
@@ -454,8 +466,12 @@ def _retire(item, sf, dest, put, model=None):
         put(shutil.copy, m1["path"], os.path.join(dest, f"{base + sf + 1:09d}{m1['filetype']}"))
 
 
-def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coef=None, log=print, fps_out=None):
+def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coef=None, log=print, fps_out=None,
+                    flow_scale=1):
     """Interpolate a Y4M stream (8-bit 4:2:0; also 10 / 12 bits and 4:2:2 / 4:4:4, below) into another: no image folder, no RGB frame anywhere.
+
+    ``flow_scale`` 2 or 4 (:mod:`rrin_amd.flowscale`) goes to the model's ``interpolate_*`` call:
+    the Flow U-Net runs at 1/s of the frame size.
 
     ``src`` / ``dst`` are binary file objects (files or pipes: they are read and written
     sequentially, never sought) or paths.  Every step takes the next ``batch`` pairs: their
@@ -482,10 +498,13 @@ def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coe
     a string ``"60000/1001"`` / ``"60"``, above the stream's rate) converts the frame rate instead:
     :func:`retime_y4m`."""
     from . import y4m, yuv
+    from .flowscale import check_flow_scale
+    check_flow_scale(flow_scale)
     if (sf is None) == (fps_out is None):
         raise ValueError("interpolate_y4m takes exactly one of sf and fps_out")
     if fps_out is not None:
-        return retime_y4m(model, src, dst, fps_out, batch=batch, scene_threshold=scene_threshold, coef=coef, log=log)
+        return retime_y4m(model, src, dst, fps_out, batch=batch, scene_threshold=scene_threshold, coef=coef, log=log,
+                          flow_scale=flow_scale)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise RuntimeError("interpolate_y4m runs in a single process (a stream has one reader and one writer)")
     if sf < 1 or batch < 1:
@@ -509,6 +528,8 @@ def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coe
         on_gpu = device.type == "cuda"   # a host model (tests) has nothing to pin for and no events
         ts = [i / (sf + 1) for i in range(1, sf + 1)]
         gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
+        # kept apart from gate_kw, whose truth means "the scene gate is on"; scale 1 passes no keyword
+        scale_kw = {} if flow_scale == 1 else {"flow_scale": flow_scale}
         frames = iter(rd)
         prev = next(frames, None)
         if prev is None:
@@ -551,9 +572,10 @@ def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coe
             with torch.no_grad():
                 if deep:
                     outs = model.interpolate_yuv16(stack[:-1], stack[1:], ts, layout=layout, depth=rd.bit_depth,
-                                                   msb=False, coef=coef, **gate_kw)
+                                                   msb=False, coef=coef, **gate_kw, **scale_kw)
                 else:
-                    outs = model.interpolate_yuv(stack[:-1], stack[1:], ts, layout=layout, coef=coef, **gate_kw)
+                    outs = model.interpolate_yuv(stack[:-1], stack[1:], ts, layout=layout, coef=coef, **gate_kw,
+                                                 **scale_kw)
             host = []
             for o in outs:
                 hbuf = torch.empty(o.shape, dtype=o.dtype, pin_memory=on_gpu)
@@ -589,7 +611,7 @@ def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coe
             f.close()
 
 
-def retime_y4m(model, src, dst, fps_out, batch=4, scene_threshold=None, coef=None, log=print):
+def retime_y4m(model, src, dst, fps_out, batch=4, scene_threshold=None, coef=None, log=print, flow_scale=1):
     """Convert the frame rate of a Y4M stream to any higher rate ``fps_out`` (24 -> 60, 24000/1001 ->
     60000/1001, 25 -> 30, ...): ``interpolate_y4m(fps_out=)``.  Output j is the frame at source time
     ``j * fps_in / fps_out`` (:mod:`rrin_amd.retime`): an input frame's own bytes where that time is
@@ -604,6 +626,8 @@ def retime_y4m(model, src, dst, fps_out, batch=4, scene_threshold=None, coef=Non
     from collections import deque
 
     from . import retime, y4m, yuv
+    from .flowscale import check_flow_scale
+    check_flow_scale(flow_scale)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise RuntimeError("interpolate_y4m runs in a single process (a stream has one reader and one writer)")
     if batch < 1:
@@ -631,6 +655,9 @@ def retime_y4m(model, src, dst, fps_out, batch=4, scene_threshold=None, coef=Non
         device = next(model.parameters()).device
         on_gpu = device.type == "cuda"   # a host model (tests) has nothing to pin for and no events
         gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
+        # to the model's interpolate_items_* call (rrin_amd.flowscale); kept apart from gate_kw, whose
+        # truth means "the scene gate is on"; scale 1 passes no keyword
+        scale_kw = {} if flow_scale == 1 else {"flow_scale": flow_scale}
         rows = yuv.stack_rows(h0, layout)
         t0 = time.time()
         held = {}        # input frames still needed by an item, by index
@@ -667,9 +694,10 @@ def retime_y4m(model, src, dst, fps_out, batch=4, scene_threshold=None, coef=Non
             with torch.no_grad():
                 if deep:
                     out = model.interpolate_items_yuv16(stack, pair, ts, layout=layout, depth=rd.bit_depth, msb=False,
-                                                        coef=coef, **gate_kw)
+                                                        coef=coef, **gate_kw, **scale_kw)
                 else:
-                    out = model.interpolate_items_yuv(stack, pair, ts, layout=layout, coef=coef, **gate_kw)
+                    out = model.interpolate_items_yuv(stack, pair, ts, layout=layout, coef=coef, **gate_kw,
+                                                      **scale_kw)
             host = torch.empty(out.shape, dtype=out.dtype, pin_memory=on_gpu)
             host.copy_(out, non_blocking=True)
             codes = None
@@ -756,7 +784,7 @@ def _summarise(sse, ssim, counts, maxval):
     }
 
 
-def evaluate_y4m(model, src, hold=2, batch=4, scene_threshold=None, coef=None, log=print, report=None):
+def evaluate_y4m(model, src, hold=2, batch=4, scene_threshold=None, coef=None, log=print, report=None, flow_scale=1):
     """Hold-out evaluation on a Y4M clip (any tag :func:`interpolate_y4m` takes): what PSNR and SSIM
     does this model reach on this footage, at the model's precision, with this gate -- and what does
     it gain over repeating a frame?
@@ -780,11 +808,17 @@ def evaluate_y4m(model, src, hold=2, batch=4, scene_threshold=None, coef=None, l
     and the same under ``baseline``.  The summary: per plane the mean PSNR (over rows where it is
     finite), the PSNR of the summed squared error (also over all planes together) and the mean
     SSIM, the same for the baseline, ``cut_pairs`` / ``duplicate_pairs`` (with ``scene_threshold``),
-    ``precision``, ``hold``, the stream's ``tag`` and the frame counts.  An infinite PSNR is None."""
+    ``precision``, ``hold``, ``flow_scale``, the stream's ``tag`` and the frame counts.  An infinite
+    PSNR is None.
+
+    ``flow_scale`` 2 or 4 (:mod:`rrin_amd.flowscale`) goes to the ``interpolate_items_*`` call: this is
+    how to judge the knob on one's own footage."""
     import json
     from collections import deque
 
     from . import metrics, y4m, yuv
+    from .flowscale import check_flow_scale
+    check_flow_scale(flow_scale)
     hold = metrics._hold(hold)
     if batch < 1:
         raise ValueError(f"batch must be >= 1, got {batch}")
@@ -802,6 +836,8 @@ def evaluate_y4m(model, src, hold=2, batch=4, scene_threshold=None, coef=None, l
         device = next(model.parameters()).device
         on_gpu = device.type == "cuda"   # a host model (tests) has nothing to pin for and no events
         gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
+        # kept apart from gate_kw, whose truth means "the scene gate is on"; scale 1 passes no keyword
+        scale_kw = {} if flow_scale == 1 else {"flow_scale": flow_scale}
         depth_kw = {"depth": rd.bit_depth, "msb": False} if deep else {}
         name = "frame_metrics_yuv16" if deep else "frame_metrics_yuv"
         measure = getattr(model, name, None) or getattr(metrics, name)  # a host model: the definitions
@@ -852,7 +888,7 @@ def evaluate_y4m(model, src, hold=2, batch=4, scene_threshold=None, coef=None, l
             inputs, truth = stack[:n_in_], stack[n_in_:]
             with torch.no_grad():
                 out = forward(inputs, [p - lo for _, p, _ in part], [float(t) for _, _, t in part], layout=layout,
-                              coef=coef, **depth_kw, **gate_kw)
+                              coef=coef, **depth_kw, **gate_kw, **scale_kw)
                 got = measure(out, truth, layout=layout, **depth_kw)
                 # 16-bit frames are gathered as the same bits: index_select has no uint16 kernel everywhere
                 nearer = (inputs.view(torch.int16).index_select(0, near).view(torch.uint16) if deep
@@ -900,7 +936,7 @@ def evaluate_y4m(model, src, hold=2, batch=4, scene_threshold=None, coef=None, l
         dups = sum(1 for v in pair_dup.values() if v)
         summary = {"tag": "C" + rd.colorspace, "width": w0, "height": h0, "bit_depth": rd.bit_depth,
                    "planes": list(metrics.YUV_NAMES), "precision": getattr(model, "precision", None), "hold": hold,
-                   "batch": batch, "scene_threshold": scene_threshold, "frames": n_in, "held_out": len(rows),
+                   "batch": batch, "scene_threshold": scene_threshold, "flow_scale": flow_scale, "frames": n_in, "held_out": len(rows),
                    "ignored": ignored, "cut_pairs": sum(1 for p in pair_gated if not pair_dup.get(p)),
                    "duplicate_pairs": dups}
         summary.update(_summarise([r["sse"] for r in rows], [r["ssim"] for r in rows], counts, maxval))
@@ -976,7 +1012,8 @@ def _convert_y4m(args):
         dev = torch.device("cuda", torch.cuda.current_device())
         net = load_net(args.model_name, dev, getattr(args, "precision", "fp32"))
         interpolate_y4m(net, src, dst, None if fps_out is not None else args.sf, batch=getattr(args, "batch", 4),
-                        scene_threshold=getattr(args, "scene_threshold", None), fps_out=fps_out)
+                        scene_threshold=getattr(args, "scene_threshold", None), fps_out=fps_out,
+                        flow_scale=getattr(args, "flow_scale", 1))
         print("Finished conversion")
 
 
@@ -991,7 +1028,8 @@ def evaluate(args):
     dev = torch.device("cuda", torch.cuda.current_device())
     net = load_net(args.model_name, dev, args.precision)
     result = evaluate_y4m(net, sys.stdin.buffer if args.y4m_in == "-" else args.y4m_in, hold=args.hold,
-                          batch=args.batch, scene_threshold=args.scene_threshold, report=args.report)
+                          batch=args.batch, scene_threshold=args.scene_threshold, report=args.report,
+                          flow_scale=getattr(args, "flow_scale", 1))
     print(json.dumps(result["summary"], indent=1))
     return result
 
@@ -1061,7 +1099,8 @@ def convert(args):
     net = load_net(args.model_name, dev, getattr(args, "precision", "fp32"))
     t = time.time()
     interpolate_folder(net, src, dest, args.sf, batch=getattr(args, "batch", 4), resume=args.resume, device=dev,
-                       rank=rank, world=world, scene_threshold=getattr(args, "scene_threshold", None))
+                       rank=rank, world=world, scene_threshold=getattr(args, "scene_threshold", None),
+                       flow_scale=getattr(args, "flow_scale", 1))
     if world > 1:
         dist.barrier()
     print("end=", time.time() - t)

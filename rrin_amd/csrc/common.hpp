@@ -327,17 +327,23 @@ __device__ inline int pair_of(const int32_t* __restrict__ map, int k, int n_pair
 // The four frame packs (rrin_pack_g16_u8_h8 / _u16 in glue_h8.hip, _yuv / _yuv16 in yuv.hip) for n
 // images that read n_pairs frames of f0 / f1 through the device map (NULL: image k reads frame k
 // and n_pairs == n: the entry points' own launch); the stacks are checked for n_pairs frames.
+// mult: g16 is the frame size rounded up to this multiple -- 16, or 16 * s for a flow_scale
+// forward (32, 64: the kernels' runs start at multiples of 256, which stay left of w0 for any
+// right pad below 64 columns).
 int pack_g16_u8_items(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0, int32_t w0,
-                      const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs, hipStream_t st);
+                      const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs, hipStream_t st,
+                      int32_t mult = 16);
 int pack_g16_u16_items(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int32_t h0, int32_t w0,
                        int32_t depth, const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs,
-                       hipStream_t st);
+                       hipStream_t st, int32_t mult = 16);
 int pack_g16_yuv_items(const rrin_yuv420* f0, const rrin_yuv420* f1, const rrin_yuv_coef* coef, int32_t n, int32_t h0,
                        int32_t w0, const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs,
-                       hipStream_t st);
+                       hipStream_t st, int32_t mult = 16);
 int pack_g16_yuv16_items(const rrin_yuv420_16* f0, const rrin_yuv420_16* f1, const rrin_yuv_coef* coef, int32_t n,
                          int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs,
-                         hipStream_t st);
+                         hipStream_t st, int32_t mult = 16);
+// a frame dimension rounded up to the pad multiple of a forward (16, 32 or 64)
+inline int pad_up(int v, int mult) { return (v + mult - 1) / mult * mult; }
 // cfg 18's tile on 8 waves of 4 accumulators (<= 128 VGPRs: 4 waves per SIMD),
 // two stages of [raw 680 | U 1024] records (three in A/B builds: two blocks per
 // CU would fill 163,584 B)

@@ -146,7 +146,9 @@ __global__ void __launch_bounds__(256) pack_g16_u8_kernel(const uint8_t* __restr
   const int sy = y > top ? y - top : 0;
   const int src = ITEMS ? pair_of(map, img, n_pairs) : img;
   const int64_t row = (int64_t)src * f_img + ((int64_t)sy * w0 + xs) * 3;
-  const int nb = min(256, w0 - xs) * 3;  // xs < w0: the right pad is < 16 columns, xs a multiple of 256
+  // xs < w0: w is w0 rounded up to a multiple m of 16, 32 or 64 (16 * flow_scale), so the right pad is
+  // < m columns; xs < w is a multiple of 256, hence of m: xs <= w - m < w0
+  const int nb = min(256, w0 - xs) * 3;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int b = tid + 256 * k;
@@ -186,7 +188,9 @@ __global__ void __launch_bounds__(256) pack_g16_u16_kernel(const uint16_t* __res
   const int sy = y > top ? y - top : 0;
   const int src = ITEMS ? pair_of(map, img, n_pairs) : img;
   const int64_t row = (int64_t)src * f_img + ((int64_t)sy * w0 + xs) * 3;
-  const int nb = min(256, w0 - xs) * 3;  // xs < w0: the right pad is < 16 columns, xs a multiple of 256
+  // xs < w0: w is w0 rounded up to a multiple m of 16, 32 or 64 (16 * flow_scale), so the right pad is
+  // < m columns; xs < w is a multiple of 256, hence of m: xs <= w - m < w0
+  const int nb = min(256, w0 - xs) * 3;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int b = tid + 256 * k;
@@ -542,20 +546,7 @@ __global__ void flow_tblend_kernel(RecView fr, RecView g, const float* coef, int
   px.template store<8, 10>(o + 2);
 }
 
-// ---- host side ---------------------------------------------------------------------
-// fn(F{}) with the record format F of a record precision (rec_prec(prec) checked by the caller)
-template <class Fn>
-static int with_format(int prec, Fn&& fn) {
-  if (prec == RRIN_PREC_F32R) return fn(RecR32{});
-  return planes_of(prec) == 2 ? fn(RecH8<2>{}) : fn(RecH8<1>{});
-}
-
-static RecView rec_view(const rrin_h8& v) {
-  const int64_t off = (int64_t)v.g_off * v.g.plane;
-  return RecView{static_cast<uint4*>(v.hi) + off, v.lo ? static_cast<uint4*>(v.lo) + off : nullptr, v.img_stride,
-                 v.g.plane, v.g.wp};
-}
-
+// ---- host side (with_format, rec_view: rec_fmt.hpp) ---------------------------------
 int clear_channels_h8(const rrin_h8* v, int32_t n, int32_t c0, int32_t c1, int32_t prec, hipStream_t st) {
   if (!v || n < 1 || c0 < 0 || c1 <= c0 || !rec_prec(prec) || c1 > chans_per_rec(prec) * v->groups) return RRIN_E_ARG;
   const int64_t total = (int64_t)n * (c1 - c0) * v->g.h * v->g.w;
@@ -807,12 +798,13 @@ namespace rrin {
 // rrin_pack_g16_u8_h8 for n images that read the frames of n_pairs pairs through the device map
 // (NULL: image k reads frame k, n_pairs == n); the stride rule is on the n_pairs frames of a stack
 int pack_g16_u8_items(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, int32_t n, int32_t h0, int32_t w0,
-                      const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs, hipStream_t st) {
+                      const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs, hipStream_t st,
+                      int32_t mult) {
   if (!f0 || !f1 || !g16 || n < 1 || !rec_prec(prec)) return RRIN_E_ARG;
   if (n_pairs < 1 || n_pairs > n || (!map && n_pairs != n)) return RRIN_E_ARG;
   if (!h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16) return RRIN_E_SHAPE;
   const int h = g16->g.h, w = g16->g.w;
-  if (h0 < 1 || w0 < 1 || h != (h0 + 15) / 16 * 16 || w != (w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  if (h0 < 1 || w0 < 1 || h != pad_up(h0, mult) || w != pad_up(w0, mult)) return RRIN_E_SHAPE;
   if (img_stride < (int64_t)h0 * w0 * 3 && n_pairs > 1) return RRIN_E_ARG;
   if (n > 65535 || h > 65535) return RRIN_E_SHAPE;  // grid y / z
   const dim3 grid((w + 255) / 256, h, n);
@@ -829,12 +821,12 @@ int pack_g16_u8_items(const uint8_t* f0, const uint8_t* f1, int64_t img_stride, 
 
 int pack_g16_u16_items(const uint16_t* f0, const uint16_t* f1, int64_t img_stride, int32_t n, int32_t h0, int32_t w0,
                        int32_t depth, const rrin_h8* g16, int32_t prec, const int32_t* map, int32_t n_pairs,
-                       hipStream_t st) {
+                       hipStream_t st, int32_t mult) {
   if (!f0 || !f1 || !g16 || n < 1 || !rec_prec(prec) || depth < 9 || depth > 16) return RRIN_E_ARG;
   if (n_pairs < 1 || n_pairs > n || (!map && n_pairs != n)) return RRIN_E_ARG;
   if (!h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16) return RRIN_E_SHAPE;
   const int h = g16->g.h, w = g16->g.w;
-  if (h0 < 1 || w0 < 1 || h != (h0 + 15) / 16 * 16 || w != (w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  if (h0 < 1 || w0 < 1 || h != pad_up(h0, mult) || w != pad_up(w0, mult)) return RRIN_E_SHAPE;
   if (img_stride < (int64_t)h0 * w0 * 3 && n_pairs > 1) return RRIN_E_ARG;
   if (n > 65535 || h > 65535) return RRIN_E_SHAPE;  // grid y / z
   const dim3 grid((w + 255) / 256, h, n);

@@ -728,7 +728,16 @@ static int items_of(const rrin_items* it, int n, Items& out) {
 // Flow U-Net on them alone, which leaves the pairs' raw Flow in FLOWRAW; the item phase packs
 // item k from the frames of pair map[k] into image k, blends that pair's raw Flow with item k's
 // coefficients -- the skip_flow path, indexed -- and runs the other three U-Nets on the d->n items.
-static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, const Items& items, void* stream) {
+//
+// With fs (flow_scale s = 2 or 4, record layouts only; checked by flow_scale_check) the Flow U-Net
+// runs on a second plan at (h / s, w / s) with its own workspace, conv table and scratch -- its
+// interior writes would land in the zero halos of the full-size plan's buffers -- and the range
+// flag of this call: pack into the full-size g16, rrin_g16_downscale_h8 into the low-res g16, the
+// Flow U-Net there, rrin_flow_upscale_h8 of its raw Flow into the full-size FLOWRAW, then the
+// blend of the kept raw Flow as for skip_flow.  A plain forward's pack is not repeated.
+static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, const Items& items, void* stream,
+                        const rrin_flow_scale* fs = nullptr) {
+  const int mult = fs ? 16 * fs->s : 16;
   const rrin_net_u8_desc* u8 = f.u8;
   const rrin_net_yuv_desc* yuv = f.yuv;
   const rrin_net_u16_desc* u16 = f.u16;
@@ -736,6 +745,11 @@ static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, const Items& i
   Plan p;
   make_plan(d->n, d->h, d->w, d->prec, reinterpret_cast<char*>(d->workspace), p);
   if (d->workspace_bytes < p.bytes) return RRIN_E_WORKSPACE;
+  Plan pl;  // fs: the plan of the Flow phase at (h / s, w / s), sized for the d->n images
+  if (fs) {
+    make_plan(d->n, d->h / fs->s, d->w / fs->s, d->prec, reinterpret_cast<char*>(fs->workspace), pl);
+    if (fs->workspace_bytes < pl.bytes) return RRIN_E_WORKSPACE;
+  }
   attach_scratch(p, d->scratch, d->scratch_bytes,
                  scratch_tickets_of(d->n, d->h, d->w, d->prec, d->convs, kUNets, 4, d->scratch));
   p.prof = d->prof;  // per call: concurrent calls never share launch state
@@ -749,15 +763,43 @@ static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, const Items& i
     const rrin_h8 gall = hview(p.G, 0, 16);
     // the frame pack of m images: image k from frame k, or with a map from frame map[k] of np
     auto pack = [&](int m, const int32_t* map, int np) {
-      return u8    ? pack_g16_u8_items(u8->f0, u8->f1, u8->img_stride, m, u8->h0, u8->w0, &gall, d->prec, map, np, st)
-             : yuv ? pack_g16_yuv_items(&yuv->f0, &yuv->f1, &yuv->coef, m, yuv->h0, yuv->w0, &gall, d->prec, map, np, st)
+      return u8    ? pack_g16_u8_items(u8->f0, u8->f1, u8->img_stride, m, u8->h0, u8->w0, &gall, d->prec, map, np, st,
+                                       mult)
+             : yuv ? pack_g16_yuv_items(&yuv->f0, &yuv->f1, &yuv->coef, m, yuv->h0, yuv->w0, &gall, d->prec, map, np, st,
+                                        mult)
              : u16 ? pack_g16_u16_items(u16->f0, u16->f1, u16->img_stride, m, u16->h0, u16->w0, u16->depth, &gall,
-                                        d->prec, map, np, st)
-                   : pack_g16_yuv16_items(&y16->f0, &y16->f1, &y16->coef, m, y16->h0, y16->w0, &gall, d->prec, map, np,
-                                          st);
+                                        d->prec, map, np, st, mult)
+             : y16 ? pack_g16_yuv16_items(&y16->f0, &y16->f1, &y16->coef, m, y16->h0, y16->w0, &gall, d->prec, map, np,
+                                          st, mult)
+                   : rrin_pack_g16_h8(d->i0, d->i1, m, &gall, d->prec, st);
     };
     int rc = 0;
-    if (items.map && !d->skip_flow) {  // Flow phase: the Flow U-Net once per pair
+    bool packed = false;  // the full-size g16 already holds the d->n images of the call
+    if (fs && !d->skip_flow) {  // Flow phase at (h / s, w / s), once per pair
+      const int nf = items.map ? items.n_pairs : d->n;
+      attach_scratch(pl, fs->scratch, fs->scratch_bytes,
+                     scratch_tickets_of(d->n, d->h / fs->s, d->w / fs->s, d->prec, fs->convs, kUNets, 4, fs->scratch));
+      pl.n = nf;
+      pl.prof = p.prof;
+      pl.status = p.status;
+      const rrin_h8 glow = hview(pl.G, 0, 16);
+      {
+        ProfScope ps(p.prof, st, RRIN_KIND_LAYOUT, 0.0);
+        rc = pack(nf, nullptr, nf);
+      }
+      if (!rc) {
+        ProfScope ps(p.prof, st, RRIN_KIND_LAYOUT, 0.0);
+        rc = rrin_g16_downscale_h8(&gall, &glow, nf, fs->s, d->prec, st);
+      }
+      // its head also blends into the low-res g16 (channels 6-9, which the next downscale zeroes)
+      if (!rc) rc = run_unet_h8(pl, kUNets[0], fs->convs, d->heads[0], HeadIO{d->coef, nullptr, nullptr}, st);
+      if (!rc) {
+        ProfScope ps(p.prof, st, RRIN_KIND_LAYOUT, 0.0);
+        const rrin_h8 frl = hview(pl.FLOWRAW, 0, 4), frh = hview(p.FLOWRAW, 0, 4);
+        rc = rrin_flow_upscale_h8(&frl, &frh, nf, fs->s, d->prec, p.status, st);
+      }
+      packed = !items.map;
+    } else if (items.map && !d->skip_flow) {  // Flow phase: the Flow U-Net once per pair
       Plan pf = p;
       pf.n = items.n_pairs;
       {
@@ -768,13 +810,12 @@ static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, const Items& i
       // pack below overwrites those channels
       if (!rc) rc = run_unet_h8(pf, kUNets[0], d->convs, d->heads[0], HeadIO{d->coef, nullptr, nullptr}, st);
     }
-    const bool blend = d->skip_flow || items.map;  // Ft0 / Ft1 from the kept raw Flow
+    const bool blend = d->skip_flow || items.map || fs;  // Ft0 / Ft1 from the kept raw Flow
     if (!rc) {
       ProfScope ps(p.prof, st, RRIN_KIND_LAYOUT, 0.0);
       // x0, x1 into channels 0-5; channels 6-15 zeroed, so the first convs (cin 6/9/10)
       // can stage whole records (their tail channels are finite and meet zero weights)
-      rc = u8 || yuv || u16 || y16 ? pack(d->n, items.map, items.map ? items.n_pairs : d->n)
-                                   : rrin_pack_g16_h8(d->i0, d->i1, d->n, &gall, d->prec, st);
+      if (!packed) rc = pack(d->n, items.map, items.map ? items.n_pairs : d->n);
       if (!rc && blend) {
         const rrin_h8 fr = hview(p.FLOWRAW, 0, 4);
         rc = items.map ? rrin_flow_tblend_items_h8(&fr, &gall, d->coef, d->n, items.map, items.n_pairs, d->prec, st)
@@ -850,19 +891,19 @@ extern "C" int rrin_net_fwd(const rrin_net_desc* d, void* stream) {
 // The argument checks of the frame forwards, shared with their item forms: `frames` is the number
 // of frames of f0 and of f1 -- net.n for a plain forward, the pairs of an item forward -- and the
 // output always holds net.n frames.
-static int net_u8_check(const rrin_net_u8_desc* d, int frames) {
+static int net_u8_check(const rrin_net_u8_desc* d, int frames, int mult = 16) {
   if (!d || !d->f0 || !d->f1 || !d->out_u8) return RRIN_E_ARG;
   const rrin_net_desc* nd = &d->net;
   if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
   // the record precisions only: the planar fp32 path has no 8-bit pack / store
   if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
   if (nd->n < 1 || d->h0 < 1 || d->w0 < 1) return RRIN_E_SHAPE;
-  if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  if (nd->h != pad_up(d->h0, mult) || nd->w != pad_up(d->w0, mult)) return RRIN_E_SHAPE;
   if (frames > 1 && d->img_stride < (int64_t)d->h0 * d->w0 * 3) return RRIN_E_ARG;
   return 0;
 }
 
-static int net_yuv_check(const rrin_net_yuv_desc* d, int frames) {
+static int net_yuv_check(const rrin_net_yuv_desc* d, int frames, int mult = 16) {
   if (!d) return RRIN_E_ARG;
   const rrin_net_desc* nd = &d->net;
   if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
@@ -873,23 +914,23 @@ static int net_yuv_check(const rrin_net_yuv_desc* d, int frames) {
     if (int rc = yuv420_check(*s, s == &d->out ? nd->n : frames, d->h0, d->w0)) return rc;
     if (s->chroma != d->f0.chroma) return RRIN_E_ARG;
   }
-  if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  if (nd->h != pad_up(d->h0, mult) || nd->w != pad_up(d->w0, mult)) return RRIN_E_SHAPE;
   return 0;
 }
 
-static int net_u16_check(const rrin_net_u16_desc* d, int frames) {
+static int net_u16_check(const rrin_net_u16_desc* d, int frames, int mult = 16) {
   if (!d || !d->f0 || !d->f1 || !d->out_u16 || d->depth < 9 || d->depth > 16) return RRIN_E_ARG;
   const rrin_net_desc* nd = &d->net;
   if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
   // the record precisions only, as rrin_net_u8_fwd
   if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
   if (nd->n < 1 || d->h0 < 1 || d->w0 < 1) return RRIN_E_SHAPE;
-  if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  if (nd->h != pad_up(d->h0, mult) || nd->w != pad_up(d->w0, mult)) return RRIN_E_SHAPE;
   if (frames > 1 && d->img_stride < (int64_t)d->h0 * d->w0 * 3) return RRIN_E_ARG;
   return 0;
 }
 
-static int net_yuv16_check(const rrin_net_yuv16_desc* d, int frames) {
+static int net_yuv16_check(const rrin_net_yuv16_desc* d, int frames, int mult = 16) {
   if (!d) return RRIN_E_ARG;
   const rrin_net_desc* nd = &d->net;
   if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
@@ -899,7 +940,7 @@ static int net_yuv16_check(const rrin_net_yuv16_desc* d, int frames) {
     if (s->depth != d->f0.depth || s->shift != d->f0.shift || s->chroma != d->f0.chroma) return RRIN_E_ARG;
   }
   if (int rc = yuv_coef_check16(&d->coef, d->f0.depth)) return rc;
-  if (nd->h != (d->h0 + 15) / 16 * 16 || nd->w != (d->w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  if (nd->h != pad_up(d->h0, mult) || nd->w != pad_up(d->w0, mult)) return RRIN_E_SHAPE;
   return 0;
 }
 
@@ -972,6 +1013,72 @@ extern "C" int rrin_net_yuv16_items_fwd(const rrin_net_yuv16_desc* d, const rrin
   FrameIO f;
   f.yuv16 = d;
   return net_fwd_impl(&d->net, f, items, stream);
+}
+
+// ---- flow_scale forwards: rrin_flow_scale beside the descriptors ---------------------------
+// The second plan first (RRIN_E_ARG: null members, s not 2 or 4, taps, the planar precision;
+// RRIN_E_SHAPE: a padded size that is no multiple of 16 * s), then the forward's own checks with the
+// pad multiple 16 * s.  items may be NULL (a plain forward).
+static int flow_scale_check(const rrin_net_desc* nd, const rrin_flow_scale* fs) {
+  if (!nd || !fs || (fs->s != 2 && fs->s != 4) || !fs->convs || !fs->workspace || nd->taps) return RRIN_E_ARG;
+  if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
+  if (nd->n < 1 || nd->h < 16 * fs->s || nd->w < 16 * fs->s || nd->h % (16 * fs->s) || nd->w % (16 * fs->s))
+    return RRIN_E_SHAPE;
+  return 0;
+}
+
+static int scaled_items(const rrin_items* it, int n, Items& items) {
+  return it ? items_of(it, n, items) : 0;
+}
+
+extern "C" int rrin_net_scaled_fwd(const rrin_net_desc* d, const rrin_flow_scale* fs, void* stream) {
+  if (int rc = flow_scale_check(d, fs)) return rc;
+  if (!d->i0 || !d->i1 || !d->out || !d->coef || !d->convs || !d->heads || !d->workspace) return RRIN_E_ARG;
+  return net_fwd_impl(d, FrameIO{}, Items{}, stream, fs);
+}
+
+extern "C" int rrin_net_u8_scaled_fwd(const rrin_net_u8_desc* d, const rrin_items* it, const rrin_flow_scale* fs,
+                                      void* stream) {
+  Items items;
+  if (int rc = flow_scale_check(d ? &d->net : nullptr, fs)) return rc;
+  if (int rc = scaled_items(it, d->net.n, items)) return rc;
+  if (int rc = net_u8_check(d, it ? items.n_pairs : d->net.n, 16 * fs->s)) return rc;
+  FrameIO f;
+  f.u8 = d;
+  return net_fwd_impl(&d->net, f, items, stream, fs);
+}
+
+extern "C" int rrin_net_yuv_scaled_fwd(const rrin_net_yuv_desc* d, const rrin_items* it, const rrin_flow_scale* fs,
+                                       void* stream) {
+  Items items;
+  if (int rc = flow_scale_check(d ? &d->net : nullptr, fs)) return rc;
+  if (int rc = scaled_items(it, d->net.n, items)) return rc;
+  if (int rc = net_yuv_check(d, it ? items.n_pairs : d->net.n, 16 * fs->s)) return rc;
+  FrameIO f;
+  f.yuv = d;
+  return net_fwd_impl(&d->net, f, items, stream, fs);
+}
+
+extern "C" int rrin_net_u16_scaled_fwd(const rrin_net_u16_desc* d, const rrin_items* it, const rrin_flow_scale* fs,
+                                       void* stream) {
+  Items items;
+  if (int rc = flow_scale_check(d ? &d->net : nullptr, fs)) return rc;
+  if (int rc = scaled_items(it, d->net.n, items)) return rc;
+  if (int rc = net_u16_check(d, it ? items.n_pairs : d->net.n, 16 * fs->s)) return rc;
+  FrameIO f;
+  f.u16 = d;
+  return net_fwd_impl(&d->net, f, items, stream, fs);
+}
+
+extern "C" int rrin_net_yuv16_scaled_fwd(const rrin_net_yuv16_desc* d, const rrin_items* it, const rrin_flow_scale* fs,
+                                         void* stream) {
+  Items items;
+  if (int rc = flow_scale_check(d ? &d->net : nullptr, fs)) return rc;
+  if (int rc = scaled_items(it, d->net.n, items)) return rc;
+  if (int rc = net_yuv16_check(d, it ? items.n_pairs : d->net.n, 16 * fs->s)) return rc;
+  FrameIO f;
+  f.yuv16 = d;
+  return net_fwd_impl(&d->net, f, items, stream, fs);
 }
 
 // One U-Net alone (reference UNet.forward, unet.py:40-51): NCHW in -> NCHW out,

@@ -188,4 +188,18 @@ struct RecR32 {
   };
 };
 
+// ---- host side ---------------------------------------------------------------------
+// fn(F{}) with the record format F of a record precision (rec_prec(prec) checked by the caller)
+template <class Fn>
+static int with_format(int prec, Fn&& fn) {
+  if (prec == RRIN_PREC_F32R) return fn(RecR32{});
+  return planes_of(prec) == 2 ? fn(RecH8<2>{}) : fn(RecH8<1>{});
+}
+
+static inline RecView rec_view(const rrin_h8& v) {
+  const int64_t off = (int64_t)v.g_off * v.g.plane;
+  return RecView{static_cast<uint4*>(v.hi) + off, v.lo ? static_cast<uint4*>(v.lo) + off : nullptr, v.img_stride,
+                 v.g.plane, v.g.wp};
+}
+
 }  // namespace rrin

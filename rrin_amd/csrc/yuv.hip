@@ -34,7 +34,8 @@ __device__ inline void pack_g16_yuv_body(const rrin_yuv420& f0, const rrin_yuv42
   const int xs = blockIdx.x * 256, y = blockIdx.y;
   s_tab[tid] = kU8Scale.v[tid];
   const int sy = y > top ? y - top : 0;
-  // xs < w0: the right pad is < 16 columns, xs a multiple of 256; np is even unless 4:4:4 (w0 odd)
+  // xs < w0: w is w0 rounded up to a multiple m of 16, 32 or 64 (16 * flow_scale), so the right pad is
+  // < m columns; xs < w is a multiple of 256, hence of m: xs <= w - m < w0.  np is even unless 4:4:4 (w0 odd)
   const int np = min(256, w0 - xs);
   const int cy = CH == RRIN_CHROMA_420 ? sy >> 1 : sy;
   const int which = tid >> 7, blk = tid & 127;
@@ -124,7 +125,8 @@ __device__ inline void pack_g16_yuv16_body(const rrin_yuv420_16& f0, const rrin_
   const int tid = threadIdx.x;
   const int xs = blockIdx.x * 256, y = blockIdx.y;
   const int sy = y > top ? y - top : 0;
-  // xs < w0: the right pad is < 16 columns, xs a multiple of 256; np is even unless 4:4:4 (w0 odd)
+  // xs < w0: w is w0 rounded up to a multiple m of 16, 32 or 64 (16 * flow_scale), so the right pad is
+  // < m columns; xs < w is a multiple of 256, hence of m: xs <= w - m < w0.  np is even unless 4:4:4 (w0 odd)
   const int np = min(256, w0 - xs);
   const int cy = CH == RRIN_CHROMA_420 ? sy >> 1 : sy;
   const int which = tid >> 7, blk = tid & 127;
@@ -263,7 +265,7 @@ extern "C" int rrin_yuv_coef_std(int32_t standard, int32_t full_range, rrin_yuv_
 // (NULL: image k reads frame k, n_pairs == n); the stacks are checked for their n_pairs frames
 int rrin::pack_g16_yuv_items(const rrin_yuv420* f0, const rrin_yuv420* f1, const rrin_yuv_coef* coef, int32_t n,
                              int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec, const int32_t* map,
-                             int32_t n_pairs, hipStream_t stream) {
+                             int32_t n_pairs, hipStream_t stream, int32_t mult) {
   if (!f0 || !f1 || !g16 || n < 1 || !rec_prec(prec)) return RRIN_E_ARG;
   if (n_pairs < 1 || n_pairs > n || (!map && n_pairs != n)) return RRIN_E_ARG;
   if (int rc = yuv_coef_check(coef)) return rc;
@@ -272,7 +274,7 @@ int rrin::pack_g16_yuv_items(const rrin_yuv420* f0, const rrin_yuv420* f1, const
   if (f0->chroma != f1->chroma) return RRIN_E_ARG;
   if (!h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16) return RRIN_E_SHAPE;
   const int h = g16->g.h, w = g16->g.w;
-  if (h != (h0 + 15) / 16 * 16 || w != (w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  if (h != pad_up(h0, mult) || w != pad_up(w0, mult)) return RRIN_E_SHAPE;
   if (n > 65535 || h > 65535) return RRIN_E_SHAPE;  // grid y / z
   const dim3 grid((w + 255) / 256, h, n);
   const int top = h - h0;
@@ -313,7 +315,7 @@ extern "C" int rrin_yuv_coef_std16(int32_t standard, int32_t full_range, int32_t
 
 int rrin::pack_g16_yuv16_items(const rrin_yuv420_16* f0, const rrin_yuv420_16* f1, const rrin_yuv_coef* coef,
                                int32_t n, int32_t h0, int32_t w0, const rrin_h8* g16, int32_t prec,
-                               const int32_t* map, int32_t n_pairs, hipStream_t stream) {
+                               const int32_t* map, int32_t n_pairs, hipStream_t stream, int32_t mult) {
   if (!f0 || !f1 || !g16 || n < 1 || !rec_prec(prec)) return RRIN_E_ARG;
   if (n_pairs < 1 || n_pairs > n || (!map && n_pairs != n)) return RRIN_E_ARG;
   if (int rc = yuv420_16_check(*f0, n_pairs, h0, w0)) return rc;
@@ -322,7 +324,7 @@ int rrin::pack_g16_yuv16_items(const rrin_yuv420_16* f0, const rrin_yuv420_16* f
   if (int rc = yuv_coef_check16(coef, f0->depth)) return rc;
   if (!h8_ok(*g16, prec) || g16->g_off != 0 || g16->groups * chans_per_rec(prec) < 16) return RRIN_E_SHAPE;
   const int h = g16->g.h, w = g16->g.w;
-  if (h != (h0 + 15) / 16 * 16 || w != (w0 + 15) / 16 * 16) return RRIN_E_SHAPE;
+  if (h != pad_up(h0, mult) || w != pad_up(w0, mult)) return RRIN_E_SHAPE;
   if (n > 65535 || h > 65535) return RRIN_E_SHAPE;  // grid y / z
   const dim3 grid((w + 255) / 256, h, n);
   const int top = h - h0;

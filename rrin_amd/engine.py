@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from .convert import scene_cut_code, scene_limit, scene_limit_len
+from .flowscale import check_flow_scale, flow_tag, padded_size
 from .unet import _level_of
 
 UNET_ORDER = ("Flow", "refine_flow", "Mask", "final")
@@ -615,7 +616,10 @@ def pack_h8_host(records, cfgs, prec: int):
 # the buffers of one forward part, obtained before the fork (RRINEngine._run_parts): key = (pairs,
 # h, w, stream slot), its workspace, conv table, split-K / ring scratch (or None) and fp16 range
 # flag (None for the fp32 precisions)
-Part = namedtuple("Part", "key ws convs scratch status")
+Part = namedtuple("Part", "key ws convs scratch status low", defaults=(None,))
+# the second plan of a flow_scale forward part (the Flow U-Net at (h / s, w / s)): the
+# rrin_flow_scale that names it and the buffers it points to, kept alive with the part
+Low = namedtuple("Low", "fs ws convs scratch")
 
 
 class RRINEngine:
@@ -777,9 +781,14 @@ class RRINEngine:
             nbytes = self.lib.rrin_net_workspace_bytes(n, h, w, self.prec)
             if nbytes < 0:
                 _lib.check(int(nbytes), "rrin_net_workspace_bytes")
-            while len(self._ws) >= self.MAX_WORKSPACES:
-                lru = next(iter(self._ws))   # least recently used part: evict its whole shape
-                for old in [k for k in self._ws if k[1:3] == lru[1:3]]:
+            # a second plan of a flow_scale part (slot ("flow_scale", s, H, W, slot), _part) is not
+            # counted: it lives and goes with the parts of its full size (H, W), at most two per part
+            # (s = 2 and 4), so a 4-stream flow_scale forward still leaves room for a second shape
+            second = lambda k: isinstance(k[3], tuple)  # noqa: E731
+            while not second(key) and sum(1 for k in self._ws if not second(k)) >= self.MAX_WORKSPACES:
+                lru = next(k for k in self._ws if not second(k))   # least recently used part: evict its whole shape
+                for old in [k for k in self._ws
+                            if (k[3][2:4] if second(k) else k[1:3]) == lru[1:3]]:
                     del self._ws[old]
                     self._flow_valid.pop(old, None)
                     for sk in [k for k in self._scratch if k[0] == old]:
@@ -825,7 +834,8 @@ class RRINEngine:
         return self._sides[:k]
 
     def forward(self, i0: torch.Tensor, i1: torch.Tensor, t=0.5, prof=None, reuse_flow: bool = False,
-                streams: int | None = 1, split=None, taps: dict | None = None) -> torch.Tensor:
+                streams: int | None = 1, split=None, taps: dict | None = None,
+                flow_scale: int = 1) -> torch.Tensor:
         """One Net.forward.  ``reuse_flow=True`` promises that (i0, i1) is the pair
         of the previous call with the same shape: the Flow U-Net (t-independent,
         model.py:35, 30 % of the FLOPs) is skipped and its kept raw output is
@@ -839,7 +849,16 @@ class RRINEngine:
         ``taps`` (test / debug, one stream only): a dict that receives the four
         U-Nets' raw outputs (their ``last`` conv before the model.py glue,
         unet.py:51 as used at model.py:35,42,52,62) as NCHW fp32 tensors under
-        "Flow", "refine_flow", "Mask", "final"."""
+        "Flow", "refine_flow", "Mask", "final".
+
+        ``flow_scale`` 2 or 4 (:mod:`rrin_amd.flowscale`): the Flow U-Net runs at 1/s of the size
+        and its flow is scaled up; H and W must be multiples of 16 * s; record precisions only;
+        no taps.  A kept raw Flow is reused only by a call of the same scale."""
+        flow_scale = check_flow_scale(flow_scale)
+        if flow_scale > 1:
+            self._need_records(f"flow_scale={flow_scale}")
+            if taps is not None:
+                raise ValueError("taps need flow_scale=1")
         if i0.device != self.device or i1.device != self.device:
             raise RuntimeError(f"inputs on {i0.device}/{i1.device}, model on {self.device}")
         if i0.dtype != torch.float32 or i1.dtype != torch.float32:
@@ -850,6 +869,9 @@ class RRINEngine:
         if h % 16 or w % 16 or n < 1:
             raise RuntimeError(f"H and W must be multiples of 16 (the Flow U-Net pools 4 times); "
                                f"got {h}x{w} (reference fails at model.py:41)")
+        if (h, w) != padded_size(h, w, flow_scale):
+            raise RuntimeError(f"flow_scale={flow_scale} needs H and W that are multiples of {16 * flow_scale}; "
+                               f"got {h}x{w}")
         self._poll_range()
         i0 = i0.contiguous()
         i1 = i1.contiguous()
@@ -870,7 +892,7 @@ class RRINEngine:
             d.taps = tapbuf.data_ptr() if tapbuf is not None else None
             self._launch(self.lib.rrin_net_fwd, "rrin_net_fwd", d, d, p, "f32", reuse_flow, stream)
 
-        self._run_parts(h, w, bounds, part)
+        self._run_parts(h, w, bounds, part, flow_scale)
         if tapbuf is not None:
             off = 0
             for name, c in zip(UNET_ORDER, (4, 4, 2, 3)):
@@ -1015,7 +1037,8 @@ class RRINEngine:
         return sad
 
     def forward_u8(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, reuse_flow: bool = False,
-                   streams: int | None = None, split=None, scene_threshold=None, gate=None) -> torch.Tensor:
+                   streams: int | None = None, split=None, scene_threshold=None, gate=None,
+                   flow_scale: int = 1) -> torch.Tensor:
         """One Net.forward on 8-bit frames of any size: ``f0`` / ``f1`` uint8 ``[N,H0,W0,3]`` (RGB
         interleaved) on the engine's device -> uint8 ``[N,H0,W0,3]``.  Bit for bit
         ``convert.load_frame`` -> :meth:`forward` -> ``convert.to_uint8_image``: the edge padding
@@ -1044,11 +1067,17 @@ class RRINEngine:
         The network still runs for a gated pair and its frame is overwritten afterwards:
         skipping it would need the codes on the host, a device-to-host sync per step.  The range
         guard does not look at the gate: a gated frame is the copied input even when its pair
-        overflowed, and ``check_range`` still raises."""
+        overflowed, and ``check_range`` still raises.
+
+        ``flow_scale`` 2 or 4 (:mod:`rrin_amd.flowscale`): the Flow U-Net runs on the frames at 1/s
+        of their size and its flow is scaled up; the padding is then to a multiple of 16 * s, and
+        the definition reads pad -> ``forward(..., flow_scale=s)`` -> ``to_uint8_image`` -> crop.  The
+        gate and its codes do not depend on it; a kept raw Flow is reused only at the same scale."""
+        flow_scale = check_flow_scale(flow_scale)
         self._need_records("forward_u8")
         f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_u8", rgb=True)
         n = f0.shape[0]
-        h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
+        h, w = padded_size(h0, w0, flow_scale)
         self._poll_range()
         coef = t_coefficients(t, n).to(self.device, non_blocking=True)
         bounds = self._bounds(n, streams, split)
@@ -1067,7 +1096,7 @@ class RRINEngine:
             if g is not None:
                 self._enqueue_gate(g, p0, p1, s0, lo, hi, h0, w0, po, stream)
 
-        self._run_parts(h, w, bounds, part)
+        self._run_parts(h, w, bounds, part, flow_scale)
         return out
 
     def _need_records(self, what: str):
@@ -1123,7 +1152,7 @@ class RRINEngine:
 
     def forward_yuv(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, layout: str = "nv12", coef=None,
                     reuse_flow: bool = False, streams: int | None = None, split=None, scene_threshold=None,
-                    gate=None) -> torch.Tensor:
+                    gate=None, flow_scale: int = 1) -> torch.Tensor:
         """One Net.forward on 8-bit YUV 4:2:0 frames: ``f0`` / ``f1`` uint8 ``[N, 3*H0//2, W0]``
         (H0, W0 even; ``layout`` "nv12" or "i420", see :mod:`rrin_amd.yuv`) on the engine's device
         -> uint8 ``[N, 3*H0//2, W0]`` of the same layout.  By definition, and bit for bit,
@@ -1150,8 +1179,11 @@ class RRINEngine:
         ``[N, 3*H0, W0]``, any size) run the same way: by definition ``yuv.rgb_to_yuv(forward_u8(
         yuv.yuv_to_rgb(f0, layout), yuv.yuv_to_rgb(f1, layout), t), layout)``, the output a stack of
         the input's layout and shape.  Their gate sums the frame's ``2*H0*W0`` / ``3*H0*W0`` bytes
-        (rrin_pair_sad_u8_len): a cut exceeds ``floor(scene_threshold * that count)``."""
+        (rrin_pair_sad_u8_len): a cut exceeds ``floor(scene_threshold * that count)``.
+
+        ``flow_scale``: as in :meth:`forward_u8`, which the definition passes it to."""
         from . import yuv
+        flow_scale = check_flow_scale(flow_scale)
         self._need_records("forward_yuv")
         if layout not in yuv.ALL_LAYOUTS:
             raise ValueError(f"layout must be one of {yuv.ALL_LAYOUTS}, got {layout!r}")
@@ -1159,7 +1191,7 @@ class RRINEngine:
         f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_yuv", rgb=False, layout=layout)
         samples = self._yuv_gate_samples(h0, w0, layout)
         n = f0.shape[0]
-        h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
+        h, w = padded_size(h0, w0, flow_scale)
         self._poll_range()
         tcoef = t_coefficients(t, n).to(self.device, non_blocking=True)
         bounds = self._bounds(n, streams, split)
@@ -1183,7 +1215,7 @@ class RRINEngine:
             if g is not None:
                 self._enqueue_gate(g, p0, p1, s0, lo, hi, h0 // 2, w0, po, stream, samples=samples)
 
-        self._run_parts(h, w, bounds, part)
+        self._run_parts(h, w, bounds, part, flow_scale)
         return out
 
     def pair_stats_yuv(self, f0: torch.Tensor, f1: torch.Tensor, layout: str = "nv12") -> torch.Tensor:
@@ -1203,7 +1235,8 @@ class RRINEngine:
         return depth
 
     def forward_u16(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, depth: int = 10, reuse_flow: bool = False,
-                    streams: int | None = None, split=None, scene_threshold=None, gate=None) -> torch.Tensor:
+                    streams: int | None = None, split=None, scene_threshold=None, gate=None,
+                    flow_scale: int = 1) -> torch.Tensor:
         """:meth:`forward_u8` on 16-bit frames: ``f0`` / ``f1`` uint16 ``[N,H0,W0,3]`` holding RGB
         samples of ``depth`` 9..16 in the words' low bits -> uint16 ``[N,H0,W0,3]`` of that depth.
         Bit for bit ``convert.frames_u16_to_float`` -> :meth:`forward` ->
@@ -1213,12 +1246,14 @@ class RRINEngine:
         views of one stack without a copy, the stream split, ``reuse_flow``, the range guard and
         the scene gate -- with ``scene_threshold`` a mean absolute sample difference in
         [0, maxval] over ``min(word, maxval)`` (rrin_pair_sad_u16), and a gated frame its input
-        frame's words as they are.  A kept raw Flow is only reused by this path at this depth."""
+        frame's words as they are.  A kept raw Flow is only reused by this path at this depth.
+        ``flow_scale``: as in :meth:`forward_u8` (``forward(..., flow_scale=s)`` in the definition)."""
+        flow_scale = check_flow_scale(flow_scale)
         self._need_records("forward_u16")
         depth = self._depth16(depth, 9, "forward_u16")
         f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_u16", rgb=True, dtype=torch.uint16)
         n = f0.shape[0]
-        h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
+        h, w = padded_size(h0, w0, flow_scale)
         self._poll_range()
         coef = t_coefficients(t, n).to(self.device, non_blocking=True)
         bounds = self._bounds(n, streams, split)
@@ -1236,7 +1271,7 @@ class RRINEngine:
             if g is not None:
                 self._enqueue_gate(g, p0, p1, s0, lo, hi, h0, w0, po, stream, wide=(depth, 0))
 
-        self._run_parts(h, w, bounds, part)
+        self._run_parts(h, w, bounds, part, flow_scale)
         return out
 
     def pair_stats_u16(self, f0: torch.Tensor, f1: torch.Tensor, depth: int = 10) -> torch.Tensor:
@@ -1266,7 +1301,7 @@ class RRINEngine:
 
     def forward_yuv16(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, layout: str = "nv12", depth: int = 10,
                       msb: bool = False, coef=None, reuse_flow: bool = False, streams: int | None = None, split=None,
-                      scene_threshold=None, gate=None) -> torch.Tensor:
+                      scene_threshold=None, gate=None, flow_scale: int = 1) -> torch.Tensor:
         """:meth:`forward_yuv` on 10- or 12-bit 4:2:0 frames in 16-bit words: ``f0`` / ``f1`` uint16
         ``[N, 3*H0//2, W0]`` -> uint16 of the same shape, layout, depth and alignment (``msb=False``:
         the sample in the low bits, as yuv420p10le and Y4M C420p10; ``True``: in the high bits, as
@@ -1278,8 +1313,10 @@ class RRINEngine:
         ``min(word >> shift, maxval)``, luma and chroma, with ``scene_threshold`` in [0, maxval]; a
         kept raw Flow is only reused by a call of the same layout, depth, alignment and matrix.
         The 4:2:2 and 4:4:4 layouts ("nv16", "i422", "i444") run as in :meth:`forward_yuv`, defined by
-        ``yuv.rgb16_to_yuv`` / ``yuv.yuv_to_rgb16``, the gate on the frame's samples (rrin_pair_sad_u16_len)."""
+        ``yuv.rgb16_to_yuv`` / ``yuv.yuv_to_rgb16``, the gate on the frame's samples (rrin_pair_sad_u16_len).
+        ``flow_scale``: as in :meth:`forward_u16`, which the definition passes it to."""
         from . import yuv
+        flow_scale = check_flow_scale(flow_scale)
         self._need_records("forward_yuv16")
         if layout not in yuv.ALL_LAYOUTS:
             raise ValueError(f"layout must be one of {yuv.ALL_LAYOUTS}, got {layout!r}")
@@ -1289,7 +1326,7 @@ class RRINEngine:
         f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_yuv16", rgb=False, dtype=torch.uint16, layout=layout)
         samples = self._yuv_gate_samples(h0, w0, layout)
         n = f0.shape[0]
-        h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
+        h, w = padded_size(h0, w0, flow_scale)
         self._poll_range()
         tcoef = t_coefficients(t, n).to(self.device, non_blocking=True)
         bounds = self._bounds(n, streams, split)
@@ -1313,7 +1350,7 @@ class RRINEngine:
                 self._enqueue_gate(g, p0, p1, s0, lo, hi, h0 // 2, w0, po, stream, wide=(depth, shift),
                                    samples=samples)
 
-        self._run_parts(h, w, bounds, part)
+        self._run_parts(h, w, bounds, part, flow_scale)
         return out
 
     def pair_stats_yuv16(self, f0: torch.Tensor, f1: torch.Tensor, depth: int = 10, msb: bool = False,
@@ -1372,7 +1409,7 @@ class RRINEngine:
     # raw Flow (reuse_flow) are the two bitwise guarantees it rests on.
 
     def _run_items(self, f0, f1, s0: int, h0: int, w0: int, pairs, ts, out, make, fwd, streams, split, prof,
-                   gate_cfg):
+                   gate_cfg, flow_scale: int = 1):
         """The item forward of every frame path.  f0 / f1: the checked views ``frames[:-1]`` /
         ``frames[1:]`` (stride s0 elements); pairs / ts: :func:`check_items`' result; out: the ``[M,
         ...]`` output stack; ``make(p0, p1, po)`` returns the path's descriptor with its frames set
@@ -1382,10 +1419,12 @@ class RRINEngine:
         of its own items (a pair whose items straddle two parts is computed in both).  A part's
         pairs are a run of the stack, so its frames are views; pairs that skip some (an arbitrary
         caller) are gathered into a copy.  ``gate_cfg``: None or (scene_threshold, gate, maxval,
-        frame length in elements, (depth, shift) or None)."""
+        frame length in elements, (depth, shift) or None).  ``flow_scale`` s > 1: the library's
+        ``_scaled_fwd`` entry of the path with the part's second plan, the Flow phase at 1/s of the
+        size on the part's pairs."""
         m = len(pairs)
         n_stack = f0.shape[0]
-        h, w = (h0 + 15) // 16 * 16, (w0 + 15) // 16 * 16
+        h, w = padded_size(h0, w0, flow_scale)
         self._poll_range()
         tl = ts.tolist() if isinstance(ts, torch.Tensor) else ts
         bounds = self._bounds(m, streams, split)
@@ -1445,7 +1484,12 @@ class RRINEngine:
             it = _lib.Items()
             it.n_pairs, it.pair_map = npairs, maps[lo:hi].data_ptr()
             nd.skip_flow = 0
-            _lib.check(getattr(self.lib, fwd)(C.byref(desc), C.byref(it), C.c_void_p(stream.cuda_stream)), fwd)
+            if p.low is None:
+                _lib.check(getattr(self.lib, fwd)(C.byref(desc), C.byref(it), C.c_void_p(stream.cuda_stream)), fwd)
+            else:
+                sfwd = fwd.replace("_items_fwd", "_scaled_fwd")
+                _lib.check(getattr(self.lib, sfwd)(C.byref(desc), C.byref(it), C.byref(p.low.fs),
+                                                   C.c_void_p(stream.cuda_stream)), sfwd)
             # the workspace now keeps the raw Flow of this call's pairs: no forward_* may reuse it
             self._flow_valid[p.key] = False
             if p.status is not None:
@@ -1477,7 +1521,7 @@ class RRINEngine:
                                                               maps[lo:hi].data_ptr(), npairs, sp),
                        "rrin_gate_frames_items_u8_len")
 
-        self._run_parts(h, w, bounds, part)
+        self._run_parts(h, w, bounds, part, flow_scale)
         return out
 
     def _item_frames(self, frames, what: str, rgb: bool, dtype=torch.uint8, layout: str = "nv12"):
@@ -1487,7 +1531,7 @@ class RRINEngine:
         return self._frames(frames[:-1], frames[1:], what, rgb=rgb, dtype=dtype, layout=layout)
 
     def interpolate_items_u8(self, frames: torch.Tensor, pair, t, streams: int | None = None, split=None,
-                             scene_threshold=None, gate=None, prof=None) -> torch.Tensor:
+                             scene_threshold=None, gate=None, prof=None, flow_scale: int = 1) -> torch.Tensor:
         """A batch of M items ``(pair[k], t[k])`` over one stack of 8-bit frames: ``frames`` uint8
         ``[P+1,H0,W0,3]`` on the device (pair p is frames p and p + 1), ``pair`` M non-decreasing
         ints in [0, P) (list or int32 tensor), ``t`` M floats in [0, 1) (list or fp32 tensor) ->
@@ -1501,7 +1545,9 @@ class RRINEngine:
         frame, a cut pair the nearer frame by the item's own t (``scene_cut_code(t[k])``).  The sums
         run once per distinct pair.  ``gate``: an int32 device tensor ``[P]`` of pair codes (1: a
         duplicate, 2: a cut, else interpolate).  :attr:`last_gate` is then the ``[M]`` item codes
-        (1: the first frame, 2: the second, 0: interpolated)."""
+        (1: the first frame, 2: the second, 0: interpolated).  ``flow_scale`` is passed to the
+        defining ``forward_u8`` (rrin_net_u8_scaled_fwd with the items)."""
+        flow_scale = check_flow_scale(flow_scale)
         self._need_records("interpolate_items_u8")
         f0, f1, h0, w0, s0 = self._item_frames(frames, "interpolate_items_u8", rgb=True)
         pairs, ts = check_items(pair, t, f0.shape[0])
@@ -1514,12 +1560,14 @@ class RRINEngine:
             return d, d.net
 
         return self._run_items(f0, f1, s0, h0, w0, pairs, ts, out, make, "rrin_net_u8_items_fwd", streams, split,
-                               prof, (scene_threshold, gate, 255, h0 * w0 * 3, None))
+                               prof, (scene_threshold, gate, 255, h0 * w0 * 3, None), flow_scale)
 
     def interpolate_items_u16(self, frames: torch.Tensor, pair, t, depth: int = 10, streams: int | None = None,
-                              split=None, scene_threshold=None, gate=None, prof=None) -> torch.Tensor:
+                              split=None, scene_threshold=None, gate=None, prof=None,
+                              flow_scale: int = 1) -> torch.Tensor:
         """:meth:`interpolate_items_u8` on uint16 ``[P+1,H0,W0,3]`` frames of ``depth`` 9..16, defined
-        by :meth:`forward_u16` (rrin_net_u16_items_fwd)."""
+        by :meth:`forward_u16` (rrin_net_u16_items_fwd) with the same ``flow_scale``."""
+        flow_scale = check_flow_scale(flow_scale)
         self._need_records("interpolate_items_u16")
         depth = self._depth16(depth, 9, "interpolate_items_u16")
         f0, f1, h0, w0, s0 = self._item_frames(frames, "interpolate_items_u16", rgb=True, dtype=torch.uint16)
@@ -1533,15 +1581,18 @@ class RRINEngine:
             return d, d.net
 
         return self._run_items(f0, f1, s0, h0, w0, pairs, ts, out, make, "rrin_net_u16_items_fwd", streams,
-                               split, prof, (scene_threshold, gate, (1 << depth) - 1, h0 * w0 * 3, (depth, 0)))
+                               split, prof, (scene_threshold, gate, (1 << depth) - 1, h0 * w0 * 3, (depth, 0)),
+                               flow_scale)
 
     def interpolate_items_yuv(self, frames: torch.Tensor, pair, t, layout: str = "nv12", coef=None,
                               streams: int | None = None, split=None, scene_threshold=None, gate=None,
-                              prof=None) -> torch.Tensor:
+                              prof=None, flow_scale: int = 1) -> torch.Tensor:
         """:meth:`interpolate_items_u8` on one stack of 8-bit YUV frames (``[P+1, rows, W0]`` of
         ``layout``, as :meth:`forward_yuv` takes them), defined by :meth:`forward_yuv` with the same
-        ``layout`` and ``coef`` (rrin_net_yuv_items_fwd); the gate on the frames' bytes as there."""
+        ``layout``, ``coef`` and ``flow_scale`` (rrin_net_yuv_items_fwd); the gate on the frames'
+        bytes as there."""
         from . import yuv
+        flow_scale = check_flow_scale(flow_scale)
         self._need_records("interpolate_items_yuv")
         if layout not in yuv.ALL_LAYOUTS:
             raise ValueError(f"layout must be one of {yuv.ALL_LAYOUTS}, got {layout!r}")
@@ -1559,15 +1610,16 @@ class RRINEngine:
             return d, d.net
 
         return self._run_items(f0, f1, s0, h0, w0, pairs, ts, out, make, "rrin_net_yuv_items_fwd", streams,
-                               split, prof, (scene_threshold, gate, 255, frame, None))
+                               split, prof, (scene_threshold, gate, 255, frame, None), flow_scale)
 
     def interpolate_items_yuv16(self, frames: torch.Tensor, pair, t, layout: str = "nv12", depth: int = 10,
                                 msb: bool = False, coef=None, streams: int | None = None, split=None,
-                                scene_threshold=None, gate=None, prof=None) -> torch.Tensor:
+                                scene_threshold=None, gate=None, prof=None, flow_scale: int = 1) -> torch.Tensor:
         """:meth:`interpolate_items_yuv` on 10- or 12-bit frames in 16-bit words, defined by
-        :meth:`forward_yuv16` with the same ``layout``, ``depth``, ``msb`` and ``coef``
+        :meth:`forward_yuv16` with the same ``layout``, ``depth``, ``msb``, ``coef`` and ``flow_scale``
         (rrin_net_yuv16_items_fwd)."""
         from . import yuv
+        flow_scale = check_flow_scale(flow_scale)
         self._need_records("interpolate_items_yuv16")
         if layout not in yuv.ALL_LAYOUTS:
             raise ValueError(f"layout must be one of {yuv.ALL_LAYOUTS}, got {layout!r}")
@@ -1589,7 +1641,8 @@ class RRINEngine:
             return d, d.net
 
         return self._run_items(f0, f1, s0, h0, w0, pairs, ts, out, make, "rrin_net_yuv16_items_fwd", streams,
-                               split, prof, (scene_threshold, gate, (1 << depth) - 1, frame, (depth, shift)))
+                               split, prof, (scene_threshold, gate, (1 << depth) - 1, frame, (depth, shift)),
+                               flow_scale)
 
     def unet_forward(self, x: torch.Tensor) -> torch.Tensor:
         """The single packed U-Net (engine built with one unit) on x [N,C,H,W]:
@@ -1657,7 +1710,7 @@ class RRINEngine:
             self._graphs[key] = g
         return g
 
-    def _run_parts(self, h: int, w: int, bounds, part):
+    def _run_parts(self, h: int, w: int, bounds, part, flow_scale: int = 1):
         """The forward parts ``bounds`` at h x w: part j on its own stream (main, then the side
         streams), forked from and joined to the current stream.  ``part(j, lo, hi, stream, p)``
         enqueues pairs [lo, hi) on ``stream`` with the buffers p (a Part).
@@ -1668,7 +1721,7 @@ class RRINEngine:
         Inside a graph capture (NetGraph) every one of them is a cache hit: nothing allocates."""
         with torch.cuda.device(self.device):
             main = torch.cuda.current_stream(self.device)
-            parts = [self._part(hi - lo, h, w, j) for j, (lo, hi) in enumerate(bounds)]
+            parts = [self._part(hi - lo, h, w, j, flow_scale) for j, (lo, hi) in enumerate(bounds)]
             sides = self._side_streams(len(bounds) - 1)
             for s in sides:
                 s.wait_stream(main)
@@ -1677,13 +1730,29 @@ class RRINEngine:
             for s in sides:
                 main.wait_stream(s)
 
-    def _part(self, m: int, h: int, w: int, slot: int) -> Part:
+    def _part(self, m: int, h: int, w: int, slot: int, flow_scale: int = 1) -> Part:
         """The buffers of the forward part of m pairs at h x w in stream slot ``slot``, cached; a
-        new one is zero-filled on the current stream."""
+        new one is zero-filled on the current stream.  ``flow_scale`` s > 1 adds the second plan
+        (:mod:`rrin_amd.flowscale`): workspace, conv table and scratch of (m, h / s, w / s), cached
+        like the others under a slot of their own, so no forward at that size shares them; the
+        range flag is the part's."""
         convs = self.conv_table_for(m, h, w)
         prec16 = self.prec in (_lib.PREC_F16X3, _lib.PREC_F16)
-        return Part((m, h, w, slot), self.workspace(m, h, w, slot), convs, self._net_scratch(m, h, w, slot, convs),
-                    self._status_of(slot) if prec16 else None)
+        ws = self.workspace(m, h, w, slot)
+        low = None
+        if flow_scale > 1:
+            lh, lw, lslot = h // flow_scale, w // flow_scale, ("flow_scale", flow_scale, h, w, slot)
+            lconvs = self.conv_table_for(m, lh, lw)
+            lws = self.workspace(m, lh, lw, lslot)
+            lsc = self._net_scratch(m, lh, lw, lslot, lconvs)
+            fs = _lib.FlowScale()
+            fs.s, fs.convs = flow_scale, lconvs
+            fs.workspace, fs.workspace_bytes = lws.data_ptr(), lws.numel()
+            if lsc is not None:
+                fs.scratch, fs.scratch_bytes = lsc.data_ptr(), lsc.numel()
+            low = Low(fs, lws, lconvs, lsc)
+        return Part((m, h, w, slot), ws, convs, self._net_scratch(m, h, w, slot, convs),
+                    self._status_of(slot) if prec16 else None, low)
 
     def _fill_net(self, nd, p: Part, coef):
         """The rrin_net_desc fields every path shares (``nd``: a NetDesc or the ``net`` of a
@@ -1707,7 +1776,17 @@ class RRINEngine:
         """Library entry ``fwd`` on descriptor d (nd: its rrin_net_desc) for part p on ``stream``.
         ``tag`` names the path -- and for YUV its layout and matrix -- whose raw Flow the part's
         workspace keeps afterwards: the Flow U-Net is skipped only for ``reuse_flow`` with the
-        same tag, so no path takes another's pair for its own previous one."""
+        same tag, so no path takes another's pair for its own previous one.  A part with a second
+        plan (``p.low``: flow_scale > 1) goes to the entry's ``_scaled_fwd`` sibling, and its tag
+        carries the scale (:func:`rrin_amd.flowscale.flow_tag`)."""
+        if p.low is not None:
+            tag = flow_tag(tag, p.low.fs.s)
+            name = name.replace("_fwd", "_scaled_fwd")
+            scaled, fs = getattr(self.lib, name), C.byref(p.low.fs)
+            if name == "rrin_net_scaled_fwd":
+                fwd = lambda dd, st: scaled(dd, fs, st)
+            else:  # a frame forward: no items
+                fwd = lambda dd, st: scaled(dd, None, fs, st)
         nd.skip_flow = 1 if reuse_flow and self._flow_valid.get(p.key) == tag else 0
         _lib.check(fwd(C.byref(d), C.c_void_p(stream.cuda_stream)), name)
         self._flow_valid[p.key] = tag

@@ -100,17 +100,23 @@ class Net(nn.Module):
         if self._engine is not None:
             self._engine._poll_range(wait=wait)
 
-    def interpolate(self, input0, input1, ts):
+    def interpolate(self, input0, input1, ts, flow_scale=1):
         """All intermediate frames of one (batch of) pair(s): ``[forward(I0, I1, t) for t in ts]``
         with the t-independent Flow U-Net computed once (the
-        reference recomputes it per t, convert.py:127-130)."""
+        reference recomputes it per t, convert.py:127-130).
+
+        ``flow_scale`` 2 or 4, here and on every frame method below: the Flow U-Net runs at 1/s of
+        the size and its flow is scaled up (:mod:`rrin_amd.flowscale`, which is the definition);
+        the frame paths then pad to a multiple of 16 * s.  Record precisions, inference only."""
+        from .flowscale import check_flow_scale
+        check_flow_scale(flow_scale)
         if torch.is_grad_enabled():
             raise RuntimeError("rrin_amd.Net.interpolate is inference-only: use torch.no_grad()")
         eng = self.engine()
-        return [eng.forward(input0, input1, t, reuse_flow=(k > 0), streams=self.streams)
+        return [eng.forward(input0, input1, t, reuse_flow=(k > 0), streams=self.streams, flow_scale=flow_scale)
                 for k, t in enumerate(ts)]
 
-    def forward_u8(self, f0, f1, t=0.5, scene_threshold=None, gate=None):
+    def forward_u8(self, f0, f1, t=0.5, scene_threshold=None, gate=None, flow_scale=1):
         """``forward`` on 8-bit frames of any size: uint8 ``[N,H0,W0,3]`` in and out, on the
         device; bit for bit ``convert.load_frame`` -> ``forward`` -> ``convert.to_uint8_image``
         (``RRINEngine.forward_u8``).  Inference-only; not for ``precision='fp32_planar'``.
@@ -124,9 +130,9 @@ class Net(nn.Module):
         if torch.is_grad_enabled():
             raise RuntimeError("rrin_amd.Net.forward_u8 is inference-only: use torch.no_grad()")
         return self.engine().forward_u8(f0, f1, t, streams=self.streams, scene_threshold=scene_threshold,
-                                        gate=gate)
+                                        gate=gate, flow_scale=flow_scale)
 
-    def interpolate_u8(self, f0, f1, ts, scene_threshold=None, gate=None):
+    def interpolate_u8(self, f0, f1, ts, scene_threshold=None, gate=None, flow_scale=1):
         """``[forward_u8(f0, f1, t) for t in ts]`` with the Flow U-Net computed once, as
         :meth:`interpolate`; with ``scene_threshold`` the pairs' sums of absolute differences are
         computed once too (the cut code depends on t, so :attr:`last_gate` is that of ``ts[-1]``)."""
@@ -134,7 +140,7 @@ class Net(nn.Module):
             raise RuntimeError("rrin_amd.Net.interpolate_u8 is inference-only: use torch.no_grad()")
         eng = self.engine()
         return [eng.forward_u8(f0, f1, t, reuse_flow=(k > 0), streams=self.streams,
-                               scene_threshold=scene_threshold, gate=gate)
+                               scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
                 for k, t in enumerate(ts)]
 
     def pair_stats_u8(self, f0, f1):
@@ -143,7 +149,7 @@ class Net(nn.Module):
         with ``floor(threshold * H0*W0*3)``, for callers who pass their own ``gate``."""
         return self.engine().pair_stats_u8(f0, f1)
 
-    def forward_yuv(self, f0, f1, t=0.5, layout="nv12", coef=None, scene_threshold=None, gate=None):
+    def forward_yuv(self, f0, f1, t=0.5, layout="nv12", coef=None, scene_threshold=None, gate=None, flow_scale=1):
         """``forward`` on 8-bit YUV 4:2:0 frames, as decoders and video pipes deliver them: uint8
         ``[N, 3*H0//2, W0]`` in and out on the device (H0, W0 even; ``layout`` "nv12" or "i420") -- or
         4:2:2 (``layout`` "nv16" / "i422": ``[N, 2*H0, W0]``, W0 even) and 4:4:4 ("i444": ``[N, 3*H0,
@@ -161,9 +167,9 @@ class Net(nn.Module):
         if torch.is_grad_enabled():
             raise RuntimeError("rrin_amd.Net.forward_yuv is inference-only: use torch.no_grad()")
         return self.engine().forward_yuv(f0, f1, t, layout=layout, coef=coef, streams=self.streams,
-                                         scene_threshold=scene_threshold, gate=gate)
+                                         scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
 
-    def interpolate_yuv(self, f0, f1, ts, layout="nv12", coef=None, scene_threshold=None, gate=None):
+    def interpolate_yuv(self, f0, f1, ts, layout="nv12", coef=None, scene_threshold=None, gate=None, flow_scale=1):
         """``[forward_yuv(f0, f1, t) for t in ts]`` with the Flow U-Net (and, with
         ``scene_threshold``, the pairs' sums of absolute differences) computed once, as
         :meth:`interpolate_u8`."""
@@ -171,7 +177,7 @@ class Net(nn.Module):
             raise RuntimeError("rrin_amd.Net.interpolate_yuv is inference-only: use torch.no_grad()")
         eng = self.engine()
         return [eng.forward_yuv(f0, f1, t, layout=layout, coef=coef, reuse_flow=(k > 0), streams=self.streams,
-                                scene_threshold=scene_threshold, gate=gate)
+                                scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
                 for k, t in enumerate(ts)]
 
     def pair_stats_yuv(self, f0, f1, layout="nv12"):
@@ -180,7 +186,7 @@ class Net(nn.Module):
         ``floor(threshold * H0*W0*3/2)`` (a 4:2:2 / 4:4:4 ``layout``: ``2*H0*W0`` / ``3*H0*W0`` bytes)."""
         return self.engine().pair_stats_yuv(f0, f1, layout=layout)
 
-    def forward_u16(self, f0, f1, t=0.5, depth=10, scene_threshold=None, gate=None):
+    def forward_u16(self, f0, f1, t=0.5, depth=10, scene_threshold=None, gate=None, flow_scale=1):
         """``forward_u8`` on 16-bit frames: uint16 ``[N,H0,W0,3]`` RGB samples of ``depth`` 9..16 (in
         the words' low bits; a word above ``maxval = 2**depth - 1`` is read as maxval) in and out on
         the device; bit for bit ``convert.frames_u16_to_float`` -> ``forward`` ->
@@ -190,16 +196,16 @@ class Net(nn.Module):
         if torch.is_grad_enabled():
             raise RuntimeError("rrin_amd.Net.forward_u16 is inference-only: use torch.no_grad()")
         return self.engine().forward_u16(f0, f1, t, depth=depth, streams=self.streams,
-                                         scene_threshold=scene_threshold, gate=gate)
+                                         scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
 
-    def interpolate_u16(self, f0, f1, ts, depth=10, scene_threshold=None, gate=None):
+    def interpolate_u16(self, f0, f1, ts, depth=10, scene_threshold=None, gate=None, flow_scale=1):
         """``[forward_u16(f0, f1, t, depth) for t in ts]`` with the Flow U-Net (and the pairs' sums
         of absolute differences) computed once, as :meth:`interpolate_u8`."""
         if torch.is_grad_enabled():
             raise RuntimeError("rrin_amd.Net.interpolate_u16 is inference-only: use torch.no_grad()")
         eng = self.engine()
         return [eng.forward_u16(f0, f1, t, depth=depth, reuse_flow=(k > 0), streams=self.streams,
-                                scene_threshold=scene_threshold, gate=gate)
+                                scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
                 for k, t in enumerate(ts)]
 
     def pair_stats_u16(self, f0, f1, depth=10):
@@ -208,7 +214,7 @@ class Net(nn.Module):
         return self.engine().pair_stats_u16(f0, f1, depth=depth)
 
     def forward_yuv16(self, f0, f1, t=0.5, layout="nv12", depth=10, msb=False, coef=None, scene_threshold=None,
-                      gate=None):
+                      gate=None, flow_scale=1):
         """``forward_yuv`` on 10- or 12-bit 4:2:0 frames in 16-bit words: uint16 ``[N, 3*H0//2, W0]`` in
         and out on the device, ``msb=False`` for samples in the low bits (yuv420p10le, Y4M C420p10),
         ``True`` for the high bits (P010 / P012).  By definition, and bit for bit,
@@ -218,17 +224,19 @@ class Net(nn.Module):
         if torch.is_grad_enabled():
             raise RuntimeError("rrin_amd.Net.forward_yuv16 is inference-only: use torch.no_grad()")
         return self.engine().forward_yuv16(f0, f1, t, layout=layout, depth=depth, msb=msb, coef=coef,
-                                           streams=self.streams, scene_threshold=scene_threshold, gate=gate)
+                                           streams=self.streams, scene_threshold=scene_threshold, gate=gate,
+                                           flow_scale=flow_scale)
 
     def interpolate_yuv16(self, f0, f1, ts, layout="nv12", depth=10, msb=False, coef=None, scene_threshold=None,
-                          gate=None):
+                          gate=None, flow_scale=1):
         """``[forward_yuv16(f0, f1, t, ...) for t in ts]`` with the Flow U-Net (and the pairs' sums of
         absolute differences) computed once, as :meth:`interpolate_yuv`."""
         if torch.is_grad_enabled():
             raise RuntimeError("rrin_amd.Net.interpolate_yuv16 is inference-only: use torch.no_grad()")
         eng = self.engine()
         return [eng.forward_yuv16(f0, f1, t, layout=layout, depth=depth, msb=msb, coef=coef, reuse_flow=(k > 0),
-                                  streams=self.streams, scene_threshold=scene_threshold, gate=gate)
+                                  streams=self.streams, scene_threshold=scene_threshold, gate=gate,
+                                  flow_scale=flow_scale)
                 for k, t in enumerate(ts)]
 
     def pair_stats_yuv16(self, f0, f1, depth=10, msb=False, layout="nv12"):
@@ -262,14 +270,16 @@ class Net(nn.Module):
         """The item forward ``name`` of the engine, after the host checks of ``pair`` and ``t``
         (ValueError before any device work)."""
         from .engine import check_items
+        from .flowscale import check_flow_scale
         if not isinstance(frames, torch.Tensor) or frames.dim() < 1:
             raise TypeError(f"{name} takes one stack of frames")
         check_items(pair, t, frames.shape[0] - 1)
+        check_flow_scale(kw.get("flow_scale", 1))
         if torch.is_grad_enabled():
             raise RuntimeError(f"rrin_amd.Net.{name} is inference-only: use torch.no_grad()")
         return getattr(self.engine(), name)(frames, pair, t, streams=self.streams, **kw)
 
-    def interpolate_items_u8(self, frames, pair, t, scene_threshold=None, gate=None):
+    def interpolate_items_u8(self, frames, pair, t, scene_threshold=None, gate=None, flow_scale=1):
         """A batch of M items over one stack of 8-bit frames, for frame-rate conversion
         (:mod:`rrin_amd.retime`): ``frames`` uint8 ``[P+1,H0,W0,3]`` on the device (pair p is
         ``frames[p]``, ``frames[p+1]``), ``pair`` M non-decreasing ints in [0, P) (list or int32
@@ -282,25 +292,27 @@ class Net(nn.Module):
         inherits its pair's decision: a duplicate returns the first frame, a cut the nearer frame
         by the item's own t; :attr:`last_gate` is then ``[M]``.  Output quality at uneven t has not
         been validated on footage."""
-        return self._items("interpolate_items_u8", frames, pair, t, scene_threshold=scene_threshold, gate=gate)
+        return self._items("interpolate_items_u8", frames, pair, t, scene_threshold=scene_threshold, gate=gate,
+                           flow_scale=flow_scale)
 
-    def interpolate_items_yuv(self, frames, pair, t, layout="nv12", coef=None, scene_threshold=None, gate=None):
+    def interpolate_items_yuv(self, frames, pair, t, layout="nv12", coef=None, scene_threshold=None, gate=None,
+                              flow_scale=1):
         """:meth:`interpolate_items_u8` on one stack of 8-bit YUV frames, defined by
         :meth:`forward_yuv` with the same ``layout`` and ``coef``."""
         return self._items("interpolate_items_yuv", frames, pair, t, layout=layout, coef=coef,
-                           scene_threshold=scene_threshold, gate=gate)
+                           scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
 
-    def interpolate_items_u16(self, frames, pair, t, depth=10, scene_threshold=None, gate=None):
+    def interpolate_items_u16(self, frames, pair, t, depth=10, scene_threshold=None, gate=None, flow_scale=1):
         """:meth:`interpolate_items_u8` on uint16 RGB frames of ``depth``, defined by :meth:`forward_u16`."""
         return self._items("interpolate_items_u16", frames, pair, t, depth=depth, scene_threshold=scene_threshold,
-                           gate=gate)
+                           gate=gate, flow_scale=flow_scale)
 
     def interpolate_items_yuv16(self, frames, pair, t, layout="nv12", depth=10, msb=False, coef=None,
-                                scene_threshold=None, gate=None):
+                                scene_threshold=None, gate=None, flow_scale=1):
         """:meth:`interpolate_items_yuv` on 10- or 12-bit frames in 16-bit words, defined by
         :meth:`forward_yuv16` with the same ``layout``, ``depth``, ``msb`` and ``coef``."""
         return self._items("interpolate_items_yuv16", frames, pair, t, layout=layout, depth=depth, msb=msb, coef=coef,
-                           scene_threshold=scene_threshold, gate=gate)
+                           scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
 
     @property
     def last_gate(self):
