@@ -113,9 +113,8 @@ def frames_float_to_u8(t: torch.Tensor, height: int, width: int) -> torch.Tensor
 
 
 def _depth_maxval(depth) -> int:
-    if isinstance(depth, bool) or not isinstance(depth, int) or not 9 <= depth <= 16:
-        raise ValueError(f"16-bit RGB frames are 9 to 16 bits deep, got {depth!r}")
-    return (1 << depth) - 1
+    from .framefmt import check_depth
+    return (1 << check_depth(depth, 9, "16-bit RGB frames are 9 to 16 bits deep")) - 1
 
 
 def frames_u16_to_float(frames: torch.Tensor, depth: int, flow_scale: int = 1) -> torch.Tensor:
@@ -148,11 +147,7 @@ def scene_limit(threshold, h0: int, w0: int, maxval: int = 255) -> int:
     """The largest sum of absolute byte differences of an H0 x W0 RGB pair that is not a cut:
     ``floor(threshold * H0*W0*3)`` for a mean absolute byte difference ``threshold`` in [0, 255]
     (16-bit frames: a mean absolute sample difference in [0, ``maxval``])."""
-    th = float(threshold)
-    if not 0.0 <= th <= float(maxval):
-        what = "byte" if maxval == 255 else "sample"
-        raise ValueError(f"scene_threshold is a mean absolute {what} difference in [0, {maxval}], got {threshold!r}")
-    return math.floor(th * (h0 * w0 * 3))
+    return scene_limit_len(threshold, h0 * w0 * 3, maxval)
 
 
 def scene_limit_len(threshold, samples: int, maxval: int = 255) -> int:
@@ -466,6 +461,15 @@ def _retire(item, sf, dest, put, model=None):
         put(shutil.copy, m1["path"], os.path.join(dest, f"{base + sf + 1:09d}{m1['filetype']}"))
 
 
+def frame_path_of(src):
+    """The frame path of an opened ``y4m.Reader`` or a ``finetune.Clip``: the suffix of the model's methods
+    (``interpolate_<suffix>``, ``interpolate_items_<suffix>``, ``frame_metrics_<suffix>``, ``pair_stats_<suffix>``)
+    and their depth keywords -- ``("yuv", {})`` at 8 bits, else ``("yuv16", {"depth": d, "msb": False})``
+    (Y4M keeps its samples in the words' low bits)."""
+    depth = src.bit_depth
+    return ("yuv16", {"depth": depth, "msb": False}) if depth > 8 else ("yuv", {})
+
+
 def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coef=None, log=print, fps_out=None,
                     flow_scale=1):
     """Interpolate a Y4M stream (8-bit 4:2:0; also 10 / 12 bits and 4:2:2 / 4:4:4, below) into another: no image folder, no RGB frame anywhere.
@@ -522,8 +526,8 @@ def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coe
         wr = y4m.Writer(dst, w0, h0, rd.fps_num * (sf + 1), rd.fps_den, rd.colorspace, depths=(8, 10, 12),
                         chroma=yuv.CHROMAS)
         layout = "i" + rd.chroma
-        deep = rd.bit_depth > 8
-        dtype = torch.uint16 if deep else torch.uint8
+        suffix, depth_kw = frame_path_of(rd)
+        dtype = torch.uint16 if depth_kw else torch.uint8
         device = next(model.parameters()).device
         on_gpu = device.type == "cuda"   # a host model (tests) has nothing to pin for and no events
         ts = [i / (sf + 1) for i in range(1, sf + 1)]
@@ -570,12 +574,8 @@ def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coe
                 stack[j].view(-1).copy_(torch.from_numpy(fr))
             stack = stack.to(device, non_blocking=True)
             with torch.no_grad():
-                if deep:
-                    outs = model.interpolate_yuv16(stack[:-1], stack[1:], ts, layout=layout, depth=rd.bit_depth,
-                                                   msb=False, coef=coef, **gate_kw, **scale_kw)
-                else:
-                    outs = model.interpolate_yuv(stack[:-1], stack[1:], ts, layout=layout, coef=coef, **gate_kw,
-                                                 **scale_kw)
+                outs = getattr(model, "interpolate_" + suffix)(stack[:-1], stack[1:], ts, layout=layout, coef=coef,
+                                                               **depth_kw, **gate_kw, **scale_kw)
             host = []
             for o in outs:
                 hbuf = torch.empty(o.shape, dtype=o.dtype, pin_memory=on_gpu)
@@ -650,8 +650,8 @@ def retime_y4m(model, src, dst, fps_out, batch=4, scene_threshold=None, coef=Non
         wr = y4m.Writer(dst, w0, h0, rate_out.numerator, rate_out.denominator, rd.colorspace, depths=(8, 10, 12),
                         chroma=yuv.CHROMAS)
         layout = "i" + rd.chroma
-        deep = rd.bit_depth > 8
-        dtype = torch.uint16 if deep else torch.uint8
+        suffix, depth_kw = frame_path_of(rd)
+        dtype = torch.uint16 if depth_kw else torch.uint8
         device = next(model.parameters()).device
         on_gpu = device.type == "cuda"   # a host model (tests) has nothing to pin for and no events
         gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
@@ -692,12 +692,8 @@ def retime_y4m(model, src, dst, fps_out, batch=4, scene_threshold=None, coef=Non
             stack = stack.to(device, non_blocking=True)
             pair, ts = [p - lo for p, _ in part], [t for _, t in part]
             with torch.no_grad():
-                if deep:
-                    out = model.interpolate_items_yuv16(stack, pair, ts, layout=layout, depth=rd.bit_depth, msb=False,
-                                                        coef=coef, **gate_kw, **scale_kw)
-                else:
-                    out = model.interpolate_items_yuv(stack, pair, ts, layout=layout, coef=coef, **gate_kw,
-                                                      **scale_kw)
+                out = getattr(model, "interpolate_items_" + suffix)(stack, pair, ts, layout=layout, coef=coef,
+                                                                    **depth_kw, **gate_kw, **scale_kw)
             host = torch.empty(out.shape, dtype=out.dtype, pin_memory=on_gpu)
             host.copy_(out, non_blocking=True)
             codes = None
@@ -838,10 +834,10 @@ def evaluate_y4m(model, src, hold=2, batch=4, scene_threshold=None, coef=None, l
         gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
         # kept apart from gate_kw, whose truth means "the scene gate is on"; scale 1 passes no keyword
         scale_kw = {} if flow_scale == 1 else {"flow_scale": flow_scale}
-        depth_kw = {"depth": rd.bit_depth, "msb": False} if deep else {}
-        name = "frame_metrics_yuv16" if deep else "frame_metrics_yuv"
+        suffix, depth_kw = frame_path_of(rd)
+        name = "frame_metrics_" + suffix
         measure = getattr(model, name, None) or getattr(metrics, name)  # a host model: the definitions
-        forward = model.interpolate_items_yuv16 if deep else model.interpolate_items_yuv
+        forward = getattr(model, "interpolate_items_" + suffix)
         planes = metrics.planes_of("yuv", h0, w0, layout)
         counts = [p[3] * p[4] for p in planes]
         rows_per = yuv.stack_rows(h0, layout)

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -691,13 +692,83 @@ extern "C" int64_t rrin_net_scratch_bytes(const rrin_net_desc* d) {
   return scratch_bytes_of(d->n, d->h, d->w, d->prec, d->convs, kUNets, 4);
 }
 
-// The frames of a forward that is not rrin_net_fwd: at most one member is set
-struct FrameIO {
-  const rrin_net_u8_desc* u8 = nullptr;
-  const rrin_net_yuv_desc* yuv = nullptr;
-  const rrin_net_u16_desc* u16 = nullptr;
-  const rrin_net_yuv16_desc* yuv16 = nullptr;
+// Where a frame pack puts its images: the full-size g16 view, the precision, the stream and the pad
+// multiple (16, or 16 * s of a flow_scale forward)
+struct PackTo {
+  const rrin_h8* g;
+  int prec;
+  hipStream_t st;
+  int mult;
 };
+
+// The frames of a forward, whatever their format: what net_fwd_impl needs of a descriptor, filled by
+// the frame_io overload of its type (below the checks).  h0 = w0 = 0: rrin_net_fwd's fp32 NCHW frames.
+struct FrameIO {
+  int h0 = 0, w0 = 0;
+  // the frame pack of m images: image k from frame k, or with a map from frame map[k] of np
+  std::function<int(int m, const int32_t* map, int np, const PackTo& to)> pack;
+  HeadIO store{};  // the output members of the FINAL store; coef, raw and the crop are head_io's
+  HeadIO head_io(const float* coef, float* raw, int h) const {
+    HeadIO io = store;
+    io.coef = coef;
+    io.raw = raw;
+    io.h0 = h0;
+    io.w0 = w0;
+    io.top = h0 ? h - h0 : 0;
+    return io;
+  }
+};
+
+// rrin_net_fwd: fp32 NCHW frames d.i0 / i1 in, d.out out (the record precisions; the planar one reads
+// them itself)
+static FrameIO frame_io(const rrin_net_desc& d) {
+  FrameIO f;
+  f.pack = [&d](int m, const int32_t*, int, const PackTo& to) {
+    return rrin_pack_g16_h8(d.i0, d.i1, m, to.g, to.prec, to.st);
+  };
+  f.store.out = d.out;
+  return f;
+}
+
+static FrameIO frame_io(const rrin_net_u8_desc& d) {
+  FrameIO f{d.h0, d.w0};
+  f.pack = [&d](int m, const int32_t* map, int np, const PackTo& to) {
+    return pack_g16_u8_items(d.f0, d.f1, d.img_stride, m, d.h0, d.w0, to.g, to.prec, map, np, to.st, to.mult);
+  };
+  f.store.out_u8 = d.out_u8;
+  return f;
+}
+
+static FrameIO frame_io(const rrin_net_yuv_desc& d) {
+  FrameIO f{d.h0, d.w0};
+  f.pack = [&d](int m, const int32_t* map, int np, const PackTo& to) {
+    return pack_g16_yuv_items(&d.f0, &d.f1, &d.coef, m, d.h0, d.w0, to.g, to.prec, map, np, to.st, to.mult);
+  };
+  f.store.out_yuv = &d.out;
+  f.store.yuv_coef = &d.coef;
+  return f;
+}
+
+static FrameIO frame_io(const rrin_net_u16_desc& d) {
+  FrameIO f{d.h0, d.w0};
+  f.pack = [&d](int m, const int32_t* map, int np, const PackTo& to) {
+    return pack_g16_u16_items(d.f0, d.f1, d.img_stride, m, d.h0, d.w0, d.depth, to.g, to.prec, map, np, to.st,
+                              to.mult);
+  };
+  f.store.out_u16 = d.out_u16;
+  f.store.u16_depth = d.depth;
+  return f;
+}
+
+static FrameIO frame_io(const rrin_net_yuv16_desc& d) {
+  FrameIO f{d.h0, d.w0};
+  f.pack = [&d](int m, const int32_t* map, int np, const PackTo& to) {
+    return pack_g16_yuv16_items(&d.f0, &d.f1, &d.coef, m, d.h0, d.w0, to.g, to.prec, map, np, to.st, to.mult);
+  };
+  f.store.out_yuv16 = &d.out;
+  f.store.yuv_coef = &d.coef;
+  return f;
+}
 
 // An item forward (ABI 25): d->n items over n_pairs pairs through the device map; map NULL: a
 // plain forward (every rrin_net_*_fwd)
@@ -716,11 +787,11 @@ static int items_of(const rrin_items* it, int n, Items& out) {
   return 0;
 }
 
-// The schedule of the forwards: rrin_net_fwd (no member of f set: fp32 NCHW frames d->i0 / i1
-// in, d->out out), rrin_net_u8_fwd (8-bit RGB frames in and out), rrin_net_yuv_fwd (8-bit
-// 4:2:0 frames in and out) and their 16-bit siblings rrin_net_u16_fwd / rrin_net_yuv16_fwd; the
-// frame forwards leave d->i0 / i1 / out unused and run on the record layouts only.  The callers
-// have validated d (and the member of f).
+// The schedule of the forwards: rrin_net_fwd (fp32 NCHW frames d->i0 / i1 in, d->out out),
+// rrin_net_u8_fwd (8-bit RGB frames in and out), rrin_net_yuv_fwd (8-bit 4:2:0 frames in and out)
+// and their 16-bit siblings rrin_net_u16_fwd / rrin_net_yuv16_fwd; the frame forwards leave d->i0 /
+// i1 / out unused and run on the record layouts only.  f is the frame_io of the entry's descriptor,
+// which the callers have validated with d.
 //
 // With a map (items.map, frame forwards only) the call is an item forward.  One plan, sized for
 // the d->n items, serves both of its phases, since no buffer's image stride depends on the batch:
@@ -737,11 +808,6 @@ static int items_of(const rrin_items* it, int n, Items& out) {
 // blend of the kept raw Flow as for skip_flow.  A plain forward's pack is not repeated.
 static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, const Items& items, void* stream,
                         const rrin_flow_scale* fs = nullptr) {
-  const int mult = fs ? 16 * fs->s : 16;
-  const rrin_net_u8_desc* u8 = f.u8;
-  const rrin_net_yuv_desc* yuv = f.yuv;
-  const rrin_net_u16_desc* u16 = f.u16;
-  const rrin_net_yuv16_desc* y16 = f.yuv16;
   Plan p;
   make_plan(d->n, d->h, d->w, d->prec, reinterpret_cast<char*>(d->workspace), p);
   if (d->workspace_bytes < p.bytes) return RRIN_E_WORKSPACE;
@@ -761,18 +827,8 @@ static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, const Items& i
   }
   if (d->prec != RRIN_PREC_F32) {
     const rrin_h8 gall = hview(p.G, 0, 16);
-    // the frame pack of m images: image k from frame k, or with a map from frame map[k] of np
-    auto pack = [&](int m, const int32_t* map, int np) {
-      return u8    ? pack_g16_u8_items(u8->f0, u8->f1, u8->img_stride, m, u8->h0, u8->w0, &gall, d->prec, map, np, st,
-                                       mult)
-             : yuv ? pack_g16_yuv_items(&yuv->f0, &yuv->f1, &yuv->coef, m, yuv->h0, yuv->w0, &gall, d->prec, map, np, st,
-                                        mult)
-             : u16 ? pack_g16_u16_items(u16->f0, u16->f1, u16->img_stride, m, u16->h0, u16->w0, u16->depth, &gall,
-                                        d->prec, map, np, st, mult)
-             : y16 ? pack_g16_yuv16_items(&y16->f0, &y16->f1, &y16->coef, m, y16->h0, y16->w0, &gall, d->prec, map, np,
-                                          st, mult)
-                   : rrin_pack_g16_h8(d->i0, d->i1, m, &gall, d->prec, st);
-    };
+    const PackTo to{&gall, d->prec, st, fs ? 16 * fs->s : 16};
+    auto pack = [&](int m, const int32_t* map, int np) { return f.pack(m, map, np, to); };
     int rc = 0;
     bool packed = false;  // the full-size g16 already holds the d->n images of the call
     if (fs && !d->skip_flow) {  // Flow phase at (h / s, w / s), once per pair
@@ -825,31 +881,7 @@ static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, const Items& i
     int k = 0;
     for (int u = 0; u < 4 && !rc; ++u) {
       if (!(u == 0 && blend)) {
-        HeadIO io{d->coef, u8 || yuv || u16 || y16 ? nullptr : d->out, tap_of(d, kUNets[u])};
-        if (u8) {
-          io.out_u8 = u8->out_u8;
-          io.h0 = u8->h0;
-          io.w0 = u8->w0;
-          io.top = d->h - u8->h0;
-        } else if (yuv) {
-          io.out_yuv = &yuv->out;
-          io.yuv_coef = &yuv->coef;
-          io.h0 = yuv->h0;
-          io.w0 = yuv->w0;
-          io.top = d->h - yuv->h0;
-        } else if (u16) {
-          io.out_u16 = u16->out_u16;
-          io.u16_depth = u16->depth;
-          io.h0 = u16->h0;
-          io.w0 = u16->w0;
-          io.top = d->h - u16->h0;
-        } else if (y16) {
-          io.out_yuv16 = &y16->out;
-          io.yuv_coef = &y16->coef;
-          io.h0 = y16->h0;
-          io.w0 = y16->w0;
-          io.top = d->h - y16->h0;
-        }
+        const HeadIO io = f.head_io(d->coef, tap_of(d, kUNets[u]), d->h);
         rc = run_unet_h8(p, kUNets[u], d->convs + k, d->heads[u], io, st);
       }
       k += convs_of(kUNets[u].depth);
@@ -885,140 +917,69 @@ extern "C" int rrin_net_fwd(const rrin_net_desc* d, void* stream) {
     return RRIN_E_ARG;
   if (d->n < 1 || d->h < 16 || d->w < 16 || (d->h % 16) || (d->w % 16)) return RRIN_E_SHAPE;
   if (d->prec < RRIN_PREC_F32 || d->prec > RRIN_PREC_F32R) return RRIN_E_ARG;
-  return net_fwd_impl(d, FrameIO{}, Items{}, stream);
+  return net_fwd_impl(d, frame_io(*d), Items{}, stream);
 }
 
 // The argument checks of the frame forwards, shared with their item forms: `frames` is the number
 // of frames of f0 and of f1 -- net.n for a plain forward, the pairs of an item forward -- and the
-// output always holds net.n frames.
-static int net_u8_check(const rrin_net_u8_desc* d, int frames, int mult = 16) {
-  if (!d || !d->f0 || !d->f1 || !d->out_u8) return RRIN_E_ARG;
-  const rrin_net_desc* nd = &d->net;
+// output always holds net.n frames.  net_check is what every format shares, in the order of the
+// codes it returns: the null members of net and the record precisions (RRIN_E_ARG: the planar fp32
+// path has no frame pack / store), then the format's own checks `own`, then the padded size against
+// the pad multiple (RRIN_E_SHAPE).
+template <class Own>
+static int net_check(const rrin_net_desc* nd, int h0, int w0, int mult, Own own) {
   if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
-  // the record precisions only: the planar fp32 path has no 8-bit pack / store
   if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
-  if (nd->n < 1 || d->h0 < 1 || d->w0 < 1) return RRIN_E_SHAPE;
-  if (nd->h != pad_up(d->h0, mult) || nd->w != pad_up(d->w0, mult)) return RRIN_E_SHAPE;
-  if (frames > 1 && d->img_stride < (int64_t)d->h0 * d->w0 * 3) return RRIN_E_ARG;
+  if (int rc = own()) return rc;
+  if (nd->h != pad_up(h0, mult) || nd->w != pad_up(w0, mult)) return RRIN_E_SHAPE;
   return 0;
 }
 
-static int net_yuv_check(const rrin_net_yuv_desc* d, int frames, int mult = 16) {
+// interleaved RGB frames (8 or 16 bit): ok = the format's pointers (and depth) are there
+static int net_rgb_check(bool ok, const rrin_net_desc* nd, int h0, int w0, int64_t img_stride, int frames, int mult) {
+  if (!ok) return RRIN_E_ARG;
+  if (int rc = net_check(nd, h0, w0, mult, [&] { return nd->n < 1 || h0 < 1 || w0 < 1 ? RRIN_E_SHAPE : 0; }))
+    return rc;
+  if (frames > 1 && img_stride < (int64_t)h0 * w0 * 3) return RRIN_E_ARG;
+  return 0;
+}
+
+static int frame_check(const rrin_net_u8_desc* d, int frames, int mult) {
   if (!d) return RRIN_E_ARG;
-  const rrin_net_desc* nd = &d->net;
-  if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
-  // the record precisions only, as rrin_net_u8_fwd
-  if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
-  if (int rc = yuv_coef_check(&d->coef)) return rc;
-  for (const rrin_yuv420* s : {&d->f0, &d->f1, &d->out}) {
-    if (int rc = yuv420_check(*s, s == &d->out ? nd->n : frames, d->h0, d->w0)) return rc;
-    if (s->chroma != d->f0.chroma) return RRIN_E_ARG;
-  }
-  if (nd->h != pad_up(d->h0, mult) || nd->w != pad_up(d->w0, mult)) return RRIN_E_SHAPE;
-  return 0;
+  return net_rgb_check(d->f0 && d->f1 && d->out_u8, &d->net, d->h0, d->w0, d->img_stride, frames, mult);
 }
 
-static int net_u16_check(const rrin_net_u16_desc* d, int frames, int mult = 16) {
-  if (!d || !d->f0 || !d->f1 || !d->out_u16 || d->depth < 9 || d->depth > 16) return RRIN_E_ARG;
-  const rrin_net_desc* nd = &d->net;
-  if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
-  // the record precisions only, as rrin_net_u8_fwd
-  if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
-  if (nd->n < 1 || d->h0 < 1 || d->w0 < 1) return RRIN_E_SHAPE;
-  if (nd->h != pad_up(d->h0, mult) || nd->w != pad_up(d->w0, mult)) return RRIN_E_SHAPE;
-  if (frames > 1 && d->img_stride < (int64_t)d->h0 * d->w0 * 3) return RRIN_E_ARG;
-  return 0;
-}
-
-static int net_yuv16_check(const rrin_net_yuv16_desc* d, int frames, int mult = 16) {
+static int frame_check(const rrin_net_u16_desc* d, int frames, int mult) {
   if (!d) return RRIN_E_ARG;
-  const rrin_net_desc* nd = &d->net;
-  if (!nd->coef || !nd->convs || !nd->heads || !nd->workspace) return RRIN_E_ARG;
-  if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
-  for (const rrin_yuv420_16* s : {&d->f0, &d->f1, &d->out}) {
-    if (int rc = yuv420_16_check(*s, s == &d->out ? nd->n : frames, d->h0, d->w0)) return rc;
-    if (s->depth != d->f0.depth || s->shift != d->f0.shift || s->chroma != d->f0.chroma) return RRIN_E_ARG;
-  }
-  if (int rc = yuv_coef_check16(&d->coef, d->f0.depth)) return rc;
-  if (nd->h != pad_up(d->h0, mult) || nd->w != pad_up(d->w0, mult)) return RRIN_E_SHAPE;
-  return 0;
+  return net_rgb_check(d->f0 && d->f1 && d->out_u16 && d->depth >= 9 && d->depth <= 16, &d->net, d->h0, d->w0,
+                       d->img_stride, frames, mult);
 }
 
-extern "C" int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream) {
-  if (int rc = net_u8_check(d, d ? d->net.n : 0)) return rc;
-  FrameIO f;
-  f.u8 = d;
-  return net_fwd_impl(&d->net, f, Items{}, stream);
+static int frame_check(const rrin_net_yuv_desc* d, int frames, int mult) {
+  if (!d) return RRIN_E_ARG;
+  return net_check(&d->net, d->h0, d->w0, mult, [&] {
+    if (int rc = yuv_coef_check(&d->coef)) return rc;
+    for (const rrin_yuv420* s : {&d->f0, &d->f1, &d->out}) {
+      if (int rc = yuv420_check(*s, s == &d->out ? d->net.n : frames, d->h0, d->w0)) return rc;
+      if (s->chroma != d->f0.chroma) return (int)RRIN_E_ARG;
+    }
+    return 0;
+  });
 }
 
-extern "C" int rrin_net_yuv_fwd(const rrin_net_yuv_desc* d, void* stream) {
-  if (int rc = net_yuv_check(d, d ? d->net.n : 0)) return rc;
-  FrameIO f;
-  f.yuv = d;
-  return net_fwd_impl(&d->net, f, Items{}, stream);
+static int frame_check(const rrin_net_yuv16_desc* d, int frames, int mult) {
+  if (!d) return RRIN_E_ARG;
+  return net_check(&d->net, d->h0, d->w0, mult, [&] {
+    for (const rrin_yuv420_16* s : {&d->f0, &d->f1, &d->out}) {
+      if (int rc = yuv420_16_check(*s, s == &d->out ? d->net.n : frames, d->h0, d->w0)) return rc;
+      if (s->depth != d->f0.depth || s->shift != d->f0.shift || s->chroma != d->f0.chroma) return (int)RRIN_E_ARG;
+    }
+    return yuv_coef_check16(&d->coef, d->f0.depth);
+  });
 }
 
-extern "C" int rrin_net_u16_fwd(const rrin_net_u16_desc* d, void* stream) {
-  if (int rc = net_u16_check(d, d ? d->net.n : 0)) return rc;
-  FrameIO f;
-  f.u16 = d;
-  return net_fwd_impl(&d->net, f, Items{}, stream);
-}
-
-extern "C" int rrin_net_yuv16_fwd(const rrin_net_yuv16_desc* d, void* stream) {
-  if (int rc = net_yuv16_check(d, d ? d->net.n : 0)) return rc;
-  FrameIO f;
-  f.yuv16 = d;
-  return net_fwd_impl(&d->net, f, Items{}, stream);
-}
-
-// ---- item forwards (ABI 25): rrin_items beside the frame descriptors ----------------------
-// The items first (RRIN_E_ARG), then the frame forward's own checks with the stacks' n_pairs frames.
-// taps are a plain forward's: an item forward refuses them.
-extern "C" int rrin_net_u8_items_fwd(const rrin_net_u8_desc* d, const rrin_items* it, void* stream) {
-  Items items;
-  if (!d || d->net.taps) return RRIN_E_ARG;
-  if (int rc = items_of(it, d->net.n, items)) return rc;
-  if (int rc = net_u8_check(d, items.n_pairs)) return rc;
-  FrameIO f;
-  f.u8 = d;
-  return net_fwd_impl(&d->net, f, items, stream);
-}
-
-extern "C" int rrin_net_yuv_items_fwd(const rrin_net_yuv_desc* d, const rrin_items* it, void* stream) {
-  Items items;
-  if (!d || d->net.taps) return RRIN_E_ARG;
-  if (int rc = items_of(it, d->net.n, items)) return rc;
-  if (int rc = net_yuv_check(d, items.n_pairs)) return rc;
-  FrameIO f;
-  f.yuv = d;
-  return net_fwd_impl(&d->net, f, items, stream);
-}
-
-extern "C" int rrin_net_u16_items_fwd(const rrin_net_u16_desc* d, const rrin_items* it, void* stream) {
-  Items items;
-  if (!d || d->net.taps) return RRIN_E_ARG;
-  if (int rc = items_of(it, d->net.n, items)) return rc;
-  if (int rc = net_u16_check(d, items.n_pairs)) return rc;
-  FrameIO f;
-  f.u16 = d;
-  return net_fwd_impl(&d->net, f, items, stream);
-}
-
-extern "C" int rrin_net_yuv16_items_fwd(const rrin_net_yuv16_desc* d, const rrin_items* it, void* stream) {
-  Items items;
-  if (!d || d->net.taps) return RRIN_E_ARG;
-  if (int rc = items_of(it, d->net.n, items)) return rc;
-  if (int rc = net_yuv16_check(d, items.n_pairs)) return rc;
-  FrameIO f;
-  f.yuv16 = d;
-  return net_fwd_impl(&d->net, f, items, stream);
-}
-
-// ---- flow_scale forwards: rrin_flow_scale beside the descriptors ---------------------------
-// The second plan first (RRIN_E_ARG: null members, s not 2 or 4, taps, the planar precision;
-// RRIN_E_SHAPE: a padded size that is no multiple of 16 * s), then the forward's own checks with the
-// pad multiple 16 * s.  items may be NULL (a plain forward).
+// The second plan of a flow_scale forward (RRIN_E_ARG: null members, s not 2 or 4, taps, the planar
+// precision; RRIN_E_SHAPE: a padded size that is no multiple of 16 * s).
 static int flow_scale_check(const rrin_net_desc* nd, const rrin_flow_scale* fs) {
   if (!nd || !fs || (fs->s != 2 && fs->s != 4) || !fs->convs || !fs->workspace || nd->taps) return RRIN_E_ARG;
   if (nd->prec != RRIN_PREC_F16X3 && nd->prec != RRIN_PREC_F16 && nd->prec != RRIN_PREC_F32R) return RRIN_E_ARG;
@@ -1027,58 +988,75 @@ static int flow_scale_check(const rrin_net_desc* nd, const rrin_flow_scale* fs) 
   return 0;
 }
 
-static int scaled_items(const rrin_items* it, int n, Items& items) {
-  return it ? items_of(it, n, items) : 0;
+// The three entries of a frame format D, rrin_net_D_fwd, _items_fwd (ABI 25: rrin_items beside the
+// descriptor) and _scaled_fwd (rrin_flow_scale beside both):
+//   Plain:  the descriptor's checks.
+//   Items:  a null descriptor or taps (a plain forward's: an item forward refuses them), then the
+//           items (RRIN_E_ARG), then the descriptor's checks with the stacks' n_pairs frames.
+//   Scaled: flow_scale_check, then the items -- which may be NULL, a plain forward --, then the
+//           descriptor's checks with the pad multiple 16 * s.
+enum class Entry { Plain, Items, Scaled };
+
+template <class D>
+static int frame_fwd(Entry e, const D* d, const rrin_items* it, const rrin_flow_scale* fs, void* stream) {
+  Items items;
+  if (e == Entry::Scaled) {
+    if (int rc = flow_scale_check(d ? &d->net : nullptr, fs)) return rc;
+  } else if (e == Entry::Items && (!d || d->net.taps)) {
+    return RRIN_E_ARG;
+  }
+  if (it || e == Entry::Items)
+    if (int rc = items_of(it, d->net.n, items)) return rc;
+  if (int rc = frame_check(d, it ? items.n_pairs : (d ? d->net.n : 0), fs ? 16 * fs->s : 16)) return rc;
+  return net_fwd_impl(&d->net, frame_io(*d), items, stream, fs);
+}
+
+extern "C" int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream) {
+  return frame_fwd(Entry::Plain, d, nullptr, nullptr, stream);
+}
+extern "C" int rrin_net_yuv_fwd(const rrin_net_yuv_desc* d, void* stream) {
+  return frame_fwd(Entry::Plain, d, nullptr, nullptr, stream);
+}
+extern "C" int rrin_net_u16_fwd(const rrin_net_u16_desc* d, void* stream) {
+  return frame_fwd(Entry::Plain, d, nullptr, nullptr, stream);
+}
+extern "C" int rrin_net_yuv16_fwd(const rrin_net_yuv16_desc* d, void* stream) {
+  return frame_fwd(Entry::Plain, d, nullptr, nullptr, stream);
+}
+
+extern "C" int rrin_net_u8_items_fwd(const rrin_net_u8_desc* d, const rrin_items* it, void* stream) {
+  return frame_fwd(Entry::Items, d, it, nullptr, stream);
+}
+extern "C" int rrin_net_yuv_items_fwd(const rrin_net_yuv_desc* d, const rrin_items* it, void* stream) {
+  return frame_fwd(Entry::Items, d, it, nullptr, stream);
+}
+extern "C" int rrin_net_u16_items_fwd(const rrin_net_u16_desc* d, const rrin_items* it, void* stream) {
+  return frame_fwd(Entry::Items, d, it, nullptr, stream);
+}
+extern "C" int rrin_net_yuv16_items_fwd(const rrin_net_yuv16_desc* d, const rrin_items* it, void* stream) {
+  return frame_fwd(Entry::Items, d, it, nullptr, stream);
 }
 
 extern "C" int rrin_net_scaled_fwd(const rrin_net_desc* d, const rrin_flow_scale* fs, void* stream) {
   if (int rc = flow_scale_check(d, fs)) return rc;
   if (!d->i0 || !d->i1 || !d->out || !d->coef || !d->convs || !d->heads || !d->workspace) return RRIN_E_ARG;
-  return net_fwd_impl(d, FrameIO{}, Items{}, stream, fs);
+  return net_fwd_impl(d, frame_io(*d), Items{}, stream, fs);
 }
-
 extern "C" int rrin_net_u8_scaled_fwd(const rrin_net_u8_desc* d, const rrin_items* it, const rrin_flow_scale* fs,
                                       void* stream) {
-  Items items;
-  if (int rc = flow_scale_check(d ? &d->net : nullptr, fs)) return rc;
-  if (int rc = scaled_items(it, d->net.n, items)) return rc;
-  if (int rc = net_u8_check(d, it ? items.n_pairs : d->net.n, 16 * fs->s)) return rc;
-  FrameIO f;
-  f.u8 = d;
-  return net_fwd_impl(&d->net, f, items, stream, fs);
+  return frame_fwd(Entry::Scaled, d, it, fs, stream);
 }
-
 extern "C" int rrin_net_yuv_scaled_fwd(const rrin_net_yuv_desc* d, const rrin_items* it, const rrin_flow_scale* fs,
                                        void* stream) {
-  Items items;
-  if (int rc = flow_scale_check(d ? &d->net : nullptr, fs)) return rc;
-  if (int rc = scaled_items(it, d->net.n, items)) return rc;
-  if (int rc = net_yuv_check(d, it ? items.n_pairs : d->net.n, 16 * fs->s)) return rc;
-  FrameIO f;
-  f.yuv = d;
-  return net_fwd_impl(&d->net, f, items, stream, fs);
+  return frame_fwd(Entry::Scaled, d, it, fs, stream);
 }
-
 extern "C" int rrin_net_u16_scaled_fwd(const rrin_net_u16_desc* d, const rrin_items* it, const rrin_flow_scale* fs,
                                        void* stream) {
-  Items items;
-  if (int rc = flow_scale_check(d ? &d->net : nullptr, fs)) return rc;
-  if (int rc = scaled_items(it, d->net.n, items)) return rc;
-  if (int rc = net_u16_check(d, it ? items.n_pairs : d->net.n, 16 * fs->s)) return rc;
-  FrameIO f;
-  f.u16 = d;
-  return net_fwd_impl(&d->net, f, items, stream, fs);
+  return frame_fwd(Entry::Scaled, d, it, fs, stream);
 }
-
-extern "C" int rrin_net_yuv16_scaled_fwd(const rrin_net_yuv16_desc* d, const rrin_items* it, const rrin_flow_scale* fs,
-                                         void* stream) {
-  Items items;
-  if (int rc = flow_scale_check(d ? &d->net : nullptr, fs)) return rc;
-  if (int rc = scaled_items(it, d->net.n, items)) return rc;
-  if (int rc = net_yuv16_check(d, it ? items.n_pairs : d->net.n, 16 * fs->s)) return rc;
-  FrameIO f;
-  f.yuv16 = d;
-  return net_fwd_impl(&d->net, f, items, stream, fs);
+extern "C" int rrin_net_yuv16_scaled_fwd(const rrin_net_yuv16_desc* d, const rrin_items* it,
+                                         const rrin_flow_scale* fs, void* stream) {
+  return frame_fwd(Entry::Scaled, d, it, fs, stream);
 }
 
 // One U-Net alone (reference UNet.forward, unet.py:40-51): NCHW in -> NCHW out,

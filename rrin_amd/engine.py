@@ -22,11 +22,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from .convert import scene_cut_code, scene_limit, scene_limit_len
+from .convert import scene_cut_code, scene_limit_len
 from .flowscale import check_flow_scale, flow_tag, padded_size
+from .framefmt import FrameFormat
 from .unet import _level_of
 
 UNET_ORDER = ("Flow", "refine_flow", "Mask", "final")
+# rrin_net_fwd and its flow_scale sibling (RRINEngine._launch); the frame paths' are FrameFormat.entries
+FLOAT_ENTRIES = ("rrin_net_fwd", "rrin_net_scaled_fwd")
 
 # g16 = [x0 0-2 | x1 3-5 | Ft0 6-7 | Ft1 8-9 | xt1 10-12 | xt2 13-15]; reference input orders:
 #   refine_flow: cat(Ft0, Ft1, x)            model.py:41
@@ -689,7 +692,7 @@ class RRINEngine:
         self._status = {}           # slot -> device int32 range flag (fp16-stored precisions)
         self._pending_status = []   # (event, pinned host copy) of flags not checked yet
         self._gate_bufs = {}        # pairs -> (int64 sums, int32 codes) of the scene gate
-        self._sad_key = None        # (path, pairs, byte rows, byte columns, parts) whose sums the buffers hold
+        self._sad_key = None        # FrameFormat.sums_key of the batch whose sums the buffers hold
         self.last_gate = None       # int32 device codes of the last gated forward_u8 / forward_yuv
         self._metrics_ws = None     # workspace of the frame metrics (per-workgroup partials)
 
@@ -890,7 +893,7 @@ class RRINEngine:
             d = self._float_desc(p, i0[lo:hi], i1[lo:hi], out[lo:hi], coef[lo:hi])
             d.prof = prof
             d.taps = tapbuf.data_ptr() if tapbuf is not None else None
-            self._launch(self.lib.rrin_net_fwd, "rrin_net_fwd", d, d, p, "f32", reuse_flow, stream)
+            self._launch(FLOAT_ENTRIES, d, d, p, "f32", reuse_flow, stream)
 
         self._run_parts(h, w, bounds, part, flow_scale)
         if tapbuf is not None:
@@ -900,66 +903,57 @@ class RRINEngine:
                 off += n * c * h * w
         return out
 
-    def _frames(self, f0, f1, what: str, rgb: bool, dtype=torch.uint8, layout: str = "nv12"):
-        """Checks two frame stacks of ``what`` (uint8, or uint16 for the 16-bit paths) --
-        ``[N,H0,W0,3]`` (``rgb``) or YUV planes of ``layout`` (4:2:0: ``[N, 3*H0//2, W0]``; 4:2:2:
-        ``[N, 2*H0, W0]``; 4:4:4: ``[N, 3*H0, W0]``) -- and returns them with (H0, W0) and
-        the elements (bytes or 16-bit words) between their frames: every frame dense, a uniform
-        stride over dim 0 taken as it is (``frames[:-1]`` / ``frames[1:]`` of one stack need no
-        copy), anything else copied."""
-        name = str(dtype).split(".")[-1]
-        if not isinstance(f0, torch.Tensor) or not isinstance(f1, torch.Tensor):
-            raise TypeError(f"{what} takes two {name} tensors")
-        if f0.device != self.device or f1.device != self.device:
-            raise RuntimeError(f"inputs on {f0.device}/{f1.device}, model on {self.device}")
-        if f0.dtype != dtype or f1.dtype != dtype:
-            raise TypeError(f"{what} takes {name} frames (forward takes float32)")
-        if rgb:
-            if f0.dim() != 4 or f0.shape != f1.shape or f0.shape[3] != 3:
-                raise ValueError(f"expected two [N,H0,W0,3] {name} tensors, got {tuple(f0.shape)} / {tuple(f1.shape)}")
-            h0, w0 = f0.shape[1:3]
-        else:
-            from . import yuv
-            if f0.shape != f1.shape:
-                raise ValueError(f"expected two equal [N, 3*H0//2, W0] stacks, got {tuple(f0.shape)} / "
-                                 f"{tuple(f1.shape)}")
-            h0, w0 = yuv.stack_size(f0, layout)
+    # ---- the byte-frame paths: one implementation per operation over a FrameFormat ------------
+    # (rrin_amd.framefmt).  The public forward_* / interpolate_items_* / pair_stats_* methods below
+    # are the written contract; each builds its format and calls one of these.
+
+    def _frame_call(self, what: str, flow_scale) -> int:
+        """What every frame forward refuses first: a bad flow_scale, the planar precision."""
+        flow_scale = check_flow_scale(flow_scale)
+        self._need_records(what)
+        return flow_scale
+
+    def _forward_frames(self, fmt: FrameFormat, what: str, f0, f1, t, reuse_flow, streams, split, scene_threshold,
+                        gate, flow_scale: int) -> torch.Tensor:
+        """``forward_*`` of every frame path: the call ``what`` on two stacks of ``fmt``."""
+        f0, f1, h0, w0, s0 = fmt.check(f0, f1, self.device, what)
         n = f0.shape[0]
-        if n < 1 or h0 < 1 or w0 < 1:
-            raise ValueError(f"empty frames: {tuple(f0.shape)}")
-        frame = math.prod(f0.shape[1:])
+        h, w = padded_size(h0, w0, flow_scale)
+        self._poll_range()
+        coef = t_coefficients(t, n).to(self.device, non_blocking=True)
+        bounds = self._bounds(n, streams, split)
+        g = self._scene_gate(fmt, n, h0, w0, t, bounds, reuse_flow, scene_threshold, gate)
+        out = torch.empty(fmt.out_shape(n, h0, w0), dtype=fmt.dtype, device=self.device)
+        # the raw Flow kept in a workspace is that of these frames read as this format (path, layout,
+        # matrix, depth, shift): no other one, and not the float path, may take it for its previous pair
+        tag, entries, flen = fmt.tag, fmt.entries, fmt.frame_len(h0, w0)
+        make = fmt.desc_for(s0, h0, w0)  # everything but the parts' addresses, once
 
-        def stride_of(f):  # elements between frames, or None if f needs a copy
-            dense = 1
-            for d in range(f.dim() - 1, 0, -1):  # the trailing dims: dense (a dim of 1 has no stride to check)
-                if f.shape[d] > 1 and f.stride(d) != dense:
-                    return None
-                dense *= f.shape[d]
-            return frame if n == 1 else (f.stride(0) if f.stride(0) >= frame else None)
+        def part(j, lo, hi, stream, p):
+            p0, p1, po = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), out[lo:hi].data_ptr()
+            d, nd = make(p0, p1, po)
+            self._fill_net(nd, p, coef[lo:hi])
+            self._launch(entries, d, nd, p, tag, reuse_flow, stream)
+            if g is not None:
+                self._enqueue_gate(g, fmt, p0, p1, s0, lo, hi, flen, po, stream)
 
-        s0, s1 = stride_of(f0), stride_of(f1)
-        if s0 is None or s0 != s1:
-            f0, f1 = f0.contiguous(), f1.contiguous()
-            s0 = frame
-        return f0, f1, h0, w0, s0
+        self._run_parts(h, w, bounds, part, flow_scale)
+        return out
 
-    def _scene_gate(self, path: str, n: int, rows: int, cols: int, t, bounds, reuse_flow, scene_threshold, gate,
-                    maxval: int = 255, samples: int | None = None):
-        """The scene gate of a byte-frame forward whose frames are ``rows x cols x 3`` bytes each
-        (RGB: H0 x W0; 4:2:0: H0/2 x W0) or, with ``samples``, blobs of that many bytes or 16-bit
-        samples (4:2:2, 4:4:4: no multiple of 3 in general).  Checks ``scene_threshold`` against ``gate`` and the gate
-        tensor, keeps :attr:`last_gate` and the key of the cached sums, and returns None (gate
-        off) or (sums or None, sums already there, limit, cut code, codes) for _enqueue_gate.
-        Changes state, so it runs after everything else that may refuse the call."""
+    def _scene_gate(self, fmt: FrameFormat, n: int, h0: int, w0: int, t, bounds, reuse_flow, scene_threshold, gate):
+        """The scene gate of a forward of n pairs of H0 x W0 frames of ``fmt``.  Checks
+        ``scene_threshold`` against ``gate`` and the gate tensor, keeps :attr:`last_gate` and the key
+        of the cached sums, and returns None (gate off) or (sums or None, sums already there, limit,
+        cut code, codes) for _enqueue_gate.  Changes state, so it runs after everything else that
+        may refuse the call."""
         if scene_threshold is not None and gate is not None:
             raise ValueError("scene_threshold and gate exclude each other")
         sad, have_sad, limit, cut_code = None, False, None, None
         if scene_threshold is not None:
-            limit = (scene_limit(scene_threshold, rows, cols, maxval) if samples is None
-                     else scene_limit_len(scene_threshold, samples, maxval))
+            limit = scene_limit_len(scene_threshold, fmt.frame_len(h0, w0), fmt.maxval)
             cut_code = scene_cut_code(t)
             # the sums belong to the batch and its split: kept for the next t of the same pairs
-            skey = (path, n, rows, cols, tuple(bounds)) if samples is None else (path, n, samples, tuple(bounds))
+            skey = fmt.sums_key(n, h0, w0, bounds)
             have_sad = bool(reuse_flow) and self._sad_key == skey
             sad, gate = self._gate_buffers(n)
             self._sad_key = skey
@@ -975,65 +969,47 @@ class RRINEngine:
         self.last_gate = gate
         return sad, have_sad, limit, cut_code, gate
 
-    def _enqueue_gate(self, g, p0: int, p1: int, img_stride: int, lo: int, hi: int, rows: int, cols: int, out: int,
-                      stream, wide=None, samples: int | None = None):
+    def _sums(self, fmt: FrameFormat, p0: int, p1: int, stride: int, m: int, flen: int, sums: int, sp):
+        """The sums of absolute sample differences of m pairs of frames of ``flen`` elements at p0 / p1
+        (``stride`` elements apart) into the int64 at ``sums``: bytes, or ``fmt.wide`` samples."""
+        if fmt.wide is None:
+            _lib.check(self.lib.rrin_pair_sad_u8_len(p0, p1, stride, m, flen, sums, sp), "rrin_pair_sad_u8_len")
+        else:
+            _lib.check(self.lib.rrin_pair_sad_u16_len(p0, p1, stride, m, flen, fmt.depth, fmt.shift, sums, sp),
+                       "rrin_pair_sad_u16_len")
+
+    def _gate_codes(self, fmt: FrameFormat, p0: int, p1: int, stride: int, m: int, flen: int, sums: int, have_sums,
+                    limit: int, cut_code: int, codes: int, sp):
+        """The part of the gate a forward and an item forward share: the sums of m pairs (unless
+        kept) and the codes from the sums."""
+        if not have_sums:
+            self._sums(fmt, p0, p1, stride, m, flen, sums, sp)
+        _lib.check(self.lib.rrin_gate_from_sad_u8(sums, m, limit, cut_code, codes, sp), "rrin_gate_from_sad_u8")
+
+    def _enqueue_gate(self, g, fmt: FrameFormat, p0: int, p1: int, img_stride: int, lo: int, hi: int, flen: int,
+                      out: int, stream):
         """The gate kernels of pairs [lo, hi) on ``stream``, behind the part's forward: the sums
         (unless kept), the codes from the sums (unless given), the copy of the gated frames from
-        the frames at p0 / p1 (``rows x cols x 3`` bytes each) over those at ``out``.  ``wide``
-        (depth, shift): the frames are 16-bit words and ``img_stride`` counts them; the sums are
-        rrin_pair_sad_u16's, and the byte-wise copy kernel runs on twice the width.  ``samples``:
-        the frames are blobs of that many elements (``rows`` / ``cols`` unused): the _len entry points."""
+        the frames at p0 / p1 (``flen`` elements each, ``img_stride`` apart) over those at ``out``.
+        The sums take elements; the copy kernel is byte-wise, so 16-bit frames pass it twice the
+        stride and twice the length."""
         sad, have_sad, limit, cut_code, codes = g
-        sp, m = C.c_void_p(stream.cuda_stream), hi - lo
+        sp, m, k = C.c_void_p(stream.cuda_stream), hi - lo, fmt.esize
         cp = codes[lo:hi].data_ptr()
-        if samples is not None:
-            k = 1 if wide is None else 2
-            if sad is not None:
-                sums = sad[lo:hi].data_ptr()
-                if not have_sad and wide is None:
-                    _lib.check(self.lib.rrin_pair_sad_u8_len(p0, p1, img_stride, m, samples, sums, sp),
-                               "rrin_pair_sad_u8_len")
-                elif not have_sad:
-                    _lib.check(self.lib.rrin_pair_sad_u16_len(p0, p1, img_stride, m, samples, wide[0], wide[1], sums,
-                                                              sp), "rrin_pair_sad_u16_len")
-                _lib.check(self.lib.rrin_gate_from_sad_u8(sums, m, limit, cut_code, cp, sp), "rrin_gate_from_sad_u8")
-            _lib.check(self.lib.rrin_gate_frames_u8_len(p0, p1, img_stride * k, m, samples * k, cp, out, sp),
-                       "rrin_gate_frames_u8_len")
-            return
         if sad is not None:
-            sums = sad[lo:hi].data_ptr()
-            if not have_sad and wide is None:
-                _lib.check(self.lib.rrin_pair_sad_u8(p0, p1, img_stride, m, rows, cols, sums, sp), "rrin_pair_sad_u8")
-            elif not have_sad:
-                _lib.check(self.lib.rrin_pair_sad_u16(p0, p1, img_stride, m, rows, cols, wide[0], wide[1], sums, sp),
-                           "rrin_pair_sad_u16")
-            _lib.check(self.lib.rrin_gate_from_sad_u8(sums, m, limit, cut_code, cp, sp), "rrin_gate_from_sad_u8")
-        k = 1 if wide is None else 2
-        _lib.check(self.lib.rrin_gate_frames_u8(p0, p1, img_stride * k, m, rows, cols * k, cp, out, sp),
-                   "rrin_gate_frames_u8")
+            self._gate_codes(fmt, p0, p1, img_stride, m, flen, sad[lo:hi].data_ptr(), have_sad, limit, cut_code, cp, sp)
+        _lib.check(self.lib.rrin_gate_frames_u8_len(p0, p1, img_stride * k, m, flen * k, cp, out, sp),
+                   "rrin_gate_frames_u8_len")
 
-    def _pair_sad(self, f0, f1, img_stride: int, rows: int, cols: int, wide=None,
-                  samples: int | None = None) -> torch.Tensor:
-        """rrin_pair_sad_u8 (``wide`` = (depth, shift): rrin_pair_sad_u16) of two checked stacks on
-        the current stream: a fresh int64 ``[N]``.  ``samples``: frames of that many elements, through
-        the _len entry points."""
+    def _pair_sums(self, fmt: FrameFormat, what: str, f0, f1) -> torch.Tensor:
+        """``pair_stats_*`` of every frame path: the sums of two stacks of ``fmt`` on the current
+        stream, a fresh int64 ``[N]``."""
+        f0, f1, h0, w0, s0 = fmt.check(f0, f1, self.device, what)
         n = f0.shape[0]
         sad = torch.empty(n, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            if samples is not None and wide is None:
-                _lib.check(self.lib.rrin_pair_sad_u8_len(f0.data_ptr(), f1.data_ptr(), img_stride, n, samples,
-                                                         sad.data_ptr(), st), "rrin_pair_sad_u8_len")
-            elif samples is not None:
-                _lib.check(self.lib.rrin_pair_sad_u16_len(f0.data_ptr(), f1.data_ptr(), img_stride, n, samples,
-                                                          wide[0], wide[1], sad.data_ptr(), st),
-                           "rrin_pair_sad_u16_len")
-            elif wide is None:
-                _lib.check(self.lib.rrin_pair_sad_u8(f0.data_ptr(), f1.data_ptr(), img_stride, n, rows, cols,
-                                                     sad.data_ptr(), st), "rrin_pair_sad_u8")
-            else:
-                _lib.check(self.lib.rrin_pair_sad_u16(f0.data_ptr(), f1.data_ptr(), img_stride, n, rows, cols,
-                                                      wide[0], wide[1], sad.data_ptr(), st), "rrin_pair_sad_u16")
+            self._sums(fmt, f0.data_ptr(), f1.data_ptr(), s0, n, fmt.frame_len(h0, w0), sad.data_ptr(), st)
         return sad
 
     def forward_u8(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, reuse_flow: bool = False,
@@ -1057,7 +1033,7 @@ class RRINEngine:
         exceeds ``floor(scene_threshold * H0*W0*3)`` (a shot change) returns the nearer input
         frame, ``f0``'s for t < 0.5 and ``f1``'s from t = 0.5 on (``scene_cut_code``; one t for the
         batch).  Three small kernels per forward part, on the part's stream after its forward:
-        rrin_pair_sad_u8, rrin_gate_from_sad_u8, rrin_gate_frames_u8; the sums and codes live in
+        rrin_pair_sad_u8_len, rrin_gate_from_sad_u8, rrin_gate_frames_u8_len; the sums and codes live in
         cached device buffers and nothing comes back to the host.  With ``reuse_flow=True`` the
         sums of the previous gated call of the same batch are reused as the Flow is.
         ``gate``: an int32 device tensor ``[N]`` of explicit codes (1: ``f0``'s frame, 2: ``f1``'s,
@@ -1073,31 +1049,10 @@ class RRINEngine:
         of their size and its flow is scaled up; the padding is then to a multiple of 16 * s, and
         the definition reads pad -> ``forward(..., flow_scale=s)`` -> ``to_uint8_image`` -> crop.  The
         gate and its codes do not depend on it; a kept raw Flow is reused only at the same scale."""
-        flow_scale = check_flow_scale(flow_scale)
-        self._need_records("forward_u8")
-        f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_u8", rgb=True)
-        n = f0.shape[0]
-        h, w = padded_size(h0, w0, flow_scale)
-        self._poll_range()
-        coef = t_coefficients(t, n).to(self.device, non_blocking=True)
-        bounds = self._bounds(n, streams, split)
-        g = self._scene_gate("u8", n, h0, w0, t, bounds, reuse_flow, scene_threshold, gate)
-        out = torch.empty((n, h0, w0, 3), dtype=torch.uint8, device=self.device)
-
-        def part(j, lo, hi, stream, p):
-            d = _lib.NetU8Desc()
-            self._fill_net(d.net, p, coef[lo:hi])
-            p0, p1, po = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), out[lo:hi].data_ptr()
-            d.f0, d.f1, d.img_stride, d.out_u8 = p0, p1, s0, po
-            d.h0, d.w0 = h0, w0
-            # the raw Flow kept in the workspace is that of 8-bit frames: forward(reuse_flow=True)
-            # must not take it for its own previous pair, nor forward_u8 the float path's
-            self._launch(self.lib.rrin_net_u8_fwd, "rrin_net_u8_fwd", d, d.net, p, "u8", reuse_flow, stream)
-            if g is not None:
-                self._enqueue_gate(g, p0, p1, s0, lo, hi, h0, w0, po, stream)
-
-        self._run_parts(h, w, bounds, part, flow_scale)
-        return out
+        flow_scale = self._frame_call("forward_u8", flow_scale)
+        fmt = FrameFormat.u8()
+        return self._forward_frames(fmt, "forward_u8", f0, f1, t, reuse_flow, streams, split, scene_threshold,
+                                    gate, flow_scale)
 
     def _need_records(self, what: str):
         if self.prec == _lib.PREC_F32:
@@ -1119,37 +1074,10 @@ class RRINEngine:
     def pair_stats_u8(self, f0: torch.Tensor, f1: torch.Tensor) -> torch.Tensor:
         """The sum of absolute byte differences of every pair of two uint8 ``[N,H0,W0,3]`` stacks
         (as :meth:`forward_u8` takes them): a fresh int64 device tensor ``[N]``, exact, enqueued
-        on the current stream (rrin_pair_sad_u8) -- for a caller with its own rule for ``gate``."""
-        f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_u8", rgb=True)
-        return self._pair_sad(f0, f1, s0, h0, w0)
+        on the current stream (rrin_pair_sad_u8_len) -- for a caller with its own rule for ``gate``."""
+        return self._pair_sums(FrameFormat.u8(), "pair_stats_u8", f0, f1)
 
     # ---- 8-bit YUV 4:2:0 frames (NV12 / I420) ------------------------------------------
-    @staticmethod
-    def _yuv_stack(ptr: int, img_stride: int, h0: int, w0: int, layout: str) -> "_lib.Yuv420":
-        """The rrin_yuv420 of a dense-frame stack at device address ``ptr``."""
-        s = _lib.Yuv420()
-        s.y, s.u = ptr, ptr + h0 * w0
-        s.img_stride, s.y_pitch = img_stride, w0
-        if layout == "nv12":
-            s.v, s.c_pitch, s.c_step = s.u + 1, w0, 2
-        elif layout == "i420":
-            s.v, s.c_pitch, s.c_step = s.u + (h0 // 2) * (w0 // 2), w0 // 2, 1
-        elif layout == "nv16":
-            s.v, s.c_pitch, s.c_step, s.chroma = s.u + 1, w0, 2, _lib.CHROMA_422
-        elif layout == "i422":
-            s.v, s.c_pitch, s.c_step, s.chroma = s.u + h0 * (w0 // 2), w0 // 2, 1, _lib.CHROMA_422
-        else:  # i444
-            s.v, s.c_pitch, s.c_step, s.chroma = s.u + h0 * w0, w0, 1, _lib.CHROMA_444
-        return s
-
-    @staticmethod
-    def _yuv_gate_samples(h0: int, w0: int, layout: str):
-        """None for a 4:2:0 layout (its gate keeps running on (H0/2) x W0 x 3 bytes), else the
-        samples of a 4:2:2 / 4:4:4 frame: 2*H0*W0 / 3*H0*W0."""
-        from . import yuv
-        chroma = yuv.chroma_of(layout)
-        return None if chroma == "420" else (2 if chroma == "422" else 3) * h0 * w0
-
     def forward_yuv(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, layout: str = "nv12", coef=None,
                     reuse_flow: bool = False, streams: int | None = None, split=None, scene_threshold=None,
                     gate=None, flow_scale: int = 1) -> torch.Tensor:
@@ -1182,58 +1110,21 @@ class RRINEngine:
         (rrin_pair_sad_u8_len): a cut exceeds ``floor(scene_threshold * that count)``.
 
         ``flow_scale``: as in :meth:`forward_u8`, which the definition passes it to."""
-        from . import yuv
-        flow_scale = check_flow_scale(flow_scale)
-        self._need_records("forward_yuv")
-        if layout not in yuv.ALL_LAYOUTS:
-            raise ValueError(f"layout must be one of {yuv.ALL_LAYOUTS}, got {layout!r}")
-        k = yuv.as_coef(coef)
-        f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_yuv", rgb=False, layout=layout)
-        samples = self._yuv_gate_samples(h0, w0, layout)
-        n = f0.shape[0]
-        h, w = padded_size(h0, w0, flow_scale)
-        self._poll_range()
-        tcoef = t_coefficients(t, n).to(self.device, non_blocking=True)
-        bounds = self._bounds(n, streams, split)
-        # the gate of forward_u8 on the frames' bytes: (H0/2) * W0 * 3 of them per frame
-        g = self._scene_gate("yuv", n, h0 // 2, w0, t, bounds, reuse_flow, scene_threshold, gate, samples=samples)
-        out = torch.empty((n, yuv.stack_rows(h0, layout), w0), dtype=torch.uint8, device=self.device)
-        # the raw Flow kept in a workspace is that of these frames under this layout and matrix:
-        # no other path, layout or matrix may take it for its previous pair
-        tag = "yuv:" + layout + ":" + ",".join(str(v) for v in k)
-        kc = _lib.YuvCoef(*k)
-        frame = out.stride(0)
-
-        def part(j, lo, hi, stream, p):
-            d = _lib.NetYuvDesc()
-            self._fill_net(d.net, p, tcoef[lo:hi])
-            p0, p1, po = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), out[lo:hi].data_ptr()
-            d.f0, d.f1 = self._yuv_stack(p0, s0, h0, w0, layout), self._yuv_stack(p1, s0, h0, w0, layout)
-            d.out = self._yuv_stack(po, frame, h0, w0, layout)
-            d.coef, d.h0, d.w0 = kc, h0, w0
-            self._launch(self.lib.rrin_net_yuv_fwd, "rrin_net_yuv_fwd", d, d.net, p, tag, reuse_flow, stream)
-            if g is not None:
-                self._enqueue_gate(g, p0, p1, s0, lo, hi, h0 // 2, w0, po, stream, samples=samples)
-
-        self._run_parts(h, w, bounds, part, flow_scale)
-        return out
+        flow_scale = self._frame_call("forward_yuv", flow_scale)
+        fmt = FrameFormat.yuv(layout, coef)
+        return self._forward_frames(fmt, "forward_yuv", f0, f1, t, reuse_flow, streams, split, scene_threshold,
+                                    gate, flow_scale)
 
     def pair_stats_yuv(self, f0: torch.Tensor, f1: torch.Tensor, layout: str = "nv12") -> torch.Tensor:
         """The sum of absolute byte differences (luma and chroma) of every pair of two 4:2:0
         stacks as :meth:`forward_yuv` takes them: a fresh int64 device tensor ``[N]``, exact
-        (rrin_pair_sad_u8 on the frames' bytes) -- what its ``scene_threshold`` compares with
+        (rrin_pair_sad_u8_len on the frames' bytes) -- what its ``scene_threshold`` compares with
         ``floor(threshold * H0*W0*3/2)``.  ``layout`` matters for the stack's shape only: a 4:2:2 or
         4:4:4 layout sums the frame's ``2*H0*W0`` / ``3*H0*W0`` bytes (rrin_pair_sad_u8_len)."""
-        f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_yuv", rgb=False, layout=layout)
-        return self._pair_sad(f0, f1, s0, h0 // 2, w0, samples=self._yuv_gate_samples(h0, w0, layout))
+        # the sums read samples only: no matrix, and the layout is checked with the stack
+        return self._pair_sums(FrameFormat.samples(layout), "pair_stats_yuv", f0, f1)
 
     # ---- 10- to 16-bit frames in 16-bit words ----------------------------------------------
-    @staticmethod
-    def _depth16(depth, lo: int, what: str) -> int:
-        if isinstance(depth, bool) or not isinstance(depth, int) or not lo <= depth <= 16:
-            raise ValueError(f"{what}: depth must be an int in {lo}..16, got {depth!r}")
-        return depth
-
     def forward_u16(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, depth: int = 10, reuse_flow: bool = False,
                     streams: int | None = None, split=None, scene_threshold=None, gate=None,
                     flow_scale: int = 1) -> torch.Tensor:
@@ -1245,59 +1136,18 @@ class RRINEngine:
         ``(uint16)(v * maxval)`` (rrin_net_u16_fwd).  Everything else is :meth:`forward_u8`'s:
         views of one stack without a copy, the stream split, ``reuse_flow``, the range guard and
         the scene gate -- with ``scene_threshold`` a mean absolute sample difference in
-        [0, maxval] over ``min(word, maxval)`` (rrin_pair_sad_u16), and a gated frame its input
+        [0, maxval] over ``min(word, maxval)`` (rrin_pair_sad_u16_len), and a gated frame its input
         frame's words as they are.  A kept raw Flow is only reused by this path at this depth.
         ``flow_scale``: as in :meth:`forward_u8` (``forward(..., flow_scale=s)`` in the definition)."""
-        flow_scale = check_flow_scale(flow_scale)
-        self._need_records("forward_u16")
-        depth = self._depth16(depth, 9, "forward_u16")
-        f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_u16", rgb=True, dtype=torch.uint16)
-        n = f0.shape[0]
-        h, w = padded_size(h0, w0, flow_scale)
-        self._poll_range()
-        coef = t_coefficients(t, n).to(self.device, non_blocking=True)
-        bounds = self._bounds(n, streams, split)
-        tag = f"u16:{depth}"
-        g = self._scene_gate(tag, n, h0, w0, t, bounds, reuse_flow, scene_threshold, gate, (1 << depth) - 1)
-        out = torch.empty((n, h0, w0, 3), dtype=torch.uint16, device=self.device)
-
-        def part(j, lo, hi, stream, p):
-            d = _lib.NetU16Desc()
-            self._fill_net(d.net, p, coef[lo:hi])
-            p0, p1, po = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), out[lo:hi].data_ptr()
-            d.f0, d.f1, d.img_stride, d.out_u16 = p0, p1, s0, po
-            d.h0, d.w0, d.depth = h0, w0, depth
-            self._launch(self.lib.rrin_net_u16_fwd, "rrin_net_u16_fwd", d, d.net, p, tag, reuse_flow, stream)
-            if g is not None:
-                self._enqueue_gate(g, p0, p1, s0, lo, hi, h0, w0, po, stream, wide=(depth, 0))
-
-        self._run_parts(h, w, bounds, part, flow_scale)
-        return out
+        flow_scale = self._frame_call("forward_u16", flow_scale)
+        fmt = FrameFormat.u16(depth, "forward_u16")
+        return self._forward_frames(fmt, "forward_u16", f0, f1, t, reuse_flow, streams, split, scene_threshold,
+                                    gate, flow_scale)
 
     def pair_stats_u16(self, f0: torch.Tensor, f1: torch.Tensor, depth: int = 10) -> torch.Tensor:
         """:meth:`pair_stats_u8` for two uint16 ``[N,H0,W0,3]`` stacks of ``depth`` 9..16: the exact
-        sum of ``|min(a, maxval) - min(b, maxval)|`` per pair (rrin_pair_sad_u16), int64 ``[N]``."""
-        depth = self._depth16(depth, 9, "pair_stats_u16")
-        f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_u16", rgb=True, dtype=torch.uint16)
-        return self._pair_sad(f0, f1, s0, h0, w0, wide=(depth, 0))
-
-    @staticmethod
-    def _yuv16_stack(ptr: int, img_stride: int, h0: int, w0: int, layout: str, depth: int, shift: int):
-        """The rrin_yuv420_16 of a dense-frame uint16 stack at device address ``ptr`` (strides in words)."""
-        s = _lib.Yuv420x16()
-        s.y, s.u = ptr, ptr + 2 * h0 * w0
-        s.img_stride, s.y_pitch, s.depth, s.shift = img_stride, w0, depth, shift
-        if layout == "nv12":
-            s.v, s.c_pitch, s.c_step = s.u + 2, w0, 2
-        elif layout == "i420":
-            s.v, s.c_pitch, s.c_step = s.u + 2 * (h0 // 2) * (w0 // 2), w0 // 2, 1
-        elif layout == "nv16":
-            s.v, s.c_pitch, s.c_step, s.chroma = s.u + 2, w0, 2, _lib.CHROMA_422
-        elif layout == "i422":
-            s.v, s.c_pitch, s.c_step, s.chroma = s.u + 2 * h0 * (w0 // 2), w0 // 2, 1, _lib.CHROMA_422
-        else:  # i444
-            s.v, s.c_pitch, s.c_step, s.chroma = s.u + 2 * h0 * w0, w0, 1, _lib.CHROMA_444
-        return s
+        sum of ``|min(a, maxval) - min(b, maxval)|`` per pair (rrin_pair_sad_u16_len), int64 ``[N]``."""
+        return self._pair_sums(FrameFormat.u16(depth, "pair_stats_u16"), "pair_stats_u16", f0, f1)
 
     def forward_yuv16(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, layout: str = "nv12", depth: int = 10,
                       msb: bool = False, coef=None, reuse_flow: bool = False, streams: int | None = None, split=None,
@@ -1315,53 +1165,20 @@ class RRINEngine:
         The 4:2:2 and 4:4:4 layouts ("nv16", "i422", "i444") run as in :meth:`forward_yuv`, defined by
         ``yuv.rgb16_to_yuv`` / ``yuv.yuv_to_rgb16``, the gate on the frame's samples (rrin_pair_sad_u16_len).
         ``flow_scale``: as in :meth:`forward_u16`, which the definition passes it to."""
-        from . import yuv
-        flow_scale = check_flow_scale(flow_scale)
-        self._need_records("forward_yuv16")
-        if layout not in yuv.ALL_LAYOUTS:
-            raise ValueError(f"layout must be one of {yuv.ALL_LAYOUTS}, got {layout!r}")
-        depth = yuv.check_depth16(depth)
-        shift = 16 - depth if msb else 0
-        k = yuv.as_coef(coef, depth)
-        f0, f1, h0, w0, s0 = self._frames(f0, f1, "forward_yuv16", rgb=False, dtype=torch.uint16, layout=layout)
-        samples = self._yuv_gate_samples(h0, w0, layout)
-        n = f0.shape[0]
-        h, w = padded_size(h0, w0, flow_scale)
-        self._poll_range()
-        tcoef = t_coefficients(t, n).to(self.device, non_blocking=True)
-        bounds = self._bounds(n, streams, split)
-        g = self._scene_gate(f"yuv16:{depth}:{shift}", n, h0 // 2, w0, t, bounds, reuse_flow, scene_threshold, gate,
-                             (1 << depth) - 1, samples=samples)
-        out = torch.empty((n, yuv.stack_rows(h0, layout), w0), dtype=torch.uint16, device=self.device)
-        tag = f"yuv16:{depth}:{shift}:{layout}:" + ",".join(str(v) for v in k)
-        kc = _lib.YuvCoef(*k)
-        frame = out.stride(0)
-
-        def part(j, lo, hi, stream, p):
-            d = _lib.NetYuv16Desc()
-            self._fill_net(d.net, p, tcoef[lo:hi])
-            p0, p1, po = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), out[lo:hi].data_ptr()
-            d.f0 = self._yuv16_stack(p0, s0, h0, w0, layout, depth, shift)
-            d.f1 = self._yuv16_stack(p1, s0, h0, w0, layout, depth, shift)
-            d.out = self._yuv16_stack(po, frame, h0, w0, layout, depth, shift)
-            d.coef, d.h0, d.w0 = kc, h0, w0
-            self._launch(self.lib.rrin_net_yuv16_fwd, "rrin_net_yuv16_fwd", d, d.net, p, tag, reuse_flow, stream)
-            if g is not None:
-                self._enqueue_gate(g, p0, p1, s0, lo, hi, h0 // 2, w0, po, stream, wide=(depth, shift),
-                                   samples=samples)
-
-        self._run_parts(h, w, bounds, part, flow_scale)
-        return out
+        flow_scale = self._frame_call("forward_yuv16", flow_scale)
+        fmt = FrameFormat.yuv16(layout, depth, msb, coef)
+        return self._forward_frames(fmt, "forward_yuv16", f0, f1, t, reuse_flow, streams, split, scene_threshold,
+                                    gate, flow_scale)
 
     def pair_stats_yuv16(self, f0: torch.Tensor, f1: torch.Tensor, depth: int = 10, msb: bool = False,
                          layout: str = "nv12") -> torch.Tensor:
         """:meth:`pair_stats_yuv` for two uint16 4:2:0 stacks: the exact sum of absolute differences
-        of the samples ``min(word >> shift, maxval)``, luma and chroma (rrin_pair_sad_u16)."""
+        of the samples ``min(word >> shift, maxval)``, luma and chroma (rrin_pair_sad_u16_len)."""
         from . import yuv
         depth = yuv.check_depth16(depth)
-        f0, f1, h0, w0, s0 = self._frames(f0, f1, "pair_stats_yuv16", rgb=False, dtype=torch.uint16, layout=layout)
-        return self._pair_sad(f0, f1, s0, h0 // 2, w0, wide=(depth, 16 - depth if msb else 0),
-                              samples=self._yuv_gate_samples(h0, w0, layout))
+        # the sums read samples only: no matrix, and the layout is checked with the stack
+        fmt = FrameFormat.samples(layout, depth, 16 - depth if msb else 0)
+        return self._pair_sums(fmt, "pair_stats_yuv16", f0, f1)
 
     # ---- frame metrics: squared error, PSNR and SSIM per plane, on the device -----------------
     def _metrics_workspace(self, nbytes: int) -> torch.Tensor:
@@ -1408,21 +1225,22 @@ class RRINEngine:
     # frames[pair[k]+1:pair[k]+2], t=t[k])[0]: batch-size independence and the t-blend of a kept
     # raw Flow (reuse_flow) are the two bitwise guarantees it rests on.
 
-    def _run_items(self, f0, f1, s0: int, h0: int, w0: int, pairs, ts, out, make, fwd, streams, split, prof,
-                   gate_cfg, flow_scale: int = 1):
-        """The item forward of every frame path.  f0 / f1: the checked views ``frames[:-1]`` /
-        ``frames[1:]`` (stride s0 elements); pairs / ts: :func:`check_items`' result; out: the ``[M,
-        ...]`` output stack; ``make(p0, p1, po)`` returns the path's descriptor with its frames set
-        to the device addresses of a part's first pair (two of them) and output frame, and its
-        rrin_net_desc; ``fwd``: the name of the library's item entry.  The items are split over
-        ``streams`` as a forward's pairs are; each part runs the Flow U-Net on the distinct pairs
+    def _run_items(self, fmt: FrameFormat, what: str, frames, pair, t, streams, split, scene_threshold, gate, prof,
+                   flow_scale: int) -> torch.Tensor:
+        """``interpolate_items_*`` of every frame path: the call ``what`` on one ``[P+1, ...]`` stack of
+        ``fmt``, whose views ``frames[:-1]`` / ``frames[1:]`` are the pairs' frames.  The items are split
+        over ``streams`` as a forward's pairs are; each part runs the Flow U-Net on the distinct pairs
         of its own items (a pair whose items straddle two parts is computed in both).  A part's
         pairs are a run of the stack, so its frames are views; pairs that skip some (an arbitrary
-        caller) are gathered into a copy.  ``gate_cfg``: None or (scene_threshold, gate, maxval,
-        frame length in elements, (depth, shift) or None).  ``flow_scale`` s > 1: the library's
-        ``_scaled_fwd`` entry of the path with the part's second plan, the Flow phase at 1/s of the
-        size on the part's pairs."""
+        caller) are gathered into a copy.  ``flow_scale`` s > 1: the library's ``_scaled_fwd`` entry
+        of the path with the part's second plan, the Flow phase at 1/s of the size on the part's
+        pairs."""
+        if not isinstance(frames, torch.Tensor) or frames.dim() < 1 or frames.shape[0] < 2:
+            raise ValueError(f"{what} takes one stack of at least two frames")
+        f0, f1, h0, w0, s0 = fmt.check(frames[:-1], frames[1:], self.device, what)
+        pairs, ts = check_items(pair, t, f0.shape[0])
         m = len(pairs)
+        out = torch.empty(fmt.out_shape(m, h0, w0), dtype=fmt.dtype, device=self.device)
         n_stack = f0.shape[0]
         h, w = padded_size(h0, w0, flow_scale)
         self._poll_range()
@@ -1430,20 +1248,19 @@ class RRINEngine:
         bounds = self._bounds(m, streams, split)
         if prof is not None and len(bounds) != 1:
             raise ValueError("prof needs a single forward part (streams=1)")
+        flen, (_, items_fwd, scaled_fwd) = fmt.frame_len(h0, w0), fmt.entries
+        make = fmt.desc_for(s0, h0, w0)  # everything but the parts' addresses, once (a gathered part: its own)
         glimit = pair_gate = None
-        if gate_cfg is not None:
-            scene_threshold, gate, maxval, flen, wide = gate_cfg
-            if scene_threshold is not None and gate is not None:
-                raise ValueError("scene_threshold and gate exclude each other")
-            if scene_threshold is not None:
-                glimit = scene_limit_len(scene_threshold, flen, maxval)
-            elif gate is not None:
-                if (not isinstance(gate, torch.Tensor) or gate.dtype != torch.int32 or gate.device != self.device
-                        or tuple(gate.shape) != (n_stack,)):
-                    raise ValueError(f"gate must be an int32 tensor [{n_stack}] (one code per pair) on {self.device}")
-                pair_gate = gate.contiguous()
-            else:
-                gate_cfg = None
+        if scene_threshold is not None and gate is not None:
+            raise ValueError("scene_threshold and gate exclude each other")
+        if scene_threshold is not None:
+            glimit = scene_limit_len(scene_threshold, flen, fmt.maxval)
+        elif gate is not None:
+            if (not isinstance(gate, torch.Tensor) or gate.dtype != torch.int32 or gate.device != self.device
+                    or tuple(gate.shape) != (n_stack,)):
+                raise ValueError(f"gate must be an int32 tensor [{n_stack}] (one code per pair) on {self.device}")
+            pair_gate = gate.contiguous()
+        gated = glimit is not None or pair_gate is not None
         # per part: its distinct pairs; per item: its pair's index among them and its cut code
         distinct, local = [], []
         for lo, hi in bounds:
@@ -1456,13 +1273,12 @@ class RRINEngine:
         maps, cuts = dev[:m], dev[m:]
         coef = item_coefficients(ts, m).to(self.device, non_blocking=True)
         codes = None
-        if gate_cfg is not None:
+        if gated:
             # sums and codes of the pairs (per part: at most its items), the items' codes
             sad, pcodes = self._gate_buffers(m) if glimit is not None else (None, None)
             codes = torch.empty(m, dtype=torch.int32, device=self.device)
             self._sad_key = None  # the cached sums of a forward_* call are gone
             self.last_gate = codes
-        esize = f0.element_size()
 
         def part(j, lo, hi, stream, p):
             d = distinct[j]
@@ -1478,34 +1294,29 @@ class RRINEngine:
                     b.record_stream(stream)
                 stride = a.stride(0)
             p0, p1, po = a.data_ptr(), b.data_ptr(), out[lo:hi].data_ptr()
-            desc, nd = make(p0, p1, po, stride)
+            desc, nd = (make if stride == s0 else fmt.desc_for(stride, h0, w0))(p0, p1, po)
             self._fill_net(nd, p, coef[lo:hi])
             nd.prof = prof
             it = _lib.Items()
             it.n_pairs, it.pair_map = npairs, maps[lo:hi].data_ptr()
             nd.skip_flow = 0
+            sp = C.c_void_p(stream.cuda_stream)
             if p.low is None:
-                _lib.check(getattr(self.lib, fwd)(C.byref(desc), C.byref(it), C.c_void_p(stream.cuda_stream)), fwd)
+                _lib.check(getattr(self.lib, items_fwd)(C.byref(desc), C.byref(it), sp), items_fwd)
             else:
-                sfwd = fwd.replace("_items_fwd", "_scaled_fwd")
-                _lib.check(getattr(self.lib, sfwd)(C.byref(desc), C.byref(it), C.byref(p.low.fs),
-                                                   C.c_void_p(stream.cuda_stream)), sfwd)
+                _lib.check(getattr(self.lib, scaled_fwd)(C.byref(desc), C.byref(it), C.byref(p.low.fs), sp),
+                           scaled_fwd)
             # the workspace now keeps the raw Flow of this call's pairs: no forward_* may reuse it
             self._flow_valid[p.key] = False
             if p.status is not None:
                 self._queue_status(p.key[3], stream)
-            if gate_cfg is None:
+            if not gated:
                 return
-            sp, k = C.c_void_p(stream.cuda_stream), esize
+            k = fmt.esize  # the copy kernel is byte-wise
             if glimit is not None:
-                sums, pc = sad[lo:lo + npairs].data_ptr(), pcodes[lo:lo + npairs].data_ptr()
-                if wide is None:
-                    _lib.check(self.lib.rrin_pair_sad_u8_len(p0, p1, stride, npairs, flen, sums, sp),
-                               "rrin_pair_sad_u8_len")
-                else:
-                    _lib.check(self.lib.rrin_pair_sad_u16_len(p0, p1, stride, npairs, flen, wide[0], wide[1], sums, sp),
-                               "rrin_pair_sad_u16_len")
-                _lib.check(self.lib.rrin_gate_from_sad_u8(sums, npairs, glimit, 2, pc, sp), "rrin_gate_from_sad_u8")
+                pc = pcodes[lo:lo + npairs].data_ptr()
+                self._gate_codes(fmt, p0, p1, stride, npairs, flen, sad[lo:lo + npairs].data_ptr(), False, glimit, 2,
+                                 pc, sp)
             else:
                 if d[-1] - d[0] + 1 == npairs:
                     pg = pair_gate[d[0]:d[-1] + 1]
@@ -1524,12 +1335,6 @@ class RRINEngine:
         self._run_parts(h, w, bounds, part, flow_scale)
         return out
 
-    def _item_frames(self, frames, what: str, rgb: bool, dtype=torch.uint8, layout: str = "nv12"):
-        """The two checked views of a ``[P+1, ...]`` frame stack (:meth:`_frames`)."""
-        if not isinstance(frames, torch.Tensor) or frames.dim() < 1 or frames.shape[0] < 2:
-            raise ValueError(f"{what} takes one stack of at least two frames")
-        return self._frames(frames[:-1], frames[1:], what, rgb=rgb, dtype=dtype, layout=layout)
-
     def interpolate_items_u8(self, frames: torch.Tensor, pair, t, streams: int | None = None, split=None,
                              scene_threshold=None, gate=None, prof=None, flow_scale: int = 1) -> torch.Tensor:
         """A batch of M items ``(pair[k], t[k])`` over one stack of 8-bit frames: ``frames`` uint8
@@ -1547,42 +1352,20 @@ class RRINEngine:
         duplicate, 2: a cut, else interpolate).  :attr:`last_gate` is then the ``[M]`` item codes
         (1: the first frame, 2: the second, 0: interpolated).  ``flow_scale`` is passed to the
         defining ``forward_u8`` (rrin_net_u8_scaled_fwd with the items)."""
-        flow_scale = check_flow_scale(flow_scale)
-        self._need_records("interpolate_items_u8")
-        f0, f1, h0, w0, s0 = self._item_frames(frames, "interpolate_items_u8", rgb=True)
-        pairs, ts = check_items(pair, t, f0.shape[0])
-        out = torch.empty((len(pairs), h0, w0, 3), dtype=torch.uint8, device=self.device)
-
-        def make(p0, p1, po, stride):
-            d = _lib.NetU8Desc()
-            d.f0, d.f1, d.img_stride, d.out_u8 = p0, p1, stride, po
-            d.h0, d.w0 = h0, w0
-            return d, d.net
-
-        return self._run_items(f0, f1, s0, h0, w0, pairs, ts, out, make, "rrin_net_u8_items_fwd", streams, split,
-                               prof, (scene_threshold, gate, 255, h0 * w0 * 3, None), flow_scale)
+        flow_scale = self._frame_call("interpolate_items_u8", flow_scale)
+        fmt = FrameFormat.u8()
+        return self._run_items(fmt, "interpolate_items_u8", frames, pair, t, streams, split, scene_threshold, gate,
+                               prof, flow_scale)
 
     def interpolate_items_u16(self, frames: torch.Tensor, pair, t, depth: int = 10, streams: int | None = None,
                               split=None, scene_threshold=None, gate=None, prof=None,
                               flow_scale: int = 1) -> torch.Tensor:
         """:meth:`interpolate_items_u8` on uint16 ``[P+1,H0,W0,3]`` frames of ``depth`` 9..16, defined
         by :meth:`forward_u16` (rrin_net_u16_items_fwd) with the same ``flow_scale``."""
-        flow_scale = check_flow_scale(flow_scale)
-        self._need_records("interpolate_items_u16")
-        depth = self._depth16(depth, 9, "interpolate_items_u16")
-        f0, f1, h0, w0, s0 = self._item_frames(frames, "interpolate_items_u16", rgb=True, dtype=torch.uint16)
-        pairs, ts = check_items(pair, t, f0.shape[0])
-        out = torch.empty((len(pairs), h0, w0, 3), dtype=torch.uint16, device=self.device)
-
-        def make(p0, p1, po, stride):
-            d = _lib.NetU16Desc()
-            d.f0, d.f1, d.img_stride, d.out_u16 = p0, p1, stride, po
-            d.h0, d.w0, d.depth = h0, w0, depth
-            return d, d.net
-
-        return self._run_items(f0, f1, s0, h0, w0, pairs, ts, out, make, "rrin_net_u16_items_fwd", streams,
-                               split, prof, (scene_threshold, gate, (1 << depth) - 1, h0 * w0 * 3, (depth, 0)),
-                               flow_scale)
+        flow_scale = self._frame_call("interpolate_items_u16", flow_scale)
+        fmt = FrameFormat.u16(depth, "interpolate_items_u16")
+        return self._run_items(fmt, "interpolate_items_u16", frames, pair, t, streams, split, scene_threshold, gate,
+                               prof, flow_scale)
 
     def interpolate_items_yuv(self, frames: torch.Tensor, pair, t, layout: str = "nv12", coef=None,
                               streams: int | None = None, split=None, scene_threshold=None, gate=None,
@@ -1591,26 +1374,10 @@ class RRINEngine:
         ``layout``, as :meth:`forward_yuv` takes them), defined by :meth:`forward_yuv` with the same
         ``layout``, ``coef`` and ``flow_scale`` (rrin_net_yuv_items_fwd); the gate on the frames'
         bytes as there."""
-        from . import yuv
-        flow_scale = check_flow_scale(flow_scale)
-        self._need_records("interpolate_items_yuv")
-        if layout not in yuv.ALL_LAYOUTS:
-            raise ValueError(f"layout must be one of {yuv.ALL_LAYOUTS}, got {layout!r}")
-        kc = _lib.YuvCoef(*yuv.as_coef(coef))
-        f0, f1, h0, w0, s0 = self._item_frames(frames, "interpolate_items_yuv", rgb=False, layout=layout)
-        pairs, ts = check_items(pair, t, f0.shape[0])
-        out = torch.empty((len(pairs), yuv.stack_rows(h0, layout), w0), dtype=torch.uint8, device=self.device)
-        frame = out.stride(0)
-
-        def make(p0, p1, po, stride):
-            d = _lib.NetYuvDesc()
-            d.f0, d.f1 = self._yuv_stack(p0, stride, h0, w0, layout), self._yuv_stack(p1, stride, h0, w0, layout)
-            d.out = self._yuv_stack(po, frame, h0, w0, layout)
-            d.coef, d.h0, d.w0 = kc, h0, w0
-            return d, d.net
-
-        return self._run_items(f0, f1, s0, h0, w0, pairs, ts, out, make, "rrin_net_yuv_items_fwd", streams,
-                               split, prof, (scene_threshold, gate, 255, frame, None), flow_scale)
+        flow_scale = self._frame_call("interpolate_items_yuv", flow_scale)
+        fmt = FrameFormat.yuv(layout, coef)
+        return self._run_items(fmt, "interpolate_items_yuv", frames, pair, t, streams, split, scene_threshold, gate,
+                               prof, flow_scale)
 
     def interpolate_items_yuv16(self, frames: torch.Tensor, pair, t, layout: str = "nv12", depth: int = 10,
                                 msb: bool = False, coef=None, streams: int | None = None, split=None,
@@ -1618,31 +1385,10 @@ class RRINEngine:
         """:meth:`interpolate_items_yuv` on 10- or 12-bit frames in 16-bit words, defined by
         :meth:`forward_yuv16` with the same ``layout``, ``depth``, ``msb``, ``coef`` and ``flow_scale``
         (rrin_net_yuv16_items_fwd)."""
-        from . import yuv
-        flow_scale = check_flow_scale(flow_scale)
-        self._need_records("interpolate_items_yuv16")
-        if layout not in yuv.ALL_LAYOUTS:
-            raise ValueError(f"layout must be one of {yuv.ALL_LAYOUTS}, got {layout!r}")
-        depth = yuv.check_depth16(depth)
-        shift = 16 - depth if msb else 0
-        kc = _lib.YuvCoef(*yuv.as_coef(coef, depth))
-        f0, f1, h0, w0, s0 = self._item_frames(frames, "interpolate_items_yuv16", rgb=False, dtype=torch.uint16,
-                                               layout=layout)
-        pairs, ts = check_items(pair, t, f0.shape[0])
-        out = torch.empty((len(pairs), yuv.stack_rows(h0, layout), w0), dtype=torch.uint16, device=self.device)
-        frame = out.stride(0)
-
-        def make(p0, p1, po, stride):
-            d = _lib.NetYuv16Desc()
-            d.f0 = self._yuv16_stack(p0, stride, h0, w0, layout, depth, shift)
-            d.f1 = self._yuv16_stack(p1, stride, h0, w0, layout, depth, shift)
-            d.out = self._yuv16_stack(po, frame, h0, w0, layout, depth, shift)
-            d.coef, d.h0, d.w0 = kc, h0, w0
-            return d, d.net
-
-        return self._run_items(f0, f1, s0, h0, w0, pairs, ts, out, make, "rrin_net_yuv16_items_fwd", streams,
-                               split, prof, (scene_threshold, gate, (1 << depth) - 1, frame, (depth, shift)),
-                               flow_scale)
+        flow_scale = self._frame_call("interpolate_items_yuv16", flow_scale)
+        fmt = FrameFormat.yuv16(layout, depth, msb, coef)
+        return self._run_items(fmt, "interpolate_items_yuv16", frames, pair, t, streams, split, scene_threshold, gate,
+                               prof, flow_scale)
 
     def unet_forward(self, x: torch.Tensor) -> torch.Tensor:
         """The single packed U-Net (engine built with one unit) on x [N,C,H,W]:
@@ -1772,23 +1518,22 @@ class RRINEngine:
         d.i0, d.i1, d.out = i0.data_ptr(), i1.data_ptr(), out.data_ptr()
         return d
 
-    def _launch(self, fwd, name: str, d, nd, p: Part, tag: str, reuse_flow, stream):
-        """Library entry ``fwd`` on descriptor d (nd: its rrin_net_desc) for part p on ``stream``.
-        ``tag`` names the path -- and for YUV its layout and matrix -- whose raw Flow the part's
-        workspace keeps afterwards: the Flow U-Net is skipped only for ``reuse_flow`` with the
+    def _launch(self, entries, d, nd, p: Part, tag: str, reuse_flow, stream):
+        """The library's forward on descriptor d (nd: its rrin_net_desc) for part p on ``stream``.
+        ``entries``: the names of the plain entry and, last, of its flow_scale sibling
+        (FLOAT_ENTRIES, or a frame format's ``entries``, whose ``_scaled_fwd`` also takes items: none
+        here).  ``tag`` names the path -- and for YUV its layout and matrix -- whose raw Flow the
+        part's workspace keeps afterwards: the Flow U-Net is skipped only for ``reuse_flow`` with the
         same tag, so no path takes another's pair for its own previous one.  A part with a second
-        plan (``p.low``: flow_scale > 1) goes to the entry's ``_scaled_fwd`` sibling, and its tag
-        carries the scale (:func:`rrin_amd.flowscale.flow_tag`)."""
+        plan (``p.low``: flow_scale > 1) goes to the ``_scaled_fwd`` entry, and its tag carries the
+        scale (:func:`rrin_amd.flowscale.flow_tag`)."""
+        name, extra = entries[0], ()
         if p.low is not None:
             tag = flow_tag(tag, p.low.fs.s)
-            name = name.replace("_fwd", "_scaled_fwd")
-            scaled, fs = getattr(self.lib, name), C.byref(p.low.fs)
-            if name == "rrin_net_scaled_fwd":
-                fwd = lambda dd, st: scaled(dd, fs, st)
-            else:  # a frame forward: no items
-                fwd = lambda dd, st: scaled(dd, None, fs, st)
+            name = entries[-1]
+            extra = (C.byref(p.low.fs),) if entries is FLOAT_ENTRIES else (None, C.byref(p.low.fs))
         nd.skip_flow = 1 if reuse_flow and self._flow_valid.get(p.key) == tag else 0
-        _lib.check(fwd(C.byref(d), C.c_void_p(stream.cuda_stream)), name)
+        _lib.check(getattr(self.lib, name)(C.byref(d), *extra, C.c_void_p(stream.cuda_stream)), name)
         self._flow_valid[p.key] = tag
         if p.status is not None:
             self._queue_status(p.key[3], stream)

@@ -40,6 +40,7 @@ import numpy as np
 import torch
 
 from . import metrics, yuv
+from .framefmt import check_depth, frame_stride
 
 MAX_ITEMS = 64   # RRIN_TRIPLET_MAX_ITEMS: items of one sampler call
 W_CHARB, W_L1, EPS = 1e-3, 1e-1, 1e-6   # train.py:105, losses.py:40
@@ -171,8 +172,7 @@ def _check_items(items, n_frames, h0, w0, ch, cw, block):
 
 
 def _depth_of(depth, layout, coef):
-    if isinstance(depth, bool) or not isinstance(depth, int) or not (depth == 8 or 9 <= depth <= 16):
-        raise ValueError(f"depth is 8 or 9..16, got {depth!r}")
+    check_depth(depth, 8, "depth is 8 or 9..16")
     if layout == "rgb":
         if coef is not None:
             raise ValueError("RGB frames take no colour coefficients")
@@ -227,10 +227,10 @@ def sample_triplets(frames, items, crop, layout="i420", coef=None, depth=8, msb=
         return _sample_ref(frames, items, ch, cw, layout, coef, depth, msb)
     from . import _lib
     lib = _lib.lib()
-    stride = metrics._frame_stride(frames)
+    stride = frame_stride(frames)
     if stride is None:
         frames = frames.contiguous()
-        stride = metrics._frame_stride(frames)
+        stride = frame_stride(frames)
     k = len(items)
     arr = (_lib.Plane * 3)(*[_lib.Plane(off, pitch, step, h, w, 0) for off, step, pitch, h, w in planes])
     flat = (C.c_int32 * (6 * k))(*[v for it in items for v in it])
@@ -259,9 +259,15 @@ class Clip:
         self.width, self.height, self.tag, self.truncated = width, height, tag, truncated
 
     @property
+    def bit_depth(self):
+        """``depth``, under the name a ``y4m.Reader`` gives it."""
+        return self.depth
+
+    @property
     def kw(self):
         """The depth arguments of the 16-bit frame paths ({} at 8 bits)."""
-        return {"depth": self.depth, "msb": False} if self.depth > 8 else {}
+        from .convert import frame_path_of
+        return frame_path_of(self)[1]
 
 
 def read_clip(src, device, max_bytes=8 << 30):
@@ -330,7 +336,9 @@ def validate(model, clip, first=0, hold=2, batch=4, coef=None):
     planes = metrics.planes_of("yuv", clip.height, clip.width, clip.layout)
     counts = [p[3] * p[4] for p in planes]
     maxval = (1 << clip.depth) - 1
-    name = "frame_metrics_yuv16" if deep else "frame_metrics_yuv"
+    from .convert import frame_path_of
+    suffix = frame_path_of(clip)[0]
+    name = "frame_metrics_" + suffix
     measure = getattr(model, name) if on_gpu else getattr(metrics, name)
 
     def take(idx):
@@ -344,7 +352,7 @@ def validate(model, clip, first=0, hold=2, batch=4, coef=None):
             part = items[lo:lo + batch]
             truth = take([f for f, _, _ in part])
             if on_gpu:
-                fwd = model.interpolate_items_yuv16 if deep else model.interpolate_items_yuv
+                fwd = getattr(model, "interpolate_items_" + suffix)
                 p0 = part[0][1]
                 out = fwd(inputs[p0:part[-1][1] + 2], [p - p0 for _, p, _ in part], [float(t) for _, _, t in part],
                           layout=clip.layout, coef=coef, **clip.kw)
@@ -370,8 +378,7 @@ def excluded_pairs(model, clip, n, scene_threshold):
         return [], []
     f0, f1 = clip.frames[:n - 1], clip.frames[1:n]
     if clip.frames.device.type == "cuda":
-        sad = (model.pair_stats_yuv16(f0, f1, layout=clip.layout, **clip.kw) if clip.depth > 8
-               else model.pair_stats_yuv(f0, f1, layout=clip.layout))
+        sad = getattr(model, "pair_stats_" + convert.frame_path_of(clip)[0])(f0, f1, layout=clip.layout, **clip.kw)
     else:
         a, b = metrics.samples_of(f0, clip.depth, 0), metrics.samples_of(f1, clip.depth, 0)
         sad = (a - b).abs().reshape(n - 1, -1).sum(1)

@@ -43,6 +43,7 @@ from fractions import Fraction
 import torch
 
 from . import yuv
+from .framefmt import FrameFormat, check_depth, frame_stride
 
 RGB_NAMES = ("r", "g", "b")
 YUV_NAMES = ("y", "u", "v")
@@ -165,16 +166,6 @@ def _check_pair(a, b, dtype, dims):
         raise RuntimeError(f"frames on {a.device} / {b.device}")
 
 
-def _frame_stride(f: torch.Tensor):
-    """Elements between the dense frames of a stack, or None if it needs a copy."""
-    dense = 1
-    for d in range(f.dim() - 1, 0, -1):
-        if f.shape[d] > 1 and f.stride(d) != dense:
-            return None
-        dense *= f.shape[d]
-    return dense if f.shape[0] == 1 else (f.stride(0) if f.stride(0) >= dense else None)
-
-
 def _host_metrics(a, b, planes, depth, shift, ssim):
     maxval = (1 << depth) - 1
     sse, val = [], []
@@ -192,13 +183,13 @@ def device_metrics(a, b, planes, depth, shift, ssim, workspace=None):
     many bytes (default: a fresh one per call)."""
     from . import _lib
     lib = _lib.lib()
-    sa, sb = _frame_stride(a), _frame_stride(b)
+    sa, sb = frame_stride(a), frame_stride(b)
     if sa is None:
         a = a.contiguous()
-        sa = _frame_stride(a)
+        sa = frame_stride(a)
     if sb is None:
         b = b.contiguous()
-        sb = _frame_stride(b)
+        sb = frame_stride(b)
     n, p = a.shape[0], len(planes)
     arr = (_lib.Plane * p)(*[_lib.Plane(off, pitch, step, h, w, 0) for off, step, pitch, h, w in planes])
     flags = 1 if ssim else 0
@@ -234,48 +225,43 @@ def _metrics(a, b, planes, depth, shift, ssim, names, workspace=None):
     return FrameMetrics(sse, val, [pl[3] * pl[4] for pl in planes], (1 << depth) - 1, names)
 
 
-def _depth(depth, lo):
-    if isinstance(depth, bool) or not isinstance(depth, int) or not lo <= depth <= 16:
-        raise ValueError(f"depth must be an int in {lo}..16, got {depth!r}")
-    return depth
+def _frame_metrics(fmt: FrameFormat, a, b, ssim, workspace) -> FrameMetrics:
+    """The metrics of two stacks of ``fmt`` (only its layout, depth and shift matter here)."""
+    _check_pair(a, b, fmt.dtype, 4 if fmt.layout is None else 3)
+    if fmt.layout is None:
+        if a.shape[3] != 3:
+            raise ValueError(f"expected [N,H0,W0,3] frames, got {tuple(a.shape)}")
+        h0, w0 = a.shape[1], a.shape[2]
+    else:
+        h0, w0 = yuv.stack_size(a, fmt.layout)
+    names = RGB_NAMES if fmt.layout is None else YUV_NAMES
+    return _metrics(a, b, fmt.planes(h0, w0), fmt.depth, fmt.shift, ssim, names, workspace)
 
 
 def frame_metrics_u8(a, b, ssim=True, _workspace=None) -> FrameMetrics:
     """Per frame and channel of two uint8 ``[N,H0,W0,3]`` RGB stacks (``a`` typically a forward's
     output, ``b`` the truth): squared error, SSIM, PSNR.  Device stacks stay on the device and
     nothing synchronises; every frame dense, any stride between frames (views need no copy)."""
-    _check_pair(a, b, torch.uint8, 4)
-    if a.shape[3] != 3:
-        raise ValueError(f"expected [N,H0,W0,3] frames, got {tuple(a.shape)}")
-    return _metrics(a, b, planes_of("rgb", a.shape[1], a.shape[2]), 8, 0, ssim, RGB_NAMES, _workspace)
+    return _frame_metrics(FrameFormat.u8(), a, b, ssim, _workspace)
 
 
 def frame_metrics_yuv(a, b, layout="nv12", ssim=True, _workspace=None) -> FrameMetrics:
     """:func:`frame_metrics_u8` per Y, U and V plane of two uint8 YUV stacks of ``layout``
     (:mod:`rrin_amd.yuv`: ``[N, 3*H0//2, W0]``, ``[N, 2*H0, W0]`` or ``[N, 3*H0, W0]``)."""
-    _check_pair(a, b, torch.uint8, 3)
-    h0, w0 = yuv.stack_size(a, layout)
-    return _metrics(a, b, planes_of("yuv", h0, w0, layout), 8, 0, ssim, YUV_NAMES, _workspace)
+    return _frame_metrics(FrameFormat.samples(layout), a, b, ssim, _workspace)
 
 
 def frame_metrics_u16(a, b, depth=10, ssim=True, _workspace=None) -> FrameMetrics:
     """:func:`frame_metrics_u8` for uint16 ``[N,H0,W0,3]`` RGB stacks of ``depth`` 9..16 (samples
     ``min(word, maxval)``)."""
-    depth = _depth(depth, 9)
-    _check_pair(a, b, torch.uint16, 4)
-    if a.shape[3] != 3:
-        raise ValueError(f"expected [N,H0,W0,3] frames, got {tuple(a.shape)}")
-    return _metrics(a, b, planes_of("rgb", a.shape[1], a.shape[2]), depth, 0, ssim, RGB_NAMES, _workspace)
+    return _frame_metrics(FrameFormat.samples(None, check_depth(depth)), a, b, ssim, _workspace)
 
 
 def frame_metrics_yuv16(a, b, layout="nv12", depth=10, msb=False, ssim=True, _workspace=None) -> FrameMetrics:
     """:func:`frame_metrics_yuv` for uint16 stacks of ``depth`` 9..16; ``msb=True`` reads the sample
     from the word's high bits (``shift = 16 - depth``)."""
-    depth = _depth(depth, 9)
-    _check_pair(a, b, torch.uint16, 3)
-    h0, w0 = yuv.stack_size(a, layout)
-    return _metrics(a, b, planes_of("yuv", h0, w0, layout), depth, 16 - depth if msb else 0, ssim, YUV_NAMES,
-                    _workspace)
+    depth = check_depth(depth)
+    return _frame_metrics(FrameFormat.samples(layout, depth, 16 - depth if msb else 0), a, b, ssim, _workspace)
 
 
 # ---- the hold-out schedule -----------------------------------------------------------------------

@@ -116,6 +116,18 @@ class Net(nn.Module):
         return [eng.forward(input0, input1, t, reuse_flow=(k > 0), streams=self.streams, flow_scale=flow_scale)
                 for k, t in enumerate(ts)]
 
+    def _frames(self, path, f0, f1, t, many, **kw):
+        """``forward_<path>`` (one ``t``) or, ``many``, ``interpolate_<path>`` (a list ``t``) of the frame
+        paths: the engine's ``forward_<path>`` once, or for every t of the list with the Flow U-Net (and
+        the gate's sums) of the first call reused by the others."""
+        if torch.is_grad_enabled():
+            what = ("interpolate_" if many else "forward_") + path
+            raise RuntimeError(f"rrin_amd.Net.{what} is inference-only: use torch.no_grad()")
+        fwd = getattr(self.engine(), "forward_" + path)
+        if not many:
+            return fwd(f0, f1, t, streams=self.streams, **kw)
+        return [fwd(f0, f1, v, reuse_flow=(k > 0), streams=self.streams, **kw) for k, v in enumerate(t)]
+
     def forward_u8(self, f0, f1, t=0.5, scene_threshold=None, gate=None, flow_scale=1):
         """``forward`` on 8-bit frames of any size: uint8 ``[N,H0,W0,3]`` in and out, on the
         device; bit for bit ``convert.load_frame`` -> ``forward`` -> ``convert.to_uint8_image``
@@ -127,25 +139,19 @@ class Net(nn.Module):
         on), decided and applied on the device (``RRINEngine.forward_u8``).  The network still
         runs for a gated pair: skipping it would need a host sync.  No threshold has been
         validated on real footage; :attr:`last_gate` reports what a call decided."""
-        if torch.is_grad_enabled():
-            raise RuntimeError("rrin_amd.Net.forward_u8 is inference-only: use torch.no_grad()")
-        return self.engine().forward_u8(f0, f1, t, streams=self.streams, scene_threshold=scene_threshold,
-                                        gate=gate, flow_scale=flow_scale)
+        return self._frames("u8", f0, f1, t, False, scene_threshold=scene_threshold, gate=gate,
+                            flow_scale=flow_scale)
 
     def interpolate_u8(self, f0, f1, ts, scene_threshold=None, gate=None, flow_scale=1):
         """``[forward_u8(f0, f1, t) for t in ts]`` with the Flow U-Net computed once, as
         :meth:`interpolate`; with ``scene_threshold`` the pairs' sums of absolute differences are
         computed once too (the cut code depends on t, so :attr:`last_gate` is that of ``ts[-1]``)."""
-        if torch.is_grad_enabled():
-            raise RuntimeError("rrin_amd.Net.interpolate_u8 is inference-only: use torch.no_grad()")
-        eng = self.engine()
-        return [eng.forward_u8(f0, f1, t, reuse_flow=(k > 0), streams=self.streams,
-                               scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
-                for k, t in enumerate(ts)]
+        return self._frames("u8", f0, f1, ts, True, scene_threshold=scene_threshold, gate=gate,
+                            flow_scale=flow_scale)
 
     def pair_stats_u8(self, f0, f1):
         """int64 device tensor ``[N]``: the sum of absolute byte differences of every pair of two
-        uint8 ``[N,H0,W0,3]`` stacks, exact (rrin_pair_sad_u8) -- what ``scene_threshold`` compares
+        uint8 ``[N,H0,W0,3]`` stacks, exact (rrin_pair_sad_u8_len) -- what ``scene_threshold`` compares
         with ``floor(threshold * H0*W0*3)``, for callers who pass their own ``gate``."""
         return self.engine().pair_stats_u8(f0, f1)
 
@@ -164,21 +170,15 @@ class Net(nn.Module):
         frame's YUV bytes unchanged.  ``scene_threshold`` is a mean absolute difference over luma
         and chroma bytes, so not the same number as the RGB path's; no value has been validated
         on real footage."""
-        if torch.is_grad_enabled():
-            raise RuntimeError("rrin_amd.Net.forward_yuv is inference-only: use torch.no_grad()")
-        return self.engine().forward_yuv(f0, f1, t, layout=layout, coef=coef, streams=self.streams,
-                                         scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
+        return self._frames("yuv", f0, f1, t, False, layout=layout, coef=coef,
+                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
 
     def interpolate_yuv(self, f0, f1, ts, layout="nv12", coef=None, scene_threshold=None, gate=None, flow_scale=1):
         """``[forward_yuv(f0, f1, t) for t in ts]`` with the Flow U-Net (and, with
         ``scene_threshold``, the pairs' sums of absolute differences) computed once, as
         :meth:`interpolate_u8`."""
-        if torch.is_grad_enabled():
-            raise RuntimeError("rrin_amd.Net.interpolate_yuv is inference-only: use torch.no_grad()")
-        eng = self.engine()
-        return [eng.forward_yuv(f0, f1, t, layout=layout, coef=coef, reuse_flow=(k > 0), streams=self.streams,
-                                scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
-                for k, t in enumerate(ts)]
+        return self._frames("yuv", f0, f1, ts, True, layout=layout, coef=coef,
+                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
 
     def pair_stats_yuv(self, f0, f1, layout="nv12"):
         """int64 device tensor ``[N]``: the sum of absolute byte differences, luma and chroma, of
@@ -193,20 +193,14 @@ class Net(nn.Module):
         ``convert.frames_float_to_u16`` (``RRINEngine.forward_u16``).  Inference-only; not for
         ``precision='fp32_planar'``.  The scene gate is ``forward_u8``'s with ``scene_threshold`` a
         mean absolute sample difference in [0, maxval]."""
-        if torch.is_grad_enabled():
-            raise RuntimeError("rrin_amd.Net.forward_u16 is inference-only: use torch.no_grad()")
-        return self.engine().forward_u16(f0, f1, t, depth=depth, streams=self.streams,
-                                         scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
+        return self._frames("u16", f0, f1, t, False, depth=depth, scene_threshold=scene_threshold, gate=gate,
+                            flow_scale=flow_scale)
 
     def interpolate_u16(self, f0, f1, ts, depth=10, scene_threshold=None, gate=None, flow_scale=1):
         """``[forward_u16(f0, f1, t, depth) for t in ts]`` with the Flow U-Net (and the pairs' sums
         of absolute differences) computed once, as :meth:`interpolate_u8`."""
-        if torch.is_grad_enabled():
-            raise RuntimeError("rrin_amd.Net.interpolate_u16 is inference-only: use torch.no_grad()")
-        eng = self.engine()
-        return [eng.forward_u16(f0, f1, t, depth=depth, reuse_flow=(k > 0), streams=self.streams,
-                                scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
-                for k, t in enumerate(ts)]
+        return self._frames("u16", f0, f1, ts, True, depth=depth, scene_threshold=scene_threshold, gate=gate,
+                            flow_scale=flow_scale)
 
     def pair_stats_u16(self, f0, f1, depth=10):
         """int64 device tensor ``[N]``: the exact sum of absolute sample differences (samples
@@ -221,23 +215,15 @@ class Net(nn.Module):
         ``yuv.rgb16_to_yuv420(forward_u16(yuv.yuv420_to_rgb16(f0), yuv.yuv420_to_rgb16(f1), t,
         depth))`` (``RRINEngine.forward_yuv16``); ``coef`` None is BT.709 limited range at this
         depth.  Other depths raise.  Inference-only; not for ``precision='fp32_planar'``."""
-        if torch.is_grad_enabled():
-            raise RuntimeError("rrin_amd.Net.forward_yuv16 is inference-only: use torch.no_grad()")
-        return self.engine().forward_yuv16(f0, f1, t, layout=layout, depth=depth, msb=msb, coef=coef,
-                                           streams=self.streams, scene_threshold=scene_threshold, gate=gate,
-                                           flow_scale=flow_scale)
+        return self._frames("yuv16", f0, f1, t, False, layout=layout, depth=depth, msb=msb, coef=coef,
+                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
 
     def interpolate_yuv16(self, f0, f1, ts, layout="nv12", depth=10, msb=False, coef=None, scene_threshold=None,
                           gate=None, flow_scale=1):
         """``[forward_yuv16(f0, f1, t, ...) for t in ts]`` with the Flow U-Net (and the pairs' sums of
         absolute differences) computed once, as :meth:`interpolate_yuv`."""
-        if torch.is_grad_enabled():
-            raise RuntimeError("rrin_amd.Net.interpolate_yuv16 is inference-only: use torch.no_grad()")
-        eng = self.engine()
-        return [eng.forward_yuv16(f0, f1, t, layout=layout, depth=depth, msb=msb, coef=coef, reuse_flow=(k > 0),
-                                  streams=self.streams, scene_threshold=scene_threshold, gate=gate,
-                                  flow_scale=flow_scale)
-                for k, t in enumerate(ts)]
+        return self._frames("yuv16", f0, f1, ts, True, layout=layout, depth=depth, msb=msb, coef=coef,
+                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
 
     def pair_stats_yuv16(self, f0, f1, depth=10, msb=False, layout="nv12"):
         """int64 device tensor ``[N]``: the exact sum of absolute differences of the samples

@@ -10,7 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rrin_amd import Net  # noqa: E402
-from rrin_amd.engine import t_coefficients  # noqa: E402
+from rrin_amd.engine import FLOAT_ENTRIES, t_coefficients  # noqa: E402
 from rrin_amd.synthetic import keyed_state_dict, synthetic_batch  # noqa: E402
 
 
@@ -54,7 +54,7 @@ def main():
                     st = main_s if j == 0 else side
                     ev[j][k].record(st)
                     d = eng._float_desc(ps[j], i0[lo:hi], i1[lo:hi], out[lo:hi], coef[lo:hi])
-                    eng._launch(eng.lib.rrin_net_fwd, "rrin_net_fwd", d, d, ps[j], "f32", False, st)
+                    eng._launch(FLOAT_ENTRIES, d, d, ps[j], "f32", False, st)
         torch.cuda.synchronize()
         return sum(2 * (b - a) / (ev[j][a].elapsed_time(ev[j][b]) * 1e-3) for j in range(2))
 
