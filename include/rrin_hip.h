@@ -984,6 +984,74 @@ int64_t rrin_tloss_workspace_bytes(int64_t count);
 int rrin_tloss(const float* out, const float* target, int64_t count, int32_t n, double w_charb, double w_l1,
                float eps, double* sums, float* grad, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- An extra plane (alpha, depth, ID) through the byte-frame forwards (csrc/plane.hip, net.hip) --
+ * History: added after ABI 25 without a new version number -- a new struct passed to new entry
+ * points only, no existing struct or entry point changes, so RRIN_ABI_VERSION stays 25; a caller
+ * finds out whether a build has them by looking the symbols up.
+ *
+ * One single-channel image per input frame, in the frames' element type, carried to time t by the
+ * picture's own motion (rrin_amd/plane.py is the definition): with A0 / A1 the planes padded as the
+ * frames are (edge replication on top and on the right) and divided by maxval,
+ *   at0 = warp(A0, Flow_t_0)   at1 = warp(A1, Flow_t_1)      the refined flows (model.py:44-45)
+ *   A_t = clamp((w1 at0 + w2 at1) / (w1 + w2 + 1e-8), 0, 1)   w1, w2: the picture's mask weights
+ * stored as (int)(A_t * maxval), the crop only.  The final U-Net does not touch the plane.
+ *
+ * rrin_aux_plane (the name rrin_plane is the metrics' plane description): a0 / a1 the planes of the
+ * pairs' first / second frames, [frames][h0] rows of in_pitch elements, in_stride elements between
+ * frames (two views of one [frames + 1] stack are fine); out [n][h0] rows of out_pitch elements,
+ * out_stride between frames.  depth 8: uint8 elements (shift 0); depth 9..16: uint16 words at even
+ * addresses, a sample is min(word >> shift, 2^depth - 1) and is stored << shift,
+ * 0 <= shift <= 16 - depth.  scratch: rrin_plane_scratch_bytes(n, h, w) bytes of device memory, 16 per
+ * padded pixel: fp32 [n][2][h][w] at0 / at1, then fp32 [n][2][h][w] mask logits.
+ *
+ * rrin_plane_warp_h8: at0 / at1 of n images into the scratch, from the flows that the REFINE head
+ * stored in channels 6-9 of g16 (read as the record format stores them) and the same warp_taps as
+ * the picture's backwarp: bilinear, zeros outside the padded h x w = g16's size, align_corners =
+ * False; padded pixel (y, x) is plane sample (max(y - top, 0), min(x, w0 - 1)), top = h - h0.
+ * pair_map NULL: image k reads frame k (n_pairs == n); else frame clamp(pair_map[k], 0, n_pairs - 1).
+ * rrin_plane_blend_h8: A_t of n images of padded size h x w from the scratch (at0 / at1 and the two
+ * mask logits per pixel, as the MASK head's raw_out wrote them) with coef [n][8] (rrin_net_desc.coef),
+ * quantised into the crop of out.  status: optional fp16 range flag; where it is set and prec is
+ * F16X3 or F16 every sample is stored as 0, as the FINAL head stores its bytes.  Padding pixels and
+ * elements between rows or frames of out are not written.
+ * Both: a null pointer, a prec that is no record precision, depth outside 8..16 or shift outside
+ * 0..16 - depth (depth 8: shift 0), an odd word address, a pitch below w0, a stride below h0 * pitch
+ * with more than one frame, scratch_bytes too small, n_pairs outside [1, n] or != n without a map:
+ * RRIN_E_ARG; n, h0, w0 < 1, h0 > h, w0 > w, a g16 that fails the layout checks: RRIN_E_SHAPE.
+ * Validated before any launch.
+ *
+ * rrin_net_*_plane_fwd: the frame forwards with three nullable companions.  items NULL: a plain
+ * forward, else an item forward; fs NULL: flow_scale 1, else the rrin_net_*_scaled_fwd call; plane
+ * NULL: exactly those calls.  With a plane the forward launches rrin_plane_warp_h8 behind the REFINE
+ * head (the MASK head overwrites g16 channels 6-8, so the refined flows are gone by the time the
+ * mask is known), points the MASK head's raw_out into the scratch and launches rrin_plane_blend_h8
+ * behind it; nothing else changes, the frames are the same bits.  The planes hold the frames'
+ * n (items: n_pairs) and the output net.n images.  Refused with RRIN_E_ARG before any launch:
+ * RRIN_PREC_F32, a plane whose depth is not the frames', net.taps, and what the kernels refuse. */
+typedef struct rrin_aux_plane {
+  const void* a0;
+  const void* a1;
+  void* out;
+  int64_t in_stride, out_stride; /* elements between frames                              */
+  int32_t in_pitch, out_pitch;   /* elements between rows                                */
+  int32_t depth, shift;
+  void* scratch;
+  int64_t scratch_bytes;
+} rrin_aux_plane;
+int64_t rrin_plane_scratch_bytes(int32_t n, int32_t h, int32_t w);
+int rrin_plane_warp_h8(const rrin_h8* g16, const rrin_aux_plane* plane, int32_t n, int32_t h0, int32_t w0,
+                       const int32_t* pair_map, int32_t n_pairs, int32_t prec, void* stream);
+int rrin_plane_blend_h8(const rrin_aux_plane* plane, const float* coef, int32_t n, int32_t h, int32_t w, int32_t h0,
+                        int32_t w0, int32_t prec, const int32_t* status, void* stream);
+int rrin_net_u8_plane_fwd(const rrin_net_u8_desc* d, const rrin_items* items, const rrin_flow_scale* fs,
+                          const rrin_aux_plane* plane, void* stream);
+int rrin_net_u16_plane_fwd(const rrin_net_u16_desc* d, const rrin_items* items, const rrin_flow_scale* fs,
+                           const rrin_aux_plane* plane, void* stream);
+int rrin_net_yuv_plane_fwd(const rrin_net_yuv_desc* d, const rrin_items* items, const rrin_flow_scale* fs,
+                           const rrin_aux_plane* plane, void* stream);
+int rrin_net_yuv16_plane_fwd(const rrin_net_yuv16_desc* d, const rrin_items* items, const rrin_flow_scale* fs,
+                             const rrin_aux_plane* plane, void* stream);
+
 /* ---- Training path (autograd): NCHW fp32 kernels ------------------------- */
 /* With autograd on (the reference trains through Net.forward, train.py:98, and
  * loss.backward(), train.py:144) rrin_amd.train wraps these in autograd

@@ -47,6 +47,10 @@ def build_parser():
                     help="estimate the flow on frames reduced by this factor and scale it up (large frames, large "
                          "motion); warp, mask and refinement stay at full size.  Quality is not validated: judge "
                          "it with `evaluate --flow_scale`")
+    cv.add_argument("--alpha", action="store_true", default=False,
+                    help="image folders: read the frames as RGBA and carry the alpha plane along with the picture's "
+                         "own motion; the interpolated frames are RGBA PNGs.  RGB is taken as stored (no premultiply); "
+                         "one GPU only.  Without it a matte is dropped")
     cv.add_argument("--y4m_in", type=str, default=None, metavar="PATH|-",
                     help="read a Y4M stream (4:2:0, 4:2:2 or 4:4:4 of 8, 10 or 12 bits; \"-\": stdin, e.g. from "
                          "ffmpeg -f yuv4mpegpipe) instead "

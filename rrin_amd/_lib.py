@@ -180,6 +180,14 @@ class Plane(C.Structure):
                 ("pad", C.c_int32)]
 
 
+class AuxPlane(C.Structure):
+    """rrin_aux_plane: the extra plane (alpha, depth, ID) of a byte-frame forward (rrin_amd.plane); strides and
+    pitches in elements, ``scratch`` of rrin_plane_scratch_bytes."""
+    _fields_ = [("a0", C.c_void_p), ("a1", C.c_void_p), ("out", C.c_void_p), ("in_stride", C.c_int64),
+                ("out_stride", C.c_int64), ("in_pitch", C.c_int32), ("out_pitch", C.c_int32), ("depth", C.c_int32),
+                ("shift", C.c_int32), ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
+
+
 class TConvDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
                 ("mode", C.c_int32), ("leaky", C.c_int32), ("slope", C.c_float), ("x", C.c_void_p),
@@ -297,6 +305,19 @@ SIGNATURES = {
                                           C.c_void_p]),
     "rrin_net_yuv16_scaled_fwd": (C.c_int, [C.POINTER(NetYuv16Desc), C.POINTER(Items), C.POINTER(FlowScale),
                                             C.c_void_p]),
+    "rrin_plane_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "rrin_plane_warp_h8": (C.c_int, [C.POINTER(H8), C.POINTER(AuxPlane), C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_int32, C.c_int32, C.c_void_p]),
+    "rrin_plane_blend_h8": (C.c_int, [C.POINTER(AuxPlane), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rrin_net_u8_plane_fwd": (C.c_int, [C.POINTER(NetU8Desc), C.POINTER(Items), C.POINTER(FlowScale),
+                                        C.POINTER(AuxPlane), C.c_void_p]),
+    "rrin_net_u16_plane_fwd": (C.c_int, [C.POINTER(NetU16Desc), C.POINTER(Items), C.POINTER(FlowScale),
+                                         C.POINTER(AuxPlane), C.c_void_p]),
+    "rrin_net_yuv_plane_fwd": (C.c_int, [C.POINTER(NetYuvDesc), C.POINTER(Items), C.POINTER(FlowScale),
+                                         C.POINTER(AuxPlane), C.c_void_p]),
+    "rrin_net_yuv16_plane_fwd": (C.c_int, [C.POINTER(NetYuv16Desc), C.POINTER(Items), C.POINTER(FlowScale),
+                                           C.POINTER(AuxPlane), C.c_void_p]),
     "rrin_gate_items_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p]),
     "rrin_gate_frames_items_u8_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,

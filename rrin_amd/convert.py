@@ -88,6 +88,18 @@ def load_frame_u8(path):
                                           "filetype": os.path.splitext(path)[1], "path": path}
 
 
+def load_frame_rgba(path):
+    """:func:`load_frame_u8` with the alpha plane: the raw uint8 [H,W,4] frame (PIL RGBA; a file without
+    alpha gets 255 everywhere) for ``interpolate_folder(alpha=True)``, whose outputs are PNGs."""
+    from PIL import Image
+    with Image.open(path) as im:
+        arr = np.asarray(im.convert("RGBA"), dtype=np.uint8)
+    h, w = arr.shape[:2]
+    top, _ = pad_amounts(w, h)
+    return torch.from_numpy(arr.copy()), {"width": w, "height": h, "top": top, "out_filetype": ".png",
+                                          "filetype": os.path.splitext(path)[1], "path": path}
+
+
 def frames_u8_to_float(frames: torch.Tensor, flow_scale: int = 1) -> torch.Tensor:
     """The input mapping of the byte path in plain torch: uint8 [...,H0,W0,3] -> float32
     [...,3,H,W] with H, W the next multiples of 16 (of 16 * ``flow_scale``), edge-replicated on top
@@ -235,7 +247,8 @@ class _Reader:
 
 
 def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None, writers=4, log=print,
-                       rank=0, world=1, group=None, gather=True, u8="auto", scene_threshold=None, flow_scale=1):
+                       rank=0, world=1, group=None, gather=True, u8="auto", scene_threshold=None, flow_scale=1,
+                       alpha=False):
     """Interpolate every consecutive pair of frames in ``src`` into ``dest``.
 
     ``flow_scale`` 2 or 4 (byte pipeline only; :mod:`rrin_amd.flowscale`) is passed to
@@ -269,7 +282,14 @@ def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None,
     (``Net.forward_u8``; the rule is ``scene_gate_codes``).  The model's ``last_gate`` codes of
     every step -- those of ``ts[-1]``, where t >= 0.5 makes a cut code 2 and leaves 1 to the
     duplicates -- come back with the step's output copy, and the final log line counts both.  No
-    threshold has been validated on real footage, hence no default."""
+    threshold has been validated on real footage, hence no default.
+
+    ``alpha=True`` (byte pipeline on one device only; default off: frames are read as RGB and a matte is
+    dropped, as before) carries the alpha plane along (:mod:`rrin_amd.plane`): frames are read as RGBA
+    (a file without alpha gets 255), RGB and A go up in the same pinned stack,
+    ``model.interpolate_u8(..., plane=(a0, a1))`` returns the interpolated matte with every frame, and
+    the interpolated frames are written as RGBA PNGs.  RGB is taken as stored (no premultiply).  Raises
+    ValueError without the byte pipeline (``u8=False``, or no device) and for ``world > 1``."""
     if u8 == "auto":
         u8 = (device is not None and hasattr(model, "interpolate_u8")
               and getattr(model, "precision", None) != "fp32_planar")
@@ -277,6 +297,10 @@ def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None,
         raise ValueError("u8=True needs a model with interpolate_u8(f0, f1, ts)")
     if scene_threshold is not None and not u8:
         raise ValueError("scene_threshold needs the byte pipeline (u8): the gate works on 8-bit frames")
+    if alpha and not u8:
+        raise ValueError("alpha needs the byte pipeline (u8) on a ROCm device: the plane is carried by forward_u8")
+    if alpha and world > 1:
+        raise ValueError("alpha is not covered by multi-GPU sharding (world > 1)")
     from .flowscale import check_flow_scale
     if check_flow_scale(flow_scale) > 1 and not u8:
         raise ValueError("flow_scale needs the byte pipeline (u8): the float pipeline pads to 16 only")
@@ -316,7 +340,8 @@ def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None,
             os.path.join(dest, f"{img_count0:09d}{os.path.splitext(frames[first_pair])[1]}"))
     t0 = time.time()
     steps = max((b - a + batch - 1) // batch for a, b in shards)
-    reader = _Reader(src, frames, lo, hi, 2 * batch + 2, load_frame_u8 if u8 else load_frame) if hi > lo else None
+    loader = load_frame_rgba if alpha else load_frame_u8 if u8 else load_frame
+    reader = _Reader(src, frames, lo, hi, 2 * batch + 2, loader) if hi > lo else None
     prev = reader.get() if reader else None
     pending = []
     for s_ in range(steps):
@@ -339,7 +364,12 @@ def interpolate_folder(model, src, dest, sf, batch=4, resume=False, device=None,
             if device is not None:
                 stack = stack.to(device, non_blocking=True)
             with torch.no_grad():
-                outs = model.interpolate_u8(stack[:-1], stack[1:], ts, **gate_kw, **scale_kw)
+                if alpha:  # [n,H,W,4] -> dense RGB frames and the matte, on the device
+                    rgb, a = stack[..., :3].contiguous(), stack[..., 3].contiguous()
+                    outs = [torch.cat((f, p.unsqueeze(-1)), -1) for f, p in
+                            model.interpolate_u8(rgb[:-1], rgb[1:], ts, plane=(a[:-1], a[1:]), **gate_kw, **scale_kw)]
+                else:
+                    outs = model.interpolate_u8(stack[:-1], stack[1:], ts, **gate_kw, **scale_kw)
             if gate_kw:
                 gate_codes.append(_codes_to_host(getattr(model, "last_gate", None), nloc, device))
         elif nloc:
@@ -453,8 +483,8 @@ def _retire(item, sf, dest, put, model=None):
         model.check_range(wait=False)  # fp16-stored precisions: raise instead of writing NaN frames
     for p, (m0, m1, base) in enumerate(zip(metas0, metas1, bases)):
         for i in range(sf):
-            path = os.path.join(dest, f"{base + i + 1:09d}{m0['filetype']}")
-            if host[i].dtype == torch.uint8:  # the byte pipeline: already cropped [H,W,3] frames
+            path = os.path.join(dest, f"{base + i + 1:09d}{m0.get('out_filetype', m0['filetype'])}")
+            if host[i].dtype == torch.uint8:  # the byte pipeline: already cropped [H,W,3] (alpha: [H,W,4]) frames
                 put(lambda t, path: save_image(t.numpy(), path), host[i][p], path)
                 continue
             put(lambda t, m, path: save_image(to_uint8_image(t, m), path), host[i][p], m0, path)
@@ -1096,7 +1126,7 @@ def convert(args):
     t = time.time()
     interpolate_folder(net, src, dest, args.sf, batch=getattr(args, "batch", 4), resume=args.resume, device=dev,
                        rank=rank, world=world, scene_threshold=getattr(args, "scene_threshold", None),
-                       flow_scale=getattr(args, "flow_scale", 1))
+                       flow_scale=getattr(args, "flow_scale", 1), alpha=getattr(args, "alpha", False))
     if world > 1:
         dist.barrier()
     print("end=", time.time() - t)

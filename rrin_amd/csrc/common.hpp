@@ -344,6 +344,12 @@ int pack_g16_yuv16_items(const rrin_yuv420_16* f0, const rrin_yuv420_16* f1, con
                          hipStream_t st, int32_t mult = 16);
 // a frame dimension rounded up to the pad multiple of a forward (16, 32 or 64)
 inline int pad_up(int v, int mult) { return (v + mult - 1) / mult * mult; }
+// The extra plane of a frame forward (plane.hip).  plane_check: what rrin_plane_warp_h8 and
+// rrin_plane_blend_h8 refuse of a descriptor whose inputs hold `frames` frames and whose output n, at
+// frame size h0 x w0 padded to h x w (0, RRIN_E_ARG or RRIN_E_SHAPE; nothing is launched).
+// plane_logits: where the MASK head's raw_out goes in the plane's scratch.
+int plane_check(const rrin_aux_plane* pl, int frames, int n, int h0, int w0, int h, int w);
+float* plane_logits(const rrin_aux_plane* pl, int n, int h, int w);
 // cfg 18's tile on 8 waves of 4 accumulators (<= 128 VGPRs: 4 waves per SIMD),
 // two stages of [raw 680 | U 1024] records (three in A/B builds: two blocks per
 // CU would fill 163,584 B)

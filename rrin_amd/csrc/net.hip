@@ -806,8 +806,12 @@ static int items_of(const rrin_items* it, int n, Items& out) {
 // flag of this call: pack into the full-size g16, rrin_g16_downscale_h8 into the low-res g16, the
 // Flow U-Net there, rrin_flow_upscale_h8 of its raw Flow into the full-size FLOWRAW, then the
 // blend of the kept raw Flow as for skip_flow.  A plain forward's pack is not repeated.
+//
+// With pa (an extra plane, frame forwards only; checked by plane_of) rrin_plane_warp_h8 follows the
+// REFINE head, the MASK head's raw output goes into the plane's scratch and rrin_plane_blend_h8
+// follows that head: two launches and one pointer, nothing else moves.
 static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, const Items& items, void* stream,
-                        const rrin_flow_scale* fs = nullptr) {
+                        const rrin_flow_scale* fs = nullptr, const rrin_aux_plane* pa = nullptr) {
   Plan p;
   make_plan(d->n, d->h, d->w, d->prec, reinterpret_cast<char*>(d->workspace), p);
   if (d->workspace_bytes < p.bytes) return RRIN_E_WORKSPACE;
@@ -881,8 +885,17 @@ static int net_fwd_impl(const rrin_net_desc* d, const FrameIO& f, const Items& i
     int k = 0;
     for (int u = 0; u < 4 && !rc; ++u) {
       if (!(u == 0 && blend)) {
-        const HeadIO io = f.head_io(d->coef, tap_of(d, kUNets[u]), d->h);
+        HeadIO io = f.head_io(d->coef, tap_of(d, kUNets[u]), d->h);
+        const int mode = kUNets[u].head_mode;
+        if (pa && mode == RRIN_HEAD_MASK) io.raw = plane_logits(pa, d->n, d->h, d->w);
         rc = run_unet_h8(p, kUNets[u], d->convs + k, d->heads[u], io, st);
+        if (!rc && pa && (mode == RRIN_HEAD_REFINE || mode == RRIN_HEAD_MASK)) {
+          ProfScope ps(p.prof, st, RRIN_KIND_LAYOUT, 0.0);
+          rc = mode == RRIN_HEAD_REFINE
+                   ? rrin_plane_warp_h8(&gall, pa, d->n, f.h0, f.w0, items.map, items.map ? items.n_pairs : d->n,
+                                        d->prec, st)
+                   : rrin_plane_blend_h8(pa, d->coef, d->n, d->h, d->w, f.h0, f.w0, d->prec, p.status, st);
+        }
       }
       k += convs_of(kUNets[u].depth);
     }
@@ -997,8 +1010,23 @@ static int flow_scale_check(const rrin_net_desc* nd, const rrin_flow_scale* fs) 
 //           descriptor's checks with the pad multiple 16 * s.
 enum class Entry { Plain, Items, Scaled };
 
+// bits of a sample of the frames of a descriptor: what an extra plane's depth must equal
+static int frame_depth(const rrin_net_u8_desc&) { return 8; }
+static int frame_depth(const rrin_net_yuv_desc&) { return 8; }
+static int frame_depth(const rrin_net_u16_desc& d) { return d.depth; }
+static int frame_depth(const rrin_net_yuv16_desc& d) { return d.f0.depth; }
+
+// The extra plane of a frame forward whose own checks have passed (rrin_net_*_plane_fwd), before any
+// launch: RRIN_E_ARG for taps or a depth that is not the frames', then plane_check
 template <class D>
-static int frame_fwd(Entry e, const D* d, const rrin_items* it, const rrin_flow_scale* fs, void* stream) {
+static int plane_of(const D* d, const rrin_aux_plane* pa, int frames) {
+  if (d->net.taps || pa->depth != frame_depth(*d)) return RRIN_E_ARG;
+  return plane_check(pa, frames, d->net.n, d->h0, d->w0, d->net.h, d->net.w);
+}
+
+template <class D>
+static int frame_fwd(Entry e, const D* d, const rrin_items* it, const rrin_flow_scale* fs, void* stream,
+                     const rrin_aux_plane* pa = nullptr) {
   Items items;
   if (e == Entry::Scaled) {
     if (int rc = flow_scale_check(d ? &d->net : nullptr, fs)) return rc;
@@ -1008,7 +1036,16 @@ static int frame_fwd(Entry e, const D* d, const rrin_items* it, const rrin_flow_
   if (it || e == Entry::Items)
     if (int rc = items_of(it, d->net.n, items)) return rc;
   if (int rc = frame_check(d, it ? items.n_pairs : (d ? d->net.n : 0), fs ? 16 * fs->s : 16)) return rc;
-  return net_fwd_impl(&d->net, frame_io(*d), items, stream, fs);
+  if (pa)
+    if (int rc = plane_of(d, pa, it ? items.n_pairs : d->net.n)) return rc;
+  return net_fwd_impl(&d->net, frame_io(*d), items, stream, fs, pa);
+}
+
+// rrin_net_*_plane_fwd: the entry that the nullable companions select, with the plane
+template <class D>
+static int plane_fwd(const D* d, const rrin_items* it, const rrin_flow_scale* fs, const rrin_aux_plane* pa,
+                     void* stream) {
+  return frame_fwd(fs ? Entry::Scaled : it ? Entry::Items : Entry::Plain, d, it, fs, stream, pa);
 }
 
 extern "C" int rrin_net_u8_fwd(const rrin_net_u8_desc* d, void* stream) {
@@ -1057,6 +1094,23 @@ extern "C" int rrin_net_u16_scaled_fwd(const rrin_net_u16_desc* d, const rrin_it
 extern "C" int rrin_net_yuv16_scaled_fwd(const rrin_net_yuv16_desc* d, const rrin_items* it,
                                          const rrin_flow_scale* fs, void* stream) {
   return frame_fwd(Entry::Scaled, d, it, fs, stream);
+}
+
+extern "C" int rrin_net_u8_plane_fwd(const rrin_net_u8_desc* d, const rrin_items* it, const rrin_flow_scale* fs,
+                                     const rrin_aux_plane* pa, void* stream) {
+  return plane_fwd(d, it, fs, pa, stream);
+}
+extern "C" int rrin_net_u16_plane_fwd(const rrin_net_u16_desc* d, const rrin_items* it, const rrin_flow_scale* fs,
+                                      const rrin_aux_plane* pa, void* stream) {
+  return plane_fwd(d, it, fs, pa, stream);
+}
+extern "C" int rrin_net_yuv_plane_fwd(const rrin_net_yuv_desc* d, const rrin_items* it, const rrin_flow_scale* fs,
+                                      const rrin_aux_plane* pa, void* stream) {
+  return plane_fwd(d, it, fs, pa, stream);
+}
+extern "C" int rrin_net_yuv16_plane_fwd(const rrin_net_yuv16_desc* d, const rrin_items* it, const rrin_flow_scale* fs,
+                                        const rrin_aux_plane* pa, void* stream) {
+  return plane_fwd(d, it, fs, pa, stream);
 }
 
 // One U-Net alone (reference UNet.forward, unet.py:40-51): NCHW in -> NCHW out,

@@ -24,7 +24,8 @@ import torch
 from . import _lib
 from .convert import scene_cut_code, scene_limit_len
 from .flowscale import check_flow_scale, flow_tag, padded_size
-from .framefmt import FrameFormat
+from .framefmt import FrameFormat, frame_stride
+from .plane import check_planes
 from .unet import _level_of
 
 UNET_ORDER = ("Flow", "refine_flow", "Mask", "final")
@@ -695,6 +696,7 @@ class RRINEngine:
         self._sad_key = None        # FrameFormat.sums_key of the batch whose sums the buffers hold
         self.last_gate = None       # int32 device codes of the last gated forward_u8 / forward_yuv
         self._metrics_ws = None     # workspace of the frame metrics (per-workgroup partials)
+        self._plane_sc = {}         # part key -> scratch of an extra plane (plane=)
 
     def _pack_h8(self, size: str, h: int = None, w: int = None):
         """(weight blob, bias blob, ConvWeights table, cfgs) of size class ``size`` at image
@@ -914,11 +916,15 @@ class RRINEngine:
         return flow_scale
 
     def _forward_frames(self, fmt: FrameFormat, what: str, f0, f1, t, reuse_flow, streams, split, scene_threshold,
-                        gate, flow_scale: int) -> torch.Tensor:
-        """``forward_*`` of every frame path: the call ``what`` on two stacks of ``fmt``."""
+                        gate, flow_scale: int, plane=None):
+        """``forward_*`` of every frame path: the call ``what`` on two stacks of ``fmt``.  ``plane``: a
+        pair ``(a0, a1)`` of ``[N,H0,W0]`` stacks of the frames' dtype (:mod:`rrin_amd.plane`); the call
+        then goes to the path's ``_plane_fwd`` entry and returns ``(frames, plane)``."""
         f0, f1, h0, w0, s0 = fmt.check(f0, f1, self.device, what)
         n = f0.shape[0]
         h, w = padded_size(h0, w0, flow_scale)
+        if plane is not None:  # refused before any state changes
+            a0, a1, sa, pout = self._plane_args(fmt, plane, n, n, h0, w0, items=False)
         self._poll_range()
         coef = t_coefficients(t, n).to(self.device, non_blocking=True)
         bounds = self._bounds(n, streams, split)
@@ -933,12 +939,21 @@ class RRINEngine:
             p0, p1, po = f0[lo:hi].data_ptr(), f1[lo:hi].data_ptr(), out[lo:hi].data_ptr()
             d, nd = make(p0, p1, po)
             self._fill_net(nd, p, coef[lo:hi])
-            self._launch(entries, d, nd, p, tag, reuse_flow, stream)
+            ap = None
+            if plane is not None:
+                ap = (fmt.plane_entry, self._aux_plane(fmt, p, a0[lo:hi], a1[lo:hi], sa, pout[lo:hi], w0))
+            self._launch(entries, d, nd, p, tag, reuse_flow, stream, ap)
             if g is not None:
                 self._enqueue_gate(g, fmt, p0, p1, s0, lo, hi, flen, po, stream)
+                if ap is not None:  # a gated pair's plane: the same frame's plane bytes, by the same kernel
+                    k = fmt.esize
+                    _lib.check(self.lib.rrin_gate_frames_u8_len(ap[1].a0, ap[1].a1, sa * k, hi - lo, h0 * w0 * k,
+                                                                g[4][lo:hi].data_ptr(), ap[1].out,
+                                                                C.c_void_p(stream.cuda_stream)),
+                               "rrin_gate_frames_u8_len")
 
         self._run_parts(h, w, bounds, part, flow_scale)
-        return out
+        return out if plane is None else (out, pout)
 
     def _scene_gate(self, fmt: FrameFormat, n: int, h0: int, w0: int, t, bounds, reuse_flow, scene_threshold, gate):
         """The scene gate of a forward of n pairs of H0 x W0 frames of ``fmt``.  Checks
@@ -1014,7 +1029,7 @@ class RRINEngine:
 
     def forward_u8(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, reuse_flow: bool = False,
                    streams: int | None = None, split=None, scene_threshold=None, gate=None,
-                   flow_scale: int = 1) -> torch.Tensor:
+                   flow_scale: int = 1, plane=None):
         """One Net.forward on 8-bit frames of any size: ``f0`` / ``f1`` uint8 ``[N,H0,W0,3]`` (RGB
         interleaved) on the engine's device -> uint8 ``[N,H0,W0,3]``.  Bit for bit
         ``convert.load_frame`` -> :meth:`forward` -> ``convert.to_uint8_image``: the edge padding
@@ -1048,11 +1063,21 @@ class RRINEngine:
         ``flow_scale`` 2 or 4 (:mod:`rrin_amd.flowscale`): the Flow U-Net runs on the frames at 1/s
         of their size and its flow is scaled up; the padding is then to a multiple of 16 * s, and
         the definition reads pad -> ``forward(..., flow_scale=s)`` -> ``to_uint8_image`` -> crop.  The
-        gate and its codes do not depend on it; a kept raw Flow is reused only at the same scale."""
+        gate and its codes do not depend on it; a kept raw Flow is reused only at the same scale.
+
+        ``plane`` (:mod:`rrin_amd.plane`, the definition): a pair ``(a0, a1)`` of uint8 ``[N,H0,W0]``
+        stacks, one extra single-channel image per input frame (an alpha matte, a depth or ID plane),
+        dense or uniformly strided as the frames are.  The call then returns ``(frames, plane)``,
+        the plane uint8 ``[N,H0,W0]``: the two input planes backwarped by the picture's refined flows
+        and blended with the picture's mask weights (rrin_net_u8_plane_fwd: two small kernels more,
+        rrin_plane_warp_h8 and rrin_plane_blend_h8).  The frames are the same bits as without it.  A
+        gated pair's plane is the plane bytes of the frame the gate chose (the gate's copy kernel on
+        the plane); the gate decision does not read the plane.  With the range guard set the plane is
+        0.  Without the keyword nothing changes."""
         flow_scale = self._frame_call("forward_u8", flow_scale)
         fmt = FrameFormat.u8()
         return self._forward_frames(fmt, "forward_u8", f0, f1, t, reuse_flow, streams, split, scene_threshold,
-                                    gate, flow_scale)
+                                    gate, flow_scale, plane)
 
     def _need_records(self, what: str):
         if self.prec == _lib.PREC_F32:
@@ -1080,7 +1105,7 @@ class RRINEngine:
     # ---- 8-bit YUV 4:2:0 frames (NV12 / I420) ------------------------------------------
     def forward_yuv(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, layout: str = "nv12", coef=None,
                     reuse_flow: bool = False, streams: int | None = None, split=None, scene_threshold=None,
-                    gate=None, flow_scale: int = 1) -> torch.Tensor:
+                    gate=None, flow_scale: int = 1, plane=None):
         """One Net.forward on 8-bit YUV 4:2:0 frames: ``f0`` / ``f1`` uint8 ``[N, 3*H0//2, W0]``
         (H0, W0 even; ``layout`` "nv12" or "i420", see :mod:`rrin_amd.yuv`) on the engine's device
         -> uint8 ``[N, 3*H0//2, W0]`` of the same layout.  By definition, and bit for bit,
@@ -1109,11 +1134,12 @@ class RRINEngine:
         the input's layout and shape.  Their gate sums the frame's ``2*H0*W0`` / ``3*H0*W0`` bytes
         (rrin_pair_sad_u8_len): a cut exceeds ``floor(scene_threshold * that count)``.
 
-        ``flow_scale``: as in :meth:`forward_u8`, which the definition passes it to."""
+        ``flow_scale``: as in :meth:`forward_u8`, which the definition passes it to.  ``plane``: as in
+        :meth:`forward_u8`, full-size uint8 ``[N,H0,W0]`` planes whatever the chroma layout."""
         flow_scale = self._frame_call("forward_yuv", flow_scale)
         fmt = FrameFormat.yuv(layout, coef)
         return self._forward_frames(fmt, "forward_yuv", f0, f1, t, reuse_flow, streams, split, scene_threshold,
-                                    gate, flow_scale)
+                                    gate, flow_scale, plane)
 
     def pair_stats_yuv(self, f0: torch.Tensor, f1: torch.Tensor, layout: str = "nv12") -> torch.Tensor:
         """The sum of absolute byte differences (luma and chroma) of every pair of two 4:2:0
@@ -1127,7 +1153,7 @@ class RRINEngine:
     # ---- 10- to 16-bit frames in 16-bit words ----------------------------------------------
     def forward_u16(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, depth: int = 10, reuse_flow: bool = False,
                     streams: int | None = None, split=None, scene_threshold=None, gate=None,
-                    flow_scale: int = 1) -> torch.Tensor:
+                    flow_scale: int = 1, plane=None):
         """:meth:`forward_u8` on 16-bit frames: ``f0`` / ``f1`` uint16 ``[N,H0,W0,3]`` holding RGB
         samples of ``depth`` 9..16 in the words' low bits -> uint16 ``[N,H0,W0,3]`` of that depth.
         Bit for bit ``convert.frames_u16_to_float`` -> :meth:`forward` ->
@@ -1138,11 +1164,13 @@ class RRINEngine:
         the scene gate -- with ``scene_threshold`` a mean absolute sample difference in
         [0, maxval] over ``min(word, maxval)`` (rrin_pair_sad_u16_len), and a gated frame its input
         frame's words as they are.  A kept raw Flow is only reused by this path at this depth.
-        ``flow_scale``: as in :meth:`forward_u8` (``forward(..., flow_scale=s)`` in the definition)."""
+        ``flow_scale``: as in :meth:`forward_u8` (``forward(..., flow_scale=s)`` in the definition).
+        ``plane``: as in :meth:`forward_u8` with uint16 planes of the frames' ``depth`` (a word above
+        maxval reads as maxval)."""
         flow_scale = self._frame_call("forward_u16", flow_scale)
         fmt = FrameFormat.u16(depth, "forward_u16")
         return self._forward_frames(fmt, "forward_u16", f0, f1, t, reuse_flow, streams, split, scene_threshold,
-                                    gate, flow_scale)
+                                    gate, flow_scale, plane)
 
     def pair_stats_u16(self, f0: torch.Tensor, f1: torch.Tensor, depth: int = 10) -> torch.Tensor:
         """:meth:`pair_stats_u8` for two uint16 ``[N,H0,W0,3]`` stacks of ``depth`` 9..16: the exact
@@ -1151,7 +1179,7 @@ class RRINEngine:
 
     def forward_yuv16(self, f0: torch.Tensor, f1: torch.Tensor, t=0.5, layout: str = "nv12", depth: int = 10,
                       msb: bool = False, coef=None, reuse_flow: bool = False, streams: int | None = None, split=None,
-                      scene_threshold=None, gate=None, flow_scale: int = 1) -> torch.Tensor:
+                      scene_threshold=None, gate=None, flow_scale: int = 1, plane=None):
         """:meth:`forward_yuv` on 10- or 12-bit 4:2:0 frames in 16-bit words: ``f0`` / ``f1`` uint16
         ``[N, 3*H0//2, W0]`` -> uint16 of the same shape, layout, depth and alignment (``msb=False``:
         the sample in the low bits, as yuv420p10le and Y4M C420p10; ``True``: in the high bits, as
@@ -1164,11 +1192,13 @@ class RRINEngine:
         kept raw Flow is only reused by a call of the same layout, depth, alignment and matrix.
         The 4:2:2 and 4:4:4 layouts ("nv16", "i422", "i444") run as in :meth:`forward_yuv`, defined by
         ``yuv.rgb16_to_yuv`` / ``yuv.yuv_to_rgb16``, the gate on the frame's samples (rrin_pair_sad_u16_len).
-        ``flow_scale``: as in :meth:`forward_u16`, which the definition passes it to."""
+        ``flow_scale``: as in :meth:`forward_u16`, which the definition passes it to.  ``plane``: as in
+        :meth:`forward_u8`: full-size uint16 ``[N,H0,W0]`` planes of the frames' depth and alignment
+        (a sample is ``min(word >> shift, maxval)``, stored ``<< shift``)."""
         flow_scale = self._frame_call("forward_yuv16", flow_scale)
         fmt = FrameFormat.yuv16(layout, depth, msb, coef)
         return self._forward_frames(fmt, "forward_yuv16", f0, f1, t, reuse_flow, streams, split, scene_threshold,
-                                    gate, flow_scale)
+                                    gate, flow_scale, plane)
 
     def pair_stats_yuv16(self, f0: torch.Tensor, f1: torch.Tensor, depth: int = 10, msb: bool = False,
                          layout: str = "nv12") -> torch.Tensor:
@@ -1226,7 +1256,7 @@ class RRINEngine:
     # raw Flow (reuse_flow) are the two bitwise guarantees it rests on.
 
     def _run_items(self, fmt: FrameFormat, what: str, frames, pair, t, streams, split, scene_threshold, gate, prof,
-                   flow_scale: int) -> torch.Tensor:
+                   flow_scale: int, plane=None):
         """``interpolate_items_*`` of every frame path: the call ``what`` on one ``[P+1, ...]`` stack of
         ``fmt``, whose views ``frames[:-1]`` / ``frames[1:]`` are the pairs' frames.  The items are split
         over ``streams`` as a forward's pairs are; each part runs the Flow U-Net on the distinct pairs
@@ -1234,12 +1264,15 @@ class RRINEngine:
         pairs are a run of the stack, so its frames are views; pairs that skip some (an arbitrary
         caller) are gathered into a copy.  ``flow_scale`` s > 1: the library's ``_scaled_fwd`` entry
         of the path with the part's second plan, the Flow phase at 1/s of the size on the part's
-        pairs."""
+        pairs.  ``plane``: one ``[P+1,H0,W0]`` stack of the frames' dtype (:mod:`rrin_amd.plane`), gathered
+        as the frames are; the call goes to the path's ``_plane_fwd`` entry and returns ``(frames, plane)``."""
         if not isinstance(frames, torch.Tensor) or frames.dim() < 1 or frames.shape[0] < 2:
             raise ValueError(f"{what} takes one stack of at least two frames")
         f0, f1, h0, w0, s0 = fmt.check(frames[:-1], frames[1:], self.device, what)
         pairs, ts = check_items(pair, t, f0.shape[0])
         m = len(pairs)
+        if plane is not None:  # refused before any state changes
+            a0, a1, sa, pout = self._plane_args(fmt, plane, f0.shape[0], m, h0, w0, items=True)
         out = torch.empty(fmt.out_shape(m, h0, w0), dtype=fmt.dtype, device=self.device)
         n_stack = f0.shape[0]
         h, w = padded_size(h0, w0, flow_scale)
@@ -1283,15 +1316,22 @@ class RRINEngine:
         def part(j, lo, hi, stream, p):
             d = distinct[j]
             npairs = len(d)
+            pa = pb = None
             if d[-1] - d[0] + 1 == npairs:  # a run of the stack: views
                 a, b = f0[d[0]:d[-1] + 1], f1[d[0]:d[-1] + 1]
                 stride = s0
+                if plane is not None:
+                    pa, pb, pstride = a0[d[0]:d[-1] + 1], a1[d[0]:d[-1] + 1], sa
             else:
                 idx = torch.tensor(d, dtype=torch.int64, device=self.device)
                 with torch.cuda.stream(stream):
                     a, b = f0.index_select(0, idx), f1.index_select(0, idx)
                     a.record_stream(stream)
                     b.record_stream(stream)
+                    if plane is not None:
+                        pa, pb, pstride = a0.index_select(0, idx), a1.index_select(0, idx), h0 * w0
+                        pa.record_stream(stream)
+                        pb.record_stream(stream)
                 stride = a.stride(0)
             p0, p1, po = a.data_ptr(), b.data_ptr(), out[lo:hi].data_ptr()
             desc, nd = (make if stride == s0 else fmt.desc_for(stride, h0, w0))(p0, p1, po)
@@ -1301,7 +1341,12 @@ class RRINEngine:
             it.n_pairs, it.pair_map = npairs, maps[lo:hi].data_ptr()
             nd.skip_flow = 0
             sp = C.c_void_p(stream.cuda_stream)
-            if p.low is None:
+            if plane is not None:
+                ap = self._aux_plane(fmt, p, pa, pb, pstride, pout[lo:hi], w0)
+                _lib.check(getattr(self.lib, fmt.plane_entry)(C.byref(desc), C.byref(it),
+                                                              C.byref(p.low.fs) if p.low is not None else None,
+                                                              C.byref(ap), sp), fmt.plane_entry)
+            elif p.low is None:
                 _lib.check(getattr(self.lib, items_fwd)(C.byref(desc), C.byref(it), sp), items_fwd)
             else:
                 _lib.check(getattr(self.lib, scaled_fwd)(C.byref(desc), C.byref(it), C.byref(p.low.fs), sp),
@@ -1331,12 +1376,16 @@ class RRINEngine:
             _lib.check(self.lib.rrin_gate_frames_items_u8_len(p0, p1, stride * k, hi - lo, flen * k, cp, po,
                                                               maps[lo:hi].data_ptr(), npairs, sp),
                        "rrin_gate_frames_items_u8_len")
+            if plane is not None:  # a gated item's plane: the plane bytes of the frame the gate chose
+                _lib.check(self.lib.rrin_gate_frames_items_u8_len(ap.a0, ap.a1, pstride * k, hi - lo, h0 * w0 * k, cp,
+                                                                  ap.out, maps[lo:hi].data_ptr(), npairs, sp),
+                           "rrin_gate_frames_items_u8_len")
 
         self._run_parts(h, w, bounds, part, flow_scale)
-        return out
+        return out if plane is None else (out, pout)
 
     def interpolate_items_u8(self, frames: torch.Tensor, pair, t, streams: int | None = None, split=None,
-                             scene_threshold=None, gate=None, prof=None, flow_scale: int = 1) -> torch.Tensor:
+                             scene_threshold=None, gate=None, prof=None, flow_scale: int = 1, plane=None):
         """A batch of M items ``(pair[k], t[k])`` over one stack of 8-bit frames: ``frames`` uint8
         ``[P+1,H0,W0,3]`` on the device (pair p is frames p and p + 1), ``pair`` M non-decreasing
         ints in [0, P) (list or int32 tensor), ``t`` M floats in [0, 1) (list or fp32 tensor) ->
@@ -1351,25 +1400,28 @@ class RRINEngine:
         run once per distinct pair.  ``gate``: an int32 device tensor ``[P]`` of pair codes (1: a
         duplicate, 2: a cut, else interpolate).  :attr:`last_gate` is then the ``[M]`` item codes
         (1: the first frame, 2: the second, 0: interpolated).  ``flow_scale`` is passed to the
-        defining ``forward_u8`` (rrin_net_u8_scaled_fwd with the items)."""
+        defining ``forward_u8`` (rrin_net_u8_scaled_fwd with the items).  ``plane``: one uint8
+        ``[P+1,H0,W0]`` stack (:mod:`rrin_amd.plane`); the call returns ``(frames, plane)`` with item k's
+        plane bit for bit that of the defining ``forward_u8(..., plane=(plane[p:p+1], plane[p+1:p+2]))``
+        (rrin_net_u8_plane_fwd with the items); here and on the three methods below."""
         flow_scale = self._frame_call("interpolate_items_u8", flow_scale)
         fmt = FrameFormat.u8()
         return self._run_items(fmt, "interpolate_items_u8", frames, pair, t, streams, split, scene_threshold, gate,
-                               prof, flow_scale)
+                               prof, flow_scale, plane)
 
     def interpolate_items_u16(self, frames: torch.Tensor, pair, t, depth: int = 10, streams: int | None = None,
                               split=None, scene_threshold=None, gate=None, prof=None,
-                              flow_scale: int = 1) -> torch.Tensor:
+                              flow_scale: int = 1, plane=None):
         """:meth:`interpolate_items_u8` on uint16 ``[P+1,H0,W0,3]`` frames of ``depth`` 9..16, defined
         by :meth:`forward_u16` (rrin_net_u16_items_fwd) with the same ``flow_scale``."""
         flow_scale = self._frame_call("interpolate_items_u16", flow_scale)
         fmt = FrameFormat.u16(depth, "interpolate_items_u16")
         return self._run_items(fmt, "interpolate_items_u16", frames, pair, t, streams, split, scene_threshold, gate,
-                               prof, flow_scale)
+                               prof, flow_scale, plane)
 
     def interpolate_items_yuv(self, frames: torch.Tensor, pair, t, layout: str = "nv12", coef=None,
                               streams: int | None = None, split=None, scene_threshold=None, gate=None,
-                              prof=None, flow_scale: int = 1) -> torch.Tensor:
+                              prof=None, flow_scale: int = 1, plane=None):
         """:meth:`interpolate_items_u8` on one stack of 8-bit YUV frames (``[P+1, rows, W0]`` of
         ``layout``, as :meth:`forward_yuv` takes them), defined by :meth:`forward_yuv` with the same
         ``layout``, ``coef`` and ``flow_scale`` (rrin_net_yuv_items_fwd); the gate on the frames'
@@ -1377,18 +1429,18 @@ class RRINEngine:
         flow_scale = self._frame_call("interpolate_items_yuv", flow_scale)
         fmt = FrameFormat.yuv(layout, coef)
         return self._run_items(fmt, "interpolate_items_yuv", frames, pair, t, streams, split, scene_threshold, gate,
-                               prof, flow_scale)
+                               prof, flow_scale, plane)
 
     def interpolate_items_yuv16(self, frames: torch.Tensor, pair, t, layout: str = "nv12", depth: int = 10,
                                 msb: bool = False, coef=None, streams: int | None = None, split=None,
-                                scene_threshold=None, gate=None, prof=None, flow_scale: int = 1) -> torch.Tensor:
+                                scene_threshold=None, gate=None, prof=None, flow_scale: int = 1, plane=None):
         """:meth:`interpolate_items_yuv` on 10- or 12-bit frames in 16-bit words, defined by
         :meth:`forward_yuv16` with the same ``layout``, ``depth``, ``msb``, ``coef`` and ``flow_scale``
         (rrin_net_yuv16_items_fwd)."""
         flow_scale = self._frame_call("interpolate_items_yuv16", flow_scale)
         fmt = FrameFormat.yuv16(layout, depth, msb, coef)
         return self._run_items(fmt, "interpolate_items_yuv16", frames, pair, t, streams, split, scene_threshold, gate,
-                               prof, flow_scale)
+                               prof, flow_scale, plane)
 
     def unet_forward(self, x: torch.Tensor) -> torch.Tensor:
         """The single packed U-Net (engine built with one unit) on x [N,C,H,W]:
@@ -1437,7 +1489,7 @@ class RRINEngine:
         k = max(1, min(int(streams), n))
         return [(n * j // k, n * (j + 1) // k) for j in range(k)]
 
-    def graph(self, n: int, h: int, w: int, streams: int | None = None, split=None) -> "NetGraph":
+    def graph(self, n: int, h: int, w: int, streams: int | None = None, split=None, plane=None) -> "NetGraph":
         """The forward of n pairs at h x w captured as one HIP graph and cached per (n, h, w, part
         split) on this engine -- the engine is rebuilt when the weights, precision or schedule
         change, so a graph never outlives the packing it captured.  Replaying it enqueues every
@@ -1446,6 +1498,8 @@ class RRINEngine:
         coefficients and output live in static device buffers (``NetGraph.i0 / i1 / out``); the
         bits are those of :meth:`forward` (same launches, same buffers' layout;
         ``tests/test_gpu_graph.py``).  reuse_flow and taps are eager-only."""
+        if plane is not None:
+            raise ValueError("plane= is not captured: NetGraph is the float forward (use forward_u8 eagerly)")
         if h % 16 or w % 16 or n < 1:
             raise RuntimeError(f"H and W must be multiples of 16, got {h}x{w}")
         bounds = self._bounds(n, streams, split)
@@ -1518,7 +1572,41 @@ class RRINEngine:
         d.i0, d.i1, d.out = i0.data_ptr(), i1.data_ptr(), out.data_ptr()
         return d
 
-    def _launch(self, entries, d, nd, p: Part, tag: str, reuse_flow, stream):
+    def _plane_args(self, fmt: FrameFormat, plane, n_pairs: int, n_out: int, h0: int, w0: int, items: bool):
+        """The ``plane=`` argument of a forward of ``n_pairs`` pairs with ``n_out`` outputs, checked
+        (:func:`rrin_amd.plane.check_planes`: TypeError / ValueError): ``(a0, a1, stride, out)`` -- the two
+        input stacks with dense frames ``stride`` elements apart (a uniform stride over dim 0 is taken as
+        it is, anything else copied, as the frames are) and the fresh output stack ``[n_out,H0,W0]``."""
+        a0, a1 = check_planes(plane, n_pairs, h0, w0, fmt.dtype, self.device, items=items)
+        sa = frame_stride(a0)
+        if sa is None or sa != frame_stride(a1):
+            a0, a1, sa = a0.contiguous(), a1.contiguous(), h0 * w0
+        return a0, a1, sa, torch.empty((n_out, h0, w0), dtype=fmt.dtype, device=self.device)
+
+    def _plane_scratch(self, p: Part) -> torch.Tensor:
+        """The cached scratch of an extra plane for forward part p (rrin_plane_scratch_bytes: 16 B per
+        padded pixel), kept like the workspaces; every byte a forward reads of it, it has written."""
+        m, h, w = p.key[:3]
+        sc = self._plane_sc.get(p.key)
+        if sc is None:
+            if len(self._plane_sc) >= 8:
+                self._plane_sc.clear()
+            sc = self._plane_sc[p.key] = torch.empty(m * h * w * 4, dtype=torch.float32, device=self.device)
+        return sc
+
+    def _aux_plane(self, fmt: FrameFormat, p: Part, a0, a1, stride: int, pout, w0: int) -> "_lib.AuxPlane":
+        """The rrin_aux_plane of a forward part: input plane stacks a0 / a1 (dense frames ``stride``
+        elements apart), the dense output stack pout, the part's cached scratch."""
+        ap = _lib.AuxPlane()
+        ap.a0, ap.a1, ap.out = a0.data_ptr(), a1.data_ptr(), pout.data_ptr()
+        ap.in_stride, ap.out_stride = stride, pout.stride(0)
+        ap.in_pitch = ap.out_pitch = w0
+        ap.depth, ap.shift = fmt.depth, fmt.shift
+        sc = self._plane_scratch(p)
+        ap.scratch, ap.scratch_bytes = sc.data_ptr(), sc.numel() * 4
+        return ap
+
+    def _launch(self, entries, d, nd, p: Part, tag: str, reuse_flow, stream, plane=None):
         """The library's forward on descriptor d (nd: its rrin_net_desc) for part p on ``stream``.
         ``entries``: the names of the plain entry and, last, of its flow_scale sibling
         (FLOAT_ENTRIES, or a frame format's ``entries``, whose ``_scaled_fwd`` also takes items: none
@@ -1532,6 +1620,9 @@ class RRINEngine:
             tag = flow_tag(tag, p.low.fs.s)
             name = entries[-1]
             extra = (C.byref(p.low.fs),) if entries is FLOAT_ENTRIES else (None, C.byref(p.low.fs))
+        if plane is not None:  # (entry name, rrin_aux_plane): the path's _plane_fwd, no items
+            name = plane[0]
+            extra = (None, C.byref(p.low.fs) if p.low is not None else None, C.byref(plane[1]))
         nd.skip_flow = 1 if reuse_flow and self._flow_valid.get(p.key) == tag else 0
         _lib.check(getattr(self.lib, name)(C.byref(d), *extra, C.c_void_p(stream.cuda_stream)), name)
         self._flow_valid[p.key] = tag

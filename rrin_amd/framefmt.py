@@ -138,6 +138,12 @@ class FrameFormat(namedtuple("FrameFormat", "layout depth shift coef")):
         return ENTRIES[self.path]
 
     @property
+    def plane_entry(self) -> str:
+        """The library's entry of the path that also carries an extra plane (:mod:`rrin_amd.plane`): the
+        plain, item and flow_scale forwards in one, each companion nullable."""
+        return f"rrin_net_{self.path}_plane_fwd"
+
+    @property
     def tag(self) -> str:
         """Names whose raw Flow a workspace keeps: path, and layout, matrix, depth and shift where the
         path has them (the scale is added by :func:`rrin_amd.flowscale.flow_tag`).  Equal tags: the

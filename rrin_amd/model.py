@@ -32,6 +32,12 @@ from torch import nn
 from .unet import UNet
 
 
+def _plane_kw(plane):
+    """The ``plane=`` keyword of a frame method for the engine: absent unless given, so a call without
+    it is the call it always was."""
+    return {} if plane is None else {"plane": plane}
+
+
 class Net(nn.Module):
     def __init__(self):
         super().__init__()
@@ -116,7 +122,7 @@ class Net(nn.Module):
         return [eng.forward(input0, input1, t, reuse_flow=(k > 0), streams=self.streams, flow_scale=flow_scale)
                 for k, t in enumerate(ts)]
 
-    def _frames(self, path, f0, f1, t, many, **kw):
+    def _frames(self, path, f0, f1, t, many, **kw):  # kw may carry plane=: every result is then (frames, plane)
         """``forward_<path>`` (one ``t``) or, ``many``, ``interpolate_<path>`` (a list ``t``) of the frame
         paths: the engine's ``forward_<path>`` once, or for every t of the list with the Flow U-Net (and
         the gate's sums) of the first call reused by the others."""
@@ -128,7 +134,7 @@ class Net(nn.Module):
             return fwd(f0, f1, t, streams=self.streams, **kw)
         return [fwd(f0, f1, v, reuse_flow=(k > 0), streams=self.streams, **kw) for k, v in enumerate(t)]
 
-    def forward_u8(self, f0, f1, t=0.5, scene_threshold=None, gate=None, flow_scale=1):
+    def forward_u8(self, f0, f1, t=0.5, scene_threshold=None, gate=None, flow_scale=1, plane=None):
         """``forward`` on 8-bit frames of any size: uint8 ``[N,H0,W0,3]`` in and out, on the
         device; bit for bit ``convert.load_frame`` -> ``forward`` -> ``convert.to_uint8_image``
         (``RRINEngine.forward_u8``).  Inference-only; not for ``precision='fp32_planar'``.
@@ -138,16 +144,24 @@ class Net(nn.Module):
         repeated frame returns ``f0``, a shot change the nearer input frame (``f1`` from t = 0.5
         on), decided and applied on the device (``RRINEngine.forward_u8``).  The network still
         runs for a gated pair: skipping it would need a host sync.  No threshold has been
-        validated on real footage; :attr:`last_gate` reports what a call decided."""
-        return self._frames("u8", f0, f1, t, False, scene_threshold=scene_threshold, gate=gate,
-                            flow_scale=flow_scale)
+        validated on real footage; :attr:`last_gate` reports what a call decided.
 
-    def interpolate_u8(self, f0, f1, ts, scene_threshold=None, gate=None, flow_scale=1):
+        ``plane=(a0, a1)``, here and on every frame method below: one extra single-channel image per
+        input frame, uint8 (uint16 on the 16-bit paths) ``[N,H0,W0]`` -- an alpha matte, a depth or an
+        ID plane -- carried to time t by the picture's own refined flows and mask weights
+        (:mod:`rrin_amd.plane` is the definition).  The call then returns ``(frames, plane)``; the
+        ``interpolate_*`` methods a list of such pairs, one per t; the ``interpolate_items_*`` methods
+        take one ``[P+1,H0,W0]`` stack.  RGB is taken as stored (no premultiply).  Without the keyword
+        nothing changes."""
+        return self._frames("u8", f0, f1, t, False, scene_threshold=scene_threshold, gate=gate,
+                            flow_scale=flow_scale, **_plane_kw(plane))
+
+    def interpolate_u8(self, f0, f1, ts, scene_threshold=None, gate=None, flow_scale=1, plane=None):
         """``[forward_u8(f0, f1, t) for t in ts]`` with the Flow U-Net computed once, as
         :meth:`interpolate`; with ``scene_threshold`` the pairs' sums of absolute differences are
         computed once too (the cut code depends on t, so :attr:`last_gate` is that of ``ts[-1]``)."""
         return self._frames("u8", f0, f1, ts, True, scene_threshold=scene_threshold, gate=gate,
-                            flow_scale=flow_scale)
+                            flow_scale=flow_scale, **_plane_kw(plane))
 
     def pair_stats_u8(self, f0, f1):
         """int64 device tensor ``[N]``: the sum of absolute byte differences of every pair of two
@@ -155,7 +169,8 @@ class Net(nn.Module):
         with ``floor(threshold * H0*W0*3)``, for callers who pass their own ``gate``."""
         return self.engine().pair_stats_u8(f0, f1)
 
-    def forward_yuv(self, f0, f1, t=0.5, layout="nv12", coef=None, scene_threshold=None, gate=None, flow_scale=1):
+    def forward_yuv(self, f0, f1, t=0.5, layout="nv12", coef=None, scene_threshold=None, gate=None, flow_scale=1,
+                    plane=None):
         """``forward`` on 8-bit YUV 4:2:0 frames, as decoders and video pipes deliver them: uint8
         ``[N, 3*H0//2, W0]`` in and out on the device (H0, W0 even; ``layout`` "nv12" or "i420") -- or
         4:2:2 (``layout`` "nv16" / "i422": ``[N, 2*H0, W0]``, W0 even) and 4:4:4 ("i444": ``[N, 3*H0,
@@ -171,14 +186,15 @@ class Net(nn.Module):
         and chroma bytes, so not the same number as the RGB path's; no value has been validated
         on real footage."""
         return self._frames("yuv", f0, f1, t, False, layout=layout, coef=coef,
-                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
+                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale, **_plane_kw(plane))
 
-    def interpolate_yuv(self, f0, f1, ts, layout="nv12", coef=None, scene_threshold=None, gate=None, flow_scale=1):
+    def interpolate_yuv(self, f0, f1, ts, layout="nv12", coef=None, scene_threshold=None, gate=None, flow_scale=1,
+                        plane=None):
         """``[forward_yuv(f0, f1, t) for t in ts]`` with the Flow U-Net (and, with
         ``scene_threshold``, the pairs' sums of absolute differences) computed once, as
         :meth:`interpolate_u8`."""
         return self._frames("yuv", f0, f1, ts, True, layout=layout, coef=coef,
-                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
+                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale, **_plane_kw(plane))
 
     def pair_stats_yuv(self, f0, f1, layout="nv12"):
         """int64 device tensor ``[N]``: the sum of absolute byte differences, luma and chroma, of
@@ -186,7 +202,7 @@ class Net(nn.Module):
         ``floor(threshold * H0*W0*3/2)`` (a 4:2:2 / 4:4:4 ``layout``: ``2*H0*W0`` / ``3*H0*W0`` bytes)."""
         return self.engine().pair_stats_yuv(f0, f1, layout=layout)
 
-    def forward_u16(self, f0, f1, t=0.5, depth=10, scene_threshold=None, gate=None, flow_scale=1):
+    def forward_u16(self, f0, f1, t=0.5, depth=10, scene_threshold=None, gate=None, flow_scale=1, plane=None):
         """``forward_u8`` on 16-bit frames: uint16 ``[N,H0,W0,3]`` RGB samples of ``depth`` 9..16 (in
         the words' low bits; a word above ``maxval = 2**depth - 1`` is read as maxval) in and out on
         the device; bit for bit ``convert.frames_u16_to_float`` -> ``forward`` ->
@@ -194,13 +210,13 @@ class Net(nn.Module):
         ``precision='fp32_planar'``.  The scene gate is ``forward_u8``'s with ``scene_threshold`` a
         mean absolute sample difference in [0, maxval]."""
         return self._frames("u16", f0, f1, t, False, depth=depth, scene_threshold=scene_threshold, gate=gate,
-                            flow_scale=flow_scale)
+                            flow_scale=flow_scale, **_plane_kw(plane))
 
-    def interpolate_u16(self, f0, f1, ts, depth=10, scene_threshold=None, gate=None, flow_scale=1):
+    def interpolate_u16(self, f0, f1, ts, depth=10, scene_threshold=None, gate=None, flow_scale=1, plane=None):
         """``[forward_u16(f0, f1, t, depth) for t in ts]`` with the Flow U-Net (and the pairs' sums
         of absolute differences) computed once, as :meth:`interpolate_u8`."""
         return self._frames("u16", f0, f1, ts, True, depth=depth, scene_threshold=scene_threshold, gate=gate,
-                            flow_scale=flow_scale)
+                            flow_scale=flow_scale, **_plane_kw(plane))
 
     def pair_stats_u16(self, f0, f1, depth=10):
         """int64 device tensor ``[N]``: the exact sum of absolute sample differences (samples
@@ -208,7 +224,7 @@ class Net(nn.Module):
         return self.engine().pair_stats_u16(f0, f1, depth=depth)
 
     def forward_yuv16(self, f0, f1, t=0.5, layout="nv12", depth=10, msb=False, coef=None, scene_threshold=None,
-                      gate=None, flow_scale=1):
+                      gate=None, flow_scale=1, plane=None):
         """``forward_yuv`` on 10- or 12-bit 4:2:0 frames in 16-bit words: uint16 ``[N, 3*H0//2, W0]`` in
         and out on the device, ``msb=False`` for samples in the low bits (yuv420p10le, Y4M C420p10),
         ``True`` for the high bits (P010 / P012).  By definition, and bit for bit,
@@ -216,14 +232,14 @@ class Net(nn.Module):
         depth))`` (``RRINEngine.forward_yuv16``); ``coef`` None is BT.709 limited range at this
         depth.  Other depths raise.  Inference-only; not for ``precision='fp32_planar'``."""
         return self._frames("yuv16", f0, f1, t, False, layout=layout, depth=depth, msb=msb, coef=coef,
-                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
+                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale, **_plane_kw(plane))
 
     def interpolate_yuv16(self, f0, f1, ts, layout="nv12", depth=10, msb=False, coef=None, scene_threshold=None,
-                          gate=None, flow_scale=1):
+                          gate=None, flow_scale=1, plane=None):
         """``[forward_yuv16(f0, f1, t, ...) for t in ts]`` with the Flow U-Net (and the pairs' sums of
         absolute differences) computed once, as :meth:`interpolate_yuv`."""
         return self._frames("yuv16", f0, f1, ts, True, layout=layout, depth=depth, msb=msb, coef=coef,
-                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
+                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale, **_plane_kw(plane))
 
     def pair_stats_yuv16(self, f0, f1, depth=10, msb=False, layout="nv12"):
         """int64 device tensor ``[N]``: the exact sum of absolute differences of the samples
@@ -265,7 +281,7 @@ class Net(nn.Module):
             raise RuntimeError(f"rrin_amd.Net.{name} is inference-only: use torch.no_grad()")
         return getattr(self.engine(), name)(frames, pair, t, streams=self.streams, **kw)
 
-    def interpolate_items_u8(self, frames, pair, t, scene_threshold=None, gate=None, flow_scale=1):
+    def interpolate_items_u8(self, frames, pair, t, scene_threshold=None, gate=None, flow_scale=1, plane=None):
         """A batch of M items over one stack of 8-bit frames, for frame-rate conversion
         (:mod:`rrin_amd.retime`): ``frames`` uint8 ``[P+1,H0,W0,3]`` on the device (pair p is
         ``frames[p]``, ``frames[p+1]``), ``pair`` M non-decreasing ints in [0, P) (list or int32
@@ -279,26 +295,27 @@ class Net(nn.Module):
         by the item's own t; :attr:`last_gate` is then ``[M]``.  Output quality at uneven t has not
         been validated on footage."""
         return self._items("interpolate_items_u8", frames, pair, t, scene_threshold=scene_threshold, gate=gate,
-                           flow_scale=flow_scale)
+                           flow_scale=flow_scale, **_plane_kw(plane))
 
     def interpolate_items_yuv(self, frames, pair, t, layout="nv12", coef=None, scene_threshold=None, gate=None,
-                              flow_scale=1):
+                              flow_scale=1, plane=None):
         """:meth:`interpolate_items_u8` on one stack of 8-bit YUV frames, defined by
         :meth:`forward_yuv` with the same ``layout`` and ``coef``."""
         return self._items("interpolate_items_yuv", frames, pair, t, layout=layout, coef=coef,
-                           scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
+                           scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale, **_plane_kw(plane))
 
-    def interpolate_items_u16(self, frames, pair, t, depth=10, scene_threshold=None, gate=None, flow_scale=1):
+    def interpolate_items_u16(self, frames, pair, t, depth=10, scene_threshold=None, gate=None, flow_scale=1,
+                              plane=None):
         """:meth:`interpolate_items_u8` on uint16 RGB frames of ``depth``, defined by :meth:`forward_u16`."""
         return self._items("interpolate_items_u16", frames, pair, t, depth=depth, scene_threshold=scene_threshold,
-                           gate=gate, flow_scale=flow_scale)
+                           gate=gate, flow_scale=flow_scale, **_plane_kw(plane))
 
     def interpolate_items_yuv16(self, frames, pair, t, layout="nv12", depth=10, msb=False, coef=None,
-                                scene_threshold=None, gate=None, flow_scale=1):
+                                scene_threshold=None, gate=None, flow_scale=1, plane=None):
         """:meth:`interpolate_items_yuv` on 10- or 12-bit frames in 16-bit words, defined by
         :meth:`forward_yuv16` with the same ``layout``, ``depth``, ``msb`` and ``coef``."""
         return self._items("interpolate_items_yuv16", frames, pair, t, layout=layout, depth=depth, msb=msb, coef=coef,
-                           scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale)
+                           scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale, **_plane_kw(plane))
 
     @property
     def last_gate(self):
