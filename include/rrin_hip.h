@@ -984,6 +984,48 @@ int64_t rrin_tloss_workspace_bytes(int64_t count);
 int rrin_tloss(const float* out, const float* target, int64_t count, int32_t n, double w_charb, double w_l1,
                float eps, double* sums, float* grad, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- The perceptual (VGG feature) term of fine-tuning (csrc/perceptual.hip) --------------------
+ * History: added after ABI 25 without a new version number -- entry points only, no struct or
+ * existing entry point changes, so RRIN_ABI_VERSION stays 25; a caller finds out whether a build
+ * has them by looking the symbols up.
+ *
+ * What torchvision's vgg19().features[:-10] needs besides its convs (those are rrin_tconv3x3 / the
+ * Winograd training route with leaky = 0), and the distance of two feature tensors;
+ * rrin_amd/perceptual.py is the definition.  All tensors are contiguous fp32 on the device, 4-byte
+ * aligned; 16-byte aligned tensors (pool: and w a multiple of 4) take 16-byte accesses.
+ *
+ * rrin_trelu_fwd: y = x < 0 ? +0 : x over count elements -- torch.relu's bits: -0 and a NaN pass.
+ * rrin_trelu_bwd: gx = y > 0 ? gy : 0 with y the forward's output (0 where y is a NaN).  In place is
+ * allowed: x == y, gy == gx (any other overlap is not).
+ *
+ * rrin_tmaxpool2_fwd: MaxPool2d(2, 2) of x [nc][h][w] into y [nc][h/2][w/2].  A window is scanned in
+ * row-major order and a later element replaces the maximum if it is greater or a NaN (PyTorch's CPU
+ * rule): of equal maxima the first is the arg-max, with NaNs the last NaN, and y is then a NaN.
+ * rrin_tmaxpool2_bwd: gx [nc][h][w] from gy [nc][h/2][w/2] and the forward's input x: the arg-max is
+ * found in x again and gets the window's gy, the window's other three elements get 0 -- every element
+ * of gx is written, by the one lane that owns its window; no index tensor, no atomics.
+ *
+ * rrin_tfeatdist: sums[0] = sum (a - b)^2 over count elements in float64 (each difference exact, each
+ * square rounded once) and, unless grad is NULL, grad = (a - b) / sqrt(sums[0]) divided in float64 and
+ * rounded to fp32 -- the gradient of torch.norm(a - b, 2) with respect to a; all zeros when the sum is
+ * 0.  The sum is rrin_tloss's reduction: float64 per lane, a fixed shuffle tree, one partial per
+ * workgroup in the workspace, added in index order by a one-workgroup step: no atomics, the same bits
+ * on every run.  grad is a further launch that reads sums[0] from device memory (no host round
+ * trip).  sums (1 double) and workspace are 8-byte aligned device memory, workspace_bytes >=
+ * rrin_tfeatdist_workspace_bytes(count) (RRIN_E_WORKSPACE otherwise; the query returns RRIN_E_SHAPE
+ * for count < 1).
+ *
+ * Codes, all returned before any launch: a null required pointer or a misaligned one: RRIN_E_ARG;
+ * count < 1, nc < 1, h or w odd or < 2: RRIN_E_SHAPE; a workspace that is too small:
+ * RRIN_E_WORKSPACE. */
+int rrin_trelu_fwd(const float* x, float* y, int64_t count, void* stream);
+int rrin_trelu_bwd(const float* gy, const float* y, float* gx, int64_t count, void* stream);
+int rrin_tmaxpool2_fwd(const float* x, float* y, int32_t nc, int32_t h, int32_t w, void* stream);
+int rrin_tmaxpool2_bwd(const float* gy, const float* x, float* gx, int32_t nc, int32_t h, int32_t w, void* stream);
+int64_t rrin_tfeatdist_workspace_bytes(int64_t count);
+int rrin_tfeatdist(const float* a, const float* b, int64_t count, double* sums, float* grad, void* workspace,
+                   int64_t workspace_bytes, void* stream);
+
 /* ---- An extra plane (alpha, depth, ID) through the byte-frame forwards (csrc/plane.hip, net.hip) --
  * History: added after ABI 25 without a new version number -- a new struct passed to new entry
  * points only, no existing struct or entry point changes, so RRIN_ABI_VERSION stays 25; a caller

@@ -96,7 +96,28 @@ def build_parser():
                     help="no random crop origin, flip or time reversal")
     ft.add_argument("--report", type=str, default=None, metavar="PATH",
                     help="write the losses, the schedule and both validations here as JSON")
+    ft.add_argument("--vgg_weights", type=str, default=None, metavar="PATH",
+                    help="a VGG19 state dict on disk (torchvision's vgg19-*.pth; keys features.N.weight/bias or "
+                         "N.weight/bias): adds the reference's perceptual term, w_vgg * ||VGG19[:relu4_4](out) - "
+                         "VGG19[:relu4_4](truth)||, to the loss.  The file is never downloaded; a missing or "
+                         "mismatching one is an error before the clip is read")
+    ft.add_argument("--w_vgg", type=float, default=0.1,
+                    help="weight of the perceptual term (default 0.1, the reference's CombinedLoss / 10)")
+    ft.add_argument("--vgg_cfg", type=_vgg_cfg, default=None, metavar="64,64,M,...",
+                    help="the conv stack the weights file is checked against, output channels and M for a 2x2 "
+                         "max pool (default: VGG19 up to relu4_4; other stacks are for tests)")
     return p
+
+
+def _vgg_cfg(text):
+    """``4,4,M,8`` -> (4, 4, "M", 8)."""
+    try:
+        cfg = tuple("M" if v.strip() == "M" else int(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"a conv stack is comma-separated ints and M, got {text!r}")
+    if not cfg or cfg.count("M") != 3 or any(v != "M" and v < 1 for v in cfg):
+        raise argparse.ArgumentTypeError(f"a conv stack has positive widths and three M, got {text!r}")
+    return cfg
 
 
 def _spans(text):

@@ -357,6 +357,14 @@ SIGNATURES = {
     "rrin_tloss_workspace_bytes": (C.c_int64, [C.c_int64]),
     "rrin_tloss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_float,
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rrin_trelu_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rrin_trelu_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rrin_tmaxpool2_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "rrin_tmaxpool2_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_void_p]),
+    "rrin_tfeatdist_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "rrin_tfeatdist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.c_void_p]),
     "rrin_unet_conv_count": (C.c_int64, [C.c_int32]),
     "rrin_unet_fwd": (C.c_int, [C.POINTER(UNetDesc), C.c_void_p]),
     "rrin_prof_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),

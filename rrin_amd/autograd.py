@@ -20,6 +20,10 @@ Function               forward (reference op)                       backward
 The glue between them (cat, the flow t-blend, sigmoid, the blend division,
 the residual add and clamp; `model.py:33-63`) is elementwise PyTorch autograd.
 On a CPU device the model keeps the PyTorch-operator graph (``Net._forward_autograd``).
+
+The losses of fine-tuning are Functions too: ``frame_loss`` (``csrc/finetune.hip``) and the optional
+VGG19 perceptual term ``perceptual_loss`` with its ``relu``, ``max_pool2`` and ``feature_distance``
+(``csrc/perceptual.hip``; the definition is ``rrin_amd/perceptual.py``).
 """
 from __future__ import annotations
 
@@ -397,3 +401,229 @@ def frame_loss(out, target, w_charb=1e-3, w_l1=1e-1, eps=1e-6, return_sums=False
     ``10 * log10(count / sums[2])``), from the same pass."""
     loss, sums = _FrameLoss.apply(out, target, float(w_charb), float(w_l1), float(eps))
     return (loss, sums) if return_sums else loss
+
+
+# ---- the perceptual term: VGG19 features up to relu4_4 and their distance ------------------------------
+# rrin_amd/perceptual.py is the definition (the reference's VggLoss, losses.py:6-26).  The convs are
+# the training route above with a linear epilogue (the training convs refuse a slope of 0, and ReLU is
+# its own kernel); csrc/perceptual.hip has ReLU, the 2x2 max pool and the feature distance.  The VGG
+# weights are frozen: a conv keeps nothing for its backward (it is linear in its input), there is
+# no weight gradient, and the Winograd packs of both directions are built once per VggFeatures and
+# device.  In PROF the term's launches carry kinds that start with "vgg_" (a conv as a whole,
+# layout passes included, next to the "fwd" / "dgrad" entry of its kernel).
+VGG_PACKS = 0   # Winograd packs built for frozen VGG weights since import (tests: no repacking)
+
+
+class _VggDevice:
+    """What a VggFeatures keeps on one device: weights and biases there and, on the Winograd route,
+    per conv the packs of the forward and of the data-gradient conv with their padded biases."""
+
+    def __init__(self, vgg, device):
+        self.cfg, self.layout = vgg.cfg, vgg.layout
+        self.weights = [w.to(device) for w in vgg.weights]
+        self.biases = [b.to(device) for b in vgg.biases]
+        self.fwd, self.dgrad = {}, {}
+
+    def pack(self, k, mode, st):
+        global VGG_PACKS
+        cache = self.dgrad if mode else self.fwd
+        if k not in cache:
+            _, cin, cout = self.layout[k]
+            rows, cols = (cin, cout) if mode else (cout, cin)
+            wp, cfg, bm = _wino_pack(self.weights[k], rows, cols, mode, st)
+            bp = torch.zeros(((rows + bm - 1) // bm) * bm, dtype=torch.float32, device=wp.device)
+            if not mode:
+                bp[:cout] = self.biases[k]
+            VGG_PACKS += 1
+            cache[k] = (wp, cfg, bp)
+        return cache[k]
+
+
+def _vgg_device(vgg, device):
+    st = vgg._device.get(device)
+    if st is None:
+        st = vgg._device[device] = _VggDevice(vgg, device)
+    return st
+
+
+class _FrozenConv3x3(torch.autograd.Function):
+    """Conv k of a VGG stack, bias and no activation; the gradient goes to the input only."""
+
+    @staticmethod
+    def forward(ctx, x, state, k):
+        x = _f32(x)
+        n, cin, h, w = x.shape
+        _, want, cout = state.layout[k]
+        if cin != want:
+            raise ValueError(f"VGG conv {k} takes {want} channels, got {tuple(x.shape)}")
+        st = _stream(x.device)
+        with _ProfScope(x.device, 0.0, "vgg_conv"):
+            if TRAIN_WINO:
+                wp, cfg, bp = state.pack(k, 0, st)
+                y = _wino_conv(x, wp, bp, cout, cfg, False, st, "f")
+            else:
+                y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
+                d = _lib.TConvDesc(n=n, cin=cin, cout=cout, h=h, w=w, mode=_lib.TCONV_FWD, leaky=0, slope=LEAKY_SLOPE,
+                                   x=x.data_ptr(), y=None, wt=state.weights[k].data_ptr(),
+                                   bias=state.biases[k].data_ptr(), out=y.data_ptr())
+                with _ProfScope(x.device, 2.0 * 9 * cin * cout * h * w * n, "fwd"):
+                    _lib.check(_lib.lib().rrin_tconv3x3(C.byref(d), st), "rrin_tconv3x3 (VGG forward)")
+        ctx.state, ctx.k = state, k
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        state, k = ctx.state, ctx.k
+        gy = _f32(gy)
+        n, cout, h, w = gy.shape
+        cin = state.layout[k][1]
+        st = _stream(gy.device)
+        with _ProfScope(gy.device, 0.0, "vgg_conv"):
+            if TRAIN_WINO:
+                wp, cfg, zb = state.pack(k, 1, st)
+                gx = _wino_conv(gy, wp, zb, cin, cfg, False, st, "d")
+            else:
+                gx = torch.empty((n, cin, h, w), dtype=torch.float32, device=gy.device)
+                d = _lib.TConvDesc(n=n, cin=cin, cout=cout, h=h, w=w, mode=_lib.TCONV_DGRAD, leaky=0, slope=LEAKY_SLOPE,
+                                   x=gy.data_ptr(), y=None, wt=state.weights[k].data_ptr(), bias=None,
+                                   out=gx.data_ptr())
+                with _ProfScope(gy.device, 2.0 * 9 * cin * cout * h * w * n, "dgrad"):
+                    _lib.check(_lib.lib().rrin_tconv3x3(C.byref(d), st), "rrin_tconv3x3 (VGG dgrad)")
+        return gx, None, None
+
+
+class _Relu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, inplace: bool):
+        inplace = bool(inplace) and x.is_contiguous()
+        x = _f32(x)
+        y = x if inplace else torch.empty_like(x)
+        if x.numel():
+            with _ProfScope(x.device, 0.0, "vgg_relu"):
+                _lib.check(_lib.lib().rrin_trelu_fwd(x.data_ptr(), y.data_ptr(), x.numel(), _stream(x.device)),
+                           "rrin_trelu_fwd")
+        if inplace:
+            ctx.mark_dirty(x)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        y, = ctx.saved_tensors
+        gy = _f32(gy)
+        gx = torch.empty_like(gy)
+        if gy.numel():
+            with _ProfScope(gy.device, 0.0, "vgg_relu"):
+                _lib.check(_lib.lib().rrin_trelu_bwd(gy.data_ptr(), y.data_ptr(), gx.data_ptr(), gy.numel(),
+                                                     _stream(gy.device)), "rrin_trelu_bwd")
+        return gx, None
+
+
+class _MaxPool2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = _f32(x)
+        n, c, h, w = x.shape
+        if h < 2 or w < 2 or h % 2 or w % 2:
+            raise ValueError(f"max_pool2 takes even H and W >= 2, got {tuple(x.shape)}")
+        y = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
+        with _ProfScope(x.device, 0.0, "vgg_pool"):
+            _lib.check(_lib.lib().rrin_tmaxpool2_fwd(x.data_ptr(), y.data_ptr(), n * c, h, w, _stream(x.device)),
+                       "rrin_tmaxpool2_fwd")
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, = ctx.saved_tensors
+        gy = _f32(gy)
+        n, c, h, w = x.shape
+        gx = torch.empty_like(x)
+        with _ProfScope(x.device, 0.0, "vgg_pool"):
+            _lib.check(_lib.lib().rrin_tmaxpool2_bwd(gy.data_ptr(), x.data_ptr(), gx.data_ptr(), n * c, h, w,
+                                                     _stream(x.device)), "rrin_tmaxpool2_bwd")
+        return gx
+
+
+def _tfeatdist(a, b, want_grad=True):
+    """rrin_tfeatdist on two fp32 device tensors of one shape: (sums float64 ``[1]`` on the device, grad
+    fp32 like ``a`` or None)."""
+    a, b = _f32(a), _f32(b)
+    if a.shape != b.shape or a.numel() < 1:
+        raise ValueError(f"feature_distance takes two tensors of one shape, got {tuple(a.shape)} / {tuple(b.shape)}")
+    if a.device != b.device:
+        raise RuntimeError(f"feature_distance: tensors on {a.device} / {b.device}")
+    L = _lib.lib()
+    count = a.numel()
+    need = int(L.rrin_tfeatdist_workspace_bytes(count))
+    if need < 0:
+        _lib.check(need, "rrin_tfeatdist_workspace_bytes")
+    ws = torch.empty(need // 8, dtype=torch.float64, device=a.device)
+    sums = torch.empty(1, dtype=torch.float64, device=a.device)
+    grad = torch.empty_like(a) if want_grad else None
+    with _ProfScope(a.device, 0.0, "vgg_dist"):
+        _lib.check(L.rrin_tfeatdist(a.data_ptr(), b.data_ptr(), count, sums.data_ptr(),
+                                    grad.data_ptr() if want_grad else None, ws.data_ptr(), need, _stream(a.device)),
+                   "rrin_tfeatdist")
+    return sums, grad
+
+
+class _FeatDist(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        sums, grad = _tfeatdist(a, b, want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(grad)
+        return torch.sqrt(sums[0])
+
+    @staticmethod
+    def backward(ctx, gloss):
+        grad, = ctx.saved_tensors
+        return (grad * gloss.to(grad.dtype) if grad is not None else None), None
+
+
+def relu(x, inplace=False):
+    """torch.relu on the device (rrin_trelu_fwd / _bwd: ``gx = y > 0 ? gy : 0``).  ``inplace`` overwrites a
+    contiguous ``x``, which then must not be needed by the backward of the operator that made it."""
+    return _Relu.apply(x, inplace)
+
+
+def max_pool2(x):
+    """F.max_pool2d(x, 2, 2) on the device; the backward recomputes the arg-max from ``x`` (the first
+    maximum of a window in row-major order)."""
+    return _MaxPool2.apply(x)
+
+
+def feature_distance(a, b):
+    """``torch.norm(a - b, 2)`` of two fp32 device tensors of one shape as a float64 scalar on the device,
+    one deterministic float64 sum (rrin_tfeatdist).  The gradient ``(a - b) / norm`` (zeros where the
+    norm is 0) is written by the same call and goes to ``a`` only."""
+    return _FeatDist.apply(a, b)
+
+
+def _vgg_features(state, x):
+    k = 0
+    for v in state.cfg:
+        if v == "M":
+            x = max_pool2(x)
+        else:
+            x = relu(_FrozenConv3x3.apply(x, state, k), inplace=True)   # the conv keeps nothing: in place
+            k += 1
+    return x
+
+
+def perceptual_loss(out, target, vgg):
+    """``rrin_amd.perceptual.perceptual_loss`` on a ROCm device: a float64 scalar.  ``vgg`` is a
+    :class:`rrin_amd.perceptual.VggFeatures` (on any device: its weights and Winograd packs are kept on
+    ``out``'s device after the first call).  The target branch runs under ``no_grad`` and keeps none of
+    its activations; the output branch keeps its 12 ReLU outputs (a pool reads the one in front of
+    it) and the distance's gradient.  Only data-gradient convs run in the backward."""
+    from . import perceptual
+    perceptual.check_frames(out, target, vgg)
+    if not out.is_cuda or out.device != target.device:
+        raise TypeError("rrin_amd.autograd.perceptual_loss takes two tensors on one ROCm device")
+    state = _vgg_device(vgg, out.device)
+    with torch.no_grad():
+        ft = _vgg_features(state, target.detach())
+    return feature_distance(_vgg_features(state, out), ft)

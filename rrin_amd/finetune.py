@@ -4,8 +4,10 @@ input, held-out truth, second input) crops of the clip itself.
 What is carried over from the reference: its random crop and flip (dataloader.py:36-51,132-138),
 its two loss terms that need no downloaded weights with their weights (``charbonnierLoss / 1e3 +
 L1Loss / 10``: losses.py:39-42, train.py:105), AdamW at 1e-4 (train.py:49) and its checkpoint
-(train.py:158-161).  What is not: the VGG19 perceptual term, the learning-rate schedule, PNG
-folders and the resize branch of the data loader.  The whole clip stays on the device.
+(train.py:158-161).  The VGG19 perceptual term of ``CombinedLoss`` (losses.py:6-36) is optional: it
+needs a weights file that is already on disk (:mod:`rrin_amd.perceptual`; ``finetune_y4m(vgg=)``).
+What is not: the learning-rate schedule, PNG folders and the resize branch of the data loader.  The
+whole clip stays on the device.
 
 As with :mod:`rrin_amd.yuv` and :mod:`rrin_amd.metrics` the functions here are the *definition*;
 on a device ``csrc/finetune.hip`` computes the same (the sampler bit for bit, the loss within a few
@@ -389,7 +391,7 @@ def excluded_pairs(model, clip, n, scene_threshold):
 
 def finetune_y4m(model, src, steps, batch=2, crop=256, spans=(2,), lr=1e-4, seed=0, scene_threshold=None,
                  val_fraction=0.1, max_bytes=8 << 30, save=None, augment=True, log=print, log_every=50, coef=None,
-                 epoch=0):
+                 epoch=0, vgg=None, w_vgg=0.1):
     """Fine-tune ``model`` on the Y4M clip ``src`` (a path or a binary file object; every format
     ``convert --y4m_in`` takes), in place, on the model's device.
 
@@ -401,17 +403,30 @@ def finetune_y4m(model, src, steps, batch=2, crop=256, spans=(2,), lr=1e-4, seed
     :func:`triplet_schedule` (``seed``, ``augment``) runs :func:`sample_triplets`, ``model(I0, I1, t)``
     under autograd, the loss (``autograd.frame_loss``; on the CPU :func:`frame_loss_ref` over
     ``Net._forward_autograd``), ``backward`` and ``torch.optim.AdamW(lr)`` (train.py:49).  There is no
-    VGG19 term and no learning-rate schedule.  The CPU path is slow: it is there for tests and for
-    checking.
+    learning-rate schedule.  The CPU path is slow: it is there for tests and for checking.
+
+    ``vgg``: a :class:`rrin_amd.perceptual.VggFeatures` or the path of a VGG19 state dict on disk (read
+    before the clip; the file is never fetched).  The loss is then ``frame_loss + w_vgg *
+    perceptual_loss(out, truth, vgg)``, the reference's ``CombinedLoss / 10 + charbonnierLoss / 1e3``
+    (train.py:105) at the default ``w_vgg`` (``autograd.perceptual_loss``; on the CPU
+    ``perceptual.perceptual_loss``).  None (default): no such term, and nothing else changes.
 
     Returns ``{"losses": [float per step], "logged": [{"step", "loss", "sums", "psnr"} for every
     ``log_every``-th step and the last], "val_before", "val_after" (:func:`validate`'s dicts or None),
     "schedule" (the steps), "cut_pairs", "duplicate_pairs" (counts of excluded pairs), "frames",
-    "train_frames", "val_frames", "truncated", "tag"}``.  ``save``: a path that gets ``{'model':
+    "train_frames", "val_frames", "truncated", "tag", "vgg" (the weights' file name, "synthetic", or None),
+    "w_vgg", "perceptual" ([the unweighted term per step], empty without ``vgg``; the logged steps carry
+    it too)}``.  ``save``: a path that gets ``{'model':
     state_dict, 'optim': ..., 'epoch': epoch + 1}`` on the CPU, the reference's checkpoint
     (train.py:158-161), which ``convert.load_net`` and a reference ``--resume`` read."""
     from .autograd import frame_loss
     device = next(model.parameters()).device
+    if vgg is not None:   # before the clip is read: a missing or mismatching file ends the call here
+        from . import perceptual
+        if not isinstance(vgg, perceptual.VggFeatures):
+            vgg = perceptual.VggFeatures.load(vgg)
+        if not math.isfinite(w_vgg):
+            raise ValueError(f"w_vgg must be finite, got {w_vgg!r}")
     on_gpu = device.type == "cuda"
     spans = tuple(int(s) for s in spans)
     ch, cw = _crop2(crop)
@@ -433,8 +448,10 @@ def finetune_y4m(model, src, steps, batch=2, crop=256, spans=(2,), lr=1e-4, seed
     val_before = validate(model, clip, n_train, hold, coef=coef) if n_val else None
     optim = torch.optim.AdamW(model.parameters(), lr=lr)
     count = batch * 3 * ch * cw
-    losses, logged = [], []
-    pending = []   # (step, loss tensor, sums tensor): read on the host at the logged steps only
+    losses, logged, percs = [], [], []
+    pending = []   # (step, loss tensor, sums tensor, perceptual term): read on the host at the logged steps only
+    if vgg is not None and not on_gpu:
+        vgg = vgg.to(device)
     for k, step in enumerate(schedule):
         i0, it, i1 = sample_triplets(clip.frames, step.items, (ch, cw), clip.layout, coef, clip.depth)
         t = float(step.t)
@@ -446,17 +463,32 @@ def finetune_y4m(model, src, steps, batch=2, crop=256, spans=(2,), lr=1e-4, seed
             out = model._forward_autograd(i0, i1, t)
             loss = frame_loss_ref(out, it)
             sums = frame_loss_parts_ref(out, it)[0]
+        perc = None
+        if vgg is not None:
+            if on_gpu:
+                from .autograd import perceptual_loss
+                perc = perceptual_loss(out, it, vgg)
+            else:
+                perc = perceptual.perceptual_loss(out, it, vgg).double()
+            loss = loss + w_vgg * perc
+            perc = perc.detach()
         loss.backward()
         optim.step()
-        pending.append((k + 1, loss.detach(), sums))
+        pending.append((k + 1, loss.detach(), sums, perc))
         if (k + 1) % log_every == 0 or k + 1 == len(schedule):
-            for s_, l_, m_ in pending:   # one trip to the host per logged step
+            for s_, l_, m_, p_ in pending:   # one trip to the host per logged step
                 losses.append(float(l_))
+                if p_ is not None:
+                    percs.append(float(p_))
             m = [float(v) for v in sums.tolist()]
             psnr = 10.0 * math.log10(count / m[2]) if m[2] > 0 else None   # train.py:112-113
             logged.append({"step": k + 1, "loss": losses[-1], "sums": m, "psnr": psnr})
-            log(f"step: {k + 1:5d}, psnr {psnr if psnr is None else round(psnr, 4)}, loss {losses[-1]:8.6f} "
-                f"charb {W_CHARB * m[0] / batch:8.6f}, l1 {W_L1 * m[1] / count:8.6f}")
+            line = (f"step: {k + 1:5d}, psnr {psnr if psnr is None else round(psnr, 4)}, loss {losses[-1]:8.6f} "
+                    f"charb {W_CHARB * m[0] / batch:8.6f}, l1 {W_L1 * m[1] / count:8.6f}")
+            if vgg is not None:
+                logged[-1]["perceptual"] = percs[-1]
+                line += f", vgg {w_vgg * percs[-1]:8.6f}"
+            log(line)
             pending = []
     val_after = validate(model, clip, n_train, hold, coef=coef) if n_val else None
     if save is not None:
@@ -469,7 +501,9 @@ def finetune_y4m(model, src, steps, batch=2, crop=256, spans=(2,), lr=1e-4, seed
         f"{clip.tag}) in {time.time() - t_start:.2f} s; {len(cuts)} cut and {len(dups)} duplicate pairs excluded")
     return {"losses": losses, "logged": logged, "val_before": val_before, "val_after": val_after,
             "schedule": schedule, "cut_pairs": len(cuts), "duplicate_pairs": len(dups), "frames": n,
-            "train_frames": n_train, "val_frames": n_val, "truncated": clip.truncated, "tag": clip.tag}
+            "train_frames": n_train, "val_frames": n_val, "truncated": clip.truncated, "tag": clip.tag,
+            "vgg": None if vgg is None else vgg.name, "w_vgg": None if vgg is None else float(w_vgg),
+            "perceptual": percs}
 
 
 def finetune(args):
@@ -484,6 +518,10 @@ def finetune(args):
     if args.no_cuda or not torch.cuda.is_available():
         raise RuntimeError("rrin_amd runs on ROCm GPUs only")
     dev = torch.device("cuda", torch.cuda.current_device())
+    vgg = None
+    if getattr(args, "vgg_weights", None):   # first: a missing or mismatching file is an error before the clip is read
+        from .perceptual import VGG19_RELU4_4, VggFeatures
+        vgg = VggFeatures.load(args.vgg_weights, getattr(args, "vgg_cfg", None) or VGG19_RELU4_4)
     path = convert.find_checkpoint(args.model_name)
     state = torch.load(path, map_location="cpu", weights_only=True)
     epoch = int(state.get("epoch", 0)) if isinstance(state, dict) and "model" in state else 0
@@ -492,11 +530,11 @@ def finetune(args):
     res = finetune_y4m(net, sys.stdin.buffer if args.y4m_in == "-" else args.y4m_in, args.steps, batch=args.batch,
                        crop=args.crop, spans=args.spans, lr=args.lr, seed=args.seed,
                        scene_threshold=args.scene_threshold, val_fraction=args.val_fraction, save=dest,
-                       augment=not args.no_augment, epoch=epoch)
+                       augment=not args.no_augment, epoch=epoch, vgg=vgg, w_vgg=getattr(args, "w_vgg", 0.1))
     print(f"Saved {dest}.")
     res["schedule"] = [{"span": s.span, "j": s.j, "t": float(s.t), "reversed": s.reversed,
                         "items": [list(i) for i in s.items]} for s in res["schedule"]]
-    summary = {k: v for k, v in res.items() if k not in ("schedule", "losses")}
+    summary = {k: v for k, v in res.items() if k not in ("schedule", "losses", "perceptual")}
     summary["checkpoint"] = dest
     print(json.dumps(summary, indent=1))
     if args.report:

@@ -9,6 +9,10 @@
    written with PyTorch operators on the device -- the comparison, since there is no other such
    path -- timed with HIP events over ``--calls`` calls a window, alternately, ``--rounds`` windows each.
 3. The share of the whole step that the two fused calls take.
+4. With ``--vgg``: the step with the perceptual term (``autograd.perceptual_loss`` at ``w_vgg`` 0.1 over keyed
+   synthetic weights at VGG19's real widths -- no kernel's time depends on the values), windows with and
+   without the term alternating, and the term's own share of the step from ``autograd.PROF`` (HIP events
+   around each of its launches over ``--prof-steps`` further steps).
 
 Prints one JSON line.  Not a test; needs a GPU.  One process; ``--time-limit`` seconds end it.
 
@@ -73,6 +77,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--time-limit", type=int, default=540)
+    ap.add_argument("--vgg", action="store_true", help="also time the step with the VGG19 perceptual term")
+    ap.add_argument("--prof-steps", type=int, default=3, help="--vgg: steps under autograd.PROF")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("finetune_bench needs a ROCm device")
@@ -87,25 +93,54 @@ def main():
     net = net.to(dev).train()
     optim = torch.optim.AdamW(net.parameters(), lr=1e-4)
     sched = ft.triplet_schedule(a.frames, (h0, w0), (2, 2), (2,), a.warmup + a.steps * a.rounds, a.batch, ch, 0)
+    vgg = None
+    if a.vgg:
+        from rrin_amd.perceptual import VggFeatures
+        vgg = VggFeatures.synthetic()
 
-    def step(s):
+    def step(s, term=False):
         i0, it, i1 = ft.sample_triplets(frames, s.items, ch, "i420")
         optim.zero_grad(set_to_none=True)
-        loss = autograd.frame_loss(net(i0, i1, float(s.t)), it)
+        out = net(i0, i1, float(s.t))
+        loss = autograd.frame_loss(out, it)
+        if term:
+            loss = loss + 0.1 * autograd.perceptual_loss(out, it, vgg)
         loss.backward()
         optim.step()
 
     for s in sched[:a.warmup]:
         step(s)
     torch.cuda.synchronize(dev)
-    step_ms = []
+    if a.vgg:
+        for s in sched[:a.warmup]:
+            step(s, True)
+        torch.cuda.synchronize(dev)
+    step_ms, vgg_ms = [], []
     for r in range(a.rounds):
         part = sched[a.warmup + r * a.steps:a.warmup + (r + 1) * a.steps]
-        t0 = time.perf_counter()
-        for s in part:
-            step(s)
+        for term, dest in ((False, step_ms), (True, vgg_ms))[:2 if a.vgg else 1]:   # alternating windows
+            t0 = time.perf_counter()
+            for s in part:
+                step(s, term)
+            torch.cuda.synchronize(dev)
+            dest.append((time.perf_counter() - t0) * 1e3 / len(part))
+    vgg_report = {}
+    if a.vgg:
+        autograd.PROF = []
+        for s in sched[a.warmup:a.warmup + a.prof_steps]:
+            step(s, True)
         torch.cuda.synchronize(dev)
-        step_ms.append((time.perf_counter() - t0) * 1e3 / len(part))
+        events, autograd.PROF = autograd.PROF, None
+        by_kind = {}
+        for e0, e1, _, kind in events:
+            if kind.startswith("vgg_"):   # the term's launches (a conv as a whole; its kernel is also under fwd / dgrad)
+                by_kind[kind] = by_kind.get(kind, 0.0) + e0.elapsed_time(e1) / a.prof_steps
+        med_vgg = statistics.median(vgg_ms)
+        vgg_report = {"step_ms_vgg": [round(x, 2) for x in vgg_ms], "median_step_ms_vgg": round(med_vgg, 2),
+                      "vgg_event_ms_per_step": {k: round(v, 3) for k, v in sorted(by_kind.items())},
+                      "vgg_event_ms_total": round(sum(by_kind.values()), 3),
+                      "vgg_share_of_step": round(sum(by_kind.values()) / med_vgg, 4),
+                      "record_buffers_cached": len(autograd._R32_BUFS or ()), "record_buffers_max": autograd.R32_BUFS_MAX}
 
     items = sched[0].items
     out = torch.rand((a.batch, 3, ch, ch), generator=g).to(dev)
@@ -156,7 +191,7 @@ def main():
         "median_us": {k: round(v, 1) for k, v in med.items()},
         "torch_ops_over_fused": round(med["torch_ops"] / med["fused"], 2),
         "fused_share_of_step": round(med["fused"] / (ms * 1e3), 4),
-        "triplets_max_abs_diff": diff, "loss_fused": la, "loss_torch_ops": lb}))
+        "triplets_max_abs_diff": diff, "loss_fused": la, "loss_torch_ops": lb, **vgg_report}))
 
 
 if __name__ == "__main__":
