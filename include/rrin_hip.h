@@ -1094,6 +1094,38 @@ int rrin_net_yuv_plane_fwd(const rrin_net_yuv_desc* d, const rrin_items* items, 
 int rrin_net_yuv16_plane_fwd(const rrin_net_yuv16_desc* d, const rrin_items* items, const rrin_flow_scale* fs,
                              const rrin_aux_plane* plane, void* stream);
 
+/* ---- The exposure of a synthetic shutter: the rounded mean of byte frames ---------------------
+ * History: added after ABI 25 without a new version number -- one new entry point, no struct and no
+ * existing entry point changes, so RRIN_ABI_VERSION stays 25; a caller finds out whether a build
+ * has it by looking the symbol up.
+ *
+ * rrin_mean_frames (rrin_amd/exposure.py is the definition): g output frames of len elements each,
+ * frame j at out + j * out_stride (elements).  frames: a DEVICE table of k frame pointers (8-byte
+ * aligned); start: a DEVICE int32 [g + 1] in CSR form, start[0] = 0 <= ... <= start[g] = k: output j is
+ * the mean of the S = start[j+1] - start[j] frames frames[start[j] .. start[j+1]), 1 <= S <= 256,
+ *   out[j][e] = ((sum_k s_k[e]) + S / 2) / S << shift      s_k[e] = min(word >> shift, 2^depth - 1)
+ * per element e, in integers: ties round up, a sum of 256 16-bit samples is far inside 32 bits, and
+ * the result is the same bits on every run (no atomics).  depth 8: uint8 elements (shift 0); depth
+ * 9..16: uint16 words at even addresses, 0 <= shift <= 16 - depth, as in rrin_aux_plane.  A pointer
+ * table, not base + stride, because the sources are views of a frame stack and outputs of several
+ * item forwards: a source may be listed more than once, and may start at any element.  Each source
+ * holds len elements; nothing outside [frame, frame + len) is read or written, and elements between
+ * the frames of out are not written.  A group whose S read from start is outside 1..256 (after
+ * clamping the offsets to [0, k]) is skipped: its frame is not written.
+ *
+ * access: the bytes one lane reads and writes at a time -- the element size, 4 or 16.  The caller,
+ * who knows every address, passes the largest of them that divides every source address, out and
+ * (g > 1) out_stride in bytes; the kernel takes the len % (access / element size) elements behind the
+ * last whole run one at a time.  The source addresses live in device memory, so that they are
+ * multiples of access is the caller's promise; everything else is checked here.
+ * RRIN_E_ARG: a null pointer, a table not 8-byte or a start not 4-byte aligned, depth outside 8..16,
+ * shift outside 0..16 - depth (depth 8: shift 0), access not one of the three, out (an odd word address
+ * included) or out_stride not a multiple of access, g > 1 with out_stride < len, k < g or k > 256 g.
+ * RRIN_E_SHAPE: g < 1, g > 65535, len < 1, more than 2^31 - 1 workgroups per frame.  Validated before
+ * any launch. */
+int rrin_mean_frames(const void* const* frames, int32_t k, const int32_t* start, int32_t g, void* out,
+                     int64_t out_stride, int64_t len, int32_t depth, int32_t shift, int32_t access, void* stream);
+
 /* ---- Training path (autograd): NCHW fp32 kernels ------------------------- */
 /* With autograd on (the reference trains through Net.forward, train.py:98, and
  * loss.backward(), train.py:144) rrin_amd.train wraps these in autograd

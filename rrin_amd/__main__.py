@@ -61,7 +61,15 @@ def build_parser():
     cv.add_argument("--fps_out", type=str, default=None, metavar="NUM[/DEN]",
                     help="with --y4m_in / --y4m_out: convert the stream's frame rate to this higher rate, e.g. "
                          "60000/1001 or 60 (24 -> 60, 25 -> 30, ...), instead of --sf intermediates per pair; "
-                         "needs --sf 0.  Quality at uneven t has not been validated on footage")
+                         "needs --sf 0 (with --samples: any rate).  Quality at uneven t has not been validated on "
+                         "footage")
+    cv.add_argument("--samples", type=int, default=None, metavar="S",
+                    help="with --fps_out: a synthetic shutter.  Every output frame is the mean of S (1..256) frames "
+                         "interpolated across the shutter window, and --fps_out may be ANY rate, lower ones included "
+                         "(60 -> 24, 120 -> 24).  The mean is over code values: no transfer function is applied")
+    cv.add_argument("--shutter", type=str, default=None, metavar="NUM/DEN",
+                    help="with --samples: the share of an output frame's time the shutter is open, in (0, 1], e.g. "
+                         "1/2 (the default, a 180 degree shutter)")
     ev = sub.add_parser("evaluate", help="Hold-out PSNR / SSIM of the model on a Y4M clip.")
     ev.add_argument("--y4m_in", type=str, required=True, metavar="PATH|-",
                     help="the clip: a Y4M stream of any format convert --y4m_in takes (\"-\": stdin)")

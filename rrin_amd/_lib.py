@@ -318,6 +318,8 @@ SIGNATURES = {
                                          C.POINTER(AuxPlane), C.c_void_p]),
     "rrin_net_yuv16_plane_fwd": (C.c_int, [C.POINTER(NetYuv16Desc), C.POINTER(Items), C.POINTER(FlowScale),
                                            C.POINTER(AuxPlane), C.c_void_p]),
+    "rrin_mean_frames": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+                                   C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "rrin_gate_items_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p]),
     "rrin_gate_frames_items_u8_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,

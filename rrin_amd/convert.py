@@ -501,7 +501,7 @@ def frame_path_of(src):
 
 
 def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coef=None, log=print, fps_out=None,
-                    flow_scale=1):
+                    flow_scale=1, samples=None, shutter=None):
     """Interpolate a Y4M stream (8-bit 4:2:0; also 10 / 12 bits and 4:2:2 / 4:4:4, below) into another: no image folder, no RGB frame anywhere.
 
     ``flow_scale`` 2 or 4 (:mod:`rrin_amd.flowscale`) goes to the model's ``interpolate_*`` call:
@@ -530,12 +530,24 @@ def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coe
 
     Exactly one of ``sf`` and ``fps_out`` is given.  ``fps_out`` (a ``fractions.Fraction``, an int or
     a string ``"60000/1001"`` / ``"60"``, above the stream's rate) converts the frame rate instead:
-    :func:`retime_y4m`."""
+    :func:`retime_y4m`.
+
+    ``samples`` (an int in 1..256, with ``fps_out``) turns every output into an exposure: the mean of
+    ``samples`` frames across a ``shutter`` (a Fraction, an int or a string ``"1/2"`` in (0, 1]; default
+    1/2) of the output's frame time, and ``fps_out`` may then be ANY positive rate, lower, equal or
+    higher: :func:`expose_y4m`.  Without ``samples`` nothing changes (``shutter`` alone raises)."""
     from . import y4m, yuv
     from .flowscale import check_flow_scale
     check_flow_scale(flow_scale)
     if (sf is None) == (fps_out is None):
         raise ValueError("interpolate_y4m takes exactly one of sf and fps_out")
+    if samples is None and shutter is not None:
+        raise ValueError("shutter needs samples: an exposure is the mean of `samples` frames over the shutter")
+    if samples is not None:
+        if fps_out is None:
+            raise ValueError("samples needs fps_out: an exposure belongs to a frame-rate conversion")
+        return expose_y4m(model, src, dst, fps_out, samples, shutter="1/2" if shutter is None else shutter,
+                          batch=batch, scene_threshold=scene_threshold, coef=coef, log=log, flow_scale=flow_scale)
     if fps_out is not None:
         return retime_y4m(model, src, dst, fps_out, batch=batch, scene_threshold=scene_threshold, coef=coef, log=log,
                           flow_scale=flow_scale)
@@ -779,6 +791,190 @@ def retime_y4m(model, src, dst, fps_out, batch=4, scene_threshold=None, coef=Non
         msg = (f"y4m: {n_in} frames of {w0}x{h0} at {rate_in.numerator}:{rate_in.denominator} fps -> {written} "
                f"frames at {rate_out.numerator}:{rate_out.denominator} fps in {time.time() - t0:.2f} s, "
                f"{passed} of them input frames passed through")
+        if gate_kw:
+            msg += f"; scene gate (threshold {scene_threshold:g}): {gated} items replaced by an input frame"
+        log(msg)
+        return written
+    finally:
+        for f in opened:
+            f.close()
+
+
+def expose_y4m(model, src, dst, fps_out, samples, shutter="1/2", batch=4, scene_threshold=None, coef=None, log=print,
+               flow_scale=1):
+    """Convert a Y4M stream to ANY frame rate ``fps_out`` -- lower (60 -> 24, 120 -> 24), equal or higher
+    -- with a synthetic shutter: ``interpolate_y4m(fps_out=, samples=)``.  Output j is the mean of
+    ``samples`` frames at the source times ``j * step + k * shutter * step / samples``, ``step = fps_in /
+    fps_out`` (:func:`rrin_amd.retime.exposure_schedule`; :mod:`rrin_amd.exposure` is the definition of the
+    mean: per stored byte or word, ties up, over code values -- no transfer function is applied).
+    Frames are fed to ``retime.ExposureStream``.  A step takes the next whole outputs until they hold at
+    least ``batch`` network items (or ``4 * batch`` outputs, which bounds a step whose samples all fall on
+    input frames), uploads the input frames they use as one pinned stack and calls
+    ``model.expose_items_yuv`` / ``expose_items_yuv16(stack, groups, chunk=batch, ...)``; one step is in
+    flight while the previous one is written.  An input frame that no later output needs is dropped as it
+    arrives (at 120 -> 24 with a 1/2 shutter two frames in five never go up).  An output with ``samples ==
+    1`` that falls on an input frame is written as that frame's own bytes, as :func:`retime_y4m` does, so
+    ``samples=1`` above the input's rate is that conversion.  The header carries ``fps_out`` reduced; tag,
+    depth, chroma, ``coef``, ``scene_threshold`` and ``flow_scale`` follow the stream as there (an exposure
+    across a cut mixes both shots).  Returns the frames written."""
+    from collections import deque
+
+    from . import retime, y4m, yuv
+    from .flowscale import check_flow_scale
+    check_flow_scale(flow_scale)
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("interpolate_y4m runs in a single process (a stream has one reader and one writer)")
+    if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+        raise ValueError(f"batch must be an int >= 1, got {batch!r}")
+    rate_out = retime.as_rate(fps_out)
+    n_samples = retime.check_samples(samples)
+    sh = retime.as_shutter(shutter)
+    opened = []
+    if isinstance(src, (str, os.PathLike)):
+        src = open(src, "rb")
+        opened.append(src)
+    if isinstance(dst, (str, os.PathLike)):
+        dst = open(dst, "wb")
+        opened.append(dst)
+    try:
+        rd = y4m.Reader(src, depths=(8, 10, 12), chroma=yuv.CHROMAS)
+        w0, h0 = rd.width, rd.height
+        if rd.fps_num < 1 or rd.fps_den < 1:
+            raise ValueError(f"Y4M: the stream has no frame rate to convert (F{rd.fps_num}:{rd.fps_den})")
+        rate_in = retime.as_rate(f"{rd.fps_num}/{rd.fps_den}")
+        sched = retime.ExposureStream(rate_in, rate_out, sh, n_samples)
+        wr = y4m.Writer(dst, w0, h0, rate_out.numerator, rate_out.denominator, rd.colorspace, depths=(8, 10, 12),
+                        chroma=yuv.CHROMAS)
+        layout = "i" + rd.chroma
+        suffix, depth_kw = frame_path_of(rd)
+        dtype = torch.uint16 if depth_kw else torch.uint8
+        device = next(model.parameters()).device
+        on_gpu = device.type == "cuda"   # a host model (tests) has nothing to pin for and no events
+        gate_kw = {} if scene_threshold is None else {"scene_threshold": scene_threshold}
+        scale_kw = {} if flow_scale == 1 else {"flow_scale": flow_scale}
+        rows = yuv.stack_rows(h0, layout)
+        t0 = time.time()
+        held = {}         # input frames an unsent or a future output needs, by index
+        order = deque()   # the outputs not written yet: a frame's array, None (not sent yet) or (step, index in it)
+        ready = deque()   # complete outputs not sent yet: (output index, its samples (pair, Fraction t))
+        steps = deque()   # steps on the device, oldest first
+        n_in = written = passed = gated = 0
+
+        def uses(output):
+            """The input frames an output reads: its samples' frames, and the next one where t > 0."""
+            need = set()
+            for pair, t in output:
+                need.add(pair)
+                if t != 0:
+                    need.add(pair + 1)
+            return need
+
+        def drain():
+            nonlocal written
+            while order and order[0] is not None and (not isinstance(order[0], tuple) or order[0][0]["done"]):
+                e = order.popleft()
+                wr.write(e[0]["host"][e[1]].numpy() if isinstance(e, tuple) else e)
+                written += 1
+
+        def retire(step):
+            nonlocal gated
+            if step["ev"] is not None:
+                step["ev"].synchronize()
+            if hasattr(model, "check_range"):
+                model.check_range(wait=False)  # fp16-stored precisions: raise instead of writing poisoned frames
+            if step["codes"] is not None:
+                gated += int((step["codes"] != 0).sum())
+            step["done"] = True
+            drain()
+
+        def send(outputs):
+            """One step: ``outputs`` on the stack of the frames they use.  The frames two used pairs
+            share are adjacent in it; a frame no sample reads is not in it (the outputs of a decimation
+            leave gaps), which moves no pair: both frames of a network item are always there."""
+            need = sorted(set().union(*[uses(o) for o in outputs]))  # two frames at least: samples > 1 or t > 0
+            pos = {j: i for i, j in enumerate(need)}
+            stack = torch.empty((len(need), rows, w0), dtype=dtype, pin_memory=on_gpu)
+            for j in need:
+                stack[pos[j]].view(-1).copy_(torch.from_numpy(held[j]))
+            stack = stack.to(device, non_blocking=True)
+            groups = [[(pos[p], float(t)) for p, t in o] for o in outputs]
+            with torch.no_grad():
+                out = getattr(model, "expose_items_" + suffix)(stack, groups, chunk=batch, layout=layout, coef=coef,
+                                                               **depth_kw, **gate_kw, **scale_kw)
+            host = torch.empty(out.shape, dtype=out.dtype, pin_memory=on_gpu)
+            host.copy_(out, non_blocking=True)
+            codes = None
+            if gate_kw:
+                lg = model.last_gate
+                codes = torch.empty(lg.shape, dtype=torch.int32, pin_memory=on_gpu)
+                codes.copy_(lg, non_blocking=True)
+            ev = None
+            if on_gpu:
+                ev = torch.cuda.Event()
+                ev.record()
+            step = {"ev": ev, "host": host, "codes": codes, "done": False}
+            steps.append(step)
+            k = 0
+            for i, e in enumerate(order):  # the step's outputs are the oldest unsent ones, in order
+                if e is None:
+                    order[i] = (step, k)
+                    k += 1
+                    if k == len(outputs):
+                        break
+            while len(steps) > 1:  # retire the previous step while this one computes
+                retire(steps.popleft())
+
+        def forget():
+            """Drops the frames before the first one that the oldest unsent output, or if there is none
+            the next output to come, reads."""
+            first = (ready[0][0] if ready else sched.outputs) * sched.step
+            first = first.numerator // first.denominator
+            for j in [j for j in held if j < first]:
+                del held[j]
+
+        def take(final: bool):
+            """Sends steps while the ready outputs hold ``batch`` network items or ``4 * batch`` outputs
+            (``final``: whatever is left)."""
+            while ready:
+                n_items, n_out = 0, 0
+                for _, o in ready:
+                    n_out += 1
+                    n_items += sum(1 for _, t in o if t != 0)
+                    if n_items >= batch or n_out >= 4 * batch:
+                        break
+                else:
+                    if not final:
+                        return
+                send([ready.popleft()[1] for _ in range(n_out)])
+                forget()
+
+        for fr in rd:
+            held[n_in] = fr
+            first = sched.outputs
+            for j, output in enumerate(sched.feed(), first):
+                if n_samples == 1 and output[0][1] == 0:  # the frame that has just arrived, as its own bytes
+                    order.append(fr)
+                    passed += 1
+                else:
+                    ready.append((j, output))
+                    order.append(None)
+            n_in += 1
+            take(False)
+            forget()
+            drain()
+        if n_in < 2:
+            raise ValueError("need at least two frames in the Y4M stream")
+        take(True)
+        while steps:
+            retire(steps.popleft())
+        drain()
+        if hasattr(model, "check_range"):
+            model.check_range()
+        wr.flush()
+        msg = (f"y4m: {n_in} frames of {w0}x{h0} at {rate_in.numerator}:{rate_in.denominator} fps -> {written} "
+               f"frames at {rate_out.numerator}:{rate_out.denominator} fps, each the mean of {n_samples} samples "
+               f"over a {sh.numerator}/{sh.denominator} shutter, in {time.time() - t0:.2f} s, {passed} of them input "
+               f"frames passed through")
         if gate_kw:
             msg += f"; scene gate (threshold {scene_threshold:g}): {gated} items replaced by an input frame"
         log(msg)
@@ -1039,7 +1235,8 @@ def _convert_y4m(args):
         net = load_net(args.model_name, dev, getattr(args, "precision", "fp32"))
         interpolate_y4m(net, src, dst, None if fps_out is not None else args.sf, batch=getattr(args, "batch", 4),
                         scene_threshold=getattr(args, "scene_threshold", None), fps_out=fps_out,
-                        flow_scale=getattr(args, "flow_scale", 1))
+                        flow_scale=getattr(args, "flow_scale", 1), samples=getattr(args, "samples", None),
+                        shutter=getattr(args, "shutter", None))
         print("Finished conversion")
 
 

@@ -454,6 +454,64 @@ def item_coefficients(ts, m: int) -> torch.Tensor:
     return torch.cat([t_coefficients(v, 1) for v in ts], dim=0)
 
 
+def mean_frames(groups, depth: int = 8, shift: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """rrin_mean_frames (:mod:`rrin_amd.exposure`) on the current stream: ``groups`` a list of ``G`` lists of
+    1..256 device tensors, each one dense frame of the same shape and dtype (uint8 at ``depth`` 8, else
+    uint16) -- views of any stack or buffer, starting at any element; a frame may be listed more than
+    once.  ``out``: ``[G, ...]`` with dense frames and a uniform stride over dim 0 (default: a fresh dense
+    stack); elements between its frames are not written.  Output g is ``exposure.mean_frames`` of group
+    g's frames.  The groups are checked before anything is uploaded (TypeError / ValueError); the pointer
+    table and the offsets go up as one small tensor; no host sync.  The access width (16, 4 or the
+    element's bytes) is the largest that divides every address involved."""
+    from .exposure import MAX_SAMPLES
+    from .plane import check_format
+    dtype, _ = check_format(depth, shift)
+    esize = 1 if depth == 8 else 2
+    if not isinstance(groups, (list, tuple)) or len(groups) < 1:
+        raise ValueError("mean_frames takes a list of at least one group of frames")
+    first = None
+    for g, group in enumerate(groups):
+        if not isinstance(group, (list, tuple)) or not 1 <= len(group) <= MAX_SAMPLES:
+            raise ValueError(f"group {g} must hold 1..{MAX_SAMPLES} frames")
+        for f in group:
+            if not isinstance(f, torch.Tensor):
+                raise TypeError(f"group {g} holds tensors, got {type(f).__name__}")
+            first = f if first is None else first
+            if f.dtype != dtype:
+                raise TypeError(f"frames of depth {depth} are {str(dtype).split('.')[-1]}, got {f.dtype}")
+            if f.shape != first.shape or f.device != first.device or f.numel() < 1 or not f.is_contiguous():
+                raise ValueError(f"group {g}: every frame is one dense {tuple(first.shape)} tensor on {first.device}, "
+                                 f"got {tuple(f.shape)} (strides {f.stride()}) on {f.device}")
+    if first.device.type != "cuda":
+        raise RuntimeError("rrin_amd.engine.mean_frames runs on ROCm GPUs only (exposure.mean_frames is the host form)")
+    n_out, flen = len(groups), first.numel()
+    if out is None:
+        out = torch.empty((n_out,) + tuple(first.shape), dtype=dtype, device=first.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != first.device
+          or tuple(out.shape) != (n_out,) + tuple(first.shape) or frame_stride(out) is None):
+        raise ValueError(f"out must be a {str(dtype).split('.')[-1]} stack {(n_out,) + tuple(first.shape)} of dense "
+                         f"frames on {first.device}")
+    stride = frame_stride(out)
+    ptrs = [f.data_ptr() for group in groups for f in group]
+    start = [0]
+    for group in groups:
+        start.append(start[-1] + len(group))
+    k = len(ptrs)
+    reach = 0
+    for a in ptrs + [out.data_ptr()] + ([stride * esize] if n_out > 1 else []):
+        reach |= a
+    access = 16 if reach % 16 == 0 else (4 if reach % 4 == 0 else esize)
+    host = torch.zeros(k + (n_out + 2) // 2, dtype=torch.int64)
+    host[:k] = torch.tensor(ptrs, dtype=torch.int64)
+    host[k:].view(torch.int32)[:n_out + 1] = torch.tensor(start, dtype=torch.int32)
+    with torch.cuda.device(first.device):
+        table = host.to(first.device, non_blocking=True)
+        sp = C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)
+        _lib.check(_lib.lib().rrin_mean_frames(table.data_ptr(), k, table[k:].data_ptr(), n_out, out.data_ptr(), stride,
+                                               flen, depth, shift, access, sp), "rrin_mean_frames")
+    return out
+
+
 # ---- host-only construction: the walk over the U-Nets, the per-conv schedule, the packing ----
 # No torch device and no engine: tests/test_engine_host.py checks these without a GPU.
 
@@ -1441,6 +1499,121 @@ class RRINEngine:
         fmt = FrameFormat.yuv16(layout, depth, msb, coef)
         return self._run_items(fmt, "interpolate_items_yuv16", frames, pair, t, streams, split, scene_threshold, gate,
                                prof, flow_scale, plane)
+
+    # ---- exposures: the mean of item forwards and stack frames over a shutter window ------------
+    # rrin_amd.exposure is the definition.  The t > 0 samples are item forwards (above) in runs of at
+    # most ``chunk`` items; rrin_mean_frames then averages them and the stack's own frames.
+
+    def _expose(self, fmt: FrameFormat, what: str, frames, groups, chunk, streams, scene_threshold, gate,
+                flow_scale: int, plane=None):
+        """``expose_items_*`` of every frame path: the call ``what`` on one ``[P+1, ...]`` stack of ``fmt``.
+        Every argument is checked before any device work.  The network items of the flattened groups go
+        through :meth:`_run_items` in consecutive runs of at most ``chunk``, each on the view of the stack
+        that its pairs span (item outputs do not depend on the batch, so ``chunk`` changes no bit and the
+        workspace stays that of a batch of ``chunk``); then one rrin_mean_frames launch on the current
+        stream, to which every run's streams have been joined, over views of those outputs and of the
+        stack (a second one for ``plane``).  The tensors stay referenced until both are enqueued."""
+        from . import exposure
+        if not isinstance(frames, torch.Tensor) or frames.dim() < 1 or frames.shape[0] < 2:
+            raise ValueError(f"{what} takes one stack of at least two frames")
+        n_stack = frames.shape[0] - 1
+        groups = exposure.check_groups(groups, n_stack)
+        runs = exposure.chunks(groups, chunk)
+        _, _, h0, w0, _ = fmt.check(frames[:-1], frames[1:], self.device, what)
+        if frame_stride(frames) is None:
+            frames = frames.contiguous()
+        if plane is not None:
+            check_planes(plane, n_stack, h0, w0, fmt.dtype, self.device, items=True)
+            if frame_stride(plane) is None:
+                plane = plane.contiguous()
+        if scene_threshold is not None and gate is not None:
+            raise ValueError("scene_threshold and gate exclude each other")
+        if scene_threshold is not None:
+            scene_limit_len(scene_threshold, fmt.frame_len(h0, w0), fmt.maxval)
+        if gate is not None and (not isinstance(gate, torch.Tensor) or gate.dtype != torch.int32
+                                 or gate.device != self.device or tuple(gate.shape) != (n_stack,)):
+            raise ValueError(f"gate must be an int32 tensor [{n_stack}] (one code per pair) on {self.device}")
+        gated = scene_threshold is not None or gate is not None
+        outs, planes, codes = [], [], []
+        for lo, hi, pairs, ts in runs:
+            r = self._run_items(fmt, what, frames[lo:hi + 1], pairs, ts, streams, None, scene_threshold,
+                                None if gate is None else gate[lo:hi], None, flow_scale,
+                                None if plane is None else plane[lo:hi + 1])
+            if plane is not None:
+                planes.append(r[1])
+                r = r[0]
+            outs.append(r)
+            if gated:
+                codes.append(self.last_gate)
+        if gated:
+            self.last_gate = (torch.cat(codes) if codes else
+                              torch.empty(0, dtype=torch.int32, device=self.device))
+        item = 0
+        src, psrc = [], []
+        for group in groups:
+            fs, ps = [], []
+            for p, t in group:
+                if t == 0.0:
+                    fs.append(frames[p])
+                    ps.append(None if plane is None else plane[p])
+                else:
+                    r, k = divmod(item, chunk)
+                    fs.append(outs[r][k])
+                    ps.append(None if plane is None else planes[r][k])
+                    item += 1
+            src.append(fs)
+            psrc.append(ps)
+        n_out = len(groups)
+        with torch.cuda.device(self.device):
+            out = mean_frames(src, fmt.depth, fmt.shift,
+                              torch.empty(fmt.out_shape(n_out, h0, w0), dtype=fmt.dtype, device=self.device))
+            if plane is None:
+                return out
+            return out, mean_frames(psrc, fmt.depth, fmt.shift)
+
+    def expose_items_u8(self, frames: torch.Tensor, groups, chunk: int = 4, streams: int | None = None,
+                        scene_threshold=None, gate=None, flow_scale: int = 1, plane=None):
+        """``G`` exposed frames over one stack of 8-bit frames (:mod:`rrin_amd.exposure` is the definition):
+        ``frames`` uint8 ``[P+1,H0,W0,3]`` on the device, ``groups`` a list of ``G`` lists of 1..256 samples
+        ``(pair, t)``, times non-decreasing over the flattened list, ``pair`` in [0, P] (``P`` only with
+        ``t == 0``), ``t`` in [0, 1) -> uint8 ``[G,H0,W0,3]``.  A sample with ``t == 0`` is ``frames[pair]``, any
+        other item ``(pair, t)`` of :meth:`interpolate_items_u8` with the same keywords; output g is the
+        rounded mean of its samples per byte, ties up (rrin_mean_frames).  The items run ``chunk`` at a
+        time; ``chunk`` changes no bit.  With ``scene_threshold`` or ``gate`` (int32 ``[P]`` pair codes) the
+        items inherit their pair's decision and :attr:`last_gate` is the ``[M]`` codes of the M network
+        items of the whole call, in order; an exposure across a cut mixes both shots.  ``plane``: one
+        ``[P+1,H0,W0]`` stack; the call returns ``(frames, plane)``, the plane the mean of the items' planes
+        and the stack's.  No host sync."""
+        flow_scale = self._frame_call("expose_items_u8", flow_scale)
+        return self._expose(FrameFormat.u8(), "expose_items_u8", frames, groups, chunk, streams, scene_threshold,
+                            gate, flow_scale, plane)
+
+    def expose_items_u16(self, frames: torch.Tensor, groups, chunk: int = 4, depth: int = 10,
+                         streams: int | None = None, scene_threshold=None, gate=None, flow_scale: int = 1,
+                         plane=None):
+        """:meth:`expose_items_u8` on uint16 ``[P+1,H0,W0,3]`` frames of ``depth`` 9..16 over
+        :meth:`interpolate_items_u16`; a sample is ``min(word, maxval)``."""
+        flow_scale = self._frame_call("expose_items_u16", flow_scale)
+        return self._expose(FrameFormat.u16(depth, "expose_items_u16"), "expose_items_u16", frames, groups, chunk,
+                            streams, scene_threshold, gate, flow_scale, plane)
+
+    def expose_items_yuv(self, frames: torch.Tensor, groups, chunk: int = 4, layout: str = "nv12", coef=None,
+                         streams: int | None = None, scene_threshold=None, gate=None, flow_scale: int = 1,
+                         plane=None):
+        """:meth:`expose_items_u8` on one stack of 8-bit YUV frames of ``layout`` over
+        :meth:`interpolate_items_yuv`: every stored byte, chroma included, is averaged."""
+        flow_scale = self._frame_call("expose_items_yuv", flow_scale)
+        return self._expose(FrameFormat.yuv(layout, coef), "expose_items_yuv", frames, groups, chunk, streams,
+                            scene_threshold, gate, flow_scale, plane)
+
+    def expose_items_yuv16(self, frames: torch.Tensor, groups, chunk: int = 4, layout: str = "nv12",
+                           depth: int = 10, msb: bool = False, coef=None, streams: int | None = None,
+                           scene_threshold=None, gate=None, flow_scale: int = 1, plane=None):
+        """:meth:`expose_items_yuv` on 10- or 12-bit frames in 16-bit words over
+        :meth:`interpolate_items_yuv16`: a sample is ``min(word >> shift, maxval)``, stored ``<< shift``."""
+        flow_scale = self._frame_call("expose_items_yuv16", flow_scale)
+        return self._expose(FrameFormat.yuv16(layout, depth, msb, coef), "expose_items_yuv16", frames, groups, chunk,
+                            streams, scene_threshold, gate, flow_scale, plane)
 
     def unet_forward(self, x: torch.Tensor) -> torch.Tensor:
         """The single packed U-Net (engine built with one unit) on x [N,C,H,W]:

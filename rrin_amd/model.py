@@ -317,6 +317,57 @@ class Net(nn.Module):
         return self._items("interpolate_items_yuv16", frames, pair, t, layout=layout, depth=depth, msb=msb, coef=coef,
                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale, **_plane_kw(plane))
 
+    # ---- exposures: the mean of S samples over a shutter window (rrin_amd.exposure) -----------
+    def _expose(self, name, frames, groups, chunk, **kw):
+        """The exposure ``name`` of the engine, after the host checks of ``groups`` and ``chunk``
+        (TypeError / ValueError before any device work)."""
+        from . import exposure
+        from .flowscale import check_flow_scale
+        if not isinstance(frames, torch.Tensor) or frames.dim() < 1:
+            raise TypeError(f"{name} takes one stack of frames")
+        exposure.chunks(exposure.check_groups(groups, frames.shape[0] - 1), chunk)
+        check_flow_scale(kw.get("flow_scale", 1))
+        if torch.is_grad_enabled():
+            raise RuntimeError(f"rrin_amd.Net.{name} is inference-only: use torch.no_grad()")
+        return getattr(self.engine(), name)(frames, groups, chunk, streams=self.streams, **kw)
+
+    def expose_items_u8(self, frames, groups, chunk=4, scene_threshold=None, gate=None, flow_scale=1, plane=None):
+        """``G`` exposed frames over one stack of 8-bit frames: a synthetic shutter
+        (:mod:`rrin_amd.exposure` is the definition, :func:`rrin_amd.retime.exposure_schedule` makes the
+        groups of a frame-rate conversion).  ``frames`` uint8 ``[P+1,H0,W0,3]`` on the device, ``groups`` a
+        list of ``G`` lists of 1..256 samples ``(pair, t)`` with non-decreasing times, ``pair`` in [0, P]
+        (``P`` only with ``t == 0``), ``t`` in [0, 1) -> uint8 ``[G,H0,W0,3]``.  A ``t == 0`` sample is
+        ``frames[pair]``, never sent to the network; any other is item ``(pair, t)`` of
+        :meth:`interpolate_items_u8` with the same keywords, run ``chunk`` items at a time (``chunk``
+        changes no bit).  Output g is ``((sum of its samples) + S // 2) // S`` per byte: a mean over code
+        values, no transfer function.  With ``scene_threshold`` or ``gate`` the items inherit their pair's
+        decision and :attr:`last_gate` is the ``[M]`` codes of the call's network items in order; an
+        exposure across a cut mixes both shots.  ``plane``: one ``[P+1,H0,W0]`` stack; the call returns
+        ``(frames, plane)``."""
+        return self._expose("expose_items_u8", frames, groups, chunk, scene_threshold=scene_threshold, gate=gate,
+                            flow_scale=flow_scale, **_plane_kw(plane))
+
+    def expose_items_yuv(self, frames, groups, chunk=4, layout="nv12", coef=None, scene_threshold=None, gate=None,
+                         flow_scale=1, plane=None):
+        """:meth:`expose_items_u8` on one stack of 8-bit YUV frames over :meth:`interpolate_items_yuv`;
+        every stored byte, chroma included, is averaged."""
+        return self._expose("expose_items_yuv", frames, groups, chunk, layout=layout, coef=coef,
+                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale, **_plane_kw(plane))
+
+    def expose_items_u16(self, frames, groups, chunk=4, depth=10, scene_threshold=None, gate=None, flow_scale=1,
+                         plane=None):
+        """:meth:`expose_items_u8` on uint16 RGB frames of ``depth`` over :meth:`interpolate_items_u16`."""
+        return self._expose("expose_items_u16", frames, groups, chunk, depth=depth, scene_threshold=scene_threshold,
+                            gate=gate, flow_scale=flow_scale, **_plane_kw(plane))
+
+    def expose_items_yuv16(self, frames, groups, chunk=4, layout="nv12", depth=10, msb=False, coef=None,
+                           scene_threshold=None, gate=None, flow_scale=1, plane=None):
+        """:meth:`expose_items_yuv` on 10- or 12-bit frames in 16-bit words over
+        :meth:`interpolate_items_yuv16`: a sample is ``min(word >> shift, maxval)``, stored ``<< shift``."""
+        return self._expose("expose_items_yuv16", frames, groups, chunk, layout=layout, depth=depth, msb=msb,
+                            coef=coef, scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale,
+                            **_plane_kw(plane))
+
     @property
     def last_gate(self):
         """The int32 device codes ``[N]`` of the last gated ``forward_u8`` (0: interpolated, 1:
