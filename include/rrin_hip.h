@@ -1126,6 +1126,55 @@ int rrin_net_yuv16_plane_fwd(const rrin_net_yuv16_desc* d, const rrin_items* ite
 int rrin_mean_frames(const void* const* frames, int32_t k, const int32_t* start, int32_t g, void* out,
                      int64_t out_stride, int64_t len, int32_t depth, int32_t shift, int32_t access, void* stream);
 
+/* ---- The linear-light exposure: weighted means through a transfer table ------------------------
+ * History: added after ABI 25 without a new version number -- two new entry points and one new struct,
+ * no existing struct or entry point changes, so RRIN_ABI_VERSION stays 25; a caller finds out whether
+ * a build has them by looking the symbols up.
+ *
+ * rrin_amd/transfer.py and rrin_amd/exposure.py (mean_frames_linear) are the definition.  Both entries
+ * take rrin_mean_frames' pointer table and CSR offsets, and beside them
+ *   weights: a DEVICE int32 [k] parallel to frames, every weight in 1..65535 and the sum W of a group's
+ *            weights at most 65535 (a group that breaks this is skipped like one with S outside 1..256);
+ *   table:   a DEVICE int32 [2 * (maxval + 1)], 16-byte aligned, maxval = 2^depth - 1: lin[0 .. maxval],
+ *            non-decreasing in [0, 2^30], then thr[0 .. maxval] with thr[c] = (lin[c-1] + lin[c] + 1) / 2
+ *            for c >= 1 (thr[0] is not read).  The kernels copy it into LDS, 2 KiB at 8 bits and 32 KiB
+ *            at 12, which is why depth > 12 with a table is refused.
+ * With s_k = min(word >> shift, maxval) of source k and its weight w_k, in 64-bit integers (a sum stays
+ * below 2^46), ties up, the same bits on every run:
+ *   v = ((sum_k w_k * lin[s_k]) + W / 2) / W        enc(v) = #{c in 1..maxval : thr[c] <= v}
+ *
+ * rrin_mean_frames_lut: rrin_mean_frames' arguments, meaning and codes, per stored element
+ *   out[j][e] = enc(v) << shift; with table == NULL at any depth 8..16 lin is the identity and enc is
+ *   not applied: out[j][e] = ((sum_k w_k * s_k) + W / 2) / W << shift, which with every weight 1 is
+ *   rrin_mean_frames bit for bit.  Further RRIN_E_ARG: weights null or not 4-byte aligned, a table with
+ *   depth > 12 or not 16-byte aligned.  No len is too long for a grid: a workgroup walks several runs.
+ *
+ * rrin_mean_frames_yuv_lut: the sources and the g output frames are YUV frames of one geometry, a frame
+ *   given by the address of its first luma sample (frames[] and out; output j at out + j * out_stride).
+ *   rrin_yuv_planes counts in elements (bytes at depth 8, 16-bit words at depth 10 and 12): u_off / v_off
+ *   from the first luma sample to the first U and V sample, the pitches, c_step, chroma, depth and shift
+ *   of rrin_yuv420 / rrin_yuv420_16.  Per chroma block every source's pixels go to RGB code values by
+ *   rrin_yuv_coef's way in, each R, G, B through the formula above (shift 0), and the block's RGB back
+ *   by its way out: the RGB-table mean between the two conversions of the YUV forwards, bit for bit.
+ *   RRIN_E_ARG: a null pointer (the table included), depth not 8, 10 or 12, shift not 0 or 16 - depth,
+ *   c_step not 1 or 2, an unknown chroma, a coefficient out of range, a misaligned table, start, weights
+ *   or frames, an odd out address at 16 bits, k < g or k > 256 g.  RRIN_E_SHAPE: g < 1 or > 65535, h0 /
+ *   w0 not a size of the chroma format (even at 4:2:0, w0 even at 4:2:2), a pitch smaller than its row,
+ *   planes that overlap (u_off inside the luma plane, v_off <= u_off, planar V inside U), output frames
+ *   that overlap.  Both validate before any launch. */
+typedef struct rrin_yuv_planes {
+  int64_t u_off, v_off;        /* elements from a frame's first luma sample to its first U / V sample */
+  int32_t y_pitch, c_pitch;    /* elements between rows */
+  int32_t c_step, chroma;      /* elements between chroma samples of a row: 2 or 1; rrin_chroma */
+  int32_t depth, shift;        /* 8 (bytes, shift 0), 10 or 12 (words; shift 0 or 16 - depth) */
+} rrin_yuv_planes;
+int rrin_mean_frames_lut(const void* const* frames, int32_t k, const int32_t* start, int32_t g, void* out,
+                         int64_t out_stride, int64_t len, int32_t depth, int32_t shift, int32_t access,
+                         const int32_t* weights, const int32_t* table, void* stream);
+int rrin_mean_frames_yuv_lut(const void* const* frames, int32_t k, const int32_t* start, int32_t g, void* out,
+                             int64_t out_stride, const rrin_yuv_planes* geom, const rrin_yuv_coef* coef, int32_t h0,
+                             int32_t w0, const int32_t* weights, const int32_t* table, void* stream);
+
 /* ---- Training path (autograd): NCHW fp32 kernels ------------------------- */
 /* With autograd on (the reference trains through Net.forward, train.py:98, and
  * loss.backward(), train.py:144) rrin_amd.train wraps these in autograd

@@ -70,6 +70,14 @@ def build_parser():
     cv.add_argument("--shutter", type=str, default=None, metavar="NUM/DEN",
                     help="with --samples: the share of an output frame's time the shutter is open, in (0, 1], e.g. "
                          "1/2 (the default, a 180 degree shutter)")
+    cv.add_argument("--light", type=str, default=None, choices=["srgb", "bt1886", "gamma22", "pq", "hlg"],
+                    help="with --samples (> 1): the transfer curve of the material.  The mean of the samples is then "
+                         "taken in linear light, as a shutter integrates it, and encoded back to the nearest code "
+                         "value.  Y4M carries no transfer tag, so the curve must be named: no default, no guessing "
+                         "(without it the mean stays over code values)")
+    cv.add_argument("--shutter_weights", type=str, default=None, choices=["box", "triangle"],
+                    help="with --samples (> 1): how the samples of an exposure are weighted.  box: all equal (the "
+                         "default); triangle: w_k = min(k + 1, S - k), a shutter that opens and closes gradually")
     ev = sub.add_parser("evaluate", help="Hold-out PSNR / SSIM of the model on a Y4M clip.")
     ev.add_argument("--y4m_in", type=str, required=True, metavar="PATH|-",
                     help="the clip: a Y4M stream of any format convert --y4m_in takes (\"-\": stdin)")

@@ -110,6 +110,12 @@ class YuvCoef(C.Structure):
 YUV_BT709, YUV_BT601 = 0, 1
 
 
+class YuvPlanes(C.Structure):
+    """rrin_yuv_planes: the geometry of one YUV frame in elements, for rrin_mean_frames_yuv_lut."""
+    _fields_ = [("u_off", C.c_int64), ("v_off", C.c_int64), ("y_pitch", C.c_int32), ("c_pitch", C.c_int32),
+                ("c_step", C.c_int32), ("chroma", C.c_int32), ("depth", C.c_int32), ("shift", C.c_int32)]
+
+
 class Yuv420x16(C.Structure):
     """rrin_yuv420_16: one stack of 4:2:0 frames of 16-bit words (pitches and strides in samples; depth 10 or
     12; shift 0: the sample in the low bits, 16 - depth: in the high bits)."""
@@ -320,6 +326,11 @@ SIGNATURES = {
                                            C.POINTER(AuxPlane), C.c_void_p]),
     "rrin_mean_frames": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "rrin_mean_frames_lut": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+                                       C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rrin_mean_frames_yuv_lut": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                           C.POINTER(YuvPlanes), C.POINTER(YuvCoef), C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
     "rrin_gate_items_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p]),
     "rrin_gate_frames_items_u8_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,

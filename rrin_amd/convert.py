@@ -501,7 +501,7 @@ def frame_path_of(src):
 
 
 def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coef=None, log=print, fps_out=None,
-                    flow_scale=1, samples=None, shutter=None):
+                    flow_scale=1, samples=None, shutter=None, light=None, weights=None):
     """Interpolate a Y4M stream (8-bit 4:2:0; also 10 / 12 bits and 4:2:2 / 4:4:4, below) into another: no image folder, no RGB frame anywhere.
 
     ``flow_scale`` 2 or 4 (:mod:`rrin_amd.flowscale`) goes to the model's ``interpolate_*`` call:
@@ -535,7 +535,12 @@ def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coe
     ``samples`` (an int in 1..256, with ``fps_out``) turns every output into an exposure: the mean of
     ``samples`` frames across a ``shutter`` (a Fraction, an int or a string ``"1/2"`` in (0, 1]; default
     1/2) of the output's frame time, and ``fps_out`` may then be ANY positive rate, lower, equal or
-    higher: :func:`expose_y4m`.  Without ``samples`` nothing changes (``shutter`` alone raises)."""
+    higher: :func:`expose_y4m`.  Without ``samples`` nothing changes (``shutter`` alone raises).
+
+    ``light`` (the material's transfer curve: ``"srgb"``, ``"bt1886"``, ``"gamma22"``, ``"pq"``, ``"hlg"`` or a
+    table, :mod:`rrin_amd.transfer`) takes that mean in linear light and ``weights`` (``"box"``,
+    ``"triangle"`` or ``samples`` ints) weighs the samples; Y4M carries no transfer tag, so nothing is
+    guessed.  Either without ``samples``, or with ``samples == 1`` (nothing to average), raises."""
     from . import y4m, yuv
     from .flowscale import check_flow_scale
     check_flow_scale(flow_scale)
@@ -543,11 +548,14 @@ def interpolate_y4m(model, src, dst, sf=None, batch=4, scene_threshold=None, coe
         raise ValueError("interpolate_y4m takes exactly one of sf and fps_out")
     if samples is None and shutter is not None:
         raise ValueError("shutter needs samples: an exposure is the mean of `samples` frames over the shutter")
+    if samples is None and (light is not None or weights is not None):
+        raise ValueError("light and weights need samples: they say how the `samples` frames of an exposure are averaged")
     if samples is not None:
         if fps_out is None:
             raise ValueError("samples needs fps_out: an exposure belongs to a frame-rate conversion")
         return expose_y4m(model, src, dst, fps_out, samples, shutter="1/2" if shutter is None else shutter,
-                          batch=batch, scene_threshold=scene_threshold, coef=coef, log=log, flow_scale=flow_scale)
+                          batch=batch, scene_threshold=scene_threshold, coef=coef, log=log, flow_scale=flow_scale,
+                          light=light, weights=weights)
     if fps_out is not None:
         return retime_y4m(model, src, dst, fps_out, batch=batch, scene_threshold=scene_threshold, coef=coef, log=log,
                           flow_scale=flow_scale)
@@ -801,7 +809,7 @@ def retime_y4m(model, src, dst, fps_out, batch=4, scene_threshold=None, coef=Non
 
 
 def expose_y4m(model, src, dst, fps_out, samples, shutter="1/2", batch=4, scene_threshold=None, coef=None, log=print,
-               flow_scale=1):
+               flow_scale=1, light=None, weights=None):
     """Convert a Y4M stream to ANY frame rate ``fps_out`` -- lower (60 -> 24, 120 -> 24), equal or higher
     -- with a synthetic shutter: ``interpolate_y4m(fps_out=, samples=)``.  Output j is the mean of
     ``samples`` frames at the source times ``j * step + k * shutter * step / samples``, ``step = fps_in /
@@ -816,10 +824,15 @@ def expose_y4m(model, src, dst, fps_out, samples, shutter="1/2", batch=4, scene_
     1`` that falls on an input frame is written as that frame's own bytes, as :func:`retime_y4m` does, so
     ``samples=1`` above the input's rate is that conversion.  The header carries ``fps_out`` reduced; tag,
     depth, chroma, ``coef``, ``scene_threshold`` and ``flow_scale`` follow the stream as there (an exposure
-    across a cut mixes both shots).  Returns the frames written."""
+    across a cut mixes both shots).  Returns the frames written.
+
+    ``light`` and ``weights`` go to ``expose_items_*``: the mean in linear light under the named transfer
+    curve (or a table of the stream's depth), with a box or triangle shutter or ``samples`` explicit integer
+    weights (:func:`rrin_amd.exposure.mean_frames_linear`).  With ``samples == 1`` there is nothing to
+    average and either raises; the header is the same with and without them."""
     from collections import deque
 
-    from . import retime, y4m, yuv
+    from . import exposure, retime, transfer, y4m, yuv
     from .flowscale import check_flow_scale
     check_flow_scale(flow_scale)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -829,6 +842,14 @@ def expose_y4m(model, src, dst, fps_out, samples, shutter="1/2", batch=4, scene_
     rate_out = retime.as_rate(fps_out)
     n_samples = retime.check_samples(samples)
     sh = retime.as_shutter(shutter)
+    light_kw = {}
+    if light is not None or weights is not None:
+        if n_samples == 1:
+            raise ValueError("light and weights need samples > 1: one sample leaves nothing to average")
+        exposure.shutter_weights(weights, n_samples)
+        if isinstance(light, str) and light not in transfer.CURVES:
+            raise ValueError(f"light must be one of {transfer.NAMES} or a table, got {light!r}")
+        light_kw = {"light": light, "weights": weights}
     opened = []
     if isinstance(src, (str, os.PathLike)):
         src = open(src, "rb")
@@ -842,6 +863,8 @@ def expose_y4m(model, src, dst, fps_out, samples, shutter="1/2", batch=4, scene_
         if rd.fps_num < 1 or rd.fps_den < 1:
             raise ValueError(f"Y4M: the stream has no frame rate to convert (F{rd.fps_num}:{rd.fps_den})")
         rate_in = retime.as_rate(f"{rd.fps_num}/{rd.fps_den}")
+        if light is not None:
+            transfer.as_table(light, rd.bit_depth)  # a table must fit the stream's depth: refuse before any output
         sched = retime.ExposureStream(rate_in, rate_out, sh, n_samples)
         wr = y4m.Writer(dst, w0, h0, rate_out.numerator, rate_out.denominator, rd.colorspace, depths=(8, 10, 12),
                         chroma=yuv.CHROMAS)
@@ -900,7 +923,7 @@ def expose_y4m(model, src, dst, fps_out, samples, shutter="1/2", batch=4, scene_
             groups = [[(pos[p], float(t)) for p, t in o] for o in outputs]
             with torch.no_grad():
                 out = getattr(model, "expose_items_" + suffix)(stack, groups, chunk=batch, layout=layout, coef=coef,
-                                                               **depth_kw, **gate_kw, **scale_kw)
+                                                               **depth_kw, **gate_kw, **scale_kw, **light_kw)
             host = torch.empty(out.shape, dtype=out.dtype, pin_memory=on_gpu)
             host.copy_(out, non_blocking=True)
             codes = None
@@ -975,6 +998,11 @@ def expose_y4m(model, src, dst, fps_out, samples, shutter="1/2", batch=4, scene_
                f"frames at {rate_out.numerator}:{rate_out.denominator} fps, each the mean of {n_samples} samples "
                f"over a {sh.numerator}/{sh.denominator} shutter, in {time.time() - t0:.2f} s, {passed} of them input "
                f"frames passed through")
+        if light_kw:
+            curve = light if isinstance(light, str) else "a custom table"
+            shape = weights if isinstance(weights, str) else ("box" if weights is None else "explicit")
+            msg += (f"; the mean in {'code values' if light is None else 'linear light under ' + curve}, "
+                    f"{shape} weights")
         if gate_kw:
             msg += f"; scene gate (threshold {scene_threshold:g}): {gated} items replaced by an input frame"
         log(msg)
@@ -1236,7 +1264,8 @@ def _convert_y4m(args):
         interpolate_y4m(net, src, dst, None if fps_out is not None else args.sf, batch=getattr(args, "batch", 4),
                         scene_threshold=getattr(args, "scene_threshold", None), fps_out=fps_out,
                         flow_scale=getattr(args, "flow_scale", 1), samples=getattr(args, "samples", None),
-                        shutter=getattr(args, "shutter", None))
+                        shutter=getattr(args, "shutter", None), light=getattr(args, "light", None),
+                        weights=getattr(args, "shutter_weights", None))
         print("Finished conversion")
 
 

@@ -21,10 +21,10 @@ from collections import OrderedDict, namedtuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, transfer, yuv
 from .convert import scene_cut_code, scene_limit_len
 from .flowscale import check_flow_scale, flow_tag, padded_size
-from .framefmt import FrameFormat, frame_stride
+from .framefmt import FrameFormat, _stack_geometry, frame_stride
 from .plane import check_planes
 from .unet import _level_of
 
@@ -512,6 +512,101 @@ def mean_frames(groups, depth: int = 8, shift: int = 0, out: torch.Tensor | None
     return out
 
 
+def device_table(light, depth: int, device) -> torch.Tensor:
+    """The device form of a transfer table (:mod:`rrin_amd.transfer`): ``light`` a name or a table, checked
+    on the host -> int32 ``[2 * (maxval + 1)]`` on ``device``, ``lin`` then ``thr``, as
+    :func:`mean_frames_linear` takes it."""
+    from . import transfer
+    return transfer.device_words(transfer.as_table(light, depth)).to(device, non_blocking=True)
+
+
+def mean_frames_linear(groups, fmt: FrameFormat, table, weights, out: torch.Tensor | None = None) -> torch.Tensor:
+    """rrin_mean_frames_lut / rrin_mean_frames_yuv_lut (``exposure.mean_frames_linear`` is the definition) on
+    the current stream: ``groups`` and ``out`` as in :func:`mean_frames`, the frames of the
+    :class:`FrameFormat` ``fmt`` (a YUV frame ``[rows, W0]``); ``table`` None or a :func:`device_table` of
+    ``fmt.depth``; ``weights`` None, a shutter name or an explicit list (``exposure.shutter_weights``, per
+    group).  A YUV format with a table goes through RGB per pixel (the YUV entry); everything else is the
+    element form, without a table the weighted mean of code values.  The same checks as :func:`mean_frames`
+    before anything is uploaded; pointers, group starts and weights go up as one small tensor; no host
+    sync."""
+    from . import exposure
+    from .plane import check_format
+    depth, shift = fmt.depth, fmt.shift
+    dtype, _ = check_format(depth, shift)
+    esize = fmt.esize
+    if not isinstance(groups, (list, tuple)) or len(groups) < 1:
+        raise ValueError("mean_frames_linear takes a list of at least one group of frames")
+    first = None
+    for g, group in enumerate(groups):
+        if not isinstance(group, (list, tuple)) or not 1 <= len(group) <= exposure.MAX_SAMPLES:
+            raise ValueError(f"group {g} must hold 1..{exposure.MAX_SAMPLES} frames")
+        for f in group:
+            if not isinstance(f, torch.Tensor):
+                raise TypeError(f"group {g} holds tensors, got {type(f).__name__}")
+            first = f if first is None else first
+            if f.dtype != dtype:
+                raise TypeError(f"frames of depth {depth} are {str(dtype).split('.')[-1]}, got {f.dtype}")
+            if f.shape != first.shape or f.device != first.device or f.numel() < 1 or not f.is_contiguous():
+                raise ValueError(f"group {g}: every frame is one dense {tuple(first.shape)} tensor on {first.device}, "
+                                 f"got {tuple(f.shape)} (strides {f.stride()}) on {f.device}")
+    per_group = exposure.group_weights(weights, [len(group) for group in groups])
+    as_yuv = table is not None and fmt.layout is not None
+    if table is not None:
+        if depth > 12:
+            raise ValueError(f"light needs a depth of at most 12 bits, got {depth}: a table of 2**{depth} entries "
+                             "and its thresholds would not fit in LDS")
+        if (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.device != first.device
+                or tuple(table.shape) != (2 << depth,) or not table.is_contiguous()):
+            raise ValueError(f"table must be a device_table of depth {depth}: int32 [{2 << depth}] on {first.device}")
+    if as_yuv:
+        if fmt.coef is None:
+            raise ValueError("a samples-only format has no matrix: linear light on YUV needs FrameFormat.yuv / yuv16")
+        h0, w0 = yuv.stack_size(first[None], fmt.layout)
+    if first.device.type != "cuda":
+        raise RuntimeError("rrin_amd.engine.mean_frames_linear runs on ROCm GPUs only (exposure.mean_frames_linear is "
+                           "the host form)")
+    n_out, flen = len(groups), first.numel()
+    if out is None:
+        out = torch.empty((n_out,) + tuple(first.shape), dtype=dtype, device=first.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != first.device
+          or tuple(out.shape) != (n_out,) + tuple(first.shape) or frame_stride(out) is None):
+        raise ValueError(f"out must be a {str(dtype).split('.')[-1]} stack {(n_out,) + tuple(first.shape)} of dense "
+                         f"frames on {first.device}")
+    stride = frame_stride(out)
+    ptrs = [f.data_ptr() for group in groups for f in group]
+    start = [0]
+    for group in groups:
+        start.append(start[-1] + len(group))
+    k = len(ptrs)
+    reach = 0
+    for a in ptrs + [out.data_ptr()] + ([stride * esize] if n_out > 1 else []):
+        reach |= a
+    access = 16 if reach % 16 == 0 else (4 if reach % 4 == 0 else esize)
+    # one upload: k pointers, then int32 start[n_out + 1] and weights[k]
+    host = torch.zeros(k + (n_out + 1 + k + 1) // 2, dtype=torch.int64)
+    host[:k] = torch.tensor(ptrs, dtype=torch.int64)
+    words = host[k:].view(torch.int32)
+    words[:n_out + 1] = torch.tensor(start, dtype=torch.int32)
+    words[n_out + 1:n_out + 1 + k] = torch.tensor([w for ws in per_group for w in ws], dtype=torch.int32)
+    with torch.cuda.device(first.device):
+        up = host.to(first.device, non_blocking=True)
+        p_start = up[k:].data_ptr()
+        p_weights = p_start + 4 * (n_out + 1)
+        p_table = None if table is None else table.data_ptr()
+        sp = C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)
+        if as_yuv:
+            uo, vo, c_pitch, c_step, chroma = _stack_geometry(fmt.layout, 1, h0, w0)
+            geom = _lib.YuvPlanes(uo, vo, w0, c_pitch, c_step, chroma, depth, shift)
+            _lib.check(_lib.lib().rrin_mean_frames_yuv_lut(up.data_ptr(), k, p_start, n_out, out.data_ptr(), stride,
+                                                           C.byref(geom), C.byref(_lib.YuvCoef(*fmt.coef)), h0, w0,
+                                                           p_weights, p_table, sp), "rrin_mean_frames_yuv_lut")
+        else:
+            _lib.check(_lib.lib().rrin_mean_frames_lut(up.data_ptr(), k, p_start, n_out, out.data_ptr(), stride, flen,
+                                                       depth, shift, access, p_weights, p_table, sp),
+                       "rrin_mean_frames_lut")
+    return out
+
+
 # ---- host-only construction: the walk over the U-Nets, the per-conv schedule, the packing ----
 # No torch device and no engine: tests/test_engine_host.py checks these without a GPU.
 
@@ -755,6 +850,7 @@ class RRINEngine:
         self.last_gate = None       # int32 device codes of the last gated forward_u8 / forward_yuv
         self._metrics_ws = None     # workspace of the frame metrics (per-workgroup partials)
         self._plane_sc = {}         # part key -> scratch of an extra plane (plane=)
+        self._light_tables = {}     # transfer.table_key -> device [lin, thr] of a linear-light exposure
 
     def _pack_h8(self, size: str, h: int = None, w: int = None):
         """(weight blob, bias blob, ConvWeights table, cfgs) of size class ``size`` at image
@@ -1505,20 +1601,32 @@ class RRINEngine:
     # most ``chunk`` items; rrin_mean_frames then averages them and the stack's own frames.
 
     def _expose(self, fmt: FrameFormat, what: str, frames, groups, chunk, streams, scene_threshold, gate,
-                flow_scale: int, plane=None):
+                flow_scale: int, plane=None, light=None, weights=None):
         """``expose_items_*`` of every frame path: the call ``what`` on one ``[P+1, ...]`` stack of ``fmt``.
         Every argument is checked before any device work.  The network items of the flattened groups go
         through :meth:`_run_items` in consecutive runs of at most ``chunk``, each on the view of the stack
         that its pairs span (item outputs do not depend on the batch, so ``chunk`` changes no bit and the
         workspace stays that of a batch of ``chunk``); then one rrin_mean_frames launch on the current
         stream, to which every run's streams have been joined, over views of those outputs and of the
-        stack (a second one for ``plane``).  The tensors stay referenced until both are enqueued."""
+        stack (a second one for ``plane``).  The tensors stay referenced until both are enqueued.
+
+        ``light`` (a transfer table or its name, :mod:`rrin_amd.transfer`) and ``weights`` (a shutter,
+        ``exposure.shutter_weights``): with either, the mean is ``exposure.mean_frames_linear`` --
+        rrin_mean_frames_lut, on YUV with a table rrin_mean_frames_yuv_lut -- and the plane the weighted
+        mean of code values; with both None the call launches rrin_mean_frames as it always did."""
         from . import exposure
         if not isinstance(frames, torch.Tensor) or frames.dim() < 1 or frames.shape[0] < 2:
             raise ValueError(f"{what} takes one stack of at least two frames")
         n_stack = frames.shape[0] - 1
         groups = exposure.check_groups(groups, n_stack)
         runs = exposure.chunks(groups, chunk)
+        linear = light is not None or weights is not None
+        if linear:
+            exposure.group_weights(weights, [len(group) for group in groups])
+            if light is not None and fmt.depth > 12:
+                raise ValueError(f"{what}: light needs a depth of at most 12 bits, got {fmt.depth}: a table of "
+                                 f"2**{fmt.depth} entries and its thresholds would not fit in LDS")
+            key = None if light is None else transfer.table_key(light, fmt.depth)
         _, _, h0, w0, _ = fmt.check(frames[:-1], frames[1:], self.device, what)
         if frame_stride(frames) is None:
             frames = frames.contiguous()
@@ -1565,14 +1673,26 @@ class RRINEngine:
             psrc.append(ps)
         n_out = len(groups)
         with torch.cuda.device(self.device):
-            out = mean_frames(src, fmt.depth, fmt.shift,
-                              torch.empty(fmt.out_shape(n_out, h0, w0), dtype=fmt.dtype, device=self.device))
+            out = torch.empty(fmt.out_shape(n_out, h0, w0), dtype=fmt.dtype, device=self.device)
+            if not linear:
+                out = mean_frames(src, fmt.depth, fmt.shift, out)
+                if plane is None:
+                    return out
+                return out, mean_frames(psrc, fmt.depth, fmt.shift)
+            table = None
+            if key is not None:
+                table = self._light_tables.get(key)
+                if table is None:  # [lin, thr] of a (light, depth), kept on the engine
+                    table = self._light_tables[key] = device_table(light, fmt.depth, self.device)
+            out = mean_frames_linear(src, fmt, table, weights, out)
             if plane is None:
                 return out
-            return out, mean_frames(psrc, fmt.depth, fmt.shift)
+            # a matte, depth or ID plane has no transfer curve: the weighted mean of its code values
+            return out, mean_frames_linear(psrc, FrameFormat.samples(None, fmt.depth, fmt.shift), None, weights)
 
     def expose_items_u8(self, frames: torch.Tensor, groups, chunk: int = 4, streams: int | None = None,
-                        scene_threshold=None, gate=None, flow_scale: int = 1, plane=None):
+                        scene_threshold=None, gate=None, flow_scale: int = 1, plane=None, light=None,
+                        weights=None):
         """``G`` exposed frames over one stack of 8-bit frames (:mod:`rrin_amd.exposure` is the definition):
         ``frames`` uint8 ``[P+1,H0,W0,3]`` on the device, ``groups`` a list of ``G`` lists of 1..256 samples
         ``(pair, t)``, times non-decreasing over the flattened list, ``pair`` in [0, P] (``P`` only with
@@ -1583,37 +1703,43 @@ class RRINEngine:
         items inherit their pair's decision and :attr:`last_gate` is the ``[M]`` codes of the M network
         items of the whole call, in order; an exposure across a cut mixes both shots.  ``plane``: one
         ``[P+1,H0,W0]`` stack; the call returns ``(frames, plane)``, the plane the mean of the items' planes
-        and the stack's.  No host sync."""
+        and the stack's.  ``light`` (``"srgb"``, ``"bt1886"``, ``"gamma22"``, ``"pq"``, ``"hlg"`` or a table:
+        :mod:`rrin_amd.transfer`) takes the mean in linear light and ``weights`` (``"box"``, ``"triangle"`` or a
+        list of ints) weighs the samples: ``exposure.mean_frames_linear``, rrin_mean_frames_lut (on YUV with a
+        table rrin_mean_frames_yuv_lut: through RGB per pixel); the plane is then the weighted mean of
+        its code values.  Both are checked before any device work; with both None nothing changes.  No
+        host sync."""
         flow_scale = self._frame_call("expose_items_u8", flow_scale)
         return self._expose(FrameFormat.u8(), "expose_items_u8", frames, groups, chunk, streams, scene_threshold,
-                            gate, flow_scale, plane)
+                            gate, flow_scale, plane, light, weights)
 
     def expose_items_u16(self, frames: torch.Tensor, groups, chunk: int = 4, depth: int = 10,
                          streams: int | None = None, scene_threshold=None, gate=None, flow_scale: int = 1,
-                         plane=None):
+                         plane=None, light=None, weights=None):
         """:meth:`expose_items_u8` on uint16 ``[P+1,H0,W0,3]`` frames of ``depth`` 9..16 over
         :meth:`interpolate_items_u16`; a sample is ``min(word, maxval)``."""
         flow_scale = self._frame_call("expose_items_u16", flow_scale)
         return self._expose(FrameFormat.u16(depth, "expose_items_u16"), "expose_items_u16", frames, groups, chunk,
-                            streams, scene_threshold, gate, flow_scale, plane)
+                            streams, scene_threshold, gate, flow_scale, plane, light, weights)
 
     def expose_items_yuv(self, frames: torch.Tensor, groups, chunk: int = 4, layout: str = "nv12", coef=None,
                          streams: int | None = None, scene_threshold=None, gate=None, flow_scale: int = 1,
-                         plane=None):
+                         plane=None, light=None, weights=None):
         """:meth:`expose_items_u8` on one stack of 8-bit YUV frames of ``layout`` over
         :meth:`interpolate_items_yuv`: every stored byte, chroma included, is averaged."""
         flow_scale = self._frame_call("expose_items_yuv", flow_scale)
         return self._expose(FrameFormat.yuv(layout, coef), "expose_items_yuv", frames, groups, chunk, streams,
-                            scene_threshold, gate, flow_scale, plane)
+                            scene_threshold, gate, flow_scale, plane, light, weights)
 
     def expose_items_yuv16(self, frames: torch.Tensor, groups, chunk: int = 4, layout: str = "nv12",
                            depth: int = 10, msb: bool = False, coef=None, streams: int | None = None,
-                           scene_threshold=None, gate=None, flow_scale: int = 1, plane=None):
+                           scene_threshold=None, gate=None, flow_scale: int = 1, plane=None, light=None,
+                           weights=None):
         """:meth:`expose_items_yuv` on 10- or 12-bit frames in 16-bit words over
         :meth:`interpolate_items_yuv16`: a sample is ``min(word >> shift, maxval)``, stored ``<< shift``."""
         flow_scale = self._frame_call("expose_items_yuv16", flow_scale)
         return self._expose(FrameFormat.yuv16(layout, depth, msb, coef), "expose_items_yuv16", frames, groups, chunk,
-                            streams, scene_threshold, gate, flow_scale, plane)
+                            streams, scene_threshold, gate, flow_scale, plane, light, weights)
 
     def unet_forward(self, x: torch.Tensor) -> torch.Tensor:
         """The single packed U-Net (engine built with one unit) on x [N,C,H,W]:

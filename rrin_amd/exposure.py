@@ -33,12 +33,30 @@ exactly as in ``interpolate_items_*`` (a duplicate pair: the first frame; a cut 
 by the item's own t) and are averaged as they come out.  An exposure window that spans a cut therefore
 mixes frames of both shots, as a real shutter open across a splice would.
 
+**Linear light and weights** (``light=``, ``weights=``; :func:`mean_frames_linear`).  A shutter integrates
+light, not code values.  With a transfer table ``lin`` of the material's curve (:mod:`rrin_amd.transfer`:
+``"srgb"``, ``"bt1886"``, ``"gamma22"``, ``"pq"``, ``"hlg"`` or the caller's own, ``lin[c]`` in ``[0, 2**30]``) and
+integer weights ``w_k`` with sum ``W <= 65535`` (:func:`shutter_weights`: ``"box"``, ``"triangle"`` or a list):
+
+    v = ((sum_k w_k * lin[s_k[e]]) + W // 2) // W          out[e] = enc(v) << shift
+
+``enc`` the nearest code in linear light (``transfer.encode``), all in 64-bit integers.  Under sRGB the mean
+of codes 0 and 255 is 187 or 188, not 128.  On YUV the rule applies per pixel and channel of the RGB that
+the path's two integer conversions define (``yuv.yuv_to_rgb`` in, ``yuv.rgb_to_yuv`` out); a table needs
+``depth <= 12``.  Without a table (``weights`` alone) it is the weighted mean of code values per stored
+element, at any depth, and with box weights the formula above bit for bit.  An extra ``plane=`` is a
+matte, depth or ID plane and has no curve: it always takes the weighted mean of code values.
+
 On the device (include/rrin_hip.h, csrc/exposure.hip): ``rrin_mean_frames``, one launch per call of
 ``Net.expose_items_*`` (a second one for ``plane=``) behind the item forwards on their stream; the sources
 are a table of frame pointers -- views of the stack and of the item forwards' outputs, nothing copied.
+With ``light`` or ``weights`` the launch is ``rrin_mean_frames_lut``, on YUV with a table
+``rrin_mean_frames_yuv_lut`` (csrc/exposure_linear.hip): the table in LDS, the same pointer table with the
+weights beside it.
 
 Not covered: ``NetGraph`` capture, ``precision="fp32_planar"``, the float ``Net.forward``, autograd,
-multi-GPU sharding, PNG folders, ``evaluate``, non-uniform shutter weights, linear-light averaging.
+multi-GPU sharding, PNG folders, ``evaluate``, 16-bit RGB above 12 bits with ``light``, chroma-siting-aware
+resampling (chroma is replicated in and block-averaged out, as on every YUV path).
 
 Host only: plain torch and Python, nothing here touches a device or loads the library.
 """
@@ -121,14 +139,113 @@ def chunks(groups, chunk: int) -> list:
     return runs
 
 
-def expose(frames: torch.Tensor, groups, items, depth: int = 8, shift: int = 0) -> torch.Tensor:
+SHUTTERS = ("box", "triangle")
+MAX_WEIGHT = 65535  # of one weight and of a group's sum W: W * lin <= 65535 * 2**30 < 2**46
+
+
+def shutter_weights(kind, s: int) -> list:
+    """The ``s`` integer weights of a shutter: ``"box"`` (or None) all 1, ``"triangle"`` ``w_k = min(k + 1, s -
+    k)``; an explicit list of ``s`` ints, each in 1..65535, is returned checked.  The sum ``W`` is at most
+    65535 (ValueError otherwise: ``W * lin`` must stay below 2**46)."""
+    if isinstance(s, bool) or not isinstance(s, int) or not 1 <= s <= MAX_SAMPLES:
+        raise ValueError(f"an exposure has 1..{MAX_SAMPLES} samples, got {s!r}")
+    if kind is None or (isinstance(kind, str) and kind == "box"):
+        w = [1] * s
+    elif isinstance(kind, str) and kind == "triangle":
+        w = [min(k + 1, s - k) for k in range(s)]
+    elif isinstance(kind, (str, bytes, torch.Tensor)) or not hasattr(kind, "__iter__"):
+        raise ValueError(f"weights must be one of {SHUTTERS} or a list of ints, got {kind!r}")
+    else:
+        w = list(kind)
+        if any(isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= MAX_WEIGHT for v in w):
+            raise ValueError(f"every shutter weight is an int in 1..{MAX_WEIGHT}, got {w!r}")
+        if len(w) != s:
+            raise ValueError(f"{len(w)} shutter weights for a group of {s} samples: an explicit list needs every "
+                             "group of the call to have that many")
+    if sum(w) > MAX_WEIGHT:
+        raise ValueError(f"the shutter weights sum to {sum(w)}, above {MAX_WEIGHT}")
+    return w
+
+
+def group_weights(weights, sizes) -> list:
+    """:func:`shutter_weights` per group of a call whose groups have ``sizes`` samples: a name applies to
+    each group at its own size, an explicit list must fit every group."""
+    return [shutter_weights(weights, s) for s in sizes]
+
+
+def _weighted(s: torch.Tensor, w: list, lin, thr) -> torch.Tensor:
+    """int64 samples ``[S, ...]`` -> the int64 mean ``[...]``: ``enc((sum_k w_k lin[s_k] + W // 2) // W)``, or
+    without a table ``(sum_k w_k s_k + W // 2) // W``."""
+    from . import transfer
+    wt = torch.tensor(w, dtype=torch.int64).reshape((-1,) + (1,) * (s.dim() - 1))
+    tot = sum(w)
+    v = ((wt * (s if lin is None else lin[s])).sum(dim=0) + tot // 2) // tot
+    return v if lin is None else transfer.encode(thr, v)
+
+
+def mean_frames_linear(frames: torch.Tensor, fmt, lin=None, weights=None) -> torch.Tensor:
+    """The exposed frame of ``S`` sample frames ``frames`` ``[S, ...]`` of the :class:`FrameFormat` ``fmt`` in
+    linear light: ``lin`` a transfer table (:func:`rrin_amd.transfer.as_table`: a name or ``maxval + 1``
+    integers) or None, ``weights`` a shutter (:func:`shutter_weights`) with sum ``W``.
+
+    RGB formats (and any format without a table), per stored element with ``s_k = min(word >> shift,
+    maxval)``: ``v = (sum_k w_k * lin[s_k] + W // 2) // W``, ``out = enc(v) << shift``; ``lin=None`` means no
+    table, ``v = (sum_k w_k * s_k + W // 2) // W`` and ``out = v << shift`` at any depth -- YUV is then
+    averaged per stored element with no colour conversion, and with box weights this is
+    :func:`mean_frames` bit for bit.  A table needs ``depth <= 12`` (ValueError: it would not fit in LDS).
+
+    YUV formats with a table: every sample frame goes to RGB code values by ``yuv.yuv_to_rgb`` /
+    ``yuv_to_rgb16`` with the format's ``coef``, the rule above applies per pixel and channel (shift 0), and
+    the result goes back by ``yuv.rgb_to_yuv`` / ``rgb16_to_yuv``: the convention of every YUV forward, the
+    RGB result between the two conversions.
+
+    ``S = 1``: the formula as it stands.  On RGB with a strictly increasing table it gives the sample back
+    (clamped to ``maxval``); on YUV it is then the sample after one round trip through RGB, which a frame that
+    is not itself ``rgb_to_yuv`` of some RGB frame does not survive unchanged."""
+    from . import transfer, yuv
+    check_format(fmt.depth, fmt.shift)
+    if frames.dim() < 1 or not 1 <= frames.shape[0] <= MAX_SAMPLES:
+        raise ValueError(f"an exposure has 1..{MAX_SAMPLES} sample frames, got {tuple(frames.shape)}")
+    if frames.dtype != fmt.dtype:
+        raise TypeError(f"frames of depth {fmt.depth} are {fmt.dtype}, got {frames.dtype}")
+    w = shutter_weights(weights, frames.shape[0])
+    thr = None
+    if lin is not None:
+        if fmt.depth > 12:
+            raise ValueError(f"light needs a depth of at most 12 bits, got {fmt.depth}: a table of 2**{fmt.depth} "
+                             "entries and its thresholds would not fit in LDS")
+        lin = transfer.as_table(lin, fmt.depth)
+        thr = transfer.thresholds(lin)
+    if fmt.layout is None or lin is None:
+        q = _weighted(read_samples(frames, fmt.depth, fmt.shift).to(torch.int64), w, lin, thr) << fmt.shift
+        return q.to(torch.uint8) if fmt.depth == 8 else q.to(torch.int16).view(torch.uint16)
+    if fmt.coef is None:
+        raise ValueError("a samples-only format has no matrix: linear light on YUV needs FrameFormat.yuv / yuv16")
+    if fmt.depth == 8:
+        q = _weighted(yuv.yuv_to_rgb(frames, fmt.layout, fmt.coef).to(torch.int64), w, lin, thr)
+        return yuv.rgb_to_yuv(q.to(torch.uint8)[None], fmt.layout, fmt.coef)[0]
+    msb = fmt.shift != 0
+    rgb = yuv.yuv_to_rgb16(frames, fmt.layout, fmt.coef, fmt.depth, msb)
+    q = _weighted(yuv.words_to_int(rgb).to(torch.int64), w, lin, thr)
+    return yuv.rgb16_to_yuv(yuv.int_to_words(q)[None], fmt.layout, fmt.coef, fmt.depth, msb)[0]
+
+
+def expose(frames: torch.Tensor, groups, items, depth: int = 8, shift: int = 0, light=None, weights=None,
+           fmt=None) -> torch.Tensor:
     """The definition of ``expose_items_*`` on one stack ``frames`` ``[P+1, ...]``: ``items(pair, t)`` gives
     the frame ``[...]`` of the network item ``(pair, t)``, ``t > 0`` (by definition
     ``interpolate_items_*(frames, [pair], [t], ...)[0]``); output g is :func:`mean_frames` of its samples.
-    Returns ``[G, ...]``."""
+    With ``light`` (a transfer table or its name) and / or ``weights`` (a shutter) output g is
+    :func:`mean_frames_linear` of them in ``fmt`` -- default: the element reading of ``depth`` and ``shift``,
+    which is every RGB format; a YUV call passes its :class:`FrameFormat`.  Returns ``[G, ...]``."""
     groups = check_groups(groups, frames.shape[0] - 1)
+    linear = light is not None or weights is not None
+    if linear:
+        from .framefmt import FrameFormat
+        fmt = FrameFormat.samples(None, depth, shift) if fmt is None else fmt
+        per_group = group_weights(weights, [len(group) for group in groups])
     out = []
-    for group in groups:
-        srcs = [frames[p] if t == 0.0 else items(p, t) for p, t in group]
-        out.append(mean_frames(torch.stack(srcs), depth, shift))
+    for g, group in enumerate(groups):
+        srcs = torch.stack([frames[p] if t == 0.0 else items(p, t) for p, t in group])
+        out.append(mean_frames_linear(srcs, fmt, light, per_group[g]) if linear else mean_frames(srcs, depth, shift))
     return torch.stack(out)

@@ -325,13 +325,24 @@ class Net(nn.Module):
         from .flowscale import check_flow_scale
         if not isinstance(frames, torch.Tensor) or frames.dim() < 1:
             raise TypeError(f"{name} takes one stack of frames")
-        exposure.chunks(exposure.check_groups(groups, frames.shape[0] - 1), chunk)
+        checked = exposure.check_groups(groups, frames.shape[0] - 1)
+        exposure.chunks(checked, chunk)
         check_flow_scale(kw.get("flow_scale", 1))
+        if kw.get("light") is not None or kw.get("weights") is not None:
+            from . import transfer
+            exposure.group_weights(kw.get("weights"), [len(group) for group in checked])
+            depth = kw.get("depth", 8) if name.endswith("16") else 8
+            if kw.get("light") is not None:
+                if isinstance(depth, int) and not isinstance(depth, bool) and 12 < depth <= 16:
+                    raise ValueError(f"{name}: light needs a depth of at most 12 bits, got {depth}: a table of "
+                                     f"2**{depth} entries and its thresholds would not fit in LDS")
+                transfer.table_key(kw["light"], depth)
         if torch.is_grad_enabled():
             raise RuntimeError(f"rrin_amd.Net.{name} is inference-only: use torch.no_grad()")
         return getattr(self.engine(), name)(frames, groups, chunk, streams=self.streams, **kw)
 
-    def expose_items_u8(self, frames, groups, chunk=4, scene_threshold=None, gate=None, flow_scale=1, plane=None):
+    def expose_items_u8(self, frames, groups, chunk=4, scene_threshold=None, gate=None, flow_scale=1, plane=None,
+                        light=None, weights=None):
         """``G`` exposed frames over one stack of 8-bit frames: a synthetic shutter
         (:mod:`rrin_amd.exposure` is the definition, :func:`rrin_amd.retime.exposure_schedule` makes the
         groups of a frame-rate conversion).  ``frames`` uint8 ``[P+1,H0,W0,3]`` on the device, ``groups`` a
@@ -343,29 +354,43 @@ class Net(nn.Module):
         values, no transfer function.  With ``scene_threshold`` or ``gate`` the items inherit their pair's
         decision and :attr:`last_gate` is the ``[M]`` codes of the call's network items in order; an
         exposure across a cut mixes both shots.  ``plane``: one ``[P+1,H0,W0]`` stack; the call returns
-        ``(frames, plane)``."""
+        ``(frames, plane)``.
+
+        ``light`` names the material's transfer curve (``"srgb"``, ``"bt1886"``, ``"gamma22"``, ``"pq"``,
+        ``"hlg"``, or a table: :mod:`rrin_amd.transfer`): the mean is then taken in linear light, ``enc((sum_k
+        w_k lin[s_k] + W // 2) // W)`` per element (on YUV per pixel and channel of the RGB between the
+        path's two conversions).  ``weights`` (``"box"``, ``"triangle"`` or a list of ints, sum at most 65535)
+        weighs the samples; the plane is then the weighted mean of its code values, never through the
+        table.  Both are checked before any device work; with both None the call is what it was."""
         return self._expose("expose_items_u8", frames, groups, chunk, scene_threshold=scene_threshold, gate=gate,
-                            flow_scale=flow_scale, **_plane_kw(plane))
+                            flow_scale=flow_scale, light=light, weights=weights,
+                            **_plane_kw(plane))
 
     def expose_items_yuv(self, frames, groups, chunk=4, layout="nv12", coef=None, scene_threshold=None, gate=None,
-                         flow_scale=1, plane=None):
+                         flow_scale=1, plane=None, light=None,
+                         weights=None):
         """:meth:`expose_items_u8` on one stack of 8-bit YUV frames over :meth:`interpolate_items_yuv`;
         every stored byte, chroma included, is averaged."""
         return self._expose("expose_items_yuv", frames, groups, chunk, layout=layout, coef=coef,
-                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale, **_plane_kw(plane))
+                            scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale, light=light,
+                            weights=weights, **_plane_kw(plane))
 
     def expose_items_u16(self, frames, groups, chunk=4, depth=10, scene_threshold=None, gate=None, flow_scale=1,
-                         plane=None):
+                         plane=None, light=None,
+                         weights=None):
         """:meth:`expose_items_u8` on uint16 RGB frames of ``depth`` over :meth:`interpolate_items_u16`."""
         return self._expose("expose_items_u16", frames, groups, chunk, depth=depth, scene_threshold=scene_threshold,
-                            gate=gate, flow_scale=flow_scale, **_plane_kw(plane))
+                            gate=gate, flow_scale=flow_scale, light=light, weights=weights,
+                            **_plane_kw(plane))
 
     def expose_items_yuv16(self, frames, groups, chunk=4, layout="nv12", depth=10, msb=False, coef=None,
-                           scene_threshold=None, gate=None, flow_scale=1, plane=None):
+                           scene_threshold=None, gate=None, flow_scale=1, plane=None, light=None,
+                           weights=None):
         """:meth:`expose_items_yuv` on 10- or 12-bit frames in 16-bit words over
         :meth:`interpolate_items_yuv16`: a sample is ``min(word >> shift, maxval)``, stored ``<< shift``."""
         return self._expose("expose_items_yuv16", frames, groups, chunk, layout=layout, depth=depth, msb=msb,
                             coef=coef, scene_threshold=scene_threshold, gate=gate, flow_scale=flow_scale,
+                            light=light, weights=weights,
                             **_plane_kw(plane))
 
     @property
