@@ -1,0 +1,290 @@
+"""CPU: the tests of tests/exact_ref.py, on which tests/test_gpu_h8_exact.py rests -- the int64
+references against float64 torch, the mutations that equality must reject, the representability
+of every case's data and results, and the packed weight blobs against their rational values."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from rrin_amd import _lib
+from tests import exact_ref as E
+from tests.test_gpu_h8 import pack_h8
+
+X3, F16, R32 = _lib.PREC_F16X3, _lib.PREC_F16, _lib.PREC_F32R
+# (n, cin, cout, h, w, mags) of tests/test_gpu_h8_exact.py: plain, pool, deep K (cin 256; resident 96 / 192)
+PLAIN = [(2, cin, cout, h, w, (1, 2)) for cin, cout in ((16, 32), (64, 40)) for h, w in ((9, 40), (17, 33))]
+POOLED = [(2, cin, cout, 18, 34, (1,)) for cin, cout in ((16, 32), (64, 40))]
+DEEP = [(1, cin, 32, 9, 40, (1,)) for cin in (256, 192, 96)]
+SUB = [(2, cin, cout, sh, sw, (1,)) for cin, cout in ((16, 32), (64, 40)) for sh, sw in ((5, 9), (1, 2))]
+T = lambda a: torch.from_numpy(np.asarray(a, np.float64))  # noqa: E731
+
+
+@pytest.mark.parametrize("case", PLAIN[:2] + POOLED[:1] + DEEP[2:])
+def test_int_references_equal_float64_torch(case):
+    x, wt, b, ox, ow = E.int_case(*case)
+    y = F.conv2d(T(x), T(wt), T(b), padding=1)
+    assert np.array_equal(E.pre_int(x, wt, b).f64(), y.numpy())
+    assert np.array_equal(E.pre_int(x, wt, b, 48).f64(), F.conv2d(T(x), 48 * T(wt), 48 * T(b), padding=1).numpy())
+    ly = F.leaky_relu(y, E.SLOPE)
+    assert np.array_equal(E.leaky(E.pre_int(x, wt, b)).f64(), ly.numpy())
+    if x.shape[2] % 2 == 0:
+        assert np.array_equal(E.pool(E.leaky(E.pre_int(x, wt, b))).f64(), F.avg_pool2d(ly, 2).numpy())
+    # split-fp16: the three product classes, without lo*lo
+    xf, wf = T(x) + T(ox) / E.LO, T(wt) + T(ow) / E.LO
+    full = F.conv2d(xf, wf, T(b), padding=1) - F.conv2d(T(ox) / E.LO, T(ow) / E.LO, None, padding=1)
+    assert np.array_equal(E.pre_split(x, wt, b, ox, ow).f64(), full.numpy())
+
+
+@pytest.mark.parametrize("case", SUB)
+def test_subpixel_reference_equals_float64_torch(case):
+    x, wt, b, _, _ = E.int_case(*case)
+    up = F.interpolate(T(x), scale_factor=2, mode="bilinear", align_corners=False)
+    assert np.array_equal(E.up2_int(x) / 16.0, up.numpy())
+    assert np.array_equal(E.pre_sub(x, wt, b).f64(), F.conv2d(up, T(wt), T(b), padding=1).numpy())
+    r = E.pre_sub(x, wt, b).f64()
+    assert E.f16_exact(r), float(np.abs(r).max())     # sixteenths below 128
+
+
+@pytest.mark.parametrize("case", PLAIN + POOLED + DEEP)
+def test_mutations_break_equality(case):
+    """A dropped tap of one channel at one pixel, a K chunk added twice for one co block, a zero lo
+    and two exchanged output rows: each changes the reference of every data set, the pooled one too."""
+    x, wt, b, ox, ow = E.split_case(*case)
+    assert not (x == 0).any() and not (wt == 0).any() and not (b == 0).any()
+    for r, mul in ((E.pre_int(x, wt, b), 1), (E.pre_int(x, wt, b, 48), 48), (E.pre_split(x, wt, b, ox, ow), 1)):
+        epis = (lambda q: q, E.leaky) + ((lambda q: E.pool(E.leaky(q)),) if case in POOLED else ())
+        for k, epi in enumerate(epis):
+            good = epi(r).units
+            # pooled: rows 2 and 3 share a pool pair (their exchange is invisible, rightly); rows 1 and 2 do not
+            for bad in (E.drop_one_tap(r, x, wt, mul), E.chunk_twice(r, x, wt, mul), E.swap_rows(r, 1 if k == 2 else 2)):
+                assert not np.array_equal(epi(bad).units, good)
+    assert (ox != 0).any() and (ow != 0).any()
+    assert not np.array_equal(E.pre_split(x, wt, b, ox, ow, zero_lo=True).units, E.pre_split(x, wt, b, ox, ow).units)
+
+
+@pytest.mark.parametrize("case", PLAIN + POOLED + DEEP)
+def test_results_are_representable(case):
+    """fp16: the result and its pooled value are fp16 numbers; split-fp16: the result in units of
+    2^-14 (2^-16 pooled) stays below 2^24, so the fp32 the kernel splits is exact; fp32 records:
+    every direct-form partial sum below 2^24."""
+    x, wt, b, ox, ow = E.split_case(*case)
+    assert (E.pre_split(x, wt, b, ox, ow).units == 0).sum() >= 2 and (E.pre_int(x, wt, b).units == 0).sum() >= 2
+    pooled = case in POOLED
+    for r in (E.pre_int(x, wt, b), E.leaky(E.pre_int(x, wt, b))):
+        assert E.f16_exact(r.f64()), float(np.abs(r.f64()).max())
+    s = E.leaky(E.pre_split(x, wt, b, ox, ow))
+    assert int(np.abs(s.units).max()) < E.P24 and E.f32_exact(s.f64())
+    if pooled:
+        assert E.f16_exact(E.pool(E.leaky(E.pre_int(x, wt, b))).f64())
+        p = E.pool(s)
+        assert int(np.abs(p.units).max()) < E.P24 and E.f32_exact(p.f64())
+    assert E.direct_sum_units(x, wt, b) * (E.LO + 2) < E.P24
+    assert E.direct_sum_units(x, wt, b, 48) < E.P24
+
+
+def _cfg(prec, want_kind, bm=None):
+    lib = _lib.lib()
+    return next(c for c in range(lib.rrin_conv_h8_cfg_count()) if lib.rrin_conv_h8_cfg_ok(c, prec)
+                and lib.rrin_conv_h8_cfg_wino(c) == want_kind and (bm is None or lib.rrin_conv_h8_cfg_bm(c) == bm))
+
+
+@pytest.mark.parametrize("case", PLAIN[::2] + DEEP[:1] + SUB[::2])
+def test_packed_weights_are_their_rational_values(case):
+    """Every blob the GPU tests hand to a kernel, decoded: fp32 direct = w; fp32 U = G g G^T
+    (F(2x2): quarters; kind 14 with w x 48: integers); fp16 U and the direct hi / lo halves times
+    the power-of-two scale.  Sub-pixel cases: the phase-combined weights are sixteenths."""
+    lib = _lib.lib()
+    x, wt, b, _, ow = E.int_case(*case)
+    cout, cin = wt.shape[:2]
+    sub = case in SUB
+    if sub:
+        ws = np.empty((4 * cout, cin, 3, 3), np.float32)
+        bs = np.empty(4 * cout, np.float32)
+        w32, b32 = wt.astype(np.float32), b.astype(np.float32)
+        _lib.check(lib.rrin_subpixel_weights(w32.ctypes.data, b32.ctypes.data, cout, cin, ws.ctypes.data, bs.ctypes.data))
+        assert np.array_equal(ws.astype(np.float64) * 16, E.subpixel_weights_int(wt).astype(np.float64))
+        wu, den, cout, ow = E.subpixel_weights_int(wt), 16, 4 * cout, 0 * E.subpixel_weights_int(wt)
+        bq = bs.astype(np.float64)
+    else:
+        wu, den, bq = wt, 1, b.astype(np.float64)
+    w64 = wu.astype(np.float64) / den
+    tw, tb = torch.from_numpy(w64).float(), torch.from_numpy(bq).float()
+    # fp32 records, direct form
+    c = _cfg(R32, 0)
+    bm = lib.rrin_conv_h8_cfg_bm(c)
+    assert np.array_equal(E.unpack_direct(pack_h8(tw, tb, c, R32, "cpu")[0].numpy(), cout, cin, bm, 4), w64.reshape(cout, cin, 9))
+    # fp32 Winograd F(2x2) (BM 32 and 64) and kind 14 (weights x 48)
+    for k in (3, 6):
+        c = _cfg(R32, k)
+        bm = lib.rrin_conv_h8_cfg_bm(c)
+        u = E.wino_u(wu, 1) / den
+        assert E.f32_exact(u) and E.wino_fits(1, wu, den, cin, max(case[5]))[0]
+        assert np.array_equal(E.unpack_wino(pack_h8(tw, tb, c, R32, "cpu")[0].numpy(), cout, cin, bm, 4, 16), u.reshape(cout, cin, 16))
+    c = _cfg(R32, 14)
+    u = E.wino_u(48 * wu, 14) / den
+    assert E.f32_exact(u)
+    assert np.array_equal(E.unpack_wino(pack_h8(48 * tw, tb, c, R32, "cpu")[0].numpy(), cout, cin, 32, 4, 24), u.reshape(cout, cin, 24))
+    fits, worst, coarse, grid = E.wino_fits(14, 48 * wu, den, cin, max(case[5]))
+    print(f"kind 14 cin {cin} sub {sub}: grid {grid}, worst {worst:.3g}, coarse bound {coarse:.3g}, 2^24 = {E.P24}")
+    assert fits, (worst, coarse)
+    # the coarser cin max|U| max|V| rowsum(A^T) pairs the largest U with the largest A^T coefficient,
+    # which never meet at one point.  It holds for every F(2x2) case and for kind 14 at cin 16; it
+    # cannot hold for kind 14 at cin 64 (2.1e7 with |x| <= 2, |w| <= 96), at cin 256 and for the
+    # sub-pixel conv at cin 64 (both already +-1: no smaller data exists), so one bound, the per-point
+    # one -- itself a worst case over the magnitudes -- is asserted for every case
+    assert E.wino_fits(1, wu, den, cin, max(case[5]))[2] < E.P24
+    assert (coarse < E.P24) == (cin == 16), (cin, sub, coarse)
+    if not sub:
+        assert grid == 1.0
+    # fp16 Winograd kind 6 (16-channel chunks): fp16(U 2^s) exact
+    c = _cfg(F16, 6)
+    whi, _, _, inv = pack_h8(tw, tb, c, F16, "cpu")
+    u = E.wino_u(wu, 1) / den
+    assert np.array_equal(E.unpack_wino(E.halves(whi), cout, cin, 64, 8, 16) * inv, u.reshape(cout, cin, 16))
+    # direct hi / lo halves: fp16 (hi alone) and split-fp16 on w + ow 2^-12
+    c = _cfg(F16, 0)
+    bm = lib.rrin_conv_h8_cfg_bm(c)
+    whi, _, _, inv = pack_h8(tw, tb, c, F16, "cpu")
+    assert np.array_equal(E.unpack_direct(E.halves(whi), cout, cin, bm, 8) * inv, w64.reshape(cout, cin, 9))
+    c = _cfg(X3, 0)
+    bm = lib.rrin_conv_h8_cfg_bm(c)
+    wf = w64 + ow / E.LO
+    assert E.f32_exact(wf)
+    whi, wlo, _, inv = pack_h8(torch.from_numpy(wf).float(), tb, c, X3, "cpu")
+    assert np.array_equal(E.unpack_direct(E.halves(whi), cout, cin, bm, 8) * inv, w64.reshape(cout, cin, 9))
+    assert np.array_equal(E.unpack_direct(E.halves(wlo), cout, cin, bm, 8) * inv / 2048, (ow / E.LO).reshape(cout, cin, 9))
+    assert sub or bool(wlo.any())
+
+
+@pytest.mark.parametrize("case", PLAIN + POOLED + SUB)
+def test_source_records_split_as_intended(case):
+    """x + ox 2^-12 through the CPU record encoder: hi is the integer, lo the offset (x 2^11)."""
+    x, _, _, ox, _ = E.split_case(*case)
+    hi, lo = E.records(x + ox / E.LO, "F16X3", (x.shape[1] + 15) // 16 * 2)
+    from tests import glue_ref as G
+    n, c, h, w = x.shape
+    assert np.array_equal(G.records_to_nchw(hi, None, 0, c, h, w).double().numpy(), x.astype(np.float64))
+    assert np.array_equal(G.records_to_nchw(lo, None, 0, c, h, w).double().numpy(), ox / 2.0)
+    assert bool(lo.any())
+
+
+@pytest.mark.parametrize("cin", [6, 32])
+@pytest.mark.parametrize("h,w", [(9, 40), (17, 33)])
+def test_block0_data_is_representable(cin, h, w):
+    x, wa, ba, wb, bb = E.block0_case(2, cin, h, w)
+    assert not (x == 0).any() and not (wa == 0).any() and not (wb == 0).any()
+    mid, out = E.block0_ref(x, wa, ba, wb, bb)
+    assert E.f16_exact(mid.f64()) and E.f16_exact(out.f64()), (np.abs(mid.units).max(), np.abs(out.f64()).max())
+    ref = F.leaky_relu(F.conv2d(F.leaky_relu(F.conv2d(T(x), T(wa), T(ba), padding=1), E.SLOPE), T(wb), T(bb), padding=1), E.SLOPE)
+    assert np.array_equal(out.f64(), ref.numpy())
+    ya = E.conv_int(x, wa) + ba[None, :, None, None]
+    assert (ya > 0).any() and (ya < 0).any()
+    # mutations of conv a (a dropped tap, a K chunk twice) and of conv b, and exchanged rows, reach the result
+    def out_of(ya_, wb_=wb, extra=0):
+        mid_ = np.where(ya_ > 0, ya_, ya_ // 4) if not (ya_ % 4).any() else None
+        if mid_ is None:
+            return None   # conv a left its grid of 4: the result is not even an fp16-exact integer form
+        return E.leaky(E.Ref(E.conv_int(mid_, wb_) + bb[None, :, None, None] + extra, 1)).units
+    good = out_of(ya)
+    assert np.array_equal(good, out.units)
+    r = E.Ref(ya, 1)
+    for bad in (E.drop_one_tap(r, x, wa), E.chunk_twice(r, x, wa, c0=0, width=min(8, cin))):
+        o = out_of(bad.units)
+        assert o is None or not np.array_equal(o, good)
+    rb = E.Ref(E.conv_int(mid.units, wb) + bb[None, :, None, None], 1)
+    yy, xq = (int(v) for v in np.argwhere(mid.units[0, 1, :h - 1, 1:] != 0)[0])   # conv a can be 0 there: a product that is not
+    for bad in (E.drop_one_tap(rb, mid.units, wb, at=(0, 1, yy + 1, xq)), E.chunk_twice(rb, mid.units, wb), E.swap_rows(rb)):
+        assert not np.array_equal(E.leaky(bad).units, good)
+
+
+@pytest.mark.parametrize("case", SUB)
+def test_subpixel_mutations_break_equality(case):
+    """The mutations on the sub-pixel references (integer and split-fp16 with offsets on x), applied
+    to conv(upsample(x), w); the 1 x 2 source has 2 x 4 outputs: rows 0 and 1 are exchanged."""
+    x, wt, b, ox, _ = E.split_case(*case)
+    up = E.up2_int(x)
+    for r, mul in ((E.pre_sub(x, wt, b), 1), (E.pre_sub(x, wt, b, 48), 48), (E.pre_sub_split(x, wt, b, ox), 1)):
+        at, rs = (0, 1, 1, 2), r.scale // 16     # products are in sixteenths: up carries the 16
+        bads = (E.drop_one_tap(E.Ref(r.units, rs), up, wt, mul, at=at, tap=(0, 2)), E.chunk_twice(E.Ref(r.units, rs), up, wt, mul),
+                E.swap_rows(r, 0))
+        for bad in bads:
+            assert not np.array_equal(bad.units, r.units)
+    assert (ox != 0).any()
+    assert not np.array_equal(E.pre_sub_split(x, wt, b, 0 * ox).units, E.pre_sub_split(x, wt, b, ox).units)
+    s = E.pre_sub_split(x, wt, b, ox)
+    assert int(np.abs(s.units).max()) < E.P24 and E.f32_exact(s.f64())
+    # float64 torch on x + ox 2^-12 (w has no offset: nothing is dropped)
+    upf = F.interpolate(T(x) + T(ox) / E.LO, scale_factor=2, mode="bilinear", align_corners=False)
+    assert np.array_equal(s.f64(), F.conv2d(upf, T(wt), T(b), padding=1).numpy())
+
+
+# ---- part B ------------------------------------------------------------------------------------------
+FLOAT = [(2, 16, 32, 9, 40), (2, 64, 40, 17, 33), (2, 16, 32, 17, 33), (2, 16, 32, 18, 34)]
+# worst err / (2^-24 S) of exact_ref.wino_emulate against float64 on float_case: (F(2x2) fp32, kind 14, fp16 kind 6)
+RATIOS = {FLOAT[0]: (1.81, 10.5, 6000.0), FLOAT[1]: (1.63, 5.86, 2881.3), FLOAT[2]: (1.76, 7.42, 5894.0), FLOAT[3]: (1.99, 9.36, 6392.7)}
+
+
+@pytest.mark.parametrize("case", FLOAT)
+def test_wino_emulation_ratios_are_the_recorded_ones(case):
+    """The measured amplification of the Winograd transforms, which the GPU bound multiplies by 4:
+    it fails if a ratio moves from the recorded value (to its printed precision)."""
+    got = (E.wino_ratio(*case, "R32", 1), E.wino_ratio(*case, "R32", 14), E.wino_ratio(*case, "F16", 6))
+    print(case, [round(g, 2) for g in got])
+    for g, want in zip(got, RATIOS[case]):
+        assert abs(g - want) <= 0.006 * max(want, 1.0), (got, RATIOS[case])
+    # and the emulation is the conv: float64 operands through the same code reproduce float64 to 1e-12 ... in fp32 to its ratio
+    x, wt, b = E.float_case(*case, "R32")
+    assert np.abs(E.wino_emulate(x, wt, b, 14) - E.conv64(x, wt, b)).max() < 1e-4
+
+
+@pytest.mark.parametrize("case", FLOAT)
+@pytest.mark.parametrize("prec", ["R32", "F16", "F16X3"])
+def test_float_data_is_held_exactly(case, prec):
+    """fp16: x and the packed w 2^s are fp16 numbers; split-fp16: x and w 2^s equal their hi + lo;
+    the blobs decode to w exactly."""
+    lib = _lib.lib()
+    x, wt, b = E.float_case(*case, prec)
+    cout, cin = wt.shape[:2]
+    assert E.f32_exact(x) and E.f32_exact(wt)
+    tw, tb = torch.from_numpy(wt).float(), torch.from_numpy(b).float()
+    if prec == "F16":
+        assert E.f16_exact(x) and E.f16_exact(wt)
+        c = _cfg(F16, 0)
+        whi, _, _, inv = pack_h8(tw, tb, c, F16, "cpu")
+        assert np.array_equal(E.unpack_direct(E.halves(whi), cout, cin, lib.rrin_conv_h8_cfg_bm(c), 8) * inv, wt.reshape(cout, cin, 9))
+    if prec == "F16X3":
+        hi, lo = E.split16_f64(x)
+        assert np.array_equal(hi + lo, x) and lo.any()
+        c = _cfg(X3, 0)
+        whi, wlo, _, inv = pack_h8(tw, tb, c, X3, "cpu")
+        bm = lib.rrin_conv_h8_cfg_bm(c)
+        joined = (E.unpack_direct(E.halves(whi), cout, cin, bm, 8) + E.unpack_direct(E.halves(wlo), cout, cin, bm, 8) / 2048) * inv
+        assert np.array_equal(joined, wt.reshape(cout, cin, 9)) and bool(wlo.any())
+
+
+def test_split_bound_rejects_a_dropped_hi_lo_class():
+    """got = float64 without the hx*lw products: past the split-fp16 bound somewhere (cin 16)."""
+    case = FLOAT[0]
+    x, wt, b = E.float_case(*case, "F16X3")
+    ref, s = E.conv64(x, wt, b), E.s_of(x, wt, b)
+    bnd = E.bound("F16X3", 9 * case[1], s, ref)
+    assert (np.abs(ref - ref) <= bnd).all()
+    hx, _ = E.split16_f64(x)
+    _, lw = E.split16_f64(wt)
+    got = ref - E.conv64(hx, lw)
+    assert (np.abs(got - ref) > bnd).any()
+    # ... while the lo*lo class the design drops stays inside
+    _, lx = E.split16_f64(x)
+    assert (np.abs(E.conv64(lx, lw)) <= 2.0 ** -22 * s).all()
+
+
+def test_fp16_bound_rejects_a_second_rounding():
+    """got = f16(f16(conv) + b): the sum rounded to fp16 before the bias and again after it."""
+    case = FLOAT[0]
+    x, wt, b = E.float_case(*case, "F16")
+    ref, s = E.conv64(x, wt, b), E.s_of(x, wt, b)
+    bnd = E.bound("F16", 9 * case[1], s, ref)
+    once = T(ref).half().double().numpy()
+    assert (np.abs(once - ref) <= bnd).all()
+    twice = (T(E.conv64(x, wt)).half().double() + T(b).view(1, -1, 1, 1)).half().double().numpy()
+    assert (np.abs(twice - ref) > bnd).any()

@@ -38,7 +38,7 @@ def direct_cfg(cin, cout, bm=None):
 
 
 def block0(src, cin, wa, ba, cfg_a, wb, bb, cfg_b, pool, dst=None, dst_off=0, status=None, tail_finite=0, pl=None,
-           pool_off=0):
+           pool_off=0, slope=0.1):
     """pl / pool_off: a caller-allocated pool tensor and the first channel of its view."""
     dev = src.hi.device
     n, h, w = src.n, src.h, src.w
@@ -49,7 +49,7 @@ def block0(src, cin, wa, ba, cfg_a, wb, bb, cfg_b, pool, dst=None, dst_off=0, st
     wha, _, bpa, inva = pack_h8(wa, ba, cfg_a, F16, dev)
     whb, _, bpb, invb = pack_h8(wb, bb, cfg_b, F16, dev)
     d = _lib.Block0Desc()
-    d.n, d.cin, d.cfg_a, d.cfg_b, d.slope = n, cin, cfg_a, cfg_b, 0.1
+    d.n, d.cin, d.cfg_a, d.cfg_b, d.slope = n, cin, cfg_a, cfg_b, slope
     d.inv_wscale_a, d.inv_wscale_b, d.tail_finite = inva, invb, tail_finite
     d.src = src.chunk_view(0, cin)
     d.dst = dst.view(dst_off, 32)

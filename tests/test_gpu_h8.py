@@ -152,7 +152,7 @@ def set_split(d, ksplit, dev, keep, alloc=scratch):
 
 def conv_h8(src: H8Tensor, w, b, cfg, prec, epi=_lib.EPI_LINEAR, dst=None, dst_off=0, pool=None, perm=None,
             cin=None, tail_finite=0, ksplit=0, keep=None, src_off=0, status=None, alloc=scratch, packed=None,
-            pool_off=0):
+            pool_off=0, slope=0.1):
     """src_off: first channel of the source view; status: the fp16 range flag (an int32 tensor);
     alloc: see scratch(); packed: pack_h8's result for (w, b, cfg, prec), to pack once per config."""
     dev = src.hi.device
@@ -164,7 +164,7 @@ def conv_h8(src: H8Tensor, w, b, cfg, prec, epi=_lib.EPI_LINEAR, dst=None, dst_o
         pool = H8Tensor(src.n, cout, src.h // 2, src.w // 2, dev, prec)
     whi, wlo, bp, inv = packed if packed is not None else pack_h8(w, b, cfg, prec, dev, perm)
     d = _lib.ConvH8Desc()
-    d.n, d.cin, d.cout, d.cfg, d.prec, d.epi_mode, d.slope, d.inv_wscale = src.n, cin, cout, cfg, prec, epi, 0.1, inv
+    d.n, d.cin, d.cout, d.cfg, d.prec, d.epi_mode, d.slope, d.inv_wscale = src.n, cin, cout, cfg, prec, epi, slope, inv
     d.tail_finite = tail_finite
     d.status = status.data_ptr() if status is not None else None
     d.src = src.chunk_view(src_off, cin)
