@@ -28,7 +28,7 @@ def pack(w: torch.Tensor, b: torch.Tensor, cfg: int, perm=None, dev="cuda"):
 
 
 def conv(src: PPTensor, w, b, cfg, *, src_off=0, dst=None, dst_off=0, upsample=False, epi=_lib.EPI_LINEAR,
-         pool=None, perm=None, cin=None):
+         pool=None, perm=None, cin=None, slope=0.1):
     """Run rrin_conv3x3_fwd; returns (dst PPTensor, pool PPTensor or None)."""
     dev = src.t.device
     cout, cin_w = w.shape[:2]
@@ -43,7 +43,7 @@ def conv(src: PPTensor, w, b, cfg, *, src_off=0, dst=None, dst_off=0, upsample=F
     d.n, d.cin, d.cout, d.cfg = src.n, cin, cout, cfg
     d.src_mode = _lib.SRC_UPSAMPLE2X if upsample else _lib.SRC_DIRECT
     d.epi_mode = epi
-    d.slope = 0.1
+    d.slope = slope
     d.src = src.view(src_off, cin)
     d.dst = dst.view(dst_off, cout)
     if pool is not None:
