@@ -423,7 +423,7 @@ def pool_bound(prec, bnd, ref, refp):
 G4 = G4_24.astype(np.float64) / 24
 
 
-def wino_emulate(x, wt, b, kind, f16=False):
+def wino_emulate(x, wt, b, kind, f16=False, rep=False):
     """The Winograd convs restated in numpy at the kernels' precision: U = Gy g Gx^T in double,
     rounded once (fp32; f16: x 2^s with max |U| 2^s in [2^12, 2^13), rounded to fp16); V = B^T d B
     in fp32 (f16: in fp16); M = sum over the channels in channel (= chunk) order, fp32 products
@@ -443,6 +443,8 @@ def wino_emulate(x, wt, b, kind, f16=False):
     hh, wd = -(-h // 2) * 2, -(-w // tw) * tw
     xp = np.zeros((n, cin, hh + 2, wd + 2), vd)
     xp[:, :, 1:h + 1, 1:w + 1] = x
+    if rep:   # the source's edge-replicated ring (the sub-pixel conv reads it); zero beyond it
+        xp[:, :, :h + 2, :w + 2] = np.pad(x, ((0, 0), (0, 0), (1, 1), (1, 1)), mode="edge")
     win = np.lib.stride_tricks.sliding_window_view(xp, (4, ww), axis=(2, 3))[:, :, ::2, ::tw]
     t = np.einsum("ab,ncpqbd->ncpqad", BT2.astype(vd), win).astype(vd)
     v = np.einsum("ncpqad,ed->ncpqae", t, bx.astype(vd)).astype(vd).astype(f)
@@ -462,3 +464,334 @@ def wino_ratio(n, cin, cout, h, w, prec, kind):
     x, wt, b = float_case(n, cin, cout, h, w, prec)
     err = np.abs(wino_emulate(x, wt, b, kind, prec == "F16") - conv64(x, wt, b))
     return float((err / (U * s_of(x, wt, b))).max())
+
+
+# ---- the sub-pixel up conv: more exact cases ---------------------------------------------------------
+FIX_PX = FIX_CI = 32       # the ring fix-up's tile: line pixels and input channels per chunk (common.hpp)
+
+
+def ring_mask(hh, ww):
+    m = np.zeros((hh, ww), bool)
+    m[0] = m[-1] = m[:, 0] = m[:, -1] = True
+    return m
+
+
+def edge_split(cin, prec, mode):
+    """(K groups, K runs) of a ring pixel's sum.  "fix" / "full": the standalone fix-up
+    (edge_fix.hip, edge_fix_split); "inlaunch": ring_full with the conv -- one group, fp32 records in
+    runs of one chunk; "fold": one chain (conv_wino.hip, ring_block)."""
+    if mode == "fold":
+        return 1, 1
+    if mode == "inlaunch":
+        return 1, (cin // FIX_CI if prec == "R32" and cin % FIX_CI == 0 else 1)
+    if prec == "R32":
+        ks = 2 if cin % (2 * FIX_CI) == 0 else 1
+        return ks, (cin // (ks * FIX_CI) if cin % (ks * FIX_CI) == 0 else 1)
+    ks = 2 if cin % (2 * FIX_CI) == 0 and cin >= 4 * FIX_CI else 1
+    if prec == "F16" and cin % (4 * FIX_CI) == 0 and cin >= 8 * FIX_CI:
+        ks = 4
+    return ks, 1
+
+
+def f16_round(v):
+    """float64 -> the nearest fp16 number, ties to even, as float64."""
+    return np.asarray(v, np.float64).astype(np.float16).astype(np.float64)
+
+
+def own_split(v):
+    hi, lo = split16_f64(v)
+    return bool(np.array_equal(hi + lo, np.asarray(v, np.float64)))
+
+
+def seam_shift(r, left=False):
+    """r with the first ring pixel of the second fix-up tile taken from its neighbour one further on:
+    top row x = 32 from x = 33, or (left) the left column y = 33 from y = 34 (the columns start at y = 1)."""
+    u = r.units.copy()
+    if left:
+        u[:, :, FIX_PX + 1, 0] = u[:, :, FIX_PX + 2, 0]
+    else:
+        u[:, :, 0, FIX_PX] = u[:, :, 0, FIX_PX + 1]
+    return Ref(u, r.scale)
+
+
+def ring_groups_miscounted(r, up, wt, wmul, ks):
+    """r whose ring pixels sum ks - 1 of the ks K groups: the chunks of 32 channels the last group owns
+    (chunk index = ks - 1 mod ks) are left out of every ring pixel."""
+    cin = up.shape[1]
+    sel = np.asarray([c for c in range(cin) if (c // FIX_CI) % ks == ks - 1])
+    part = (r.scale // 16) * wmul * conv_int(up[:, sel], wt[:, sel])
+    u = r.units.copy()
+    m = ring_mask(*u.shape[2:])
+    u[:, :, m] -= part[:, :, m]
+    return Ref(u, r.scale)
+
+
+# ---- the sub-pixel up conv on floats: forward bounds (DESIGN.md §8b) -----------------------------------
+@functools.lru_cache(maxsize=None)
+def sub_float_case(n, cin, cout, h, w, prec):
+    """(x, wt, b): x and b as float_case; w = m 2^-8, |m| <= 31, so that the phase-combined weights
+    (sums of k m 2^-12 with sum |k| <= 49 -- the centre tap gathers (1 + 3 + 3)^2 sixteenths -- so
+    |numerator| <= 1519 < 2^11) are fp16 numbers at any
+    power-of-two scale and the packs hold them exactly."""
+    x, _, b = float_case(n, cin, cout, h, w, prec)
+    r = np.random.default_rng([11, n, cin, cout, h, w])
+    wt = r.integers(-31, 32, size=(cout, cin, 3, 3)).astype(np.float64) / 256
+    return x, wt, b
+
+
+def phase_weights64(wt):
+    """[4, cout, cin, 3, 3]: phase 2 (Y & 1) + (X & 1) of rrin_subpixel_weights, over the low-res taps."""
+    return np.stack([np.einsum("ak,bl,oikl->oiab", KR4[ph >> 1] / 4.0, KR4[ph & 1] / 4.0, wt) for ph in range(4)])
+
+
+def phase_rows(wp):
+    """[4, cout, cin, 3, 3] -> the [4 cout, cin, 3, 3] row order of rrin_subpixel_weights."""
+    cout = wp.shape[1]
+    out = np.empty((4 * cout,) + wp.shape[2:], wp.dtype)
+    for co in range(cout):
+        for ph in range(4):
+            out[(co >> 3) * 32 + ph * 8 + (co & 7)] = wp[ph, co]
+    return out
+
+
+def replicate(x):
+    return np.pad(x, ((0, 0), (0, 0), (1, 1), (1, 1)), mode="edge")
+
+
+def conv_valid64(xp, wt, b=None):
+    import torch.nn.functional as F
+    return F.conv2d(_t(xp), _t(wt), None if b is None else _t(b)).numpy()
+
+
+def phase64(x, wp, b):
+    """The sub-pixel form in float64: output (Y, X) is the 3 x 3 conv with phase 2 (Y & 1) + (X & 1)
+    over the edge-replicated x at (Y >> 1, X >> 1), plus b.  Equal to conv(upsample(x)) off the ring."""
+    n, _, h, w = x.shape
+    xp = replicate(x)
+    out = np.empty((n, wp.shape[1], 2 * h, 2 * w))
+    for ph in range(4):
+        out[:, :, ph >> 1::2, ph & 1::2] = conv_valid64(xp, wp[ph], b)
+    return out
+
+
+def up_emulate(x, dt=np.float32, align=False):
+    """Bilinear x2 as Up8::value (edge_fix.hpp): horizontal then vertical, weights 1/4 and 3/4, edge
+    clamp, every operation rounded to dt (float64: the exact upsample of fp32 data)."""
+    import torch.nn.functional as F
+    if align:
+        return F.interpolate(_t(x), scale_factor=2, mode="bilinear", align_corners=True).numpy().astype(dt)
+    x = np.asarray(x, dt)
+    h, w = x.shape[2:]
+
+    def taps(nn):
+        o = np.arange(2 * nn)
+        odd = (o & 1) == 1
+        a = np.where(odd, o >> 1, np.maximum((o >> 1) - 1, 0))
+        b_ = np.where(odd, np.minimum((o >> 1) + 1, nn - 1), o >> 1)
+        return a, b_, np.where(odd, 0.75, 0.25).astype(dt)
+    ra, rb, wa = taps(h)
+    ca, cb, wc = taps(w)
+    wb, wd = (1 - wa).astype(dt), (1 - wc).astype(dt)
+    top = wc * x[:, :, ra][..., ca] + wd * x[:, :, ra][..., cb]
+    bot = wc * x[:, :, rb][..., ca] + wd * x[:, :, rb][..., cb]
+    out = wa[:, None] * top + wb[:, None] * bot
+    assert out.dtype == dt
+    return out
+
+
+def _fma(acc, wv, uv):
+    """acc + w u with one rounding to fp32; acc [n, cout, ...], wv [cout], uv [n, ...]."""
+    wv = wv.astype(np.float64).reshape((1, -1) + (1,) * (acc.ndim - 2))
+    return (acc.astype(np.float64) + wv * uv.astype(np.float64)[:, None]).astype(np.float32)
+
+
+def phase_emulate(x, wp):
+    """The phase convs' pre-bias value in fp32, one fma per product in channel then tap order: what the
+    direct tiles leave in the edge buffer.  [n, cout, 2h, 2w] float32."""
+    n, cin, h, w = x.shape
+    xp = replicate(x).astype(np.float32)
+    out = np.empty((n, wp.shape[1], 2 * h, 2 * w), np.float32)
+    for ph in range(4):
+        acc = np.zeros((n, wp.shape[1], h, w), np.float32)
+        for ci in range(cin):
+            for a in range(3):
+                for b_ in range(3):
+                    acc = _fma(acc, wp[ph][:, ci, a, b_], xp[:, ci, a:a + h, b_:b_ + w])
+        out[:, :, ph >> 1::2, ph & 1::2] = acc
+    return out
+
+
+def edge_emulate(x, wt, b, mode, ks=1, nsl=1, pre=None, mutate=None):
+    """The ring of the sub-pixel conv restated in numpy fp32 (edge_fix.hpp, edge_fix_body).
+
+    mode "full": from scratch -- per ring pixel the in-image taps over two staged lines of U (the
+    ring line and the next one inward, zero past the line's ends), slots in the order line 0 taps
+    0-2, line 1 taps 0-2.  mode "corr": (pre - acc) + b with acc the outside taps over the ring line
+    of U clamped at its ends, and at a corner the two further taps of the outside column, summed
+    apart (accx) and added at the end of each run.  U is recomputed in fp32 (up_emulate).  The
+    channels go in chunks of 32: run sl of nsl covers cin / nsl channels, in it group g of ks takes
+    chunks g, g + ks, ...; the groups' sums are added in group order, the runs' in run order.
+    Lines: top and bottom row with the corners, left and right column without.  Returns float32
+    [n, cout, 2h, 2w], NaN off the ring.  mutate: "no_extras", "align_corners", "group_twice",
+    "seam" -- the errors the bound must reject (tests/test_exact_ref.py)."""
+    f = np.float32
+    n, cin, h, w = x.shape
+    cout, hh, ww = wt.shape[0], 2 * h, 2 * w
+    u = up_emulate(x, f, align=mutate == "align_corners")
+    w32, b32 = wt.astype(f), b.astype(f)
+    out = np.full((n, cout, hh, ww), np.nan, f)
+    csl = cin // nsl
+    assert csl * nsl == cin and (nsl == 1 and ks == 1 or csl % (ks * FIX_CI) == 0)
+    for line, fixed, pos in ((0, 0, np.arange(ww)), (1, hh - 1, np.arange(ww)),
+                             (2, 0, np.arange(1, hh - 1)), (3, ww - 1, np.arange(1, hh - 1))):
+        if not pos.size:
+            continue
+        row = line < 2
+        full = ww if row else hh
+        out_k = 0 if line in (0, 2) else 2
+        inner = fixed + (1 if line in (0, 2) else -1)
+
+        def staged(o, q):
+            qc = np.clip(q, 0, full - 1)
+            v = u[:, :, o, qc] if row else u[:, :, qc, o]
+            return np.where((q >= 0) & (q < full), v, f(0)) if mode == "full" else v
+        extras = []
+        if mode == "full":
+            kk = 2 if inner > fixed else 0
+            slots = [((1, k) if row else (k, 1), staged(fixed, pos - 1 + k)) for k in range(3)]
+            slots += [((kk, k) if row else (k, kk), staged(inner, pos - 1 + k)) for k in range(3)]
+        else:
+            slots = [((out_k, k) if row else (k, out_k), staged(fixed, pos - 1 + k)) for k in range(3)]
+            if row and mutate != "no_extras":
+                for xc, kx in ((0, 0), (ww - 1, 2)):
+                    for m in range(2):
+                        ky = m + (1 if out_k == 0 else 0)
+                        ue = np.zeros((n, cin, pos.size), f)
+                        ue[:, :, xc] = u[:, :, fixed + ky - 1, xc]
+                        extras.append(((ky, kx), ue))
+        corner = (pos == 0) | (pos == ww - 1) if row else np.zeros(pos.size, bool)
+        tot = None
+        for sl in range(nsl):
+            sums = []
+            for g in range(ks):
+                acc = np.zeros((n, cout, pos.size), f)
+                accx = np.zeros((n, cout, pos.size), f)
+                for c0 in range(sl * csl + g * FIX_CI, (sl + 1) * csl, ks * FIX_CI):
+                    for ci in range(c0, min(c0 + FIX_CI, cin)):
+                        for (ky, kx), uv in slots:
+                            acc = _fma(acc, w32[:, ci, ky, kx], uv[:, ci])
+                    for ci in range(c0, min(c0 + FIX_CI, cin)):
+                        for (ky, kx), uv in extras:
+                            accx = _fma(accx, w32[:, ci, ky, kx], uv[:, ci])
+                sums.append(np.where(corner, acc + accx, acc) if extras else acc)
+            run = sums[0]
+            for g in range(1, ks):
+                run = run + sums[g]
+            if mutate == "group_twice" and sl == 0:
+                run = run + sums[-1]
+            tot = run if sl == 0 else tot + run
+        bb = b32[None, :, None]
+        if mode == "full":
+            v = tot + bb
+        else:
+            p = pre[:, :, fixed, pos] if row else pre[:, :, pos, fixed]
+            v = (p.astype(f) - tot) + bb
+        assert v.dtype == f
+        if row:
+            out[:, :, fixed, pos] = v
+        else:
+            out[:, :, pos, fixed] = v
+    if mutate == "seam":
+        out[:, :, 0, FIX_PX] = out[:, :, 0, FIX_PX + 1]
+    return out
+
+
+def store_emulate(v, prec):
+    """The store of an fp32 value at prec, as float64."""
+    v = np.asarray(v, np.float32)
+    if prec == "F16":
+        return v.astype(np.float16).astype(np.float64)
+    if prec == "F16X3":
+        hi, lo = split16_f64(np.nan_to_num(v.astype(np.float64)))
+        return np.where(np.isnan(v), np.nan, hi + lo)
+    return v.astype(np.float64)
+
+
+def store_bound(prec, ref):
+    """The store terms of bound(): fp16 half an ulp and the subnormal floor, split-fp16 the rounded lo."""
+    if prec == "F16":
+        return 2.0 ** -11 * np.abs(ref) + 2.0 ** -25
+    if prec == "F16X3":
+        return 2.0 ** -22 * np.abs(ref)
+    return 0.0
+
+
+def pre_bound(prec, k, s, wino_ratio=None):
+    """Bound of the conv's pre-bias fp32 value (the edge buffer): bound()'s forms without the bias
+    add, the slope multiply and the store -- K u S; split-fp16 (3 K + 1) u S + 2^-22 S; Winograd
+    4 x ratio u S."""
+    if wino_ratio is not None:
+        return 4 * wino_ratio * U * s
+    if prec == "F16X3":
+        return (3 * k + 1) * U * s + 2.0 ** -22 * s
+    return k * U * s
+
+
+def sub_terms(x, wt, b):
+    """Per output pixel of the 2h x 2w result, float64: s_phase (sum |x_rep||w_phase| + |b| of the
+    pixel's phase), s_in (sum over the in-image taps of |w| x' + |b|, x' = upsample(|x|)), s_out
+    (the same over the taps outside the image, x' clamped), n_in (in-image taps: 9, 6, 4)."""
+    cout = wt.shape[0]
+    s_phase = phase64(np.abs(x), np.abs(phase_weights64(wt)), np.abs(b))
+    xa = up_emulate(np.abs(x), np.float64)
+    aw = np.abs(wt)
+    s_in = conv64(xa, aw, np.abs(b))
+    xo = replicate(xa)
+    xo[:, :, 1:-1, 1:-1] = 0
+    s_out = conv_valid64(xo, aw)
+    n_in = conv64(np.ones((1, 1) + xa.shape[2:]), np.ones((1, 1, 3, 3)))[0, 0]
+    assert s_in.shape[1] == cout
+    return s_phase, s_in, s_out, np.rint(n_in)
+
+
+def ring_bound(prec, mode, cin, terms, ref, b, wino_ratio=None):
+    """Per-element bound of |got - ref64| on the ring (valid on ring pixels only), u = 2^-24.
+
+    Every staged U value is recomputed in fp32 with at most 4 roundings of numbers no larger than
+    x' (§8d): within 4 u x' of exact, 4 u sum |w| x' through the taps.  A chain of T fmas rounds T
+    partial sums of at most the sum of absolute values; adding G group / run sums rounds G more.
+      from scratch ("full", "inlaunch"): T = n_in cin in-image taps, G = (ks - 1) + (nsl - 1), the
+        bias add: (n_in cin + 4 + G + 1) u S_in, S_in = sum_in |w| x' + |b|.
+      correction ("fix", "fold"): the conv's pre-bias value within pre_bound over S_phase; the outside
+        taps T = (9 - n_in) cin, the U term, G and at a corner one more add (accx; none in the fold's
+        single chain): ((9 - n_in) cin + 4 + G + c) u S_out; pre - acc and + bias round results of at
+        most S_in: 2 u S_in.  In sums of absolute values: pre - acc cancels.
+    plus the store terms of bound()."""
+    s_phase, s_in, s_out, n_in = terms
+    name = "fix" if mode == "full" else mode
+    ks, nsl = edge_split(cin, prec, name)
+    g = (ks - 1) + (nsl - 1)
+    if mode in ("full", "inlaunch"):
+        return (n_in * cin + 4 + g + 1) * U * s_in + store_bound(prec, ref)
+    c = (n_in == 4) * (0 if mode == "fold" else 1)
+    s_pre = s_phase if wino_ratio is not None else s_phase - np.abs(b)[None, :, None, None]
+    return (pre_bound(prec, 9 * cin, s_pre, wino_ratio) + ((9 - n_in) * cin + 4 + g + c) * U * s_out
+            + 2 * U * s_in + store_bound(prec, ref))
+
+
+def sub_ref64(x, wt, b):
+    return conv64(up_emulate(x, np.float64), wt, b)
+
+
+@functools.lru_cache(maxsize=None)
+def sub_wino_ratio(n, cin, cout, h, w, prec, kind):
+    """Worst err / (u S) of wino_emulate on the phase weights over the edge-replicated source of
+    sub_float_case(...) against float64 (pinned by tests/test_exact_ref.py)."""
+    x, wt, b = sub_float_case(n, cin, cout, h, w, prec)
+    wp = phase_weights64(wt).reshape(4 * cout, cin, 3, 3)
+    b4 = np.tile(b, 4)
+    got = wino_emulate(x, wp, b4, kind, prec == "F16", rep=True)
+    xp = replicate(x)
+    ref = conv_valid64(xp, wp, b4)
+    s = conv_valid64(np.abs(xp), np.abs(wp), np.abs(b4))
+    return float((np.abs(got - ref) / (U * s)).max())

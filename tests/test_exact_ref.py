@@ -197,6 +197,45 @@ def test_block0_data_is_representable(cin, h, w):
         assert not np.array_equal(E.leaky(bad).units, good)
 
 
+BLOCK0_POOLED = [(cin, h, w) for cin in (6, 32) for h, w in ((10, 40), (18, 34), (2, 2), (2, 66))]
+
+
+def test_block0_pooled_store_is_one_rounding():
+    """The fused block with its pool: conv a is a multiple of 4, so mid is an integer, out sits on a
+    grid of 1/4 and is an fp16 number, and the pooled mean on a grid of 1/16.  The fp32 sum of four
+    such values (below 2^24 units) and the multiply by 1/4 are exact: the pooled store is one
+    round-to-nearest-even of a known rational, np.float16(exact).  The cases hold pooled values that
+    are no fp16 numbers and, between them, exact ties (odd sixteenths at the 1/8 spacing above
+    128), so they pin the rounding mode; a dropped tap of conv b and a chunk added twice reach the
+    rounded pooled value."""
+    ties = 0
+    for cin, h, w in BLOCK0_POOLED:
+        x, wa, ba, wb, bb = E.block0_case(2, cin, h, w)
+        mid, out = E.block0_ref(x, wa, ba, wb, bb)
+        assert out.scale == 4 and E.f16_exact(mid.f64()) and E.f16_exact(out.f64())
+        p = E.pool(out)
+        assert p.scale == 16 and p.units.shape[2:] == (h // 2, w // 2)
+        a = np.abs(out.units)
+        assert int((a[:, :, 0::2, 0::2] + a[:, :, 0::2, 1::2] + a[:, :, 1::2, 0::2] + a[:, :, 1::2, 1::2]).max()) < E.P24
+        assert np.abs(p.f64()).max() <= 752
+        ref = F.avg_pool2d(T(out.f64()), 2).numpy()
+        assert np.array_equal(p.f64(), ref)
+        want = E.f16_round(p.f64())
+        inexact = want != p.f64()
+        # a tie: the exact value halfway between two neighbouring fp16 numbers
+        up_, dn = np.nextafter(want.astype(np.float16), np.float16(np.inf)).astype(np.float64), \
+            np.nextafter(want.astype(np.float16), np.float16(-np.inf)).astype(np.float64)
+        tie = inexact & ((np.abs(p.f64() - want) == np.abs(up_ - p.f64())) | (np.abs(p.f64() - want) == np.abs(p.f64() - dn)))
+        print(f"cin {cin} {h}x{w}: {inexact.mean():.1%} of the pooled values are no fp16 numbers, {int(tie.sum())} ties")
+        assert inexact.any() or (h, w) == (2, 2)   # 64 pooled values: the union below covers it
+        ties += int(tie.sum())
+        rb = E.Ref(E.conv_int(mid.units, wb) + bb[None, :, None, None], 1)
+        yy, xq = (int(v) for v in np.argwhere(mid.units[0, 1, :h - 1, 1:] != 0)[0])
+        for bad in (E.drop_one_tap(rb, mid.units, wb, at=(0, 1, yy + 1, xq)), E.chunk_twice(rb, mid.units, wb)):
+            assert not np.array_equal(E.f16_round(E.pool(E.leaky(bad)).f64()), want)
+    assert ties > 0
+
+
 @pytest.mark.parametrize("case", SUB)
 def test_subpixel_mutations_break_equality(case):
     """The mutations on the sub-pixel references (integer and split-fp16 with offsets on x), applied
@@ -216,6 +255,51 @@ def test_subpixel_mutations_break_equality(case):
     # float64 torch on x + ox 2^-12 (w has no offset: nothing is dropped)
     upf = F.interpolate(T(x) + T(ox) / E.LO, scale_factor=2, mode="bilinear", align_corners=False)
     assert np.array_equal(s.f64(), F.conv2d(upf, T(wt), T(b), padding=1).numpy())
+
+
+SUB_RING = [(2, cin, cout, sh, sw, (1,)) for cin, cout in ((16, 32), (64, 40)) for sh, sw in ((3, 33), (18, 3))]
+SUB_DEEP = [(2, cin, 32, 3, 33, (1,)) for cin in (128, 256)]
+
+
+@pytest.mark.parametrize("case", SUB_RING + SUB_DEEP)
+def test_subpixel_ring_cases(case):
+    """The sub-pixel cases with ring lines of two tiles and a ragged third (3 x 33: 66 px rows; 18 x 3:
+    34 px columns) and with fix-up K groups 2 and 4 (cin 128, 256).  Every direct-form partial sum
+    stays below 2^24 sixteenths, so the fp32 accumulator holds the exact value and the fp16 store is
+    its single rounding, exact_ref.f16_round; fp32 records hold it as it is, split-fp16 as hi + lo.
+    The mutations -- a dropped tap, a chunk added twice, exchanged rows, a ring pixel moved across the
+    32-pixel seam, a K group left out of the ring sums -- break the equality, after the fp16
+    rounding too."""
+    deep = case in SUB_DEEP
+    x, wt, b, ox, _ = E.int_case(*case) if deep else E.split_case(*case)
+    n, cin, h, w = x.shape
+    up = E.up2_int(x)
+    r = E.pre_sub(x, wt, b)
+    upf = F.interpolate(T(x), scale_factor=2, mode="bilinear", align_corners=False)
+    assert np.array_equal(r.f64(), F.conv2d(upf, T(wt), T(b), padding=1).numpy())
+    assert E.direct_sum_units(up, wt, 16 * b) < E.P24 and E.direct_sum_units(up, wt, 16 * b, 48) < E.P24
+    assert E.f32_exact(r.f64()) and E.own_split(r.f64())
+    inexact = int((E.f16_round(r.f64()) != r.f64()).sum())
+    print(case, f"max |v| {np.abs(r.f64()).max()}, not fp16 numbers: {inexact} of {r.units.size}")
+    assert deep or not inexact         # only cin 128 and 256 may leave the range where sixteenths fit 11 bits
+    if not deep:
+        s = E.pre_sub_split(x, wt, b, ox)
+        assert int(np.abs(s.units).max()) < E.P24 and E.f32_exact(s.f64()) and E.own_split(s.f64()) and (ox != 0).any()
+        upo = F.interpolate(T(x) + T(ox) / E.LO, scale_factor=2, mode="bilinear", align_corners=False)
+        assert np.array_equal(s.f64(), F.conv2d(upo, T(wt), T(b), padding=1).numpy())
+        assert not np.array_equal(E.pre_sub_split(x, wt, b, 0 * ox).units, s.units)
+    left = w < 17
+    refs = [(r, 1), (E.pre_sub(x, wt, b, 48), 48)] + ([] if deep else [(E.pre_sub_split(x, wt, b, ox), 1)])
+    for q, mul in refs:
+        rs = E.Ref(q.units, q.scale // 16)
+        bads = [E.drop_one_tap(rs, up, wt, mul, at=(0, 1, 1, 2), tap=(0, 2)), E.chunk_twice(rs, up, wt, mul),
+                E.swap_rows(q, 0), E.seam_shift(q, left)]
+        bads += [E.ring_groups_miscounted(q, up, wt, mul, ks) for ks in (2, 4) if cin % (32 * ks) == 0]
+        assert len(bads) == 4 + (cin >= 64) + (cin >= 128)
+        for bad in bads:
+            assert not np.array_equal(bad.units, q.units)
+            if mul == 1:
+                assert not np.array_equal(E.f16_round(bad.units / q.scale), E.f16_round(q.f64()))
 
 
 # ---- part B ------------------------------------------------------------------------------------------
@@ -260,6 +344,100 @@ def test_float_data_is_held_exactly(case, prec):
         bm = lib.rrin_conv_h8_cfg_bm(c)
         joined = (E.unpack_direct(E.halves(whi), cout, cin, bm, 8) + E.unpack_direct(E.halves(wlo), cout, cin, bm, 8) / 2048) * inv
         assert np.array_equal(joined, wt.reshape(cout, cin, 9)) and bool(wlo.any())
+
+
+# ---- the sub-pixel conv on floats: data, emulation, ring bounds --------------------------------------
+SUBF = [(2, cin, cout, sh, sw) for cin, cout in ((16, 32), (64, 40)) for sh, sw in ((5, 9), (1, 2), (3, 33), (18, 3))]
+# worst err / (2^-24 S) of wino_emulate on the phase weights (exact_ref.sub_wino_ratio): (F(2x2) fp32, kind 14, fp16 kind 6)
+SUB_RATIOS = {
+    (2, 16, 32, 5, 9): (1.94, 9.63, 4824.3), (2, 16, 32, 1, 2): (1.20, 1.49, 2856.5),
+    (2, 16, 32, 3, 33): (2.12, 8.34, 4493.1), (2, 16, 32, 18, 3): (1.64, 3.15, 4420.4),
+    (2, 64, 40, 5, 9): (1.68, 7.16, 2616.5), (2, 64, 40, 1, 2): (1.25, 1.44, 1148.2),
+    (2, 64, 40, 3, 33): (2.03, 8.55, 2205.7), (2, 64, 40, 18, 3): (1.95, 2.94, 2153.3)}
+
+
+@pytest.mark.parametrize("case", SUBF)
+@pytest.mark.parametrize("prec", ["R32", "F16", "F16X3"])
+def test_subpixel_float_data_is_held_exactly(case, prec):
+    """w = m 2^-8: the phase weights are multiples of 2^-12 of at most 49 x 31 < 2^11 steps (the
+    centre tap of a phase gathers coefficients (1 + 3 + 3)^2 = 49 sixteenths), rrin_subpixel_weights
+    gives them exactly and the direct packs of every precision decode to them (split-fp16: hi alone,
+    lo zero); the phase form equals conv(upsample(x)) off the ring."""
+    lib = _lib.lib()
+    x, wt, b = E.sub_float_case(*case, prec)
+    cout, cin = wt.shape[:2]
+    wp = E.phase_weights64(wt)
+    steps = wp * 4096
+    assert np.array_equal(steps, np.rint(steps)) and np.abs(steps).max() <= 49 * 31 < 2 ** 11
+    assert E.f16_exact(wp * 2.0 ** 4)
+    rows = E.phase_rows(wp)
+    ws, bs = np.empty((4 * cout, cin, 3, 3), np.float32), np.empty(4 * cout, np.float32)
+    w32, b32 = wt.astype(np.float32), b.astype(np.float32)
+    _lib.check(lib.rrin_subpixel_weights(w32.ctypes.data, b32.ctypes.data, cout, cin, ws.ctypes.data, bs.ctypes.data))
+    assert np.array_equal(ws.astype(np.float64), rows)
+    tw, tb = torch.from_numpy(ws), torch.from_numpy(bs)
+    want = rows.reshape(4 * cout, cin, 9)
+    if prec == "R32":
+        c = _cfg(R32, 0)
+        assert np.array_equal(E.unpack_direct(pack_h8(tw, tb, c, R32, "cpu")[0].numpy(), 4 * cout, cin, lib.rrin_conv_h8_cfg_bm(c), 4), want)
+    else:
+        p = F16 if prec == "F16" else X3
+        c = _cfg(p, 0)
+        whi, wlo, _, inv = pack_h8(tw, tb, c, p, "cpu")
+        assert np.array_equal(E.unpack_direct(E.halves(whi), 4 * cout, cin, lib.rrin_conv_h8_cfg_bm(c), 8) * inv, want)
+        assert prec == "F16" or not bool(wlo.any())
+    assert np.array_equal(E.up_emulate(x, np.float64), F.interpolate(T(x), scale_factor=2, mode="bilinear", align_corners=False).numpy())
+    ref = E.sub_ref64(x, wt, b)
+    off = ~E.ring_mask(*ref.shape[2:])
+    s = E.sub_terms(x, wt, b)[0]
+    assert (np.abs(E.phase64(x, wp, b) - ref)[:, :, off] <= 2.0 ** -50 * s[:, :, off]).all()
+
+
+def _ring_got(case, prec, mode, mutate=None, cin_case=None):
+    x, wt, b = E.sub_float_case(*case, prec)
+    cin = case[1]
+    ks, nsl = E.edge_split(cin, prec, "fix" if mode == "full" else mode)
+    pre = E.phase_emulate(x, E.phase_weights64(wt)) if mode in ("fix", "fold") else None
+    v = E.edge_emulate(x, wt, b, "full" if mode in ("full", "inlaunch") else "corr", ks, nsl, pre, mutate)
+    ref = E.sub_ref64(x, wt, b)
+    bnd = E.ring_bound(prec, mode, cin, E.sub_terms(x, wt, b), ref, b)
+    m = E.ring_mask(*ref.shape[2:])
+    return np.abs(E.store_emulate(v, prec) - ref)[:, :, m], bnd[:, :, m], E.sub_terms(x, wt, b), m
+
+
+@pytest.mark.parametrize("case", SUBF)
+@pytest.mark.parametrize("prec", ["R32", "F16", "F16X3"])
+@pytest.mark.parametrize("mode", ["fix", "full", "inlaunch", "fold"])
+def test_ring_emulation_is_inside_the_derived_bound(case, prec, mode):
+    if mode == "fold" and prec != "R32":
+        return
+    err, bnd, terms, m = _ring_got(case, prec, mode)
+    assert np.isfinite(err).all() and (err <= bnd).all(), float((err / bnd).max())
+    s = (terms[1] if mode in ("full", "inlaunch") else terms[0] + terms[2])[:, :, m]
+    print(case, prec, mode, f"worst err / (u S) {float((err / (E.U * s)).max()):.2f}, err / bound {float((err / bnd).max()):.3f}")
+
+
+@pytest.mark.parametrize("prec", ["R32", "F16", "F16X3"])
+def test_ring_bound_rejects_wrong_rings(prec):
+    """A corner's extra taps dropped, an align_corners=True upsample on the ring line, one K group's
+    sum added twice at cin 128 and a ring pixel taken from x + 1 across the tile seam."""
+    wide, corner = (2, 16, 32, 3, 33), (2, 16, 32, 5, 9)
+    for case, mode, mutate in ((corner, "fix", "no_extras"), (corner, "fix", "align_corners"), (corner, "full", "align_corners"),
+                               (wide, "fix", "seam"), (wide, "full", "seam"), ((1, 128, 32, 3, 33), "fix", "group_twice"),
+                               ((1, 128, 32, 3, 33), "full", "group_twice")):
+        err, bnd, _, _ = _ring_got(case, prec, mode)
+        assert (err <= bnd).all()
+        err, bnd, _, _ = _ring_got(case, prec, mode, mutate)
+        assert (err > bnd).any(), (case, mode, mutate)
+    assert E.edge_split(128, prec, "fix")[0] == 2
+
+
+@pytest.mark.parametrize("case", SUBF)
+def test_subpixel_wino_ratios_are_the_recorded_ones(case):
+    got = (E.sub_wino_ratio(*case, "R32", 1), E.sub_wino_ratio(*case, "R32", 14), E.sub_wino_ratio(*case, "F16", 6))
+    print(case, [round(g, 2) for g in got])
+    for g, want in zip(got, SUB_RATIOS[case]):
+        assert abs(g - want) <= 0.006 * max(want, 1.0), (got, SUB_RATIOS[case])
 
 
 def test_split_bound_rejects_a_dropped_hi_lo_class():

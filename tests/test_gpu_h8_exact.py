@@ -14,7 +14,9 @@ below 2^24 grid steps, worst case over the data's magnitudes) holds for each of 
 sub-pixel conv at cin 64 (U on a grid of 1/8) and cin 256 included, and is asserted before each run.
 
 Part B (test_conv_float_bound): random floats the storage holds exactly, against float64 within a
-derived per-element forward bound (exact_ref.bound), the observed worst ratio printed."""
+derived per-element forward bound (exact_ref.bound), the observed worst ratio printed;
+test_subpixel_float_bound does the same for the sub-pixel up conv, its ring pixels under
+exact_ref.ring_bound (the operation count of the fix-up, per ring mode)."""
 import functools
 
 import numpy as np
@@ -241,8 +243,11 @@ def test_source_offset_and_perm_exact(gpu, prec):
     assert seen == {R32: {0, 1, 3, 4, 6, 7, 14}, X3: {0}, F16: {0, 6}}[prec]
 
 
+# 3 x 33: output rows of 66 px, two fix-up tiles of 32 and a ragged third; 18 x 3: columns of 34 px
+SUB_SHAPES = ((5, 9), (1, 2), (3, 33), (18, 3))
 SUB = [(mode, cin, cout, sh, sw) for mode in ("fix", "inlaunch", "fold") for cin, cout in ((16, 32), (64, 40))
-       for sh, sw in ((5, 9), (1, 2))]
+       for sh, sw in SUB_SHAPES]
+RAN_SUB = {}              # (prec, mode, cin, sh, sw) -> configs that ran
 
 
 @pytest.mark.parametrize("prec", PRECS)
@@ -272,21 +277,70 @@ def test_subpixel_exact(gpu, prec, mode, cin, cout, sh, sw):
             assert E.wino_fits(14 if kind(cfg) == 14 else 1, mul * wsub, 16, cin, 1)[0], what
         wt_t, b_t = tensors(wt, b, 0 * ow, R32, mul)
         ref, _ = reference(n, cin, cout, sh, sw, (1,), split, mul, "sub")
+        if prec == F16:   # one rounding of the exact fp32 value (the identity while sixteenths fit 11 bits)
+            ref = E.f16_round(ref)
         fresh(dst)
         subpixel_upconv(src, wt_t, b_t, cfg, prec, dst=dst, fold=mode == "fold", inlaunch=mode == "inlaunch",
                         edge_split=mode == "fix" and prec == R32)
         assert_equal(dst, 0, cout, ref, prec, what)
         RAN.setdefault((prec, "sub_" + mode), set()).add(cfg)
+        RAN_SUB.setdefault((prec, mode, cin, sh, sw), set()).add(cfg)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("cin", [128, 256])
+def test_subpixel_exact_deep_k(gpu, prec, cin):
+    """cin 128 and 256, cout 32, from 3 x 33: the fix-up's K groups (2; 4 at fp16 and cin 256) and,
+    fp32 records, its runs of one chunk per group with the cross-workgroup split.  First the standalone
+    fix-up from scratch (launched before a direct-form conv), then the correction form behind every
+    config whose sums stay below 2^24 (exact_ref.wino_fits, direct_sum_units): the direct-form ones
+    all do.  +-1 data and the int64 reference in sixteenths; fp16 stores np.float16(exact), one
+    rounding of an exact fp32 value.  Split-fp16 runs on the integers (a zero lo plane): with the
+    +-2^-12 offsets a partial sum of 6 cin joined values no longer fits 24 bits; the lo reads of the
+    ring are held at cin 16 and 64."""
+    n, cout, sh, sw = N, 32, 3, 33
+    x, wt, b, _, ow = E.int_case(n, cin, cout, sh, sw, (1,))
+    src = source(x.astype(np.float64), prec, gpu)
+    replicate_ring(src)
+    dst = H8Tensor(n, cout, 2 * sh, 2 * sw, gpu, prec)
+    wsub, up = E.subpixel_weights_int(wt), E.up2_int(x)
+    ks = E.edge_split(cin, NAME[prec], "fix")[0]
+    assert ks == (4 if prec == F16 and cin == 256 else 2)
+    direct = [c for c in all_cfgs(prec, cin) if kind(c) == 0]
+    assert direct
+    ran = []
+    for mode, todo in (("full", direct[:1]), ("fix", all_cfgs(prec, cin))):
+        for cfg in todo:
+            mul = wmul(cfg)
+            what = f"{NAME[prec]} sub {mode} cin {cin} {sh}x{sw} cfg {cfg} (kind {kind(cfg)})"
+            if kind(cfg) > 0:
+                if not E.wino_fits(14 if kind(cfg) == 14 else 1, mul * wsub, 16, cin, 1)[0]:
+                    continue
+            else:
+                assert E.direct_sum_units(up, wt, 16 * b, mul) < E.P24, what
+            wt_t, b_t = tensors(wt, b, 0 * ow, R32, mul)
+            ref, _ = reference(n, cin, cout, sh, sw, (1,), False, mul, "sub")
+            if prec == F16:
+                ref = E.f16_round(ref)
+            fresh(dst)
+            subpixel_upconv(src, wt_t, b_t, cfg, prec, dst=dst, full=mode == "full", edge_split=prec == R32)
+            assert_equal(dst, 0, cout, ref, prec, what)
+            if mode == "fix":
+                ran.append(cfg)
+    print(f"{NAME[prec]} cin {cin}: fix-up K groups {ks}, configs {ran} (kinds {sorted({kind(c) for c in ran})})")
+    assert set(direct) <= set(ran)
 
 
 @pytest.mark.parametrize("cin", [6, 32])
-@pytest.mark.parametrize("h,w", [(9, 40), (17, 33)])
+@pytest.mark.parametrize("h,w", [(9, 40), (17, 33), (10, 40), (18, 34), (2, 2), (2, 66)])
 def test_block0_exact(gpu, cin, h, w):
     """rrin_conv_block0_h8_fwd at fp16 on exact_ref.block0_case: == leaky(conv b(leaky(conv a))),
-    the intermediate an fp16 number.  No pool: with no zero in the data the pooled value (a grid of
-    1/64 after two slopes) does not fit fp16's 11 bits; the pooled store is held to equality by
-    test_conv_exact's pool cases on the unfused kernel, whose bits the fused launch must give
-    (tests/test_gpu_block0.py)."""
+    the intermediate an fp16 number.  The even sizes run with the pool: conv a is a multiple of 4,
+    so out sits on a grid of 1/4 and the pooled mean on one of 1/16; the fp32 sum of four and the
+    multiply by 1/4 are exact, so the pooled store is one round-to-nearest-even of a known rational
+    and must be np.float16(exact) bit for bit -- ties at the 1/8 spacing above 128 included
+    (tests/test_exact_ref.py)."""
+    pooled = h % 2 == 0
     x, wa, ba, wb, bb = E.block0_case(N, cin, h, w)
     mid, out = E.block0_ref(x, wa, ba, wb, bb)
     assert E.f16_exact(mid.f64()) and E.f16_exact(out.f64())
@@ -298,11 +352,17 @@ def test_block0_exact(gpu, cin, h, w):
     t = lambda a: torch.from_numpy(a.astype(np.float32))  # noqa: E731
     dst = H8Tensor(N, 32, h, w, gpu, F16)
     fresh(dst)
+    pl = None
+    if pooled:
+        pl = H8Tensor(N, 32, h // 2, w // 2, gpu, F16)
+        fresh(pl)
     status = torch.zeros(1, dtype=torch.int32, device=gpu)
-    block0(src, cin, t(wa), t(ba), direct_cfg(cin, 32), t(wb), t(bb), direct_cfg(32, 32), False, dst=dst,
-           status=status, tail_finite=1 if cin % 8 else 0, slope=E.SLOPE)
+    block0(src, cin, t(wa), t(ba), direct_cfg(cin, 32), t(wb), t(bb), direct_cfg(32, 32), pooled, dst=dst,
+           status=status, tail_finite=1 if cin % 8 else 0, slope=E.SLOPE, pl=pl)
     assert int(status.item()) == 0
     assert_equal(dst, 0, 32, ref, F16, f"block0 cin {cin} {h}x{w}")
+    if pooled:
+        assert_equal(pl, 0, 32, E.f16_round(E.pool(out).f64()), F16, f"block0 cin {cin} {h}x{w} pool")
 
 
 # ---- B. representable floats: derived forward bounds ------------------------------------------------
@@ -357,6 +417,57 @@ def test_conv_float_bound(gpu, prec, epi, cin, cout, h, w):
     print("worst err / (2^-24 S) so far:", {k_: round(v, 2) for k_, v in sorted(WORST.items())})
 
 
+SUB_WORST = {}    # (precision, kind, mode, "interior" | "ring") -> largest observed err / (2^-24 S)
+FLOAT_RAN = {}    # (prec, mode, cin, sh, sw) -> configs that ran
+
+
+@functools.lru_cache(maxsize=None)
+def sub_float_reference(n, cin, cout, sh, sw, name):
+    """(x, wt, b, float64 reference, exact_ref.sub_terms): computed once per case and precision."""
+    x, wt, b = E.sub_float_case(n, cin, cout, sh, sw, name)
+    return x, wt, b, E.sub_ref64(x, wt, b), E.sub_terms(x, wt, b)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("mode,cin,cout,sh,sw", SUB)
+def test_subpixel_float_bound(gpu, prec, mode, cin, cout, sh, sw):
+    """The sub-pixel up conv on random floats the storage and the packs hold exactly
+    (exact_ref.sub_float_case: w = m 2^-8, so the phase weights are exact), against float64
+    conv(upsample(x)) + b over the whole 2h x 2w output, every config, the three ring modes.
+    Interior pixels: exact_ref.bound with K = 9 cin and S of the pixel's phase over the
+    edge-replicated x (Winograd: 4 x exact_ref.sub_wino_ratio).  Ring pixels: exact_ref.ring_bound,
+    derived from the operation count of the fix-up per mode.  The worst err / (2^-24 S) is printed,
+    interior and ring apart."""
+    name = NAME[prec]
+    x, wt, b, ref, terms = sub_float_reference(N, cin, cout, sh, sw, name)
+    ring = E.ring_mask(2 * sh, 2 * sw)
+    s_ring = terms[1] if mode == "inlaunch" else terms[0] + terms[2]
+    src = source(x, prec, gpu)
+    replicate_ring(src)
+    dst = H8Tensor(N, cout, 2 * sh, 2 * sw, gpu, prec)
+    wt_t, b_t = torch.from_numpy(wt).float(), torch.from_numpy(b).float()
+    for cfg in [c for c in all_cfgs(prec, cin) if not (mode == "fold" and kind(c) != 3)]:
+        k = kind(cfg)
+        ratio = E.sub_wino_ratio(N, cin, cout, sh, sw, name, 14 if k == 14 else 1) if k else None
+        inner = E.bound(name, 9 * cin, terms[0], ref, ratio)
+        edge = E.ring_bound(name, mode, cin, terms, ref, b, ratio)
+        what = f"{name} sub {mode} cin {cin} {sh}x{sw} cfg {cfg} (kind {k})"
+        fresh(dst)
+        subpixel_upconv(src, wt_t, b_t, cfg, prec, dst=dst, fold=mode == "fold", inlaunch=mode == "inlaunch",
+                        edge_split=mode == "fix" and prec == R32)
+        got = dst.to_nchw(0, cout).cpu().double().numpy()
+        assert np.all(np.isfinite(got)), what
+        for part, m, bnd, s in (("interior", ~ring, inner, terms[0]), ("ring", ring, edge, s_ring)):
+            if m.any():
+                r = within(got[:, :, m], ref[:, :, m], bnd[:, :, m], s[:, :, m], f"{what} {part}")
+                key = (name, k, mode, part)
+                SUB_WORST[key] = max(SUB_WORST.get(key, 0.0), r)
+        FLOAT_RAN.setdefault((prec, mode, cin, sh, sw), set()).add(cfg)
+    for key, v in sorted(SUB_WORST.items()):
+        if key[0] == name and key[2] == mode:
+            print(f"SUBPIXEL_WORST {key[0]} kind {key[1]} {key[2]} {key[3]}: err / (2^-24 S) <= {v:.2f}")
+
+
 # ---- coverage -------------------------------------------------------------------------------------
 @pytest.mark.parametrize("prec", PRECS)
 def test_exact_coverage_is_every_config(prec):
@@ -379,3 +490,14 @@ def test_exact_coverage_is_every_config(prec):
         print(f"{NAME[prec]} {name}: configs {sorted(want)}")
         if got is not None:
             assert got == want, (name, sorted(want - got), sorted(got - want))
+    # the sub-pixel shapes -- the multi-tile ring lines among them -- are each required of every config
+    for mode in ("fix", "inlaunch", "fold"):
+        for cin in (16, 64):
+            for sh, sw in SUB_SHAPES:
+                got = RAN_SUB.get((prec, mode, cin, sh, sw))
+                if got is not None:
+                    assert got == plan["sub_" + mode], (mode, cin, sh, sw, sorted(plan["sub_" + mode] - got))
+                for ran in (FLOAT_RAN.get((prec, mode, cin, sh, sw)),):
+                    if ran is not None:
+                        assert ran == plan["sub_" + mode], ("float", mode, cin, sh, sw, sorted(plan["sub_" + mode] - ran))
+    assert len(SUB) == 3 * 2 * len(SUB_SHAPES) and {(3, 33), (18, 3)} <= set(SUB_SHAPES)
