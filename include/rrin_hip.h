@@ -289,6 +289,27 @@ int rrin_conv_h8_cfg_wino(int32_t cfg);
  * with the same arithmetic: the outputs are the same bits.  Returns the previous policy,
  * RRIN_E_ARG outside 0-3. */
 int rrin_conv_h8_set_wino42_geom(int32_t mode);
+/* The launch shape rrin_conv3x3_h8_fwd / rrin_conv_block0_h8_fwd would use for d on stream's device
+ * right now (entry points only, no ABI bump): a read-only query for tests that must know which
+ * branch a launcher takes -- the persistent grids depend on the device's CU count and the
+ * occupancy of the tile, kind 14's geometry on the tile counts and the process-wide policy.  It
+ * validates d exactly as the forward call does (same error codes, scratch pointers included),
+ * runs the launcher's own grid / variant decision and launches nothing.  `tiles`: work items of
+ * the conv part (co blocks x tile positions x images, x K slices for split-K; kind 14 in the
+ * geometry it chose).  `grid`: workgroups launched for them; grid < tiles means workgroup b walks
+ * tiles b, b + grid, ...  `extra`: workgroups at the head of the same launch that do the
+ * sub-pixel ring (ring fold, or ring_full where the tile runs it in the launch), 0 when the ring
+ * is a launch of its own.  `variant`: 0, or for kind 14 1 = 16 x 16 tiles, 2 = persistent 32 x 8
+ * tiles. */
+typedef struct rrin_launch_info {
+  int64_t tiles;
+  int64_t grid;
+  int64_t extra;
+  int32_t variant;
+  int32_t pad_;
+} rrin_launch_info;
+int rrin_conv_h8_launch_info(const rrin_conv_h8_desc* d, void* stream, rrin_launch_info* out);
+int rrin_conv_block0_h8_launch_info(const rrin_block0_h8_desc* d, void* stream, rrin_launch_info* out);
 
 /* F32R packing: [co_block][chunk of 8 ci][tap][half][bm][4] fp32 (half hh holds
  * input channels chunk*8 + 4*hh .. +3), unscaled; pass as whi (wlo NULL,

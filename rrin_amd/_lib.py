@@ -83,6 +83,12 @@ class Block0Desc(C.Structure):
                 ("bias_a", C.c_void_p), ("whi_b", C.c_void_p), ("bias_b", C.c_void_p), ("status", C.c_void_p)]
 
 
+class LaunchInfo(C.Structure):
+    """rrin_launch_info: the launch shape a conv would take (rrin_conv_h8_launch_info)."""
+    _fields_ = [("tiles", C.c_int64), ("grid", C.c_int64), ("extra", C.c_int64), ("variant", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
 class EdgeFixDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("prec", C.c_int32),
                 ("epi_mode", C.c_int32), ("slope", C.c_float), ("src", H8), ("dst", H8),
@@ -259,6 +265,8 @@ SIGNATURES = {
                                          C.c_void_p]),
     "rrin_pack_conv3x3_wino42_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "rrin_conv_h8_set_wino42_geom": (C.c_int, [C.c_int32]),
+    "rrin_conv_h8_launch_info": (C.c_int, [C.POINTER(ConvH8Desc), C.c_void_p, C.POINTER(LaunchInfo)]),
+    "rrin_conv_block0_h8_launch_info": (C.c_int, [C.POINTER(Block0Desc), C.c_void_p, C.POINTER(LaunchInfo)]),
     "rrin_pack_conv3x3_wino42": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
     "rrin_pack_conv3x3_wino_h8_halves": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

@@ -304,7 +304,18 @@ __device__ inline void dma16(const uint4* src, uint4* lds_wave_base) {
 
 // The direct-form tiles (conv_h8.hip): tile config cfg (kind 0 of the table in h8_cfg.hpp) at
 // record precision prec with epilogue epi.
-int launch_h8(const ConvH8Args& a, int cfg, int prec, int epi, hipStream_t st);
+// Every launcher below takes an optional `info`: non-null, it reports the launch shape it decided
+// on (rrin_launch_info, rrin_hip.h) through launch_report and launches nothing -- the decision is
+// made once, by the code that launches.
+inline int launch_report(rrin_launch_info* info, int64_t tiles, int64_t grid, int64_t extra, int variant) {
+  info->tiles = tiles;
+  info->grid = grid;
+  info->extra = extra;
+  info->variant = variant;
+  info->pad_ = 0;
+  return 0;
+}
+int launch_h8(const ConvH8Args& a, int cfg, int prec, int epi, hipStream_t st, rrin_launch_info* info = nullptr);
 // The ring fix-up as its own launch (edge_fix.hip): validate d and fill a (everything but the K
 // split) and its grid (ring tiles x co blocks x images); launch it with the K split of cin and
 // prec (d: the caller's cross-workgroup scratch, may be null; one_group: one K group, fp32 runs of
@@ -315,7 +326,7 @@ int edge_fix_run(EdgeFixArgs a, dim3 grid, int prec, bool full, const rrin_edge_
 // Winograd F(2x2,3x3) exact-fp32 conv (conv_wino.hip): tile config 18 of
 // the record-layout table (F32R only), its LDS bytes per block and launcher.
 constexpr size_t kWinoLds = (size_t)(2 * 704 + 2 * 16 * 2 * 32) * 16;
-int launch_wino(const ConvH8Args& a, int epi, hipStream_t st);
+int launch_wino(const ConvH8Args& a, int epi, hipStream_t st, rrin_launch_info* info = nullptr);
 // zero channels [c0, c1) of a record-layout view (glue_h8.hip)
 int clear_channels_h8(const rrin_h8* v, int32_t n, int32_t c0, int32_t c1, int32_t prec, hipStream_t st);
 // Item forwards (ABI 25): image k of the Net buffer reads the frames and the kept raw Flow of pair
@@ -355,23 +366,23 @@ float* plane_logits(const rrin_aux_plane* pl, int n, int h, int w);
 // CU would fill 163,584 B)
 constexpr size_t kWinoQLds = (size_t)3 * (680 + 1024) * 16;
 // th = 8 (cfg 20: 8 waves) or 4 (cfg 21: 4 waves, the same arithmetic on half-height tiles)
-int launch_winoq(const ConvH8Args& a, int epi, int th, hipStream_t st);
+int launch_winoq(const ConvH8Args& a, int epi, int th, hipStream_t st, rrin_launch_info* info = nullptr);
 // register-U Winograd tiles (conv_winoc.hip): 4 waves, two blocks per CU, the U operands
 // loaded straight into registers; ct = 2: BM 64 x TH 4 (kind 6), ct = 1: BM 32 x TH 8 (kind 7).
 // LDS: max(3 raw stages, the output-transform exchange)
 constexpr size_t kWinoCLds1 = (size_t)2048 * 16;  // TH 4: 3 x 512 stage records < 2048 exchange
 constexpr size_t kWinoCLds2 = (size_t)4096 * 16;  // TH 8: 3 x 768 < 4096
-int launch_winoc(const ConvH8Args& a, int epi, int ct, hipStream_t st);
+int launch_winoc(const ConvH8Args& a, int epi, int ct, hipStream_t st, rrin_launch_info* info = nullptr);
 // the register-U tile in Winograd F(4,3) x F(2,3) (conv_winoc42.hip, kind 14): BM 32 x 32 px x
 // TH 8, 4 waves, two blocks per CU; LDS: max(3 raw stages of 768, the 4 x 16 x 65 exchange)
 constexpr size_t kWinoC42Lds = (size_t)4160 * 16;
-int launch_winoc42(const ConvH8Args& a, int epi, hipStream_t st);
+int launch_winoc42(const ConvH8Args& a, int epi, hipStream_t st, rrin_launch_info* info = nullptr);
 // whether rrin_conv3x3_h8_fwd runs a ring_full fix-up inside the conv's launch for tile config
 // cfg, cin input channels and precision prec (else it launches it after the conv) -- conv_rec.hip
 bool ring_in_launch_ok(int cfg, int cin, int prec);
 // the kind-6 tile at fp16 (conv_winoh.hip): H8 records, v_mfma_f32_32x32x16_f16, packed-f16
 // input transform; same LDS as kWinoCLds1
-int launch_winoh(const ConvH8Args& a, int epi, hipStream_t st);
+int launch_winoh(const ConvH8Args& a, int epi, hipStream_t st, rrin_launch_info* info = nullptr);
 // fused level-0 UNetConvBlock at fp16 (conv_block0.hip): conv a (cin -> 32) + leaky, conv b
 // (32 -> 32) + leaky (+ pool), conv a's output tile in LDS.  Tile kB0TH x kB0TW outputs; conv a
 // runs on (kB0TH + 2) x (kB0TW + 2) positions from a (kB0TH + 4) x (kB0TW + 4) input tile

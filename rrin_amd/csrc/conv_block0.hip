@@ -426,25 +426,22 @@ __global__ __launch_bounds__(256, 2) void conv_block0_h8_kernel(Block0Args a) {
 // round 5's persistent grids (RRIN_BLOCK0_BPC, kind 10) lost in the forward and kind 10 ran
 // nondeterministically, so the knob is gone and the walk never takes a second tile.
 template <bool POOL>
-static int launch_block0_k(const Block0Args& a, hipStream_t st) {
+static int launch_block0_k(const Block0Args& a, hipStream_t st, rrin_launch_info* info) {
   auto k = conv_block0_h8_kernel<POOL>;
   static LdsAttr attr;
   if (int e = attr.ensure((const void*)k, (int)kB0Lds, st)) return e;
   const int64_t tiles = (int64_t)a.tiles_x * a.tiles_y * a.n;
+  if (info) return launch_report(info, tiles, tiles, 0, 0);
   hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(256), kB0Lds, st, a);
   return hip_code(hipGetLastError());
 }
 
-static int launch_block0(const Block0Args& a, hipStream_t st) {
-  return a.pool ? launch_block0_k<true>(a, st) : launch_block0_k<false>(a, st);
+static int launch_block0(const Block0Args& a, hipStream_t st, rrin_launch_info* info) {
+  return a.pool ? launch_block0_k<true>(a, st, info) : launch_block0_k<false>(a, st, info);
 }
 
-}  // namespace rrin
-
-using namespace rrin;
-
-// Validate and launch.
-extern "C" int rrin_conv_block0_h8_fwd(const rrin_block0_h8_desc* d, void* stream) {
+// Validate, then launch -- or, with info, only report the launch shape.
+static int conv_block0_h8_run(const rrin_block0_h8_desc* d, void* stream, rrin_launch_info* info) {
   if (!d || !d->whi_a || !d->bias_a || !d->whi_b || !d->bias_b) return RRIN_E_ARG;
   for (int cfg : {d->cfg_a, d->cfg_b})
     if (!h8_cfg(cfg) || h8_cfg(cfg)->kind > 0) return RRIN_E_CONFIG;  // direct-form packs only
@@ -498,5 +495,18 @@ extern "C" int rrin_conv_block0_h8_fwd(const rrin_block0_h8_desc* d, void* strea
   a.tiles_y = (h + kB0TH - 1) / kB0TH;
   a.status = d->status;
   if ((int64_t)a.tiles_x * a.tiles_y * a.n > 0x7fffffff) return RRIN_E_SHAPE;
-  return launch_block0(a, static_cast<hipStream_t>(stream));
+  return launch_block0(a, static_cast<hipStream_t>(stream), info);
+}
+
+}  // namespace rrin
+
+using namespace rrin;
+
+extern "C" int rrin_conv_block0_h8_fwd(const rrin_block0_h8_desc* d, void* stream) {
+  return conv_block0_h8_run(d, stream, nullptr);
+}
+
+extern "C" int rrin_conv_block0_h8_launch_info(const rrin_block0_h8_desc* d, void* stream, rrin_launch_info* out) {
+  if (!out) return RRIN_E_ARG;
+  return conv_block0_h8_run(d, stream, out);
 }

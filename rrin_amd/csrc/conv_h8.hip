@@ -730,7 +730,7 @@ static int num_cus(int dev) {
 }
 
 template <int NW, int WM, int WN, int PLANES, int EPI, bool DMA, int SCHED, bool F32 = false>
-static int launch_h8_k(const ConvH8Args& args, int persist, hipStream_t st) {
+static int launch_h8_k(const ConvH8Args& args, int persist, hipStream_t st, rrin_launch_info* info = nullptr) {
   using T = TileH8<NW, WM, WN, PLANES>;
   auto k = conv3x3_h8_kernel<NW, WM, WN, PLANES, EPI, DMA, SCHED, F32>;
   constexpr bool wres = DMA && (SCHED & SCHED_WRES) != 0;
@@ -766,54 +766,57 @@ static int launch_h8_k(const ConvH8Args& args, int persist, hipStream_t st) {
       b.nfix = ((args.fix_real + VG - 1) / VG + 7) & ~7;
       b.fix.nslices = F32 ? b.fix.cin / kFixCi : 1;  // fp32: runs of one chunk, added in run order
       b.fix.cross = 0;
+      if (info) return launch_report(info, ntiles, grid, b.nfix, 0);
       const size_t flds = (size_t)VG * kFixSubFloats * sizeof(float);
       hipLaunchKernelGGL(k, dim3((unsigned)(grid + b.nfix)), dim3(T::NT), lds > flds ? lds : flds, st, b);
       return hip_code(hipGetLastError());
     }
   }
+  if (info) return launch_report(info, ntiles, grid, 0, 0);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(T::NT), lds, st, args);
   return hip_code(hipGetLastError());
 }
 
 template <int NW, int WM, int WN, int PLANES, int EPI, int SCHED, bool F32 = false>
-static int launch_h8_t(const ConvH8Args& args, int persist, hipStream_t st) {
+static int launch_h8_t(const ConvH8Args& args, int persist, hipStream_t st, rrin_launch_info* info) {
   using T = TileH8<NW, WM, WN, PLANES>;
   if constexpr (T::LDS > kMaxLds) {
     return RRIN_E_CONFIG;
   } else {
     if (args.cin % 8 == 0 || args.tail_finite)
-      return launch_h8_k<NW, WM, WN, PLANES, EPI, true, SCHED, F32>(args, persist, st);
+      return launch_h8_k<NW, WM, WN, PLANES, EPI, true, SCHED, F32>(args, persist, st, info);
     if constexpr (EPI == RRIN_EPI_LEAKY_REP || EPI == RRIN_EPI_SUBPIXEL) {
       return RRIN_E_CONFIG;  // decoder-side modes: always whole channel groups
     } else {
-      return launch_h8_k<NW, WM, WN, PLANES, EPI, false, 0, F32>(args, persist, st);  // knobs need DMA
+      return launch_h8_k<NW, WM, WN, PLANES, EPI, false, 0, F32>(args, persist, st, info);  // knobs need DMA
     }
   }
 }
 
 template <int NW, int WM, int WN, int PLANES, int SCHED, bool F32>
-static int launch_h8_epi(const ConvH8Args& args, int epi, int persist, hipStream_t st) {
+static int launch_h8_epi(const ConvH8Args& args, int epi, int persist, hipStream_t st, rrin_launch_info* info) {
   switch (epi) {
-    case RRIN_EPI_LINEAR: return launch_h8_t<NW, WM, WN, PLANES, RRIN_EPI_LINEAR, SCHED, F32>(args, persist, st);
-    case RRIN_EPI_LEAKY: return launch_h8_t<NW, WM, WN, PLANES, RRIN_EPI_LEAKY, SCHED, F32>(args, persist, st);
-    case RRIN_EPI_LEAKY_POOL: return launch_h8_t<NW, WM, WN, PLANES, RRIN_EPI_LEAKY_POOL, SCHED, F32>(args, persist, st);
-    case RRIN_EPI_LEAKY_REP: return launch_h8_t<NW, WM, WN, PLANES, RRIN_EPI_LEAKY_REP, SCHED, F32>(args, persist, st);
-    default: return launch_h8_t<NW, WM, WN, PLANES, RRIN_EPI_SUBPIXEL, SCHED, F32>(args, persist, st);
+    case RRIN_EPI_LINEAR: return launch_h8_t<NW, WM, WN, PLANES, RRIN_EPI_LINEAR, SCHED, F32>(args, persist, st, info);
+    case RRIN_EPI_LEAKY: return launch_h8_t<NW, WM, WN, PLANES, RRIN_EPI_LEAKY, SCHED, F32>(args, persist, st, info);
+    case RRIN_EPI_LEAKY_POOL: return launch_h8_t<NW, WM, WN, PLANES, RRIN_EPI_LEAKY_POOL, SCHED, F32>(args, persist, st, info);
+    case RRIN_EPI_LEAKY_REP: return launch_h8_t<NW, WM, WN, PLANES, RRIN_EPI_LEAKY_REP, SCHED, F32>(args, persist, st, info);
+    default: return launch_h8_t<NW, WM, WN, PLANES, RRIN_EPI_SUBPIXEL, SCHED, F32>(args, persist, st, info);
   }
 }
 
 template <int NW, int WM, int WN, int SCHED>
-static int launch_h8_cfg(const ConvH8Args& args, int prec, int epi, int persist, hipStream_t st) {
-  if (prec == RRIN_PREC_F32R) return launch_h8_epi<NW, WM, WN, 1, SCHED, true>(args, epi, persist, st);
-  if (planes_of(prec) == 2) return launch_h8_epi<NW, WM, WN, 2, SCHED, false>(args, epi, persist, st);
-  return launch_h8_epi<NW, WM, WN, 1, SCHED, false>(args, epi, persist, st);
+static int launch_h8_cfg(const ConvH8Args& args, int prec, int epi, int persist, hipStream_t st,
+                         rrin_launch_info* info) {
+  if (prec == RRIN_PREC_F32R) return launch_h8_epi<NW, WM, WN, 1, SCHED, true>(args, epi, persist, st, info);
+  if (planes_of(prec) == 2) return launch_h8_epi<NW, WM, WN, 2, SCHED, false>(args, epi, persist, st, info);
+  return launch_h8_epi<NW, WM, WN, 1, SCHED, false>(args, epi, persist, st, info);
 }
 
-int launch_h8(const ConvH8Args& a, int cfg, int prec, int epi, hipStream_t st) {
+int launch_h8(const ConvH8Args& a, int cfg, int prec, int epi, hipStream_t st, rrin_launch_info* info) {
   switch (cfg) {
 #define X(id, nw, wm, wn, sc, pe) \
   case id:                        \
-    return launch_h8_cfg<nw, wm, wn, sc>(a, prec, epi, pe, st);
+    return launch_h8_cfg<nw, wm, wn, sc>(a, prec, epi, pe, st, info);
     RRIN_H8_CFGS(X)
 #undef X
   }

@@ -142,16 +142,19 @@ static int h8_prepare(const rrin_conv_h8_desc* d, ConvH8Args& a, bool need_scrat
   return 0;
 }
 
-static int conv3x3_h8_launch(const rrin_conv_h8_desc* d, const ConvH8Args& a, hipStream_t st) {
+// info (rrin_conv_h8_launch_info): the launcher reports its launch shape and launches nothing
+static int conv3x3_h8_launch(const rrin_conv_h8_desc* d, const ConvH8Args& a, hipStream_t st,
+                             rrin_launch_info* info) {
   switch (kCfgH8[d->cfg].kind) {  // h8_prepare passed: a live config
-    case 0: return launch_h8(a, d->cfg, d->prec, d->epi_mode, st);
-    case 1: return launch_wino(a, d->epi_mode, st);
-    case 3: return launch_winoq(a, d->epi_mode, 8, st);
-    case 4: return launch_winoq(a, d->epi_mode, 4, st);
+    case 0: return launch_h8(a, d->cfg, d->prec, d->epi_mode, st, info);
+    case 1: return launch_wino(a, d->epi_mode, st, info);
+    case 3: return launch_winoq(a, d->epi_mode, 8, st, info);
+    case 4: return launch_winoq(a, d->epi_mode, 4, st, info);
     case 6:
-      return d->prec == RRIN_PREC_F16 ? launch_winoh(a, d->epi_mode, st) : launch_winoc(a, d->epi_mode, 2, st);
-    case 7: return launch_winoc(a, d->epi_mode, 1, st);
-    case 14: return launch_winoc42(a, d->epi_mode, st);
+      return d->prec == RRIN_PREC_F16 ? launch_winoh(a, d->epi_mode, st, info)
+                                      : launch_winoc(a, d->epi_mode, 2, st, info);
+    case 7: return launch_winoc(a, d->epi_mode, 1, st, info);
+    case 14: return launch_winoc42(a, d->epi_mode, st, info);
   }
   return RRIN_E_CONFIG;
 }
@@ -213,7 +216,8 @@ extern "C" int64_t rrin_conv_h8_split_floats(const rrin_conv_h8_desc* d, int64_t
   return a.ksplit > 1 ? tiles * a.ksplit * 32 * 32 * kCfgH8[d->cfg].th : 0;  // 16 floats per thread of 64 x th threads
 }
 
-extern "C" int rrin_conv3x3_h8_fwd(const rrin_conv_h8_desc* d, void* stream) {
+// Validate and dispatch: the forward call (info null), or its launch shape alone.
+static int conv3x3_h8_run(const rrin_conv_h8_desc* d, void* stream, rrin_launch_info* info) {
   ConvH8Args a;
   const int rc = h8_prepare(d, a);
   if (rc) return rc;
@@ -224,12 +228,22 @@ extern "C" int rrin_conv3x3_h8_fwd(const rrin_conv_h8_desc* d, void* stream) {
     if (!ring_in_launch_ok(d->cfg, a.fix.cin, d->prec)) {
       ConvH8Args b = a;
       b.fix_real = 0;
-      if (int e = conv3x3_h8_launch(d, b, st)) return e;
+      if (int e = conv3x3_h8_launch(d, b, st, info)) return e;
+      if (info) return 0;  // the conv part alone: the ring is a launch of its own (extra 0)
       dim3 g((unsigned)a.fix_gx, (unsigned)a.fix_gy, (unsigned)d->n);
       return edge_fix_run(a.fix, g, d->prec, true, nullptr, st, true);  // the in-launch summation order
     }
   }
-  return conv3x3_h8_launch(d, a, st);
+  return conv3x3_h8_launch(d, a, st, info);
+}
+
+extern "C" int rrin_conv3x3_h8_fwd(const rrin_conv_h8_desc* d, void* stream) {
+  return conv3x3_h8_run(d, stream, nullptr);
+}
+
+extern "C" int rrin_conv_h8_launch_info(const rrin_conv_h8_desc* d, void* stream, rrin_launch_info* out) {
+  if (!out) return RRIN_E_ARG;
+  return conv3x3_h8_run(d, stream, out);
 }
 
 #ifdef RRIN_LAB

@@ -421,18 +421,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvH8Args a) {
 }
 
 template <int EPI, int ABL = 0>
-static int launch_wino_k(const ConvH8Args& a, hipStream_t st) {
+static int launch_wino_k(const ConvH8Args& a, hipStream_t st, rrin_launch_info* info = nullptr) {
   auto k = conv3x3_wino_kernel<EPI, ABL>;
   static LdsAttr attr;
   if (int e = attr.ensure((const void*)k, (int)kWinoLds, st)) return e;
   const int64_t grid = (int64_t)a.co_blocks * a.tiles_x * a.tiles_y * a.n;
+  if (info) return launch_report(info, grid, grid, 0, 0);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), kWinoLds, st, a);
   return hip_code(hipGetLastError());
 }
 
 
-int launch_wino(const ConvH8Args& a, int epi, hipStream_t st) {
-  return wino_dispatch_epi(epi, [&](auto e) { return launch_wino_k<decltype(e)::value>(a, st); });
+int launch_wino(const ConvH8Args& a, int epi, hipStream_t st, rrin_launch_info* info) {
+  return wino_dispatch_epi(epi, [&](auto e) { return launch_wino_k<decltype(e)::value>(a, st, info); });
 }
 
 // ============================================================================
@@ -1153,14 +1154,16 @@ __global__ __launch_bounds__(256 * PT, 2) void conv3x3_winoq_kernel(ConvH8Args a
 }
 
 template <int EPI, int ABL = 0, int PT = 2, int SK = 0, int RF = 0>
-static int launch_winoq_k(const ConvH8Args& a, hipStream_t st) {
+static int launch_winoq_k(const ConvH8Args& a, hipStream_t st, rrin_launch_info* info = nullptr) {
   auto k = conv3x3_winoq_kernel<EPI, ABL, PT, SK, RF>;
   static LdsAttr attr;
   constexpr size_t raw = (size_t)2 * (4 * PT + 2) * kWnRawCols;
   constexpr size_t lds = (PT == 2 && kWqStages == 3) ? (3 * raw + 2 * kWnU) * 16 : 2 * (raw + kWnU) * 16;
   if (int e = attr.ensure((const void*)k, (int)lds, st)) return e;
-  const int64_t grid = (int64_t)a.co_blocks * a.tiles_x * a.tiles_y * a.n * (SK ? a.ksplit : 1) + (RF ? a.nring : 0);
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256 * PT), lds, st, a);
+  const int64_t tiles = (int64_t)a.co_blocks * a.tiles_x * a.tiles_y * a.n * (SK ? a.ksplit : 1);
+  const int64_t nring = RF ? a.nring : 0;  // ring correction blocks at the head of the grid
+  if (info) return launch_report(info, tiles, tiles, nring, 0);
+  hipLaunchKernelGGL(k, dim3((unsigned)(tiles + nring)), dim3(256 * PT), lds, st, a);
   return hip_code(hipGetLastError());
 }
 
@@ -1172,20 +1175,20 @@ static int launch_winoq_k(const ConvH8Args& a, hipStream_t st) {
 #endif
 
 template <int PT, int SK>
-static int launch_winoq_e(const ConvH8Args& a, int epi, hipStream_t st) {
-  return wino_dispatch_epi(epi, [&](auto e) { return launch_winoq_k<decltype(e)::value, 0, PT, SK>(a, st); });
+static int launch_winoq_e(const ConvH8Args& a, int epi, hipStream_t st, rrin_launch_info* info) {
+  return wino_dispatch_epi(epi, [&](auto e) { return launch_winoq_k<decltype(e)::value, 0, PT, SK>(a, st, info); });
 }
 
-int launch_winoq(const ConvH8Args& a0, int epi, int th, hipStream_t st) {
+int launch_winoq(const ConvH8Args& a0, int epi, int th, hipStream_t st, rrin_launch_info* info) {
   ConvH8Args a = a0;
   a.cob_group =
       a.nring > 0 ? 0 : wino_cob_group(a.co_blocks, (int64_t)a.nchunks * kWnU * 16, RRIN_WINOQ_UGROUP_KB);
-  if (a.ksplit > 1) return th == 4 ? launch_winoq_e<1, 1>(a, epi, st) : launch_winoq_e<2, 1>(a, epi, st);
+  if (a.ksplit > 1) return th == 4 ? launch_winoq_e<1, 1>(a, epi, st, info) : launch_winoq_e<2, 1>(a, epi, st, info);
   if (a.nring > 0) {
     if (th != 8 || epi != RRIN_EPI_SUBPIXEL) return RRIN_E_CONFIG;
-    return launch_winoq_k<RRIN_EPI_SUBPIXEL, 0, 2, 0, 1>(a, st);
+    return launch_winoq_k<RRIN_EPI_SUBPIXEL, 0, 2, 0, 1>(a, st, info);
   }
-  return th == 4 ? launch_winoq_e<1, 0>(a, epi, st) : launch_winoq_e<2, 0>(a, epi, st);
+  return th == 4 ? launch_winoq_e<1, 0>(a, epi, st, info) : launch_winoq_e<2, 0>(a, epi, st, info);
 }
 
 #ifdef RRIN_LAB

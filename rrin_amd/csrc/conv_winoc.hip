@@ -417,7 +417,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
 }
 
 template <int EPI, int CT, int NT>
-static int launch_winoc_k(const ConvH8Args& a, hipStream_t st) {
+static int launch_winoc_k(const ConvH8Args& a, hipStream_t st, rrin_launch_info* info) {
   auto k = conv3x3_winoc_kernel<EPI, CT, NT>;
   static LdsAttr attr;
   constexpr size_t lds = WinoC<NT>::LDS;
@@ -431,28 +431,30 @@ static int launch_winoc_k(const ConvH8Args& a, hipStream_t st) {
       b.nfix = (a.fix_real + 7) & ~7;
       b.fix.nslices = b.fix.cin / kFixCi;
       b.fix.cross = 0;
+      if (info) return launch_report(info, grid, grid, b.nfix, 0);
       hipLaunchKernelGGL(k, dim3((unsigned)(grid + b.nfix)), dim3(256), lmax, st, b);
       return hip_code(hipGetLastError());
     }
   }
+  if (info) return launch_report(info, grid, grid, 0, 0);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, st, a);
   return hip_code(hipGetLastError());
 }
 
 template <int CT, int NT>
-static int launch_winoc_e(const ConvH8Args& a, int epi, hipStream_t st) {
-  return wino_dispatch_epi(epi, [&](auto e) { return launch_winoc_k<decltype(e)::value, CT, NT>(a, st); });
+static int launch_winoc_e(const ConvH8Args& a, int epi, hipStream_t st, rrin_launch_info* info) {
+  return wino_dispatch_epi(epi, [&](auto e) { return launch_winoc_k<decltype(e)::value, CT, NT>(a, st, info); });
 }
 
 // co-block groups (wino_cob_group): U of a group within this many KB
 #ifndef RRIN_WINOC_UGROUP_KB
 #define RRIN_WINOC_UGROUP_KB 2048
 #endif
-int launch_winoc(const ConvH8Args& a, int epi, int ct, hipStream_t st) {
+int launch_winoc(const ConvH8Args& a, int epi, int ct, hipStream_t st, rrin_launch_info* info) {
   ConvH8Args b = a;
   // U of one co block: nchunks x 32 BM records
   b.cob_group = wino_cob_group(a.co_blocks, (int64_t)a.nchunks * 32 * (32 * ct) * 16, RRIN_WINOC_UGROUP_KB);
-  return ct == 2 ? launch_winoc_e<2, 1>(b, epi, st) : launch_winoc_e<1, 2>(b, epi, st);
+  return ct == 2 ? launch_winoc_e<2, 1>(b, epi, st, info) : launch_winoc_e<1, 2>(b, epi, st, info);
 }
 
 }  // namespace rrin

@@ -478,9 +478,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc42_kernel(ConvH8Args a) {
 }
 
 template <int EPI, int PCW, bool PERSIST>
-static int launch_winoc42_k(const ConvH8Args& a, int64_t grid, hipStream_t st) {
+static int launch_winoc42_k(const ConvH8Args& a, int64_t grid, hipStream_t st, rrin_launch_info* info) {
   auto k = conv3x3_winoc42_kernel<EPI, PCW, PERSIST>;
   constexpr size_t lds = PERSIST ? W42P::LDS : kWinoC42Lds;
+  if (info)  // tiles in this instantiation's geometry; variant 1: 16 x 16 tiles, 2: persistent 32 x 8
+    return launch_report(info, (int64_t)a.co_blocks * a.tiles_x * a.tiles_y * a.n, grid, 0, PCW == 4 ? 1 : PERSIST ? 2 : 0);
   static LdsAttr attr;
   if (int e = attr.ensure((const void*)k, (int)lds, st)) return e;
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, st, a);
@@ -509,7 +511,7 @@ static std::atomic<int> g_wino42_geom{RRIN_WINO42_GEOM_DEFAULT};
 #ifndef RRIN_WINO42_UGROUP_KB
 #define RRIN_WINO42_UGROUP_KB 2048
 #endif
-int launch_winoc42(const ConvH8Args& a, int epi, hipStream_t st) {
+int launch_winoc42(const ConvH8Args& a, int epi, hipStream_t st, rrin_launch_info* info) {
   ConvH8Args b = a;
   b.cob_group = wino_cob_group(a.co_blocks, (int64_t)a.nchunks * 1536 * 16, RRIN_WINO42_UGROUP_KB);
   // the 16 x 16 tile when it needs fewer rounds of the 512 resident workgroups (two per CU):
@@ -531,9 +533,9 @@ int launch_winoc42(const ConvH8Args& a, int epi, hipStream_t st) {
   const int64_t grid = persist ? std::min<int64_t>(RRIN_WINO42_PERSIST_WG, wide / 2) : use_tall ? tall : wide;
   return wino_dispatch_epi(epi, [&](auto e) {
     constexpr int E = decltype(e)::value;
-    return use_tall  ? launch_winoc42_k<E, 4, false>(b, grid, st)
-           : persist ? launch_winoc42_k<E, 8, true>(b, grid, st)
-                     : launch_winoc42_k<E, 8, false>(b, grid, st);
+    return use_tall  ? launch_winoc42_k<E, 4, false>(b, grid, st, info)
+           : persist ? launch_winoc42_k<E, 8, true>(b, grid, st, info)
+                     : launch_winoc42_k<E, 8, false>(b, grid, st, info);
   });
 }
 

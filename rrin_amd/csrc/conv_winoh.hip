@@ -373,12 +373,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoh_kernel(ConvH8Args a) {
 
 
 template <int EPI>
-static int launch_winoh_k(const ConvH8Args& a, hipStream_t st) {
+static int launch_winoh_k(const ConvH8Args& a, hipStream_t st, rrin_launch_info* info) {
   auto k = conv3x3_winoh_kernel<EPI>;
   static LdsAttr attr;
   constexpr size_t lds = WinoH::LDS;
   if (int e = attr.ensure((const void*)k, (int)lds, st)) return e;
   const int64_t grid = (int64_t)a.co_blocks * a.tiles_x * a.tiles_y * a.n;
+  if (info) return launch_report(info, grid, grid, 0, 0);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, st, a);
   return hip_code(hipGetLastError());
 }
@@ -388,11 +389,11 @@ static int launch_winoh_k(const ConvH8Args& a, hipStream_t st) {
 #define RRIN_WINOH_UGROUP_KB 2048
 #endif
 
-int launch_winoh(const ConvH8Args& a, int epi, hipStream_t st) {
+int launch_winoh(const ConvH8Args& a, int epi, hipStream_t st, rrin_launch_info* info) {
   ConvH8Args b = a;
   // U of one co block: nchunks x 32 BM records
   b.cob_group = wino_cob_group(a.co_blocks, (int64_t)a.nchunks * 32 * 64 * 16, RRIN_WINOH_UGROUP_KB);
-  return wino_dispatch_epi(epi, [&](auto e) { return launch_winoh_k<decltype(e)::value>(b, st); });
+  return wino_dispatch_epi(epi, [&](auto e) { return launch_winoh_k<decltype(e)::value>(b, st, info); });
 }
 
 }  // namespace rrin

@@ -53,12 +53,17 @@ def conv_int(x, w, taps=None):
     xp = np.zeros((n, c, h + 2, wd + 2), np.int64)
     xp[:, :, 1:-1, 1:-1] = x
     y = np.zeros((n, w.shape[0], h, wd), np.int64)
+    # the products summed in float64 (BLAS) where every partial sum is an integer below 2^53 -- the
+    # same integers as the int64 product, many times faster at the launch-path shapes
+    f64 = 9 * c * int(np.abs(x).max(initial=0)) * int(np.abs(w).max(initial=0)) < 2 ** 52
+    dt = np.float64 if f64 else np.int64
     for ky in range(3):
         for kx in range(3):
             if taps is not None and (ky, kx) not in taps:
                 continue
-            cols = xp[:, :, ky:ky + h, kx:kx + wd].transpose(1, 0, 2, 3).reshape(c, -1)
-            y += (w[:, :, ky, kx].astype(np.int64) @ cols).reshape(-1, n, h, wd).transpose(1, 0, 2, 3)
+            cols = xp[:, :, ky:ky + h, kx:kx + wd].transpose(1, 0, 2, 3).reshape(c, -1).astype(dt)
+            part = w[:, :, ky, kx].astype(dt) @ cols
+            y += part.astype(np.int64).reshape(-1, n, h, wd).transpose(1, 0, 2, 3)
     return y
 
 
@@ -262,7 +267,7 @@ def block0_case(n, cin, h, w):
     one of the 9 cin products is +-mag: a dropped or doubled one still moves conv a by a grid step,
     and a K chunk added twice by +-2 mag per tap."""
     r = np.random.default_rng([7, n, cin, h, w])
-    mag = 2 if cin < 8 else 1
+    mag = 2 if cin < 16 else 1     # one group of 8 channels gives +-2 mag per tap: a multiple of 4 needs mag 2
     s = r.choice(np.asarray([-1, 1], np.int64), size=cin)
     p = r.choice(np.asarray([-1, 1], np.int64), size=(n, 1, h, w))
     x = mag * s[None, :, None, None] * p
@@ -795,3 +800,76 @@ def sub_wino_ratio(n, cin, cout, h, w, prec, kind):
     ref = conv_valid64(xp, wp, b4)
     s = conv_valid64(np.abs(xp), np.abs(wp), np.abs(b4))
     return float((np.abs(got - ref) / (U * s)).max())
+
+
+# ---- launch paths (tests/test_gpu_h8_paths.py; DESIGN.md §8b, "Launch paths") ------------------------
+# (n, cin, cout, h, w), cheapest first.  A test takes the first entry at which the launch-shape query
+# (rrin_conv_h8_launch_info) reports the branch it wants: a walk of unequal length (grid < tiles,
+# tiles % grid != 0, tiles > 2 grid) for the configs with a capped grid, grid >= 64 and grid % 8 != 0
+# for the others.  Odd sizes one past a tile multiple buy the most tiles per pixel (17 x 65 is
+# 3 x 3 tiles of 32 x 8); n and cout grow before the pixels do.  The last entries carry the capped
+# grids of 256 to 1280 workgroups that 256 CUs give; one cin 64 entry per launch form.
+LADDER = (
+    (5, 16, 40, 17, 65), (5, 16, 40, 33, 65), (5, 16, 128, 33, 65), (5, 16, 256, 33, 65), (5, 64, 40, 33, 65),
+    (5, 64, 128, 33, 65), (6, 16, 256, 49, 161), (6, 16, 256, 97, 161), (6, 16, 256, 113, 161), (6, 64, 256, 49, 161),
+    (6, 64, 256, 97, 161),
+)
+# the sub-pixel up conv: (h, w) the low-res source, cout the up conv's (the conv has 4 cout phase
+# channels, so 4 co blocks per 32); cin 32, the least at which ring_full runs inside the conv's launch
+LADDER_SUB = ((5, 32, 32, 33, 65), (5, 32, 64, 33, 65), (6, 32, 64, 49, 161), (6, 32, 64, 97, 161), (6, 32, 64, 113, 161))
+K14_TALL = [(2, 16, 32, 1, 1), (2, 16, 32, 1, 40), (2, 16, 32, 40, 1), (2, 16, 32, 17, 33), (2, 64, 40, 18, 34),
+            (2, 256, 32, 17, 33)]
+K14_TALL_AUTO = (4, 16, 256, 45, 80)      # co_blocks n = 32: 576 tiles of 32 x 8 (two rounds of 512), 480 of 16 x 16
+K14_PERSIST = [(2, 32, 96, 1024), (2, 40, 97, 950), (3, 32, 100, 900)]   # (n, cout, h, w)
+K14_PERSIST_SUB = [(2, 16, 32, 48, 512), (2, 16, 32, 49, 475), (3, 16, 32, 50, 450)]   # 768, 840, 1260 tiles
+K14_PERSIST_CIN = (8, 16, 24, 64)         # nch 1, 2, > 2 and 8 chunks; 64 at the first shape only
+# the co-block group walk (wino_cob_group): cin 256 puts U of 5 co blocks of 32 (3 of 64) past 2 MB;
+# fp16 kind 6 halves U per channel (16-channel chunks), so cout 320
+COB_SHAPE, COB_SHAPE_F16 = (3, 256, 160, 17, 65), (3, 256, 320, 17, 65)
+BLOCK0_PATHS = [(3, 8, 17, 125), (3, 16, 18, 126)]   # (n, cin, h, w): 3 x 3 x 3 = 27 tiles of 62 x 8, 27 % 8 = 3
+
+
+def tile_boxes(n, cout, h, w, bm, th, tw=32):
+    """The (image, co0, co1, y0, y1, x0, x1) box of every tile, in the launchers' order: co block
+    fastest, then x, then y, then the image (wino_tile_pos with one co-block group; conv_h8.hip)."""
+    out = []
+    for i in range(n):
+        for y0 in range(0, h, th):
+            for x0 in range(0, w, tw):
+                for c0 in range(0, cout, bm):
+                    out.append((i, c0, min(c0 + bm, cout), y0, min(y0 + th, h), x0, min(x0 + tw, w)))
+    return out
+
+
+def _box(u, b):
+    i, c0, c1, y0, y1, x0, x1 = b
+    return u[i, c0:c1, y0:y1, x0:x1]
+
+
+def tile_from_other(r, boxes, k, j):
+    """r with tile k's outputs replaced by tile j's (same box size): a workgroup that computed its
+    third tile at another tile's coordinates."""
+    u = r.units.copy()
+    a, b_ = _box(u, boxes[k]), _box(r.units, boxes[j])
+    assert a.shape == b_.shape
+    a[...] = b_
+    return Ref(u, r.scale)
+
+
+def tile_with_previous_bias(r, boxes, k, j, b, wmul=1):
+    """r (a pre-activation) with tile k carrying the bias of tile j's co block instead of its own."""
+    u = r.units.copy()
+    (_, c0, c1, *_), (_, d0, d1, *_) = boxes[k], boxes[j]
+    assert c1 - c0 == d1 - d0
+    _box(u, boxes[k])[...] += r.scale * wmul * (b[d0:d1] - b[c0:c1])[:, None, None]
+    return Ref(u, r.scale)
+
+
+def last_tiles_unwritten(v, boxes, grid, fill=np.nan):
+    """float64 v with the last len(boxes) % grid tiles left at `fill`: a walk that stops a round early."""
+    v = v.copy()
+    rem = len(boxes) % grid
+    assert rem
+    for b in boxes[-rem:]:
+        _box(v, b)[...] = fill
+    return v

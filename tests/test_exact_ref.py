@@ -466,3 +466,99 @@ def test_fp16_bound_rejects_a_second_rounding():
     assert (np.abs(once - ref) <= bnd).all()
     twice = (T(E.conv64(x, wt)).half().double() + T(b).view(1, -1, 1, 1)).half().double().numpy()
     assert (np.abs(twice - ref) > bnd).any()
+
+
+# ---- launch paths (tests/test_gpu_h8_paths.py): ladder, ranges, mutations ----------------------------
+ALL_PATH_SHAPES = sorted(set(E.LADDER) | set(E.K14_TALL) | {E.K14_TALL_AUTO}
+                         | {(n, cin, cout, h, w) for n, cout, h, w in E.K14_PERSIST[:1] for cin in E.K14_PERSIST_CIN}
+                         | {(n, cin, cout, h, w) for n, cout, h, w in E.K14_PERSIST[1:] for cin in E.K14_PERSIST_CIN[:3]})
+
+
+def test_ladder_is_ordered_and_bounded():
+    """Cheapest first within each cin; nothing beyond 96 x 640 x 4 pixels, n 2-6, cout of the four widths."""
+    for ladder, cins in ((E.LADDER, (16, 64)), (E.LADDER_SUB, (32,))):
+        for cin in cins:
+            cost = [n * cout * h * w for n, c, cout, h, w in ladder if c == cin]
+            assert cost and cost == sorted(cost)
+        for n, cin, cout, h, w in ladder:
+            assert 2 <= n <= 6 and n * h * w <= 4 * 96 * 640 and cout in (32, 40, 64, 128, 256) and cin in cins
+            assert h % 16 == 1 and w % 32 == 1        # one past a tile multiple: ragged last tiles of every geometry
+
+
+@pytest.mark.parametrize("shape", ALL_PATH_SHAPES)
+def test_path_shapes_stay_in_the_exact_range(shape):
+    """Every ladder and fixed shape keeps its reference exactly representable: the direct form's sums
+    below 2^24 grid steps at the worst signs (split-fp16: in units of 2^-12, two hi*lo classes), the
+    stored values fp16 numbers where the fp16 precisions store them, and the Winograd forms inside
+    exact_ref.wino_fits with +-1 / +-2, or with +-1 alone where the test falls back to it."""
+    n, cin, cout, h, w = shape
+    if shape in E.LADDER:      # the shapes split-fp16 runs; the kind-14 shapes run on fp32 records alone
+        assert (9 * cin * 4 + 3) * (E.LO + 2) < E.P24
+    assert 48 * (9 * cin * 4 + 3) < E.P24
+    x, wt, b, _, _ = E.int_case(n, cin, cout, h, w, (1, 2))
+    for k, mul in ((1, 1), (14, 48)):
+        fits = E.wino_fits(k, mul * wt, 1, cin, 2)[0]
+        if not fits:
+            assert E.wino_fits(k, mul * E.int_case(n, cin, cout, h, w, (1,))[1], 1, cin, 1)[0], (k, shape)
+    if shape in E.LADDER:
+        r = E.leaky(E.pre_int(x, wt, b))
+        assert E.f16_exact(r.f64()) and E.f32_exact(48 * r.f64())
+        hp, wp = h + 1, w + 1
+        x1, w1, b1, _, _ = E.int_case(n, cin, cout, hp, wp, (1,))
+        assert E.f16_exact(E.pool(E.leaky(E.pre_int(x1, w1, b1))).f64())
+
+
+@pytest.mark.parametrize("shape", list(E.LADDER_SUB) + E.K14_PERSIST_SUB)
+def test_sub_shapes_stay_in_the_exact_range(shape):
+    """Every sub-pixel ladder entry and kind 14's persistent sub-pixel shapes, +-1 data: sums in
+    sixteenths (split-fp16: x 2^12) below 2^24 at the worst signs, both Winograd forms inside
+    wino_fits, and the values of one image fp16 numbers after one rounding at most 2048."""
+    n, cin, cout, h, w = shape
+    assert (9 * cin * 16 + 16 * 3) * (E.LO + 2) // E.LO * E.LO < E.P24 * E.LO and 48 * (9 * cin * 16 + 48) < E.P24
+    x, wt, b, _, _ = E.int_case(n, cin, cout, h, w, (1,))
+    wsub = E.subpixel_weights_int(wt)
+    assert E.wino_fits(1, wsub, 16, cin, 1)[0] and E.wino_fits(14, 48 * wsub, 16, cin, 1)[0]
+    r = E.pre_sub(x[:1], wt, b)
+    assert E.f32_exact(r.f64()) and np.abs(r.f64()).max() < 2048
+
+
+@pytest.mark.parametrize("shape", [E.COB_SHAPE, E.COB_SHAPE_F16])
+def test_cob_shapes_stay_in_the_exact_range(shape):
+    """cin 256 on +-1 data: the F(2x2) forms and kind 14 inside wino_fits, the stored values fp16 numbers."""
+    n, cin, cout, h, w = shape
+    x, wt, b, _, _ = E.int_case(n, cin, cout, h, w, (1,))
+    assert E.wino_fits(1, wt, 1, cin, 1)[0] and E.wino_fits(14, 48 * wt, 1, cin, 1)[0]
+    assert E.f16_exact(E.leaky(E.pre_int(x, wt, b)).f64())
+
+
+@pytest.mark.parametrize("n,cin,h,w", E.BLOCK0_PATHS)
+def test_block0_path_shapes_stay_fp16(n, cin, h, w):
+    x, wa, ba, wb, bb = E.block0_case(n, cin, h, w)
+    mid, out = E.block0_ref(x, wa, ba, wb, bb)
+    assert E.f16_exact(mid.f64()) and E.f16_exact(out.f64())
+
+
+def test_tile_walk_mutations_break_equality():
+    """At a multi-tile shape (5 x 40 x 17 x 65: 90 tiles of 32 co x 32 px x 8 rows) the slips of a
+    tile walk each break ==: a tile's outputs taken from another tile, a tile computed with the
+    previous tile's bias, the last tiles % grid tiles never written."""
+    n, cin, cout, h, w = E.LADDER[0]
+    x, wt, b, _, _ = E.int_case(n, cin, cout, h, w)
+    pre = E.pre_int(x, wt, b)
+    ref = E.leaky(pre).f64()
+    boxes = E.tile_boxes(n, cout, h, w, 32, 8)
+    assert len(boxes) == 90 and len({bx[2] - bx[1] for bx in boxes}) == 2      # a ragged second co block
+    grid = 32
+    size = lambda bx: (bx[2] - bx[1], bx[4] - bx[3], bx[6] - bx[5])  # noqa: E731
+    # a workgroup's third tile (k = bid + 2 grid) computed at its second tile's coordinates
+    k = next(i for i in range(2 * grid, len(boxes)) if size(boxes[i]) == size(boxes[i - grid]))
+    assert not np.array_equal(E.leaky(E.tile_from_other(pre, boxes, k, k - grid)).f64(), ref)
+    # the tile after a tile of the other co block keeps that tile's bias (two full co blocks: cout 64)
+    other = E.tile_boxes(n, 64, h, w, 32, 8)
+    x2, w2, b2, _, _ = E.int_case(n, cin, 64, h, w)
+    pre2 = E.pre_int(x2, w2, b2)
+    assert other[5][1] != other[4][1] and not np.array_equal(b2[:32], b2[32:])
+    assert not np.array_equal(E.leaky(E.tile_with_previous_bias(pre2, other, 5, 4, b2)).f64(), E.leaky(pre2).f64())
+    left = E.last_tiles_unwritten(ref, boxes, grid)
+    assert len(boxes) % grid == 26 and np.isnan(left).sum() > 0 and not np.array_equal(left, ref)
+    assert not (left == ref).all()

@@ -150,11 +150,18 @@ def set_split(d, ksplit, dev, keep, alloc=scratch):
     keep.extend([part, cnt])
 
 
+def query_launch(d, dev, info):
+    """info (a _lib.LaunchInfo, or None): the launch shape of the descriptor d that is about to be launched."""
+    if info is not None:
+        _lib.check(_lib.lib().rrin_conv_h8_launch_info(C.byref(d), H.stream(dev), C.byref(info)), "rrin_conv_h8_launch_info")
+
+
 def conv_h8(src: H8Tensor, w, b, cfg, prec, epi=_lib.EPI_LINEAR, dst=None, dst_off=0, pool=None, perm=None,
             cin=None, tail_finite=0, ksplit=0, keep=None, src_off=0, status=None, alloc=scratch, packed=None,
-            pool_off=0, slope=0.1):
+            pool_off=0, slope=0.1, info=None):
     """src_off: first channel of the source view; status: the fp16 range flag (an int32 tensor);
-    alloc: see scratch(); packed: pack_h8's result for (w, b, cfg, prec), to pack once per config."""
+    alloc: see scratch(); packed: pack_h8's result for (w, b, cfg, prec), to pack once per config;
+    info: a _lib.LaunchInfo that receives the launch shape of the very descriptor launched."""
     dev = src.hi.device
     cout, cin_w = w.shape[:2]
     cin = cin or cin_w
@@ -173,6 +180,7 @@ def conv_h8(src: H8Tensor, w, b, cfg, prec, epi=_lib.EPI_LINEAR, dst=None, dst_o
         d.pool = pool.view(pool_off, cout)
     d.whi, d.wlo, d.bias = whi.data_ptr(), wlo.data_ptr() if prec == X3 else None, bp.data_ptr()
     set_split(d, ksplit, dev, keep if keep is not None else [], alloc)
+    query_launch(d, dev, info)
     _lib.check(_lib.lib().rrin_conv3x3_h8_fwd(C.byref(d), H.stream(dev)), "rrin_conv3x3_h8_fwd")
     torch.cuda.synchronize(dev)
     return dst, pool
@@ -382,14 +390,14 @@ def test_h8_leaky_rep_writes_replicated_ring(gpu, prec):
 
 def subpixel_upconv(src: H8Tensor, w, b, cfg, prec, dst=None, ksplit=0, keep=None, fold=False, edge_split=False,
                     full=False, inlaunch=False, src_off=0, dst_off=0, status=None, fix_status=None, alloc=scratch,
-                    conv=True, fix=True):
+                    conv=True, fix=True, info=None):
     """EPI_SUBPIXEL conv + ring fix-up through the C ABI (the Net's up.1 conv); fold: the
     ring in the conv launch (rrin_conv_h8_desc.ring_w, Winograd kind 3) instead of
     rrin_subpixel_edge_fix_h8; full: the fix-up's from-scratch mode (rrin_edge_fix_desc.full,
     no edge buffer), launched BEFORE the conv -- it must read nothing the conv writes, and the
     conv must write no ring pixel.  src_off / dst_off: first channel of the source / destination
     view; status / fix_status: the range flags of the conv and of the fix-up; alloc: see scratch()
-    (names "edge", "part", "cnt", "ring_corr", "ring_cnt", "fix_part", "fix_cnt"; keep receives
+    (info: as conv_h8's, for the conv's launch; names "edge", "part", "cnt", "ring_corr", "ring_cnt", "fix_part", "fix_cnt"; keep receives
     them in that order of use, the edge buffer first); conv / fix False: leave that launch of the
     separate pair out."""
     lib = _lib.lib()
@@ -427,6 +435,7 @@ def subpixel_upconv(src: H8Tensor, w, b, cfg, prec, dst=None, ksplit=0, keep=Non
         cnt = alloc("ring_cnt", nc.value, torch.int32, dev)
         d.ring_corr, d.ring_cnt = corr.data_ptr(), cnt.data_ptr()
         keep.extend([corr, cnt])
+        query_launch(d, dev, info)
         _lib.check(lib.rrin_conv3x3_h8_fwd(C.byref(d), H.stream(dev)), "rrin_conv3x3_h8_fwd(subpixel, fold)")
         torch.cuda.synchronize(dev)
         return dst
@@ -438,10 +447,12 @@ def subpixel_upconv(src: H8Tensor, w, b, cfg, prec, dst=None, ksplit=0, keep=Non
     e.status = fix_status.data_ptr() if fix_status is not None else None
     if inlaunch:  # ABI 17: the ring from scratch with the conv (rrin_conv_h8_desc.ring_full)
         d.ring_full = C.addressof(e)
+        query_launch(d, dev, info)
         _lib.check(lib.rrin_conv3x3_h8_fwd(C.byref(d), H.stream(dev)), "rrin_conv3x3_h8_fwd(subpixel, ring_full)")
         torch.cuda.synchronize(dev)
         return dst
     if not full and conv:
+        query_launch(d, dev, info)
         _lib.check(lib.rrin_conv3x3_h8_fwd(C.byref(d), H.stream(dev)), "rrin_conv3x3_h8_fwd(subpixel)")
         if not fix:
             torch.cuda.synchronize(dev)
