@@ -19,6 +19,9 @@ Fixtures (all float32, np.savez_compressed):
                                      upsample x2 / avgpool on odd sizes, one conv per
                                      shape class (6x10 spatial), UNetConvBlock, UNetUpBlock
   unet_refine.npz                  : refine_flow U-Net alone at 64x96
+
+y4m_calls.json is not made here: gen_y4m_calls.py records it from the package's own Y4M drivers and
+needs no reference.
 """
 from __future__ import annotations
 
