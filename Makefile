@@ -57,7 +57,7 @@ $(OBJ_DIR)/%.o: $(SRC_DIR)/%.hip $(HDRS)
 $(LIB): $(OBJS) $(ISA_OK)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $@ $(OBJS)
 
-LAB_SRCS := $(SRC_DIR)/conv_h8.hip $(SRC_DIR)/conv_rec.hip $(SRC_DIR)/edge_fix.hip $(SRC_DIR)/conv_block0.hip $(SRC_DIR)/conv_wino.hip $(SRC_DIR)/conv_winoc.hip $(SRC_DIR)/conv_winoc42.hip $(SRC_DIR)/conv_winoh.hip $(SRC_DIR)/pack_wino.hip
+LAB_SRCS := $(SRC_DIR)/conv_h8.hip $(SRC_DIR)/conv_rec.hip $(SRC_DIR)/edge_fix.hip $(SRC_DIR)/conv_block0.hip $(SRC_DIR)/conv_wino.hip $(SRC_DIR)/conv_winoq.hip $(SRC_DIR)/conv_winoc.hip $(SRC_DIR)/conv_winoc42.hip $(SRC_DIR)/conv_winoh.hip $(SRC_DIR)/pack_wino.hip
 $(LAB): $(LAB_SRCS) $(HDRS)
 	$(HIPCC) $(CXXFLAGS) -DRRIN_LAB -shared -o $@ $(LAB_SRCS)
 

@@ -262,7 +262,7 @@ struct ConvH8Args {
   int ksplit, kper;
   float* part;
   int* cnt;
-  // EPI_SUBPIXEL ring fold (Winograd kind 3, conv_wino.hip): nring correction blocks at
+  // EPI_SUBPIXEL ring fold (Winograd kind 3, conv_winoq.hip): nring correction blocks at
   // the head of the grid compute the out-of-image taps of every ring segment (nseg per
   // image and co block) into corr; the segment's conv tile and its correction block
   // each count themselves in rcnt, and the later one writes the ring pixels
@@ -323,8 +323,8 @@ int launch_h8(const ConvH8Args& a, int cfg, int prec, int epi, hipStream_t st, r
 int edge_fix_prepare(const rrin_edge_fix_desc* d, EdgeFixArgs& a, dim3& grid);
 int edge_fix_run(EdgeFixArgs a, dim3 grid, int prec, bool full, const rrin_edge_fix_desc* d, hipStream_t st,
                  bool one_group = false);
-// Winograd F(2x2,3x3) exact-fp32 conv (conv_wino.hip): tile config 18 of
-// the record-layout table (F32R only), its LDS bytes per block and launcher.
+// Winograd F(2x2,3x3) exact-fp32 conv, the 4-wave tile (conv_wino.hip): tile config 18
+// (kind 1) of the record-layout table (F32R only), its LDS bytes per block and launcher.
 constexpr size_t kWinoLds = (size_t)(2 * 704 + 2 * 16 * 2 * 32) * 16;
 int launch_wino(const ConvH8Args& a, int epi, hipStream_t st, rrin_launch_info* info = nullptr);
 // zero channels [c0, c1) of a record-layout view (glue_h8.hip)
@@ -361,10 +361,9 @@ inline int pad_up(int v, int mult) { return (v + mult - 1) / mult * mult; }
 // plane_logits: where the MASK head's raw_out goes in the plane's scratch.
 int plane_check(const rrin_aux_plane* pl, int frames, int n, int h0, int w0, int h, int w);
 float* plane_logits(const rrin_aux_plane* pl, int n, int h, int w);
-// cfg 18's tile on 8 waves of 4 accumulators (<= 128 VGPRs: 4 waves per SIMD),
-// two stages of [raw 680 | U 1024] records (three in A/B builds: two blocks per
-// CU would fill 163,584 B)
-constexpr size_t kWinoQLds = (size_t)3 * (680 + 1024) * 16;
+// cfg 18's tile on 8 waves of 4 accumulators (<= 128 VGPRs: 4 waves per SIMD; conv_winoq.hip),
+// two stages of [raw 680 | U 1024] records
+constexpr size_t kWinoQLds = (size_t)2 * (680 + 1024) * 16;
 // th = 8 (cfg 20: 8 waves) or 4 (cfg 21: 4 waves, the same arithmetic on half-height tiles)
 int launch_winoq(const ConvH8Args& a, int epi, int th, hipStream_t st, rrin_launch_info* info = nullptr);
 // register-U Winograd tiles (conv_winoc.hip): 4 waves, two blocks per CU, the U operands
@@ -421,7 +420,9 @@ constexpr size_t kB0Lds = (size_t)(kB0Mid + kB0Stage + 16) * 16;
 static_assert(kB0Stage <= kB0Mid, "stage Y inside the conv-a tile");
 static_assert(2 * kB0Lds <= 160 * 1024, "two fused-block workgroups per CU");
 #ifdef RRIN_LAB
-int launch_wino_lab(const ConvH8Args& a, int abl, hipStream_t st);  // ablation bits (conv_wino.hip)
+// ablation bits: 1024 + bits the 8-wave tile (conv_winoq.hip), else kind 1 (launch_wino_lab1, conv_wino.hip)
+int launch_wino_lab(const ConvH8Args& a, int abl, hipStream_t st);
+int launch_wino_lab1(const ConvH8Args& a, int abl, hipStream_t st);
 // one LEAKY conv of a direct-form tile at F16X3 (cfg 0, 1, 6) or F32R (cfg 0, 1, 3, 4, 5, 6, 16)
 // with schedule knobs sched (SCHED_*, ablations included) and grid persist (conv_h8.hip)
 int launch_h8_lab(const ConvH8Args& a, int cfg, int prec, int sched, int persist, hipStream_t st);

@@ -1,6 +1,6 @@
 // Exact-fp32 3x3 conv as Winograd F(2x2,3x3) on fp32 records (R32): the
 // "register-U" tiles, Winograd kinds 6 and 7 of the record-layout conv table.
-// Same arithmetic, in the same order, as conv3x3_winoq_kernel (conv_wino.hip):
+// Same arithmetic, in the same order, as conv3x3_winoq_kernel (conv_winoq.hip):
 // the outputs are bitwise those of configs 18-21.
 //
 // Replaces nn.Conv2d(3, pad=1) + LeakyReLU(0.1) (unet.py:29,59-63), the fused
@@ -33,9 +33,6 @@
 #include "edge_fix.hpp"
 #include "wino_tile.hpp"
 
-#ifndef RRIN_WINOC_AGPR
-#define RRIN_WINOC_AGPR 0
-#endif
 // Diagnostic build only (tools/clock_probe.py, never the product library): each
 // workgroup stamps s_memtime / s_memrealtime at its start, after its main loop and at
 // its end into g_winoc_clk[bid % kClkSlots] (the in-kernel clock: MI355X_MICROARCH.md
@@ -275,10 +272,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
   for (int t = 0; t < CT; ++t)
 #pragma unroll
     for (int i = 0; i < 16; ++i) bsv[t][i] = a.bias[(CT * cob + t) * 32 + 8 * (i >> 2) + 4 * hh + (i & 3)];
-#if RRIN_WINOC_AGPR
-  // A/B: an inline-asm AGPR operand makes the compiler keep MFMA accumulators in AGPRs
-  asm volatile("" ::"a"(acc[0][0][0][0]));
-#endif
   __syncthreads();  // every read of the stages done before the exchange reuses the LDS
 
   // ---- output transform (kind 3's order): Q[c] = sum_x M[x] A[x][c] of this wave's
@@ -370,7 +363,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc_kernel(ConvH8Args a) {
         }
         if constexpr (EPI == RRIN_EPI_LEAKY_POOL) {
           // the patch's four outputs (yw = (r, c)) meet in LDS; wave 0 writes
-          // avg = 0.25 ((Y00 + Y10) + (Y01 + Y11)), kind 3's order (conv_wino.hip)
+          // avg = 0.25 ((Y00 + Y10) + (Y01 + Y11)), kind 3's order (conv_winoq.hip)
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             floatx4 g;

@@ -29,9 +29,6 @@
 // U: rrin_pack_conv3x3_wino_cfg for this kind, [cob][chunk][xi 24][hh][32 co][4 ch].
 #include "wino_tile.hpp"
 
-#ifndef RRIN_WINO42_AGPR
-#define RRIN_WINO42_AGPR 0
-#endif
 namespace rrin {
 
 // Tile geometry PCW: 8 -> 32 px x 8 rows (8 x 4 patches), 4 -> 16 px x 16 rows (4 x 8 patches).
@@ -452,9 +449,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winoc42_kernel(ConvH8Args a) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) bsv[i] = a.bias[cob * 32 + 8 * (i >> 2) + 4 * hh + (i & 3)];
     vm_fence();  // the bias loads stay older than the next tile's prologue (make check-isa)
-#if RRIN_WINO42_AGPR
-    asm volatile("" ::"a"(acc[0][0]));
-#endif
     __syncthreads();  // every read of the stages done before the exchange / the next tile's DMA
     if constexpr (!PERSIST) {
       epilogue(std::false_type{});

@@ -68,7 +68,7 @@ struct CfgH8 {
   bool pool_ok;
   int sched, persist;
   int nt;  // threads per workgroup (the direct-form tiles; 0: Winograd configs)
-  // as rrin_conv_h8_cfg_wino reports it.  0: direct form; Winograd tile kind: 1, 3, 4 (conv_wino.hip),
+  // as rrin_conv_h8_cfg_wino reports it.  0: direct form; Winograd tile kind: 1 (conv_wino.hip), 3, 4 (conv_winoq.hip),
   // 6, 7 (conv_winoc.hip; 6 also at fp16, conv_winoh.hip), 14 (conv_winoc42.hip); -1: a retired id
   // (rrin_conv_h8_cfg_ok 0, RRIN_E_CONFIG)
   int kind;

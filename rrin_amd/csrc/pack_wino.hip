@@ -1,5 +1,5 @@
 // Host-only Winograd weight packing: U = G g G^T per (co, ci, transform point), in double, rounded
-// once, in the record order each tile loads -- F(2x2,3x3) for kinds 1-7 (conv_wino.hip,
+// once, in the record order each tile loads -- F(2x2,3x3) for kinds 1-7 (conv_wino.hip, conv_winoq.hip,
 // conv_winoc.hip), F(4,3) x F(2,3) for kind 14 (conv_winoc42.hip), F(2x2,3x3) scaled to fp16 for
 // kind 6 at fp16 (conv_winoh.hip).  No device code.
 #include <math.h>

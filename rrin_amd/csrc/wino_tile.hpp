@@ -1,5 +1,5 @@
-// What the Winograd record-conv tiles share (conv_wino.hip: kinds 1, 3, 4; conv_winoc.hip: kinds
-// 6, 7; conv_winoc42.hip: kind 14; conv_winoh.hip: kind 6 at fp16): the workgroup order (XCD
+// What the Winograd record-conv tiles share (conv_wino.hip: kind 1; conv_winoq.hip: kinds 3, 4;
+// conv_winoc.hip: kinds 6, 7; conv_winoc42.hip: kind 14; conv_winoh.hip: kind 6 at fp16): the workgroup order (XCD
 // remap, co-block groups), the LDS column swizzle and buffer-load helpers, and on the host the
 // co-block group size and the per-epilogue kernel dispatch.  Every device function inlines into
 // its kernel; what a kernel holds as a compile-time constant is one here.  The vector types are
@@ -11,6 +11,11 @@
 #include "h8.hpp"
 
 namespace rrin {
+
+// The LDS-staged F(2x2,3x3) tiles (conv_wino.hip, conv_winoq.hip), per 8-channel chunk: raw
+// tile rows of 34 columns (32 px + halo), one U slab [xi 16][half 2][co 32] of records
+constexpr int kWnRawCols = 34;
+constexpr int kWnU = 16 * 2 * 32;
 
 // LDS position of raw column col (0..33) within its row: even columns first (the stride-2
 // window reads of 16 lanes fall on distinct banks)

@@ -163,7 +163,7 @@ def size_class(pixels: int) -> str:
     return "xlarge" if pixels <= XLARGE_PX else "xxlarge"
 
 
-# Exact fp32 (F32R): Winograd F(2x2,3x3) (conv_wino.hip) for the body convs of
+# Exact fp32 (F32R): Winograd F(2x2,3x3) (conv_wino*.hip) for the body convs of
 # these size classes -- faster than the best direct-form config on every conv
 # shape of the Net but the 6-channel first conv (1280x720 x 2: 1.3-1.7x; 640x368
 # x 1: 1.0-1.6x; profiles/r02/wino/tune_*).  WINO = False (A/B) uses the

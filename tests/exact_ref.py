@@ -484,7 +484,7 @@ def ring_mask(hh, ww):
 def edge_split(cin, prec, mode):
     """(K groups, K runs) of a ring pixel's sum.  "fix" / "full": the standalone fix-up
     (edge_fix.hip, edge_fix_split); "inlaunch": ring_full with the conv -- one group, fp32 records in
-    runs of one chunk; "fold": one chain (conv_wino.hip, ring_block)."""
+    runs of one chunk; "fold": one chain (winoq_ring.hpp, ring_block)."""
     if mode == "fold":
         return 1, 1
     if mode == "inlaunch":
