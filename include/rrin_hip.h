@@ -783,7 +783,7 @@ int rrin_net_yuv_items_fwd(const rrin_net_yuv_desc* d, const rrin_items* items, 
 int rrin_net_u16_items_fwd(const rrin_net_u16_desc* d, const rrin_items* items, void* stream);
 int rrin_net_yuv16_items_fwd(const rrin_net_yuv16_desc* d, const rrin_items* items, void* stream);
 
-/* ---- Low-resolution flow estimation: flow_scale 2 and 4 (csrc/flow_scale.hip, net.hip) --------
+/* ---- Low-resolution flow estimation: flow_scale 2 and 4 (csrc/flow_scale.hip, net.hip; the byte-frame entries: net_frames.hip) ----
  * History: added after ABI 25 without a new version number -- a new struct passed to new entry
  * points only, no existing struct or entry point changes, so RRIN_ABI_VERSION stays 25; a caller
  * finds out whether a build has them by looking the symbols up.
@@ -1047,7 +1047,7 @@ int64_t rrin_tfeatdist_workspace_bytes(int64_t count);
 int rrin_tfeatdist(const float* a, const float* b, int64_t count, double* sums, float* grad, void* workspace,
                    int64_t workspace_bytes, void* stream);
 
-/* ---- An extra plane (alpha, depth, ID) through the byte-frame forwards (csrc/plane.hip, net.hip) --
+/* ---- An extra plane (alpha, depth, ID) through the byte-frame forwards (csrc/plane.hip, net.hip, net_frames.hip) --
  * History: added after ABI 25 without a new version number -- a new struct passed to new entry
  * points only, no existing struct or entry point changes, so RRIN_ABI_VERSION stays 25; a caller
  * finds out whether a build has them by looking the symbols up.

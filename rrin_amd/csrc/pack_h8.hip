@@ -1,7 +1,8 @@
 // Host-only side of the record convs: weight packing for the direct-form tiles (conv_h8.hip) at
 // fp16 / split-fp16 (rrin_pack_conv3x3_h8) and fp32 records (rrin_pack_conv3x3_r32), the
 // phase-combined weights of the sub-pixel up conv (rrin_subpixel_weights) and the size of its
-// ring (rrin_ring_pixels).  No device code.
+// ring (rrin_ring_pixels); and the packer of the planar fp32 convs (rrin_pack_conv3x3, with the
+// padded bias size every packer shares, rrin_pack_bias_floats).  No device code.
 #include <math.h>
 #include <string.h>
 
@@ -117,6 +118,45 @@ extern "C" int rrin_pack_conv3x3_r32(const float* w, const float* b, int32_t cou
               const int co = cob * bm + col, ch = c * 8 + hh * 4 + e;
               wpack[o++] = (co < cout && ch < cin) ? w[((int64_t)co * cin + (perm ? perm[ch] : ch)) * 9 + tap] : 0.f;
             }
+  for (int co = 0; co < cob_n * bm; ++co) bpack[co] = co < cout ? b[co] : 0.f;
+  return 0;
+}
+
+// ---- the planar fp32 convs (conv_mfma.hip) -----------------------------------------
+// wpack[cob][chunk][ci8][tap][bm]: the slab a block stages per K chunk is
+// contiguous; zero rows/cols pad cin to 8 and cout to bm.
+extern "C" int64_t rrin_pack_conv3x3_floats(int32_t cout, int32_t cin, int32_t bm) {
+  if (cout < 1 || cin < 1 || bm < 32 || bm % 32) return RRIN_E_ARG;
+  const int64_t cob = (cout + bm - 1) / bm, nch = (cin + 7) / 8;
+  return cob * nch * 8 * 9 * bm;
+}
+
+extern "C" int64_t rrin_pack_bias_floats(int32_t cout, int32_t bm) {
+  if (cout < 1 || bm < 32 || bm % 32) return RRIN_E_ARG;
+  return (int64_t)((cout + bm - 1) / bm) * bm;
+}
+
+extern "C" int rrin_pack_conv3x3(const float* w, const float* b, int32_t cout, int32_t cin, int32_t bm,
+                                 const int32_t* perm, float* wpack, float* bpack) {
+  if (!w || !b || !wpack || !bpack || cout < 1 || cin < 1 || bm < 32 || bm % 32) return RRIN_E_ARG;
+  if (perm)
+    for (int c = 0; c < cin; ++c)
+      if (perm[c] < 0 || perm[c] >= cin) return RRIN_E_ARG;
+  const int cob_n = (cout + bm - 1) / bm, nch = (cin + 7) / 8;
+  int64_t o = 0;
+  for (int cob = 0; cob < cob_n; ++cob)
+    for (int c = 0; c < nch; ++c)
+      for (int ci = 0; ci < 8; ++ci)
+        for (int tap = 0; tap < 9; ++tap)
+          for (int col = 0; col < bm; ++col) {
+            const int co = cob * bm + col, ch = c * 8 + ci;
+            float v = 0.f;
+            if (co < cout && ch < cin) {
+              const int src_ch = perm ? perm[ch] : ch;
+              v = w[((int64_t)co * cin + src_ch) * 9 + tap];
+            }
+            wpack[o++] = v;
+          }
   for (int co = 0; co < cob_n * bm; ++co) bpack[co] = co < cout ? b[co] : 0.f;
   return 0;
 }

@@ -498,8 +498,8 @@ def test_h8_subpixel_upconv(gpu, prec, n, cin, cout, sh, sw):
                                               (2, 512, 256, 3, 5), (1, 64, 32, 1, 1), (1, 256, 128, 1, 2),
                                               (1, 1024, 512, 2, 3)])
 def test_h8_subpixel_ring_full(gpu, prec, n, cin, cout, sh, sw):
-    """The from-scratch ring (rrin_edge_fix_desc.full; what net.hip runs on a side stream
-    beside the sub-pixel conv) launched before the conv: the whole output within the
+    """The from-scratch ring (rrin_edge_fix_desc.full; what the schedule once ran on a side
+    stream beside the sub-pixel conv) launched before the conv: the whole output within the
     tolerance of upsample-then-conv in float64, the bridge half untouched, and every K split
     of the fix-up (fp32 records: one workgroup per run) bit for bit the one-workgroup result."""
     x = torch.rand(n, cin, sh, sw, device=gpu) * 2 - 1

@@ -1,5 +1,5 @@
-"""GPU: the file that strings the kernels together (csrc/net.hip: workspace plan, run_unet /
-run_unet_h8, rrin_net_fwd, rrin_unet_fwd, the launch profiler) over its whole contract, against
+"""GPU: the files that string the kernels together (csrc/net_plan.hpp: workspace plan; unet_sched.hip:
+run_unet / run_unet_h8, rrin_unet_fwd; net.hip: rrin_net_fwd; prof.hip: the launch profiler) over its whole contract, against
 the float64 references of tests/net_contract.py.
 
 A. ``rrin_unet_fwd`` through ``rrin_amd.UNet(ci, co, d)`` at every depth 2..5, input channel
